@@ -21,7 +21,11 @@ scaling either way.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with
 `roofline` (dominant kernel, HIP-event time measured on its launch stream
-inside the timed region) and `cpu_baseline` (the oracle on host cores, N=1).
+inside the timed region).  A plain run sets up, warms up, times `--steps`
+steps, writes the last step's outputs if `--dump-outputs DIR` is given and
+prints the line.  `--full` adds the legs that take runs of their own (N=1):
+`drop_in_per_frame` (one mm_process per frame), `cpu_baseline` (the oracle on
+host cores) and `parity_vs_oracle` (the timed step against the oracle).
 """
 import argparse
 import json
@@ -164,7 +168,16 @@ def parse(argv=None):
     ap.add_argument("--replica-index", type=int, default=None,
                     help="--mode replicas: which replica's stream this process runs "
                          "(default: its RANK; seed = base + index)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: "
+                         "the per-frame drop-in leg (drop_in_per_frame), the CPU baseline "
+                         "(cpu_baseline) and the parity check against the oracle "
+                         "(parity_vs_oracle); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the "
+                         "output frames its caller receives) as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline and the parity check")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="bound on the CPU-baseline sample")
     ap.add_argument("--call-pattern", choices=("batch", "per-frame"), default="batch",
@@ -172,7 +185,7 @@ def parse(argv=None):
                          "per frame, .cs:101-143): mm_process on device pointers, one frame "
                          "per call, batch size 1 (N=1 only)")
     ap.add_argument("--drop-in-frames", type=int, default=300,
-                    help="frames of the per-frame drop-in leg reported beside the batch "
+                    help="--full: frames of the per-frame drop-in leg reported beside the batch "
                          "rate (0: skip)")
     # internal: CPU-baseline child process (cpu_baseline)
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)
@@ -482,6 +495,35 @@ def drop_in_per_frame(mm355, torch, params, W, H, frames, local, count):
                        "device-scope HIP events around each call on its stream (second pass)"}
 
 
+DUMP_WHOLE_VALUES = 1 << 23     # outputs up to 32 MB as float32 are written whole
+DUMP_SAMPLE_VALUES = 1 << 22    # else a 16 MB float32 sample
+DUMP_SEED = 0x5EED0D            # of the sample's positions
+
+
+def dump_outputs(torch, out, dirname, rank=0, world=1):
+    """--dump-outputs: the last timed step's output frames (`out`, what the
+    caller of mm_process_stream / mm_process / mm_ring_step holds after the
+    step), for comparing two builds output for output on the same arguments
+    (the synthetic input stream is a function of the arguments alone).
+    frames.npy: the whole (C, H, W, 4) output as float32 when it has at most
+    DUMP_WHOLE_VALUES values; else frames_sample.npy: the values at
+    DUMP_SAMPLE_VALUES fixed positions (ascending flat indices drawn with
+    DUMP_SEED from the output's shape).  frame_sums.npy: every frame's byte
+    sum, float64 (exact).  Ranks of an N > 1 run write <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    n = out.numel()
+    sums = out.reshape(out.shape[0], -1).sum(dim=1, dtype=torch.int64).cpu().numpy()
+    np.save(os.path.join(dirname, f"frame_sums{sfx}.npy"), sums.astype(np.float64))
+    if n <= DUMP_WHOLE_VALUES:
+        np.save(os.path.join(dirname, f"frames{sfx}.npy"), out.cpu().numpy().astype(np.float32))
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE_VALUES))
+    vals = out.reshape(-1)[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    np.save(os.path.join(dirname, f"frames_sample{sfx}.npy"), vals.astype(np.float32))
+
+
 def frame_roofline(W, H, N, fps_per_gpu, batch, dom_traffic=None, ran=None, key=None, per_frame_bytes=None):
     """Frame-level HBM roofline: the design's compulsory bytes per output
     frame (compulsory_bytes() of the kernels that ran, at this batch size, per
@@ -619,6 +661,8 @@ def main():
     stream.finish()
     if cring is not None:
         cring.close()   # retires shifts posted ahead
+    if a.dump_outputs:
+        dump_outputs(torch, out, a.dump_outputs, rank, world)
     if a.checksum:
         sums = backend.sums
         if world > 1 and a.mode == "ring":   # (gloo or nccl process group)
@@ -741,11 +785,12 @@ def main():
         "kernels": kern,
     }
     h.close()
-    if world == 1 and not per_frame and a.drop_in_frames > 0 and not steer and not a.checksum:
+    # --full: the legs that take runs of their own
+    if a.full and world == 1 and not per_frame and a.drop_in_frames > 0 and not steer:
         # the reference's call pattern beside the batch rate (same frames)
         result["drop_in_per_frame"] = drop_in_per_frame(mm355, torch, params, W, H, frames,
                                                         local, a.drop_in_frames)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not steer:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not steer:
         result["cpu_baseline"], ref = cpu_baseline(a)
         result["parity_vs_oracle"] = parity_check(mm355, torch, params, W, H, ref, local, C, B)
     if rank == 0:

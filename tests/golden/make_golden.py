@@ -34,12 +34,21 @@ CASES = [
 STANDARD = {"std_96x64_S25": (96, 64, 5, 25.0, 0, False, 3, False, {}),
             "std_64x48_S9p7_steep2": (64, 48, 5, 9.7, 1, False, 3, False,
                                        {"steep": 2.0, "high": 0.3})}
+PART_BYTES = 1 << 20   # largest fixture file; a longer array is split (save)
 
 
 def save(name, arr, manifest, entry):
     fn = f"{name}.bin"
     arr = np.ascontiguousarray(arr)
-    arr.tofile(os.path.join(HERE, fn))
+    raw = arr.tobytes()
+    if len(raw) <= PART_BYTES:
+        arr.tofile(os.path.join(HERE, fn))
+    else:   # no committed file over 1 MiB: parts, listed in order
+        fn = []
+        for k in range(0, len(raw), PART_BYTES):
+            fn.append(f"{name}.part{k // PART_BYTES}.bin")
+            with open(os.path.join(HERE, fn[-1]), "wb") as f:
+                f.write(raw[k:k + PART_BYTES])
     entry.setdefault("files", {})[name.split("__")[-1]] = {
         "file": fn, "dtype": str(arr.dtype), "shape": list(arr.shape),
         "sha256": hashlib.sha256(arr.tobytes()).hexdigest()}

@@ -66,6 +66,43 @@ def test_cpu_worker_boundary_pairs_equal_sequential(tmp_path):
     assert np.array_equal(pairs[0], seq[2]) and np.array_equal(pairs[1], seq[5])
 
 
+def test_plain_run_is_lean_and_full_is_an_option():
+    """The legs that take runs of their own (drop-in, CPU baseline, parity)
+    are behind --full, off by default."""
+    a = bench.parse(["--gpus", "1", "--steps", "4", "--warmup", "1"])
+    assert not a.full and a.dump_outputs is None and a.steps == 4 and a.warmup == 1
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: float32/float64 .npy files; a small output whole, a
+    large one as the same seeded sample on every call, within 64 MB."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(1)
+    small = torch.randint(0, 256, (3, 8, 16, 4), dtype=torch.uint8, generator=g)
+    bench.dump_outputs(torch, small, str(tmp_path / "s"))
+    fr = np.load(tmp_path / "s" / "frames.npy")
+    assert fr.dtype == np.float32 and np.array_equal(fr, small.numpy().astype(np.float32))
+    sums = np.load(tmp_path / "s" / "frame_sums.npy")
+    assert sums.dtype == np.float64
+    assert np.array_equal(sums, small.numpy().reshape(3, -1).sum(axis=1, dtype=np.int64))
+    big = torch.randint(0, 256, (5, 540, 960, 4), dtype=torch.uint8, generator=g)
+    assert big.numel() > bench.DUMP_WHOLE_VALUES
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, big, str(tmp_path / d), rank=1, world=2)
+    sa = np.load(tmp_path / "a" / "frames_sample_rank1.npy")
+    sb = np.load(tmp_path / "b" / "frames_sample_rank1.npy")
+    assert sa.dtype == np.float32 and sa.shape == (bench.DUMP_SAMPLE_VALUES,)
+    assert np.array_equal(sa, sb)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, big.numel(),
+                                                                  size=bench.DUMP_SAMPLE_VALUES))
+    assert np.array_equal(sa, big.numpy().reshape(-1)[idx].astype(np.float32))
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 << 20
+
+
 def test_boundary_frames_cover_k2_launch_shapes():
     """300 frames in batches of 150 at 1080p: each batch's prime, the packed
     block's hand-off to k_cols_tail (40 %: frame 90 of a batch), the second-half

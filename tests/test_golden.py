@@ -22,7 +22,10 @@ CASES = sorted(MAN["cases"])
 
 def load(case, key):
     f = MAN["cases"][case]["files"][key]
-    a = np.fromfile(os.path.join(GOLD, f["file"]), dtype=f["dtype"]).reshape(f["shape"])
+    # an array over 1 MiB is stored in parts ("file" is their list, in order)
+    parts = f["file"] if isinstance(f["file"], list) else [f["file"]]
+    a = np.concatenate([np.fromfile(os.path.join(GOLD, p), dtype=f["dtype"])
+                        for p in parts]).reshape(f["shape"])
     assert hashlib.sha256(a.tobytes()).hexdigest() == f["sha256"], (case, key)
     return a
 
