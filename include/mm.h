@@ -15,8 +15,9 @@
  *     packed (pitch = W * bytes-per-pixel, mm_frame_bytes).  RGBA8 is UNORM
  *     (v = byte/255); RGBA32F and RGBA16F are linear float; RGBA8_SRGB is an
  *     8-bit sRGB target as Unity's Linear colour space sees it (decoded to
- *     linear light on read, encoded on write).  The handle owns all device
- *     scratch and the one-frame temporal state.
+ *     linear light on read, encoded on write).  MM_NV12 / MM_NV12_FULL are
+ *     video frames, planar Y'CbCr 4:2:0 (see the format list).  The handle
+ *     owns all device scratch and the one-frame temporal state.
  *   - A handle is not thread-safe: one handle per video stream, calls in frame
  *     order (Unity calls OnRenderImage serially on its render thread).
  *   - The first frame after mm_create/mm_reset is passed through bitwise
@@ -26,7 +27,8 @@
  *     this build covers 16 <= N <= 8192, i.e. 9 <= max(W, H) <= 8192 (other
  *     sizes: MM_ERR_UNSUPPORTED from mm_create); MM_MODE_STEERABLE stops at
  *     N = 4096.  Odd W or H are supported in every mode (and the debug
- *     views).  The fused K3+K4 kernel runs for
+ *     views); the NV12 formats, being 4:2:0, take even W and H only and no
+ *     debug view (MM_ERR_UNSUPPORTED).  The fused K3+K4 kernel runs for
  *     even sizes with W % 8 == 0 and margins N - W >= 8, N - H >= 4; every
  *     other geometry takes the unfused pair (same results).
  *   - Every entry point that takes a handle runs on the handle's device and
@@ -55,7 +57,8 @@ extern "C" {
 #define MM_ERR_OOM         -5  /* device allocation failed */
 #define MM_ERR_NO_STATE    -6  /* mm_get_state before any frame was seen */
 
-/* frame formats (every entry point that takes frames takes each of them) */
+/* frame formats (every entry point that takes frames takes each of them;
+ * the NV12 pair for even W and H and without the debug views) */
 #define MM_RGBA8   0       /* 4 B/px, UNORM: v = byte / 255; out round(saturate(v) * 255) */
 #define MM_RGBA32F 1       /* 16 B/px, linear float                                       */
 /* The frames the reference actually receives (since ABI 10): its camera
@@ -72,6 +75,32 @@ extern "C" {
                               pipeline in linear light, out = the byte whose sRGB
                               interval holds saturate(v) (halfway points in linear
                               light; tools/gen_srgb.py); alpha byte / 255, out 255    */
+
+/* Video frames (backward-compatible addition to ABI 10: a caller detects it by
+ * mm_frame_bytes(W, H, MM_NV12, &n) == MM_OK).  8-bit Y'CbCr 4:2:0 as a
+ * decoder hands it out, tightly packed: H rows of W luma bytes, then H/2 rows
+ * of W bytes of interleaved (Cb, Cr) pairs, W H 3/2 bytes in all; frame k of a
+ * stream at k * mm_frame_bytes; frame pointers 4-byte aligned.  W and H even (else MM_ERR_UNSUPPORTED from
+ * mm_frame_bytes and every frame entry point); show_magnitude / show_phase
+ * are refused with MM_ERR_UNSUPPORTED (R-channel views).
+ * The frame IS the RGBA32F frame of its BT.601 decode, and the result the
+ * reference's result on that frame:
+ *   in:  y = (Y - 16) / 219, cb = (Cb - 128) / 224, cr = (Cr - 128) / 224
+ *        (MM_NV12_FULL: Y / 255, (C - 128) / 255), every chroma sample shared
+ *        by its 2 x 2 pixels; R = y + 1.402 cr, G = y - 0.344136 cb -
+ *        0.714136 cr, B = y + 1.772 cb, alpha 1, NOT clamped (out-of-gamut
+ *        values pass until the reference's saturate, like HDR values);
+ *   out: of the saturated RGB, Yl = 0.299 R + 0.587 G + 0.114 B,
+ *        Cb' = (B - Yl) 0.5 / 0.886, Cr' = (R - Yl) 0.5 / 0.701; luma code
+ *        Yl 219 + 16 (full: Yl 255), chroma code 128 + 224 (full: 255) x the
+ *        mean of the 2 x 2 pixels' C'; codes floor(v + 0.5) clamped to 0..255.
+ * The operator changes luma only and these are RGBToYIQ's own luma weights, so
+ * the kernels read the luma plane for the transform and the half-resolution
+ * chroma plane for the recombination: no colour conversion on the host, 1.5
+ * bytes per pixel each way.  The first frame and apply_magnification = 0 pass
+ * all W H 3/2 bytes through. */
+#define MM_NV12      16   /* 8-bit 4:2:0, BT.601 limited ("video") range */
+#define MM_NV12_FULL 17   /* the same, full ("JPEG") range               */
 
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0   /* usePyramidDecomposition = true (.cs:18, :128-131) */
@@ -152,7 +181,8 @@ int mm_get_params(const mm_handle *h, mm_params *p);
 int mm_padded_size(const mm_handle *h, int *n);
 
 /* Bytes of one W x H frame of `format` (MM_ERR_INVALID for an unknown format
- * or size).  Since ABI 10. */
+ * or size; MM_ERR_UNSUPPORTED for an NV12 format with odd W or H).  Since
+ * ABI 10. */
 int mm_frame_bytes(int width, int height, int format, size_t *bytes);
 
 /* OnRenderImage (.cs:101-143): one frame in, one frame out.
@@ -169,7 +199,7 @@ int mm_process(mm_handle *h, const void *in, void *out, int format, int flags,
                void *hip_stream);
 
 /* Consecutive frames of one stream in a single call (device pointers;
- * frame k at in + k*W*H*bpp).  Equivalent, frame for frame, to `count`
+ * frame k at in + k * mm_frame_bytes).  Equivalent, frame for frame, to `count`
  * mm_process calls; batches the launches. Asynchronous on hip_stream. */
 int mm_process_stream(mm_handle *h, const void *in, void *out, int count,
                       int format, void *hip_stream);
@@ -279,6 +309,10 @@ int mm_synth_frames(void *dev_out, int width, int height, int t0, int count,
  * stretch+pad bilinear resample, including the Hann window factor. */
 int mm_resample_table(int width, int height, int axis, int edge_mode,
                       int32_t *idx4, float *w4);
+/* The (cb, cr) -> (I, Q) matrix the NV12 compose uses, m = {I_cb, Q_cb, I_cr,
+ * Q_cr}: RGBToYIQ's I and Q rows times the BT.601 conversion above, derived
+ * in double (the kernels take it divided by the range's chroma scale). */
+int mm_nv12_chroma_matrix(double m[4]);
 
 #ifdef __cplusplus
 }

@@ -401,7 +401,15 @@ int mm_padded_size(const mm_handle *h, int *n)
 int mm_frame_bytes(int width, int height, int format, size_t *bytes)
 {
     if (!bytes || width < 1 || height < 1 || !fmt_valid(format)) return MM_ERR_INVALID;
-    *bytes = (size_t)width * (size_t)height * fmt_bpp(format);
+    if (int rc = fmt_check(width, height, format, nullptr)) return rc;   // NV12: even sizes
+    *bytes = fmt_frame_bytes(width, height, format);
+    return MM_OK;
+}
+
+int mm_nv12_chroma_matrix(double m[4])
+{
+    if (!m) return MM_ERR_INVALID;
+    nv12_chroma_matrix(m);
     return MM_OK;
 }
 
@@ -428,7 +436,7 @@ int mm_process_stream(mm_handle *h, const void *in, void *out, int count, int fo
                       void *hip_stream)
 {
     if (!h || !in || !out || count < 0) return MM_ERR_INVALID;
-    if (!fmt_valid(format)) return MM_ERR_INVALID;
+    if (int rc = fmt_check(h->W, h->H, format, &h->p)) return rc;
     if (count == 0) return MM_OK;
     hipStream_t s = (hipStream_t)hip_stream;   // NULL: the default stream (HIP convention)
     DEVICE_SCOPE(h);
@@ -444,10 +452,10 @@ int mm_process_stream(mm_handle *h, const void *in, void *out, int count, int fo
 int mm_process(mm_handle *h, const void *in, void *out, int format, int flags, void *hip_stream)
 {
     if (!h || !in || !out) return MM_ERR_INVALID;
-    if (!fmt_valid(format)) return MM_ERR_INVALID;
+    if (int rc = fmt_check(h->W, h->H, format, &h->p)) return rc;
     if (flags & MM_FRAMES_ON_DEVICE) return mm_process_stream(h, in, out, 1, format, hip_stream);
     // host frames: stage through device buffers and synchronise
-    const size_t fb = (size_t)h->W * h->H * fmt_bpp(format);
+    const size_t fb = fmt_frame_bytes(h->W, h->H, format);
     DEVICE_SCOPE(h);
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     int ro = order_after_last(h, s);
@@ -537,7 +545,7 @@ int mm_compute_state(mm_handle *h, const void *in_dev, int format, void *dev_buf
 {
     size_t need = 0;
     if (!h || !in_dev || !dev_buf || mm_state_size(h, &need) || bytes < need) return MM_ERR_INVALID;
-    if (!fmt_valid(format)) return MM_ERR_INVALID;
+    if (int rc = fmt_check(h->W, h->H, format, nullptr)) return rc;   // (computes no view)
     hipStream_t s = (hipStream_t)hip_stream;   // NULL: the default stream (HIP convention)
     DEVICE_SCOPE(h);
     // the IIR state is a history of frames, not a function of one input frame

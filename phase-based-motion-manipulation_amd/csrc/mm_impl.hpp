@@ -212,18 +212,91 @@ static inline size_t fmt_bpp(int fmt)
 {
     return fmt == MM_RGBA32F ? 16 : fmt == MM_RGBA16F ? 8 : 4;
 }
+static inline bool fmt_nv12(int fmt) { return fmt == MM_NV12 || fmt == MM_NV12_FULL; }
 static inline bool fmt_valid(int fmt)
 {
-    return fmt == MM_RGBA8 || fmt == MM_RGBA32F || fmt == MM_RGBA16F || fmt == MM_RGBA8_SRGB;
+    return fmt == MM_RGBA8 || fmt == MM_RGBA32F || fmt == MM_RGBA16F || fmt == MM_RGBA8_SRGB ||
+           fmt_nv12(fmt);
 }
-// Runs the statement with the compile-time format FMT_ of the runtime `fmt`.
+// Bytes of one W x H frame (the planar 4:2:0 formats: W H luma bytes and half
+// as many chroma bytes; W and H even, fmt_check).
+static inline size_t fmt_frame_bytes(int W, int H, int fmt)
+{
+    const size_t px = (size_t)W * (size_t)H;
+    return fmt_nv12(fmt) ? px + px / 2 : px * fmt_bpp(fmt);
+}
+// What every frame entry point asks of (format, geometry, parameters) before
+// it queues anything.  NV12 is 4:2:0: even sizes only; the debug views are
+// R-channel pictures, which it cannot hold.
+static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
+{
+    if (!fmt_valid(fmt)) return MM_ERR_INVALID;
+    if (fmt_nv12(fmt) && ((W | H) & 1)) return MM_ERR_UNSUPPORTED;
+    if (fmt_nv12(fmt) && p && (p->show_magnitude || p->show_phase)) return MM_ERR_UNSUPPORTED;
+    return MM_OK;
+}
+static_assert(kFmtNV12 == MM_NV12, "the kernels' NV12 template argument is the format code");
+// Runs the statement with the compile-time format FMT_ of the runtime `fmt`
+// (both NV12 ranges run the MM_NV12 instances; geo_of sets their uniforms).
 #define MM_FMT_SWITCH(fmt, ...)                                                \
     switch (fmt) {                                                             \
     case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
     case MM_RGBA32F: { constexpr int FMT_ = MM_RGBA32F; __VA_ARGS__; } break;  \
     case MM_RGBA16F: { constexpr int FMT_ = MM_RGBA16F; __VA_ARGS__; } break;  \
+    case MM_NV12: case MM_NV12_FULL: { constexpr int FMT_ = MM_NV12; __VA_ARGS__; } break; \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
+// ... and the kernels that have no NV12 instance (odd sizes and the debug
+// views, refused by fmt_check before any launch)
+#define MM_FMT_SWITCH_RGBA(fmt, ...)                                           \
+    switch (fmt) {                                                             \
+    case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
+    case MM_RGBA32F: { constexpr int FMT_ = MM_RGBA32F; __VA_ARGS__; } break;  \
+    case MM_RGBA16F: { constexpr int FMT_ = MM_RGBA16F; __VA_ARGS__; } break;  \
+    case MM_RGBA8_SRGB: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break; \
+    default: return MM_ERR_UNSUPPORTED;                                        \
+    }
+
+// (Cb, Cr) -> (I, Q): RGBToYIQ's I and Q rows (RGBToYIQ.shader:46-50) times the
+// BT.601 conversion R = y + 1.402 cr, G = y - 0.344136 cb - 0.714136 cr,
+// B = y + 1.772 cb, in double: m = {I_cb, Q_cb, I_cr, Q_cr}.  (The y column
+// of the product is the rows' sums, 0 for I and Q.)
+static inline void nv12_chroma_matrix(double m[4])
+{
+    const double yiq[2][3] = {{0.596, -0.274, -0.322}, {0.211, -0.523, 0.312}};
+    const double rgb_cb[3] = {0.0, -0.344136, 1.772}, rgb_cr[3] = {1.402, -0.714136, 0.0};
+    for (int q = 0; q < 2; ++q) {
+        m[q] = m[2 + q] = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            m[q] += yiq[q][c] * rgb_cb[c];
+            m[2 + q] += yiq[q][c] * rgb_cr[c];
+        }
+    }
+}
+// The launch geometry for frames of `fmt`: the handle's, plus the NV12 range's
+// scales and offsets (limited: Y 16 .. 235, C 16 .. 240; full: 0 .. 255).
+static inline Geo geo_of(const mm_handle *h, int fmt)
+{
+    Geo g = h->geo;
+    if (fmt_nv12(fmt)) {
+        const bool full = fmt == MM_NV12_FULL;
+        const double ys = full ? 255.0 : 219.0, cs = full ? 255.0 : 224.0, y0 = full ? 0.0 : 16.0;
+        double m[4];
+        nv12_chroma_matrix(m);
+        g.nv.y_off = (float)y0;
+        g.nv.y_unit = (float)(1.0 / ys);
+        g.nv.icb = (float)(m[0] / cs);
+        g.nv.qcb = (float)(m[1] / cs);
+        g.nv.icr = (float)(m[2] / cs);
+        g.nv.qcr = (float)(m[3] / cs);
+        g.nv.yo_scale = (float)ys;
+        g.nv.yo_bias = (float)(y0 + 0.5);
+        // C' = (B - Yl) 0.5 / 0.886, (R - Yl) 0.5 / 0.701; the mean of four; the code scale
+        g.nv.cbo = (float)(0.25 * cs * 0.5 / 0.886);
+        g.nv.cro = (float)(0.25 * cs * 0.5 / 0.701);
+    }
+    return g;
+}
 
 // ------------------------------------------------------------------------
 // host tables
@@ -436,7 +509,7 @@ static int set_attrs(int W)
     (void)W;   // every other kernel stays within the default 64 KiB dynamic LDS
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 2 * lds_complex<4096>());
-        for (int f = 0; f < 4; ++f)
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         // k_sb_cols: exchange buffers (73.7 KB) + its own staging (run_steer)
@@ -480,7 +553,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 11) {   // k_rows_inv_compose4: four 2048-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 4 * lds_complex<2048>());
-        for (int f = 0; f < 4; ++f)
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         // k_sb_cols with four columns per workgroup (MM_SB_MIN_GROUPS = 4):
@@ -499,7 +572,7 @@ static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, int fmt, hipS
     const int total = ppf * nframes;
     // fewer than 2 workgroups per CU at the batch form: the one-pair form
     const bool lat = (total + k1_groups<LOG2N>() - 1) / k1_groups<LOG2N>() < 512;
-    const size_t fb = (size_t)h->W * h->H * fmt_bpp(fmt);
+    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     ProfScope ps(h, s, MM_K_ROWS_FWD, nframes);
 #define MM_K1_LAUNCH(F, GEN, LAT)                                                                  \
     do {                                                                                           \
@@ -509,13 +582,17 @@ static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, int fmt, hipS
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_fwd<LOG2N, F, GEN, LAT>), \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
         hipLaunchKernelGGL((k_rows_fwd<LOG2N, F, GEN, LAT>), dim3((total + gpw - 1) / gpw),         \
-                           dim3(gpw * fft_T<LOG2N>()), lds, s, in, fb, ppf, total, h->geo,         \
+                           dim3(gpw * fft_T<LOG2N>()), lds, s, in, fb, ppf, total, g,              \
                            h->d_col3, h->d_row3, h->d_col, h->d_row, h->d_tw, G, h->g_stride);     \
     } while (0)
     const bool gen = h->geo.ox || h->geo.oy;   // odd W/H: taps span i-2 .. i+1
-    MM_FMT_SWITCH(fmt, if (gen) MM_K1_LAUNCH(FMT_, true, false);
-                       else if (lat) MM_K1_LAUNCH(FMT_, false, true);
-                       else MM_K1_LAUNCH(FMT_, false, false))
+    const Geo g = geo_of(h, fmt);
+    if (gen) {   // (no NV12 instance: odd sizes are not 4:2:0)
+        MM_FMT_SWITCH_RGBA(fmt, MM_K1_LAUNCH(FMT_, true, false))
+    } else {
+        MM_FMT_SWITCH(fmt, if (lat) MM_K1_LAUNCH(FMT_, false, true);
+                           else MM_K1_LAUNCH(FMT_, false, false))
+    }
 #undef MM_K1_LAUNCH
     HIPCHK(hipGetLastError());
     return MM_OK;
@@ -671,7 +748,7 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
 {
     const int nout = nframes - frame0;
     if (nout <= 0) return MM_OK;
-    const size_t fb = (size_t)h->W * h->H * fmt_bpp(fmt);
+    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     const int R = k34_strip_rows(h, nout);
     // Short launches (the one-frame call) at N <= 1024 whose strips fit one
     // workgroup round (4 waves per SIMD at <= 128 VGPRs: 1024 / 4T workgroups
@@ -691,7 +768,7 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
         const dim3 grid((unsigned)(strips * nout)), block(4 * fft_T<LOG2N>());
         ProfScope ps(h, s, MM_K_ROWS_INV_COMPOSE, nout);
         MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_rows_inv_compose4<LOG2N, FMT_>), grid, block, lds, s, h->d_Q,
-                                              h->q_stride, in, out, fb, frame0, strips, h->geo, h->blur,
+                                              h->q_stride, in, out, fb, frame0, strips, geo_of(h, fmt), h->blur,
                                               h->d_col3, h->d_row3, h->d_tw))
         HIPCHK(hipGetLastError());
         return MM_OK;
@@ -702,7 +779,7 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
         const dim3 grid((unsigned)(strips * nout)), block(2 * fft_T<LOG2N>());
         ProfScope ps(h, s, MM_K_ROWS_INV_COMPOSE, nout);
         MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_rows_inv_compose<LOG2N, FMT_>), grid, block, lds, s, h->d_Q,
-                                              h->q_stride, in, out, fb, frame0, strips, steps, h->geo,
+                                              h->q_stride, in, out, fb, frame0, strips, steps, geo_of(h, fmt),
                                               h->blur, h->d_col3, h->d_row3, h->d_tw))
         HIPCHK(hipGetLastError());
         return MM_OK;
@@ -730,12 +807,12 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
 {
     const int nout = nframes - frame0;
     if (nout <= 0) return MM_OK;
-    const size_t fb = (size_t)h->W * h->H * fmt_bpp(fmt);
+    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     if (h->geo.ox || h->geo.oy) {   // odd W/H: the crop samples between texels
         const size_t tot = (size_t)nout * h->W * h->H;
         ProfScope ps(h, s, MM_K_COMPOSE, nout);
         const dim3 grid((unsigned)((tot + 255) / 256));
-        MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_compose_odd<FMT_>), grid, dim3(256), 0, s, h->d_Yh,
+        MM_FMT_SWITCH_RGBA(fmt, hipLaunchKernelGGL((k_compose_odd<FMT_>), grid, dim3(256), 0, s, h->d_Yh,
                                               h->yh_stride, in, out, fb, frame0, nout, h->geo, h->blur,
                                               h->d_col, h->d_row))
         HIPCHK(hipGetLastError());
@@ -745,7 +822,7 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
     const dim3 grid(rt * ct * nout);
     ProfScope ps(h, s, MM_K_COMPOSE, nout);
     MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_compose<FMT_>), grid, dim3(kTileCols), 0, s, h->d_Yh,
-                                          h->yh_stride, in, out, fb, frame0, rt, ct, h->geo, h->blur,
+                                          h->yh_stride, in, out, fb, frame0, rt, ct, geo_of(h, fmt), h->blur,
                                           h->d_col3, h->d_row3))
     HIPCHK(hipGetLastError());
     return MM_OK;
@@ -908,7 +985,7 @@ static int run_steer(mm_handle *h, const uint8_t *in, uint8_t *out, int n, int f
         }
     }
     if (sst == h->d_sst) h->steer_valid = true;
-    const size_t fb = (size_t)h->W * h->H * fmt_bpp(fmt);
+    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     if (!write) {
         if (out) HIPCHK(hipMemcpyAsync(out, in, fb * n, hipMemcpyDeviceToDevice, s));
         return MM_OK;
@@ -948,10 +1025,10 @@ static int run_debug(mm_handle *h, uint8_t *out, int n, int first, int fmt, hipS
                        tex_stride, first, h->p.show_magnitude, h->p.show_phase, h->geo,
                        h->d_tw_half);
     HIPCHK(hipGetLastError());
-    const size_t fb = (size_t)h->W * h->H * fmt_bpp(fmt);
+    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     const size_t tot = (size_t)m * h->W * h->H;
     const dim3 grid((unsigned)((tot + 255) / 256));
-    MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_dbg_out<FMT_>), grid, dim3(256), 0, s, h->d_dbg, tex_stride,
+    MM_FMT_SWITCH_RGBA(fmt, hipLaunchKernelGGL((k_dbg_out<FMT_>), grid, dim3(256), 0, s, h->d_dbg, tex_stride,
                                           out, fb, first, m, h->p.show_magnitude, h->p.show_phase, h->geo))
     HIPCHK(hipGetLastError());
     return MM_OK;
@@ -962,7 +1039,7 @@ template <int LOG2N>
 static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, int fmt,
                      hipStream_t s)
 {
-    const size_t fb = (size_t)h->W * h->H * fmt_bpp(fmt);
+    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     const bool mag = h->p.apply_magnification != 0;
     const bool dbg = h->p.show_magnitude || h->p.show_phase;
     // the steerable path's state is its local-phase planes; every other path
@@ -1014,7 +1091,7 @@ template <int LOG2N>
 static int run_stream(mm_handle *h, const uint8_t *in, uint8_t *out, int count, int fmt,
                       hipStream_t s)
 {
-    const size_t fb = (size_t)h->W * h->H * fmt_bpp(fmt);
+    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     for (int f0 = 0; f0 < count; f0 += h->chunk) {
         const int n = std::min(h->chunk, count - f0);
         int rc = run_chunk<LOG2N>(h, in + fb * f0, out + fb * f0, n, fmt, s);

@@ -44,6 +44,15 @@ struct Geo {
     int Qs;           // Q bins per tile row (N/2 + 2; q_index)
     int TK;           // rows per Q tile (q_tile_v)
     int edge;         // 0 repeat, 1 clamp
+    // MM_NV12 / MM_NV12_FULL only (the two ranges share the kernel instances;
+    // filled per launch by geo_of, mm_impl.hpp; the other formats never read it)
+    struct Nv12 {
+        float y_off, y_unit;        // K1: luma = ((float)Yb - y_off) * y_unit
+        float icb, qcb, icr, qcr;   // compose: (I, Q) = (icb, qcb) (Cb - 128) + (icr, qcr) (Cr - 128),
+                                    // RGBToYIQ x BT.601 with the code scale folded in
+        float yo_scale, yo_bias;    // out: luma code = floor(Yl * yo_scale + yo_bias), bias = offset + 0.5
+        float cbo, cro;             // out: chroma code = floor(sum of four (B - Yl) * cbo + 128.5), Cr: R - Yl
+    } nv;
 };
 
 struct Spec {
@@ -438,6 +447,103 @@ template <int FMT> __device__ __forceinline__ void out_store(uint8_t *base, unsi
     else Pix<FMT>::store(base, i, r, g, b);
 }
 
+// ---- NV12 (planar 4:2:0) access ------------------------------------------
+// A frame is H rows of W luma bytes, then H/2 rows of W bytes of interleaved
+// (Cb, Cr) pairs, one pair per 2x2 pixels; W and H even.  It IS the RGBA32F
+// frame its BT.601 decode gives (include/mm.h), and the RGBToYIQ rows sum to
+// 1, 0, 0: the luma of the decoded pixel is its Y sample and (I, Q) a fixed
+// 2x2 matrix of (Cb, Cr).  So K1 reads the luma plane alone, the compose
+// kernels the half-resolution chroma plane alone, and neither goes through
+// Pix<FMT> (one interleaved pixel per raw_t).  MM_NV12 and MM_NV12_FULL share
+// the instances (FMT = kFmtNV12); their scales and offsets are Geo::nv.
+// Alignment: rows are W bytes and a frame W H 3/2, both only even, so the
+// luma plane is read bytewise and a (Cb, Cr) pair as one 2-byte load; dword
+// accesses only where W % 8 == 0 (the fused kernels' quads).
+constexpr int kFmtNV12 = 16;   // MM_NV12
+template <int FMT> constexpr bool kNV12 = FMT == kFmtNV12;
+// the raw sample K1 loads per pixel
+template <int FMT> struct LumaSrc {
+    using raw_t = typename Pix<FMT>::raw_t;
+    static constexpr int bpp = Pix<FMT>::bpp;
+};
+template <> struct LumaSrc<kFmtNV12> {
+    using raw_t = uint8_t;
+    static constexpr int bpp = 1;
+};
+// what the compose kernels load per source pixel
+template <int FMT> struct ChromaSrc { using raw_t = typename Pix<FMT>::raw_t; };
+template <> struct ChromaSrc<kFmtNV12> { using raw_t = uint16_t; };   // Cb | Cr << 8
+// K1's luma of a raw sample and its unit (folded into the resample weights)
+template <int FMT>
+__device__ __forceinline__ float k1_luma(typename LumaSrc<FMT>::raw_t u, const Geo &g)
+{
+    if constexpr (kNV12<FMT>) return (float)u - g.nv.y_off;
+    else return luma_units<FMT>(u);
+}
+template <int FMT> __device__ __forceinline__ float k1_unit(const Geo &g)
+{
+    if constexpr (kNV12<FMT>) return g.nv.y_unit;
+    else return kLumaUnit<FMT>;
+}
+// byte offset of the (Cb, Cr) pair of source pixel (row, col), both already
+// wrapped or clamped on PIXEL coordinates (then halved: the decoded frame's
+// REPEAT / CLAMP behaviour exactly)
+__device__ __forceinline__ unsigned nv12_c_off(const Geo &g, int row, unsigned col)
+{
+    return (unsigned)((g.H + (row >> 1)) * g.W) + (col & ~1u);
+}
+// (I, Q) of a (Cb, Cr) pair: exact zero for neutral chroma (128, 128)
+__device__ __forceinline__ c2 nv12_iq2(unsigned u, const Geo &g)
+{
+    const float cb = (float)(u & 255u) - 128.0f, cr = (float)((u >> 8) & 255u) - 128.0f;
+    return mk(g.nv.icb, g.nv.qcb) * cb + mk(g.nv.icr, g.nv.qcr) * cr;
+}
+// the compose kernels' (I, Q) of a staged raw sample
+template <int FMT>
+__device__ __forceinline__ c2 src_iq2(typename ChromaSrc<FMT>::raw_t u, const Geo &g)
+{
+    if constexpr (kNV12<FMT>) return nv12_iq2(u, g);
+    else return chroma_iq2<FMT>(u);
+}
+// Output of one pixel from yiq_rgb's saturated RGB: the luma code and the
+// unscaled chroma differences (B - Yl, R - Yl) of Y'CbCr.  A 2x2 block's
+// chroma code is the rounded scaled sum of its four differences, added as
+// (column's two rows) + (neighbour column's two rows) in every kernel, so the
+// fused and unfused outputs stay bitwise equal.
+__device__ __forceinline__ unsigned nv12_ycode(float r, float gg, float b, const Geo &g, c2 &c)
+{
+    const float yl = 0.299f * r + 0.587f * gg + 0.114f * b;
+    c = mk(b - yl, r - yl);
+    return (unsigned)(yl * g.nv.yo_scale + g.nv.yo_bias);   // in 0 .. 255: yl in [0, 1]
+}
+__device__ __forceinline__ unsigned nv12_ccode(float sum4, float k)
+{
+    return (unsigned)fminf(sum4 * k + 128.5f, 255.0f);      // >= 1: |C'| <= 1/2
+}
+// The fused kernels' store of output row i of the quad X .. X+3 (X % 4 == 0,
+// W % 8 == 0: dword aligned): four luma codes as one dword; the even row of a
+// row pair leaves its chroma differences in cd0, the odd row adds its own and
+// stores the two 2x2 blocks' (Cb, Cr) codes as one dword of chroma row i/2.
+__device__ __forceinline__ void nv12_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
+                                                const float (&rr)[4], const float (&gg)[4],
+                                                const float (&bb)[4], c2 (&cd0)[4])
+{
+    c2 cd[4];
+    unsigned y4 = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y4 |= nv12_ycode(rr[k], gg[k], bb[k], g, cd[k]) << (8 * k);
+    st_stream<uint32_t>(outp + (size_t)(unsigned)(i * g.W), (unsigned)X, y4);
+    if (!odd) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) cd0[k] = cd[k];
+    } else {
+        const c2 b0 = (cd0[0] + cd[0]) + (cd0[1] + cd[1]), b1 = (cd0[2] + cd[2]) + (cd0[3] + cd[3]);
+        const unsigned c4 = nv12_ccode(b0.x, g.nv.cbo) | nv12_ccode(b0.y, g.nv.cro) << 8 |
+                            nv12_ccode(b1.x, g.nv.cbo) << 16 | nv12_ccode(b1.y, g.nv.cro) << 24;
+        st_stream<uint32_t>(outp + (size_t)(unsigned)((g.H + (i >> 1)) * g.W), (unsigned)X, c4);
+    }
+}
+
 // =========================================================================
 // K1: luma rows -> half spectra of row pairs
 // =========================================================================
@@ -473,8 +579,9 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
     // (ra, ra+1) reads the 4 source rows ra-1..ra+2.
     float *V = reinterpret_cast<float *>(lds);   // GEN: [2][W] (rows a, b)
     c2 *V2 = lds;                                 // 3-tap path: [W] (row a, row b) pairs
-    using raw_t = typename Pix<FMT>::raw_t;
-    constexpr int BPP = Pix<FMT>::bpp;
+    using raw_t = typename LumaSrc<FMT>::raw_t;
+    constexpr int BPP = LumaSrc<FMT>::bpp;
+    const float lu = k1_unit<FMT>(g);   // a constant but for NV12 (its range's 1/219 or 1/255)
     // one-pair workgroups (LAT: short launches, latency-bound) issue the
     // column taps and twiddles with the pixel loads instead of one dependent
     // round trip each after them (batch launches: K1 +5 %, registers held
@@ -495,8 +602,8 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
             Tap4 tb = ra + 1 < g.H ? rowT[ra + 1] : ta;
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                ta.w[m] *= kLumaUnit<FMT>;
-                tb.w[m] = ra + 1 < g.H ? tb.w[m] * kLumaUnit<FMT> : 0.0f;   // the zero row of odd H
+                ta.w[m] *= lu;
+                tb.w[m] = ra + 1 < g.H ? tb.w[m] * lu : 0.0f;   // the zero row of odd H
             }
             unsigned pa[4], pb[4];   // source row byte offsets
 #pragma unroll
@@ -508,8 +615,8 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
                 float va = 0.0f, vb = 0.0f;
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    va += ta.w[m] * luma_units<FMT>(ld_off<raw_t>(img, pa[m] + (unsigned)i * BPP));
-                    vb += tb.w[m] * luma_units<FMT>(ld_off<raw_t>(img, pb[m] + (unsigned)i * BPP));
+                    va += ta.w[m] * k1_luma<FMT>(ld_off<raw_t>(img, pa[m] + (unsigned)i * BPP), g);
+                    vb += tb.w[m] * k1_luma<FMT>(ld_off<raw_t>(img, pb[m] + (unsigned)i * BPP), g);
                 }
                 V[i] = va;
                 V[g.W + i] = vb;
@@ -528,8 +635,8 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 float4 wa = rowW3[r0 + 2 * q], wb = rowW3[r0 + 2 * q + 1];
-                wa.x *= kLumaUnit<FMT>, wa.y *= kLumaUnit<FMT>, wa.z *= kLumaUnit<FMT>;
-                wb.x *= kLumaUnit<FMT>, wb.y *= kLumaUnit<FMT>, wb.z *= kLumaUnit<FMT>;
+                wa.x *= lu, wa.y *= lu, wa.z *= lu;
+                wb.x *= lu, wb.y *= lu, wb.z *= lu;
                 w[q][0] = mk(wa.x, wb.x);
                 w[q][1] = mk(wa.y, wb.y);
                 w[q][2] = mk(wa.z, wb.z);
@@ -555,7 +662,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
                     const int i = (int)threadIdx.x + (h * CB + u) * 2 * T;
                     float l[6];
 #pragma unroll
-                    for (int d = 0; d < 6; ++d) l[d] = luma_units<FMT>(px[u][d]);
+                    for (int d = 0; d < 6; ++d) l[d] = k1_luma<FMT>(px[u][d], g);
                     if (i < g.W) {
                         lds_all[i] = w[0][0] * mk(l[0], l[1]) + w[0][1] * mk(l[1], l[2]) + w[0][2] * mk(l[2], l[3]);
                         V2g1[i] = w[1][0] * mk(l[2], l[3]) + w[1][1] * mk(l[3], l[4]) + w[1][2] * mk(l[4], l[5]);
@@ -566,8 +673,8 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
     } else if (valid) {
         // odd H: the last pair's second row is outside the image (zero)
         float4 wa = rowW3[ra], wb = ra + 1 < g.H ? rowW3[ra + 1] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        wa.x *= kLumaUnit<FMT>, wa.y *= kLumaUnit<FMT>, wa.z *= kLumaUnit<FMT>;
-        wb.x *= kLumaUnit<FMT>, wb.y *= kLumaUnit<FMT>, wb.z *= kLumaUnit<FMT>;
+        wa.x *= lu, wa.y *= lu, wa.z *= lu;
+        wb.x *= lu, wb.y *= lu, wb.z *= lu;
         // rows a and b as one packed pair: (a, b) = (wa.x, wb.x) (l0, l1) +
         // (wa.y, wb.y) (l1, l2) + (wa.z, wb.z) (l2, l3), per lane the scalar
         // forms' fma chains (half the VALU instructions, one 8-B LDS store)
@@ -591,7 +698,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
                 const int i = t + (h * UB + u) * T;
                 float l[4];
 #pragma unroll
-                for (int d = 0; d < 4; ++d) l[d] = luma_units<FMT>(px[u][d]);
+                for (int d = 0; d < 4; ++d) l[d] = k1_luma<FMT>(px[u][d], g);
                 if (i < g.W) V2[i] = w0 * mk(l[0], l[1]) + w1 * mk(l[1], l[2]) + w2 * mk(l[2], l[3]);
             }
         }
@@ -2143,6 +2250,12 @@ void k_rows_inv(const c2 *__restrict__ Q, size_t q_stride, float *__restrict__ Y
 #define MM_K4_COLS 256
 #endif
 constexpr int kTileRows = MM_K4_ROWS, kTileCols = MM_K4_COLS;
+// MM_NV12_K4_PACK=1 (diagnostic): k_compose's NV12 luma codes gathered over the
+// four lanes of a quad and stored as one dword (W % 4 == 0), instead of one
+// byte store per lane.
+#ifndef MM_NV12_K4_PACK
+#define MM_NV12_K4_PACK 0
+#endif
 
 template <int FMT>
 __global__ __launch_bounds__(kTileCols)
@@ -2166,15 +2279,20 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     // or clamped like the resample's sampler.  Rows are workgroup-uniform (scalar
     // base pointers); thread tid stages column j = tid of every row, and threads
     // 0, 1 also the halo columns j = TC, TC+1.
-    using raw_t = typename Pix<FMT>::raw_t;
+    using raw_t = typename ChromaSrc<FMT>::raw_t;
     // 32-bit offsets from workgroup-uniform row pointers: scalar base + vector
     // offset addressing, no 64-bit address math per access
+    // (NV12: the pixel's (Cb, Cr) pair, shared with its 2x2 neighbours)
+    auto src_off = [&](int row, unsigned col) {
+        if constexpr (kNV12<FMT>) return nv12_c_off(g, row, col);
+        else return (unsigned)(row * g.W + col) * Pix<FMT>::bpp;
+    };
     const unsigned colA = (unsigned)wrap_near(min(c0 - 1 + tid, g.W), g.W, g.edge);
     raw_t pa[TR + 2];
 #pragma unroll
     for (int sr = 0; sr < TR + 2; ++sr) {   // all staging loads in flight, then convert
         const int row = wrap_near(min(i0 - 1 + sr, g.H), g.H, g.edge);
-        pa[sr] = ld_off<raw_t>(img, (unsigned)(row * g.W + colA) * Pix<FMT>::bpp);
+        pa[sr] = ld_off<raw_t>(img, src_off(row, colA));
     }
     const int X = c0 + tid;
     const bool vx = X < g.W;
@@ -2198,10 +2316,10 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     const int hs = min(tid, NH - 1);
     const int hrow = wrap_near(min(i0 - 1 + (hs >> 1), g.H), g.H, g.edge);
     const int hcol = wrap_near(min(c0 - 1 + TC + (hs & 1), g.W), g.W, g.edge);
-    const raw_t ph = ld_off<raw_t>(img, (unsigned)(hrow * g.W + hcol) * Pix<FMT>::bpp);
-    if (tid < NH) iq[(hs >> 1) * WC + TC + (hs & 1)] = chroma_iq2<FMT>(ph);
+    const raw_t ph = ld_off<raw_t>(img, src_off(hrow, (unsigned)hcol));
+    if (tid < NH) iq[(hs >> 1) * WC + TC + (hs & 1)] = src_iq2<FMT>(ph, g);
 #pragma unroll
-    for (int sr = 0; sr < TR + 2; ++sr) iq[sr * WC + tid] = chroma_iq2<FMT>(pa[sr]);
+    for (int sr = 0; sr < TR + 2; ++sr) iq[sr * WC + tid] = src_iq2<FMT>(pa[sr], g);
     __syncthreads();
     if (!vx) return;
     c2 hc[TR + 2];   // horizontally combined (I, Q) of each staged row
@@ -2212,6 +2330,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     }
     uint8_t *outp = frames_out + (size_t)frame * frame_bytes;
     const Blur5 bv = vblur_w<FMT>(bw);
+    [[maybe_unused]] c2 cd0;   // NV12: the even row's chroma differences
 #pragma unroll
     for (int r = 0; r < TR; ++r) {
         const int i = i0 + r;
@@ -2222,7 +2341,45 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                              bv.w2 * (yv[r] + yv[r + 4]);
             float rr, gg, bb;
             yiq_rgb<FMT>(yb, cc, rr, gg, bb);
-            out_store<FMT>(outp + (unsigned)(i * g.W * Pix<FMT>::bpp), (unsigned)X, rr, gg, bb);
+            if constexpr (kNV12<FMT>) {
+                // One luma byte per pixel.  The 2x2 chroma mean: this column's
+                // two rows (i0 and TR even: r even starts a block; H even: both
+                // rows are inside), plus the neighbour column's from the lane
+                // pair (X ^ 1 is tid ^ 1: c0 is even, and W even keeps both
+                // lanes past the vx test), exchanged with a quad-perm DPP move.
+                // The even lane stores the block's Cb, the odd lane its Cr:
+                // byte X of the chroma row.
+                static_assert(TR % 2 == 0 && TC % 2 == 0, "NV12: tiles of whole 2x2 blocks");
+                c2 cd;
+                const unsigned yc = nv12_ycode(rr, gg, bb, g, cd);
+                if (MM_NV12_K4_PACK && g.W % 4 == 0 && frame_bytes % 4 == 0) {
+                    // diagnostic: the four lanes of a quad gather their codes
+                    // (quad-perm broadcasts) and lane 0 stores one dword
+                    auto bc = [&](int ctrl) {
+                        return (unsigned)(ctrl == 0x00   ? __builtin_amdgcn_mov_dpp((int)yc, 0x00, 0xF, 0xF, true)
+                                          : ctrl == 0x55 ? __builtin_amdgcn_mov_dpp((int)yc, 0x55, 0xF, 0xF, true)
+                                          : ctrl == 0xAA ? __builtin_amdgcn_mov_dpp((int)yc, 0xAA, 0xF, 0xF, true)
+                                                         : __builtin_amdgcn_mov_dpp((int)yc, 0xFF, 0xF, 0xF, true));
+                    };
+                    const unsigned y4 = bc(0x00) | bc(0x55) << 8 | bc(0xAA) << 16 | bc(0xFF) << 24;
+                    if ((X & 3) == 0) st_off<uint32_t>(outp, (unsigned)(i * g.W + X), y4);
+                } else {
+                    st_off<uint8_t>(outp, (unsigned)(i * g.W + X), (uint8_t)yc);
+                }
+                if (r % 2 == 0) {
+                    cd0 = cd;
+                } else {
+                    const c2 v = cd0 + cd;
+                    // each lane keeps the component it stores and sends the other one
+                    const float mine = X & 1 ? v.y : v.x, send = X & 1 ? v.x : v.y;
+                    const float theirs = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
+                        __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
+                    const unsigned cc8 = nv12_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
+                    st_off<uint8_t>(outp, (unsigned)((g.H + (i >> 1)) * g.W + X), (uint8_t)cc8);
+                }
+            } else {
+                out_store<FMT>(outp + (unsigned)(i * g.W * Pix<FMT>::bpp), (unsigned)X, rr, gg, bb);
+            }
         }
     }
 }
@@ -2263,8 +2420,8 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         const c2 *__restrict__ tw)
 {
     constexpr int N = 1 << LOG2N, T = fft_T<LOG2N>(), TK = q_tile<LOG2N>();
-    using raw_t = typename Pix<FMT>::raw_t;
-    constexpr unsigned bpp = Pix<FMT>::bpp;
+    using raw_t = typename ChromaSrc<FMT>::raw_t;
+    constexpr unsigned bpp = LumaSrc<FMT>::bpp;   // (NV12: 1, the luma plane's)
     extern __shared__ __attribute__((aligned(16))) c2 lds_all[];
     const int grp = T % 64 == 0 ? __builtin_amdgcn_readfirstlane(threadIdx.x / T) : threadIdx.x / T;
     const int t = threadIdx.x % T;
@@ -2288,20 +2445,34 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     const Blur5 bv = vblur_w<FMT>(bw);   // the compose's vertical blur
     auto chroma_row = [&](int i, c2 (&hc)[4]) {
         const int row = wrap_near(min(i, g.H), g.H, g.edge);
-        const unsigned base = (unsigned)(row * g.W);
-        raw_t p[6];
-        p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
-        if constexpr (bpp == 4) {
-            const uint4 m = ld_off<uint4>(img, (base + (unsigned)X) * bpp);
-            p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) p[1 + k] = ld_off<raw_t>(img, (base + (unsigned)X + k) * bpp);
-        }
-        p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
         c2 a[6];
+        if constexpr (kNV12<FMT>) {
+            // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
+            // outer two wrapped or clamped as pixels, then halved): the quad's
+            // own two pairs as one dword (W % 8 == 0, X % 4 == 0: aligned in
+            // every frame of a stream), the outer two as 2-byte loads
+            const unsigned pl = ld_off<uint16_t>(img, nv12_c_off(g, row, cl));
+            const unsigned pm = ld_off<uint32_t>(img, nv12_c_off(g, row, (unsigned)X));
+            const unsigned pr = ld_off<uint16_t>(img, nv12_c_off(g, row, cr));
+            a[0] = nv12_iq2(pl, g);
+            a[1] = a[2] = nv12_iq2(pm, g);
+            a[3] = a[4] = nv12_iq2(pm >> 16, g);
+            a[5] = nv12_iq2(pr, g);
+        } else {
+            const unsigned base = (unsigned)(row * g.W);
+            raw_t p[6];
+            p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
+            if constexpr (bpp == 4) {
+                const uint4 m = ld_off<uint4>(img, (base + (unsigned)X) * bpp);
+                p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
+            } else {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
+                for (int k = 0; k < 4; ++k) p[1 + k] = ld_off<raw_t>(img, (base + (unsigned)X + k) * bpp);
+            }
+            p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float4 wc = colW3[X + k];
@@ -2403,9 +2574,25 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
         if (MM_K34_QPF && s + 1 < steps) load_q(s + 1);
         if (s > 0) {
             // ---- K4 on output rows i0+4s-4 .. i0+4s-1, two at a time ----
-#pragma unroll
 #ifndef MM_K34_ROWS2   // the 4 chroma rows' loads first (one memory round trip)
-            for (int r = 0; r < 4; ++r) chroma_row(i0 + 4 * s - 3 + r, hc[2 + r]);
+            if constexpr (kNV12<FMT>) {
+                // source rows 2j and 2j+1 share a chroma row (i0 % 4 == 0, H
+                // even): row i0+4s-3 has the kept row i0+4s-4's samples, row
+                // i0+4s-1 those of i0+4s-2; two loads per step, not four
+#pragma unroll
+                for (int k = 0; k < 4; ++k) hc[2][k] = hc[1][k];
+                chroma_row(i0 + 4 * s - 2, hc[3]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) hc[4][k] = hc[3][k];
+                chroma_row(i0 + 4 * s, hc[5]);
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) chroma_row(i0 + 4 * s - 3 + r, hc[2 + r]);
+            }
+#endif
+            [[maybe_unused]] c2 cd0[4];   // NV12: the even row's chroma differences
+#ifdef MM_K34_ROWS2
+#pragma unroll
 #endif
             for (int r = 0; r < 4; ++r) {
 #ifdef MM_K34_ROWS2   // diagnostic: two rows at a time (120 VGPRs; same-call K34 +8 %, r04d)
@@ -2426,8 +2613,10 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                                          bv.w2 * (yw[r][k] + yw[r + 4][k]);
                         yiq_rgb<FMT>(yb, cc, rr[k], gg[k], bb[k]);
                     }
-                    const unsigned o = (unsigned)(i * g.W + X);
-                    if constexpr (bpp == 4) {
+                    [[maybe_unused]] const unsigned o = (unsigned)(i * g.W + X);
+                    if constexpr (kNV12<FMT>) {
+                        nv12_store_quad(outp, g, i, X, r & 1, rr, gg, bb, cd0);
+                    } else if constexpr (bpp == 4) {
                         uint4 px;
                         px.x = out_pack<FMT>(rr[0], gg[0], bb[0]);
                         px.y = out_pack<FMT>(rr[1], gg[1], bb[1]);
@@ -2484,8 +2673,8 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                          const c2 *__restrict__ tw)
 {
     constexpr int N = 1 << LOG2N, T = fft_T<LOG2N>(), TK = q_tile<LOG2N>();
-    using raw_t = typename Pix<FMT>::raw_t;
-    constexpr unsigned bpp = Pix<FMT>::bpp;
+    using raw_t = typename ChromaSrc<FMT>::raw_t;
+    constexpr unsigned bpp = LumaSrc<FMT>::bpp;   // (NV12: 1, the luma plane's)
     extern __shared__ __attribute__((aligned(16))) c2 lds_all[];
     const int grp = T % 64 == 0 ? __builtin_amdgcn_readfirstlane(threadIdx.x / T) : threadIdx.x / T;
     const int t = threadIdx.x % T;
@@ -2542,20 +2731,34 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     const Blur5 bv = vblur_w<FMT>(bw);   // the compose's vertical blur
     auto chroma_row = [&](int i, c2 (&hc)[4]) {   // k_rows_inv_compose's
         const int row = wrap_near(min(i, g.H), g.H, g.edge);
-        const unsigned base = (unsigned)(row * g.W);
-        raw_t p[6];
-        p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
-        if constexpr (bpp == 4) {
-            const uint4 m = ld_off<uint4>(img, (base + (unsigned)X) * bpp);
-            p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) p[1 + k] = ld_off<raw_t>(img, (base + (unsigned)X + k) * bpp);
-        }
-        p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
         c2 a[6];
+        if constexpr (kNV12<FMT>) {
+            // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
+            // outer two wrapped or clamped as pixels, then halved): the quad's
+            // own two pairs as one dword (W % 8 == 0, X % 4 == 0: aligned in
+            // every frame of a stream), the outer two as 2-byte loads
+            const unsigned pl = ld_off<uint16_t>(img, nv12_c_off(g, row, cl));
+            const unsigned pm = ld_off<uint32_t>(img, nv12_c_off(g, row, (unsigned)X));
+            const unsigned pr = ld_off<uint16_t>(img, nv12_c_off(g, row, cr));
+            a[0] = nv12_iq2(pl, g);
+            a[1] = a[2] = nv12_iq2(pm, g);
+            a[3] = a[4] = nv12_iq2(pm >> 16, g);
+            a[5] = nv12_iq2(pr, g);
+        } else {
+            const unsigned base = (unsigned)(row * g.W);
+            raw_t p[6];
+            p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
+            if constexpr (bpp == 4) {
+                const uint4 m = ld_off<uint4>(img, (base + (unsigned)X) * bpp);
+                p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
+            } else {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
+                for (int k = 0; k < 4; ++k) p[1 + k] = ld_off<raw_t>(img, (base + (unsigned)X + k) * bpp);
+            }
+            p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float4 wc = colW3[X + k];
@@ -2564,8 +2767,16 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     };
     const int r0 = i0 + 2 * hh;   // first output row of this half
     c2 hc[4][4];                  // combined (I, Q) of source rows r0-1 .. r0+2
+    if constexpr (kNV12<FMT>) {   // rows r0, r0+1 (r0 even) share a chroma row
+        chroma_row(r0 - 1, hc[0]);
+        chroma_row(r0, hc[1]);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) chroma_row(r0 - 1 + k, hc[k]);
+        for (int k = 0; k < 4; ++k) hc[2][k] = hc[1][k];
+        chroma_row(r0 + 2, hc[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) chroma_row(r0 - 1 + k, hc[k]);
+    }
     float yw[6][4];               // list rows r0 .. r0+5 of the quad, blurred horizontally
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
@@ -2578,6 +2789,7 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
         yw[k][2] = bw.w0 * Z.x + bw.w1 * (P.w + Z.y) + bw.w2 * (P.z + Z.z);
         yw[k][3] = bw.w0 * Z.y + bw.w1 * (Z.x + Z.z) + bw.w2 * (P.w + Z.w);
     }
+    [[maybe_unused]] c2 cd0[4];   // NV12: the even row's chroma differences
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int i = r0 + r;
@@ -2591,8 +2803,10 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                                  bv.w2 * (yw[r][k] + yw[r + 4][k]);
                 yiq_rgb<FMT>(yb, cc, rr[k], gg[k], bb[k]);
             }
-            const unsigned o = (unsigned)(i * g.W + X);
-            if constexpr (bpp == 4) {
+            [[maybe_unused]] const unsigned o = (unsigned)(i * g.W + X);
+            if constexpr (kNV12<FMT>) {
+                nv12_store_quad(outp, g, i, X, r & 1, rr, gg, bb, cd0);
+            } else if constexpr (bpp == 4) {
                 uint4 px;
                 px.x = out_pack<FMT>(rr[0], gg[0], bb[0]);
                 px.y = out_pack<FMT>(rr[1], gg[1], bb[1]);

@@ -8,7 +8,7 @@
  *
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
- *          [--full-range] [--srgb] [--standard] [--show-magnitude] [--show-phase]
+ *          [--full-range] [--srgb] [--nv12] [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
  *          [--ring-local G [--compare]]
@@ -39,6 +39,11 @@
  * --srgb: the 8-bit frames are sRGB-encoded (video and display-referred
  * clips are), processed in linear light as Unity's Linear colour space does
  * (MM_RGBA8_SRGB: decoded on read, encoded on write); default UNORM.
+ * --nv12: a 4:2:0 .y4m input goes to the device as it is stored, as MM_NV12
+ * frames (MM_NV12_FULL with --full-range): the chroma planes are interleaved
+ * on the way in and split on the way out (a C420 .y4m; any other extension:
+ * the raw NV12 frames), and no colour arithmetic runs on the host.  Not with
+ * --srgb, the debug views, the ring modes, 4:4:4 / mono input or odd sizes.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -385,12 +390,14 @@ int main(int argc, char **argv)
     int W = 1920, H = 1080, F = 300, L = 5, B = 30, dev = 0;
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
+    int nv12 = 0, srgb = 0;
     float S = 25.0f;
     const char *in_path = NULL, *out_path = NULL, *ring_id_path = NULL;
     for (int i = 1; i < argc; ++i) {
         const char *a = argv[i];
         if (!strcmp(a, "--full-range")) { full_range = 1; continue; }
-        if (!strcmp(a, "--srgb")) { g_fmt = MM_RGBA8_SRGB; continue; }
+        if (!strcmp(a, "--srgb")) { g_fmt = MM_RGBA8_SRGB; srgb = 1; continue; }
+        if (!strcmp(a, "--nv12")) { nv12 = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
         if (!strcmp(a, "--show-magnitude")) { show_mag = 1; continue; }
         if (!strcmp(a, "--show-phase")) { show_phase = 1; continue; }
@@ -431,6 +438,21 @@ int main(int argc, char **argv)
         W = yi.width;
         H = yi.height;
     }
+    if (nv12) {
+        if (srgb || show_mag || show_phase || ring_local > 0 || ring_world > 0) {
+            fprintf(stderr, "--nv12 does not go with --srgb, the debug views or the ring modes\n");
+            return 2;
+        }
+        if (!y4m_in || yi.chroma != Y4M_420) {
+            fprintf(stderr, "--nv12 needs a 4:2:0 .y4m input (-i)\n");
+            return 2;
+        }
+        if ((W | H) & 1) {
+            fprintf(stderr, "--nv12 needs even width and height (%dx%d)\n", W, H);
+            return 2;
+        }
+        g_fmt = full_range ? MM_NV12_FULL : MM_NV12;
+    }
     mm_params p;
     mm_params_default(&p);
     p.levels = L;
@@ -470,7 +492,8 @@ int main(int argc, char **argv)
         return rc;
     }
 
-    const size_t fb = (size_t)W * H * 4;
+    size_t fb = (size_t)W * H * 4;
+    if (nv12) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
     void *d_in = NULL, *d_out = NULL;
     if (hipMalloc(&d_in, fb * B) != hipSuccess || hipMalloc(&d_out, fb * B) != hipSuccess) {
         fprintf(stderr, "hipMalloc failed\n");
@@ -483,7 +506,8 @@ int main(int argc, char **argv)
                                                ? y4m_frame_bytes(&yi) : 3 * (size_t)W * H)
                                          : 3 * (size_t)W * H)
         : NULL;
-    if (y4m_out && y4m_write_header(fo, W, H, yi.fps_num, yi.fps_den)) {
+    if (y4m_out && (nv12 ? y4m_write_header_420(fo, W, H, yi.fps_num, yi.fps_den)
+                         : y4m_write_header(fo, W, H, yi.fps_num, yi.fps_den))) {
         fprintf(stderr, "write failed\n");
         return 1;
     }
@@ -501,7 +525,8 @@ int main(int argc, char **argv)
                 const int r = y4m_read_frame(fi, &yi, planes);
                 if (r < 0) { fprintf(stderr, "%s: malformed frame\n", in_path); return 1; }
                 if (r == 0) break;
-                y4m_to_rgba(&yi, planes, host + fb * got, full_range);
+                if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
+                else y4m_to_rgba(&yi, planes, host + fb * got, full_range);
             }
             if (got == 0) break;
             n = got;
@@ -526,8 +551,12 @@ int main(int argc, char **argv)
             hipMemcpy(host, d_out, fb * n, hipMemcpyDeviceToHost);
             if (y4m_out) {
                 for (int k = 0; k < n; ++k) {
-                    y4m_from_rgba(W, H, host + fb * k, planes, full_range);
-                    if (y4m_write_frame(fo, W, H, planes)) { fprintf(stderr, "write failed\n"); return 1; }
+                    if (nv12) y4m_nv12_to_420(W, H, host + fb * k, planes);
+                    else y4m_from_rgba(W, H, host + fb * k, planes, full_range);
+                    if (nv12 ? y4m_write_frame_420(fo, W, H, planes) : y4m_write_frame(fo, W, H, planes)) {
+                        fprintf(stderr, "write failed\n");
+                        return 1;
+                    }
                 }
             } else {
                 fwrite(host, fb, (size_t)n, fo);

@@ -131,3 +131,37 @@ int y4m_write_frame(FILE *f, int W, int H, const uint8_t *planes444)
     const size_t nb = (size_t)3 * W * H;
     return fwrite(planes444, 1, nb, f) == nb ? 0 : -1;
 }
+
+void y4m_420_to_nv12(int W, int H, const uint8_t *planes420, uint8_t *nv12)
+{
+    const size_t ny = (size_t)W * H, nc = ny / 4;
+    const uint8_t *Cb = planes420 + ny, *Cr = Cb + nc;
+    memcpy(nv12, planes420, ny);
+    for (size_t i = 0; i < nc; ++i) {
+        nv12[ny + 2 * i] = Cb[i];
+        nv12[ny + 2 * i + 1] = Cr[i];
+    }
+}
+
+void y4m_nv12_to_420(int W, int H, const uint8_t *nv12, uint8_t *planes420)
+{
+    const size_t ny = (size_t)W * H, nc = ny / 4;
+    uint8_t *Cb = planes420 + ny, *Cr = Cb + nc;
+    memcpy(planes420, nv12, ny);
+    for (size_t i = 0; i < nc; ++i) {
+        Cb[i] = nv12[ny + 2 * i];
+        Cr[i] = nv12[ny + 2 * i + 1];
+    }
+}
+
+int y4m_write_header_420(FILE *f, int W, int H, int fps_num, int fps_den)
+{
+    return fprintf(f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420\n", W, H, fps_num, fps_den) > 0 ? 0 : -1;
+}
+
+int y4m_write_frame_420(FILE *f, int W, int H, const uint8_t *planes420)
+{
+    if (fputs("FRAME\n", f) < 0) return -1;
+    const size_t nb = (size_t)W * H * 3 / 2;
+    return fwrite(planes420, 1, nb, f) == nb ? 0 : -1;
+}

@@ -3,10 +3,11 @@
  * host driver (real clips instead of synthetic streams).
  *
  * Reads 8-bit 4:2:0 (C420, C420jpeg, C420paldv, C420mpeg2), 4:4:4 (C444) and
- * mono (Cmono) streams; writes 4:4:4.  Chroma is upsampled by sample
+ * mono (Cmono) streams; writes 4:4:4, or 4:2:0 for the NV12 path.  Chroma is upsampled by sample
  * replication (each 4:2:0 sample covers its 2x2 block).  Colour matrix BT.601,
  * limited range (Y 16..235, C 16..240) unless `full_range` (JPEG-style 0..255).
- * Host-side only: the frames then go through mm_process_stream as RGBA8.
+ * Host-side only: the frames then go through mm_process_stream as RGBA8, or,
+ * 4:2:0 streams re-interleaved to NV12, as MM_NV12 without any conversion.
  */
 #ifndef MM355_Y4M_H
 #define MM355_Y4M_H
@@ -47,6 +48,18 @@ void y4m_from_rgba(int width, int height, const uint8_t *rgba, uint8_t *planes44
 /* Write a C444 header / one C444 frame. */
 int y4m_write_header(FILE *f, int width, int height, int fps_num, int fps_den);
 int y4m_write_frame(FILE *f, int width, int height, const uint8_t *planes444);
+
+/* 4:2:0 planes (Y, Cb, Cr; even width and height) <-> one NV12 frame (Y, then
+ * rows of interleaved Cb, Cr pairs; width * height * 3/2 bytes either way):
+ * the chroma planes are interleaved / de-interleaved, no arithmetic.  Frames
+ * in this layout go through mm_process_stream as MM_NV12 / MM_NV12_FULL with
+ * no colour conversion on the host. */
+void y4m_420_to_nv12(int width, int height, const uint8_t *planes420, uint8_t *nv12);
+void y4m_nv12_to_420(int width, int height, const uint8_t *nv12, uint8_t *planes420);
+
+/* Write a C420 header / one C420 frame (planes Y, Cb, Cr). */
+int y4m_write_header_420(FILE *f, int width, int height, int fps_num, int fps_den);
+int y4m_write_frame_420(FILE *f, int width, int height, const uint8_t *planes420);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,10 @@ RGBA32F = 1
 RGBA16F = 2         # linear half (the reference camera's HDR target), ABI 10
 RGBA8_SRGB = 3      # 8-bit sRGB target in Linear colour space, ABI 10
 FORMAT_BPP = {RGBA8: 4, RGBA32F: 16, RGBA16F: 8, RGBA8_SRGB: 4}
+# video frames, planar 8-bit Y'CbCr 4:2:0 (H rows of W luma bytes, then H/2 rows
+# of W interleaved Cb, Cr bytes; W and H even): frame_bytes() gives W*H*3/2
+NV12 = 16           # BT.601 limited ("video") range
+NV12_FULL = 17      # full ("JPEG") range
 EDGE_REPEAT = 0
 EDGE_CLAMP = 1
 MODE_PYRAMID = 0
@@ -103,6 +107,7 @@ def load_library(path=None):
         "mm_get_params": (ci, [vp, pp]),
         "mm_padded_size": (ci, [vp, ctypes.POINTER(ci)]),
         "mm_frame_bytes": (ci, [ci, ci, ci, ctypes.POINTER(sz)]),
+        "mm_nv12_chroma_matrix": (ci, [ctypes.POINTER(ctypes.c_double)]),
         "mm_process": (ci, [vp, vp, vp, ci, ci, vp]),
         "mm_process_stream": (ci, [vp, vp, vp, ci, ci, vp]),
         "mm_reset": (ci, [vp]),
@@ -132,6 +137,8 @@ def load_library(path=None):
             continue
         if abi < 10 and name == "mm_frame_bytes":
             continue
+        if name == "mm_nv12_chroma_matrix" and not hasattr(L, name):
+            continue    # an A/B build from before the NV12 formats (same ABI version)
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -175,6 +182,14 @@ def frame_bytes(width, height, fmt):
     n = ctypes.c_size_t()
     check(lib().mm_frame_bytes(width, height, fmt, ctypes.byref(n)), "mm_frame_bytes")
     return n.value
+
+
+def nv12_chroma_matrix():
+    """mm_nv12_chroma_matrix: the NV12 compose's (cb, cr) -> (I, Q) matrix,
+    [[I_cb, I_cr], [Q_cb, Q_cr]] (float64)."""
+    m = (ctypes.c_double * 4)()
+    check(lib().mm_nv12_chroma_matrix(m), "mm_nv12_chroma_matrix")
+    return np.array([[m[0], m[2]], [m[1], m[3]]])
 
 
 def resample_table(width, height, axis, edge_mode=EDGE_REPEAT):

@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""RGBA8 against NV12 frames on one GPU, same process, alternating legs.
+
+The flagship stream (1920x1080, 5 levels, phase scale 25, batches of 150
+frames as bench.py) in both frame formats.  Frames are generated on the device
+(mm_synth_frames) and converted to NV12 with torch ops once, outside the
+timing.  Every launch shape is warmed up; a leg is `calls` back-to-back
+mm_process_stream calls (>= --leg-seconds of device work) between two events
+on the handle's stream, synchronised at its end; the formats alternate
+--rounds times.  Reports each format's median frames/s and spread, and the
+per-kernel device time (mm_profile_begin/end) of one call of each.
+
+usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "phase-based-motion-manipulation_amd"))
+
+
+def to_nv12(torch, rgba):
+    """[n][H][W][4] uint8 (device) -> [n][H*3/2][W] NV12, BT.601 limited range,
+    chroma the mean of each 2 x 2 block (y4m_from_rgba's formulas)."""
+    n, H, W, _ = rgba.shape
+    out = torch.empty((n, H * 3 // 2, W), dtype=torch.uint8, device=rgba.device)
+    for k in range(n):       # frame by frame: float planes of one frame at a time
+        f = rgba[k, ..., :3].float() / 255.0
+        r, g, b = f[..., 0], f[..., 1], f[..., 2]
+        yl = 0.299 * r + 0.587 * g + 0.114 * b
+        cb = ((b - yl) * (0.5 / 0.886)).reshape(H // 2, 2, W // 2, 2).mean(dim=(1, 3))
+        cr = ((r - yl) * (0.5 / 0.701)).reshape(H // 2, 2, W // 2, 2).mean(dim=(1, 3))
+        code = lambda v: torch.clamp(torch.floor(v + 0.5), 0, 255).to(torch.uint8)
+        out[k, :H] = code(yl * 219.0 + 16.0)
+        out[k, H:, 0::2] = code(cb * 224.0 + 128.0)
+        out[k, H:, 1::2] = code(cr * 224.0 + 128.0)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--batch", type=int, default=150)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--leg-seconds", type=float, default=0.6)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    import mm355
+
+    W, H, B = a.width, a.height, a.batch
+    p = mm355.Params.make(levels=5, phase_scale=25.0)
+    legs = {}
+    rgba = torch.empty((B, H, W, 4), dtype=torch.uint8, device="cuda")
+    for name, fmt in (("rgba8", mm355.RGBA8), ("nv12", mm355.NV12)):
+        h = mm355.Handle(W, H, p)
+        h.set_batch(B)
+        if name == "rgba8":
+            h.synth(rgba, 0, B, stream=torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            src = rgba
+        else:
+            src = to_nv12(torch, rgba)
+        legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[],
+                          bytes_per_frame=mm355.frame_bytes(W, H, fmt))
+    st = torch.cuda.Stream()
+
+    def leg(L, calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(st):
+            e0.record(st)
+            for _ in range(calls):
+                L["h"].process_stream(L["src"], L["dst"], B, L["fmt"], stream=st.cuda_stream)
+            e1.record(st)
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3
+
+    # warm-up: the first call holds the passthrough frame; then the timed launch shape
+    for L in legs.values():
+        leg(L, 1)
+        t = min(leg(L, 2) for _ in range(2)) / 2
+        L["calls"] = max(2, int(a.leg_seconds / t) + 1)
+    for _ in range(a.rounds):
+        for L in legs.values():
+            t = leg(L, L["calls"])
+            L["fps"].append(L["calls"] * B / t)
+    out = {"workload": f"{W}x{H}, 5 levels, phase scale 25, mm_process_stream of {B} frames, batch {B}",
+           "device": torch.cuda.get_device_name(0), "rounds": a.rounds, "formats": {}}
+    for name, L in legs.items():
+        L["h"].profile_begin()
+        L["h"].process_stream(L["src"], L["dst"], B, L["fmt"], stream=st.cuda_stream)
+        st.synchronize()
+        prof = L["h"].profile_end()
+        f = L["fps"]
+        out["formats"][name] = {
+            "bytes_per_frame": L["bytes_per_frame"], "calls_per_leg": L["calls"],
+            "leg_seconds": round(L["calls"] * B / statistics.median(f), 3),
+            "fps_legs": [round(x, 1) for x in f], "fps_median": round(statistics.median(f), 1),
+            "fps_min": round(min(f), 1), "fps_max": round(max(f), 1),
+            "spread_pct": round(100.0 * (max(f) - min(f)) / statistics.median(f), 2),
+            "kernel_us_per_frame": {k: round(1e3 * ms / fr, 3) for k, (ms, n, fr) in prof.items() if n},
+        }
+        L["h"].close()
+    r, v = out["formats"]["rgba8"], out["formats"]["nv12"]
+    out["nv12_over_rgba8"] = round(v["fps_median"] / r["fps_median"], 4)
+    txt = json.dumps(out, indent=1)
+    print(txt)
+    if a.out:
+        with open(a.out, "w") as fo:
+            fo.write(txt + "\n")
+
+
+if __name__ == "__main__":
+    main()
