@@ -16,7 +16,8 @@
  *     (v = byte/255); RGBA32F and RGBA16F are linear float; RGBA8_SRGB is an
  *     8-bit sRGB target as Unity's Linear colour space sees it (decoded to
  *     linear light on read, encoded on write).  MM_NV12 / MM_NV12_FULL are
- *     video frames, planar Y'CbCr 4:2:0 (see the format list).  The handle
+ *     video frames, planar Y'CbCr 4:2:0, and MM_P010 / MM_P010_FULL their
+ *     10-bit form (see the format list).  The handle
  *     owns all device scratch and the one-frame temporal state.
  *   - A handle is not thread-safe: one handle per video stream, calls in frame
  *     order (Unity calls OnRenderImage serially on its render thread).
@@ -27,7 +28,7 @@
  *     this build covers 16 <= N <= 8192, i.e. 9 <= max(W, H) <= 8192 (other
  *     sizes: MM_ERR_UNSUPPORTED from mm_create); MM_MODE_STEERABLE stops at
  *     N = 4096.  Odd W or H are supported in every mode (and the debug
- *     views); the NV12 formats, being 4:2:0, take even W and H only and no
+ *     views); the NV12 and P010 formats, being 4:2:0, take even W and H only and no
  *     debug view (MM_ERR_UNSUPPORTED).  The fused K3+K4 kernel runs for
  *     even sizes with W % 8 == 0 and margins N - W >= 8, N - H >= 4; every
  *     other geometry takes the unfused pair (same results).
@@ -58,7 +59,7 @@ extern "C" {
 #define MM_ERR_NO_STATE    -6  /* mm_get_state before any frame was seen */
 
 /* frame formats (every entry point that takes frames takes each of them;
- * the NV12 pair for even W and H and without the debug views) */
+ * the NV12 and P010 pairs for even W and H and without the debug views) */
 #define MM_RGBA8   0       /* 4 B/px, UNORM: v = byte / 255; out round(saturate(v) * 255) */
 #define MM_RGBA32F 1       /* 16 B/px, linear float                                       */
 /* The frames the reference actually receives (since ABI 10): its camera
@@ -101,6 +102,39 @@ extern "C" {
  * all W H 3/2 bytes through. */
 #define MM_NV12      16   /* 8-bit 4:2:0, BT.601 limited ("video") range */
 #define MM_NV12_FULL 17   /* the same, full ("JPEG") range               */
+
+/* 10-bit video frames (backward-compatible addition to ABI 10: a caller detects
+ * it by mm_frame_bytes(W, H, MM_P010, &n) == MM_OK).  10-bit Y'CbCr 4:2:0 as a
+ * HEVC Main10 / AV1 decoder hands it out (P010 / P016 surfaces), tightly
+ * packed little-endian 16-bit words: H rows of W luma words, then H/2 rows of
+ * W words of interleaved (Cb, Cr) pairs, 3 W H bytes in all; frame k of a
+ * stream at k * mm_frame_bytes; frame pointers 4-byte aligned (as NV12, no
+ * stricter).  W and H even (else MM_ERR_UNSUPPORTED from mm_frame_bytes and
+ * every frame entry point); show_magnitude / show_phase are refused with
+ * MM_ERR_UNSUPPORTED.
+ * The sample is the word read as 16-bit fixed point, v = word / 64 in 10-bit
+ * code units: P010 content has the low 6 bits zero; P016 content uses them and
+ * they are honoured, so a P016 surface is accepted as it is.
+ *   in:  y = (v - 64) / 876, cb = (v - 512) / 896, cr = (v - 512) / 896
+ *        (MM_P010_FULL: v / 1023, (v - 512) / 1023); from there exactly as
+ *        NV12: every chroma sample shared by its 2 x 2 pixels, the same BT.601
+ *        matrix, alpha 1, NOT clamped.  Neutral chroma (word 0x8000) gives
+ *        exactly zero I and Q.
+ *   out: NV12's formulas on the saturated RGB; luma code Yl 876 + 64 (full:
+ *        Yl 1023), chroma code 512 + 896 (full: 1023) x the mean of the 2 x 2
+ *        pixels' C'; codes floor(v + 0.5) clamped to 0..1023, stored as
+ *        code << 6: the low 6 bits of every output word are zero.
+ * The frame IS the RGBA32F frame of that decode and the result the reference's
+ * result on it; 3 bytes per pixel each way and no conversion on the host, with
+ * a quarter of an 8-bit source's luma quantisation noise for phase_scale to
+ * amplify.  The first frame and apply_magnification = 0 pass all 3 W H bytes
+ * through bitwise, low bits included.
+ * The matrix stays BT.601 because its luma weights are RGBToYIQ's own (what
+ * lets the transform read the luma plane alone).  Out of scope: BT.709 /
+ * BT.2020 matrices, PQ / HLG transfer curves, 4:2:2 and 4:4:4, and pitched
+ * surfaces (rows padded beyond W words). */
+#define MM_P010      18   /* 10-bit 4:2:0, BT.601 matrix, limited range */
+#define MM_P010_FULL 19   /* the same, full range                        */
 
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0   /* usePyramidDecomposition = true (.cs:18, :128-131) */
@@ -181,7 +215,7 @@ int mm_get_params(const mm_handle *h, mm_params *p);
 int mm_padded_size(const mm_handle *h, int *n);
 
 /* Bytes of one W x H frame of `format` (MM_ERR_INVALID for an unknown format
- * or size; MM_ERR_UNSUPPORTED for an NV12 format with odd W or H).  Since
+ * or size; MM_ERR_UNSUPPORTED for an NV12 or P010 format with odd W or H).  Since
  * ABI 10. */
 int mm_frame_bytes(int width, int height, int format, size_t *bytes);
 
@@ -309,7 +343,7 @@ int mm_synth_frames(void *dev_out, int width, int height, int t0, int count,
  * stretch+pad bilinear resample, including the Hann window factor. */
 int mm_resample_table(int width, int height, int axis, int edge_mode,
                       int32_t *idx4, float *w4);
-/* The (cb, cr) -> (I, Q) matrix the NV12 compose uses, m = {I_cb, Q_cb, I_cr,
+/* The (cb, cr) -> (I, Q) matrix the NV12 and P010 compose uses, m = {I_cb, Q_cb, I_cr,
  * Q_cr}: RGBToYIQ's I and Q rows times the BT.601 conversion above, derived
  * in double (the kernels take it divided by the range's chroma scale). */
 int mm_nv12_chroma_matrix(double m[4]);

@@ -213,40 +213,45 @@ static inline size_t fmt_bpp(int fmt)
     return fmt == MM_RGBA32F ? 16 : fmt == MM_RGBA16F ? 8 : 4;
 }
 static inline bool fmt_nv12(int fmt) { return fmt == MM_NV12 || fmt == MM_NV12_FULL; }
+static inline bool fmt_p010(int fmt) { return fmt == MM_P010 || fmt == MM_P010_FULL; }
+static inline bool fmt_420(int fmt) { return fmt_nv12(fmt) || fmt_p010(fmt); }   // planar, not Pix<FMT>
 static inline bool fmt_valid(int fmt)
 {
     return fmt == MM_RGBA8 || fmt == MM_RGBA32F || fmt == MM_RGBA16F || fmt == MM_RGBA8_SRGB ||
-           fmt_nv12(fmt);
+           fmt_420(fmt);
 }
-// Bytes of one W x H frame (the planar 4:2:0 formats: W H luma bytes and half
-// as many chroma bytes; W and H even, fmt_check).
+// Bytes of one W x H frame (the planar 4:2:0 formats: W H luma samples and half
+// as many chroma samples, of 1 byte (NV12) or 2 (P010); W and H even, fmt_check).
 static inline size_t fmt_frame_bytes(int W, int H, int fmt)
 {
     const size_t px = (size_t)W * (size_t)H;
-    return fmt_nv12(fmt) ? px + px / 2 : px * fmt_bpp(fmt);
+    return fmt_p010(fmt) ? 3 * px : fmt_nv12(fmt) ? px + px / 2 : px * fmt_bpp(fmt);
 }
 // What every frame entry point asks of (format, geometry, parameters) before
-// it queues anything.  NV12 is 4:2:0: even sizes only; the debug views are
-// R-channel pictures, which it cannot hold.
+// it queues anything.  NV12 and P010 are 4:2:0: even sizes only; the debug
+// views are R-channel pictures, which they cannot hold.
 static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
 {
     if (!fmt_valid(fmt)) return MM_ERR_INVALID;
-    if (fmt_nv12(fmt) && ((W | H) & 1)) return MM_ERR_UNSUPPORTED;
-    if (fmt_nv12(fmt) && p && (p->show_magnitude || p->show_phase)) return MM_ERR_UNSUPPORTED;
+    if (fmt_420(fmt) && ((W | H) & 1)) return MM_ERR_UNSUPPORTED;
+    if (fmt_420(fmt) && p && (p->show_magnitude || p->show_phase)) return MM_ERR_UNSUPPORTED;
     return MM_OK;
 }
 static_assert(kFmtNV12 == MM_NV12, "the kernels' NV12 template argument is the format code");
+static_assert(kFmtP010 == MM_P010, "the kernels' P010 template argument is the format code");
 // Runs the statement with the compile-time format FMT_ of the runtime `fmt`
-// (both NV12 ranges run the MM_NV12 instances; geo_of sets their uniforms).
+// (both NV12 ranges run the MM_NV12 instances, both P010 ranges the MM_P010
+// instances; geo_of sets their uniforms).
 #define MM_FMT_SWITCH(fmt, ...)                                                \
     switch (fmt) {                                                             \
     case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
     case MM_RGBA32F: { constexpr int FMT_ = MM_RGBA32F; __VA_ARGS__; } break;  \
     case MM_RGBA16F: { constexpr int FMT_ = MM_RGBA16F; __VA_ARGS__; } break;  \
     case MM_NV12: case MM_NV12_FULL: { constexpr int FMT_ = MM_NV12; __VA_ARGS__; } break; \
+    case MM_P010: case MM_P010_FULL: { constexpr int FMT_ = MM_P010; __VA_ARGS__; } break; \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
-// ... and the kernels that have no NV12 instance (odd sizes and the debug
+// ... and the kernels that have no NV12 / P010 instance (odd sizes and the debug
 // views, refused by fmt_check before any launch)
 #define MM_FMT_SWITCH_RGBA(fmt, ...)                                           \
     switch (fmt) {                                                             \
@@ -274,21 +279,25 @@ static inline void nv12_chroma_matrix(double m[4])
     }
 }
 // The launch geometry for frames of `fmt`: the handle's, plus the NV12 range's
-// scales and offsets (limited: Y 16 .. 235, C 16 .. 240; full: 0 .. 255).
+// scales and offsets (limited: Y 16 .. 235, C 16 .. 240; full: 0 .. 255) or
+// the P010 range's (limited: Y 64 .. 940, C 64 .. 960; full: 0 .. 1023; the
+// input side in units of the 16-bit word, 64 per code: u = 64).
 static inline Geo geo_of(const mm_handle *h, int fmt)
 {
     Geo g = h->geo;
-    if (fmt_nv12(fmt)) {
-        const bool full = fmt == MM_NV12_FULL;
-        const double ys = full ? 255.0 : 219.0, cs = full ? 255.0 : 224.0, y0 = full ? 0.0 : 16.0;
+    if (fmt_420(fmt)) {
+        const bool full = fmt == MM_NV12_FULL || fmt == MM_P010_FULL, p10 = fmt_p010(fmt);
+        const double ys = p10 ? (full ? 1023.0 : 876.0) : (full ? 255.0 : 219.0);
+        const double cs = p10 ? (full ? 1023.0 : 896.0) : (full ? 255.0 : 224.0);
+        const double y0 = full ? 0.0 : p10 ? 64.0 : 16.0, u = p10 ? 64.0 : 1.0;
         double m[4];
         nv12_chroma_matrix(m);
-        g.nv.y_off = (float)y0;
-        g.nv.y_unit = (float)(1.0 / ys);
-        g.nv.icb = (float)(m[0] / cs);
-        g.nv.qcb = (float)(m[1] / cs);
-        g.nv.icr = (float)(m[2] / cs);
-        g.nv.qcr = (float)(m[3] / cs);
+        g.nv.y_off = (float)(y0 * u);
+        g.nv.y_unit = (float)(1.0 / (ys * u));
+        g.nv.icb = (float)(m[0] / (cs * u));
+        g.nv.qcb = (float)(m[1] / (cs * u));
+        g.nv.icr = (float)(m[2] / (cs * u));
+        g.nv.qcr = (float)(m[3] / (cs * u));
         g.nv.yo_scale = (float)ys;
         g.nv.yo_bias = (float)(y0 + 0.5);
         // C' = (B - Yl) 0.5 / 0.886, (R - Yl) 0.5 / 0.701; the mean of four; the code scale
@@ -509,7 +518,7 @@ static int set_attrs(int W)
     (void)W;   // every other kernel stays within the default 64 KiB dynamic LDS
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 2 * lds_complex<4096>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         // k_sb_cols: exchange buffers (73.7 KB) + its own staging (run_steer)
@@ -553,7 +562,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 11) {   // k_rows_inv_compose4: four 2048-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 4 * lds_complex<2048>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         // k_sb_cols with four columns per workgroup (MM_SB_MIN_GROUPS = 4):
@@ -587,7 +596,7 @@ static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, int fmt, hipS
     } while (0)
     const bool gen = h->geo.ox || h->geo.oy;   // odd W/H: taps span i-2 .. i+1
     const Geo g = geo_of(h, fmt);
-    if (gen) {   // (no NV12 instance: odd sizes are not 4:2:0)
+    if (gen) {   // (no NV12 / P010 instance: odd sizes are not 4:2:0)
         MM_FMT_SWITCH_RGBA(fmt, MM_K1_LAUNCH(FMT_, true, false))
     } else {
         MM_FMT_SWITCH(fmt, if (lat) MM_K1_LAUNCH(FMT_, false, true);

@@ -45,7 +45,10 @@ struct Geo {
     int TK;           // rows per Q tile (q_tile_v)
     int edge;         // 0 repeat, 1 clamp
     // MM_NV12 / MM_NV12_FULL only (the two ranges share the kernel instances;
-    // filled per launch by geo_of, mm_impl.hpp; the other formats never read it)
+    // filled per launch by geo_of, mm_impl.hpp; the other formats never read it).
+    // MM_P010 / MM_P010_FULL use it the same way, in units of the 16-bit word
+    // on input (64 per 10-bit code: y_off 64 x, y_unit and the matrix 1/64 x)
+    // and of the 10-bit code on output (chroma bias 512.5, not 128.5).
     struct Nv12 {
         float y_off, y_unit;        // K1: luma = ((float)Yb - y_off) * y_unit
         float icb, qcb, icr, qcr;   // compose: (I, Q) = (icb, qcb) (Cb - 128) + (icr, qcr) (Cr - 128),
@@ -459,8 +462,22 @@ template <int FMT> __device__ __forceinline__ void out_store(uint8_t *base, unsi
 // Alignment: rows are W bytes and a frame W H 3/2, both only even, so the
 // luma plane is read bytewise and a (Cb, Cr) pair as one 2-byte load; dword
 // accesses only where W % 8 == 0 (the fused kernels' quads).
+//
+// MM_P010 / MM_P010_FULL (FMT = kFmtP010) are the same layout in little-endian
+// 16-bit words, the 10-bit code in the word's high bits (v = word / 64; the low
+// 6 bits of a P016 surface are honoured): 2 W bytes per row, 3 W H per frame.
+// Every NV12 statement above holds with the word as the sample, Geo::nv in
+// word units on input and 10-bit code units on output, and k420<FMT> selects
+// the shared 4:2:0 structure of the kernels.  Alignment: frames are 4-byte
+// aligned (include/mm.h), rows 2 W bytes with W even, so 2-byte luma loads,
+// 4-byte (Cb, Cr) pair loads and 4-byte stores of two words are always
+// aligned; the fused kernels' 8-byte quad stores only if the frame base is
+// 8-byte aligned too (W % 8 == 0 there), which they test per workgroup.
 constexpr int kFmtNV12 = 16;   // MM_NV12
+constexpr int kFmtP010 = 18;   // MM_P010
 template <int FMT> constexpr bool kNV12 = FMT == kFmtNV12;
+template <int FMT> constexpr bool kP010 = FMT == kFmtP010;
+template <int FMT> constexpr bool k420 = kNV12<FMT> || kP010<FMT>;
 // the raw sample K1 loads per pixel
 template <int FMT> struct LumaSrc {
     using raw_t = typename Pix<FMT>::raw_t;
@@ -473,16 +490,21 @@ template <> struct LumaSrc<kFmtNV12> {
 // what the compose kernels load per source pixel
 template <int FMT> struct ChromaSrc { using raw_t = typename Pix<FMT>::raw_t; };
 template <> struct ChromaSrc<kFmtNV12> { using raw_t = uint16_t; };   // Cb | Cr << 8
+template <> struct LumaSrc<kFmtP010> {
+    using raw_t = uint16_t;
+    static constexpr int bpp = 2;
+};
+template <> struct ChromaSrc<kFmtP010> { using raw_t = uint32_t; };   // Cb | Cr << 16
 // K1's luma of a raw sample and its unit (folded into the resample weights)
 template <int FMT>
 __device__ __forceinline__ float k1_luma(typename LumaSrc<FMT>::raw_t u, const Geo &g)
 {
-    if constexpr (kNV12<FMT>) return (float)u - g.nv.y_off;
+    if constexpr (k420<FMT>) return (float)u - g.nv.y_off;
     else return luma_units<FMT>(u);
 }
 template <int FMT> __device__ __forceinline__ float k1_unit(const Geo &g)
 {
-    if constexpr (kNV12<FMT>) return g.nv.y_unit;
+    if constexpr (k420<FMT>) return g.nv.y_unit;
     else return kLumaUnit<FMT>;
 }
 // byte offset of the (Cb, Cr) pair of source pixel (row, col), both already
@@ -498,11 +520,28 @@ __device__ __forceinline__ c2 nv12_iq2(unsigned u, const Geo &g)
     const float cb = (float)(u & 255u) - 128.0f, cr = (float)((u >> 8) & 255u) - 128.0f;
     return mk(g.nv.icb, g.nv.qcb) * cb + mk(g.nv.icr, g.nv.qcr) * cr;
 }
+// ... and of a pair of 16-bit words: exact zero for neutral chroma (0x8000)
+__device__ __forceinline__ c2 p010_iq2(unsigned u, const Geo &g)
+{
+    const float cb = (float)(u & 0xFFFFu) - 32768.0f, cr = (float)(u >> 16) - 32768.0f;
+    return mk(g.nv.icb, g.nv.qcb) * cb + mk(g.nv.icr, g.nv.qcr) * cr;
+}
+// both for a 4:2:0 format's sample size
+template <int FMT> __device__ __forceinline__ unsigned c420_off(const Geo &g, int row, unsigned col)
+{
+    if constexpr (kP010<FMT>) return nv12_c_off(g, row, col) * 2u;
+    else return nv12_c_off(g, row, col);
+}
+template <int FMT> __device__ __forceinline__ c2 c420_iq2(unsigned u, const Geo &g)
+{
+    if constexpr (kP010<FMT>) return p010_iq2(u, g);
+    else return nv12_iq2(u, g);
+}
 // the compose kernels' (I, Q) of a staged raw sample
 template <int FMT>
 __device__ __forceinline__ c2 src_iq2(typename ChromaSrc<FMT>::raw_t u, const Geo &g)
 {
-    if constexpr (kNV12<FMT>) return nv12_iq2(u, g);
+    if constexpr (k420<FMT>) return c420_iq2<FMT>(u, g);
     else return chroma_iq2<FMT>(u);
 }
 // Output of one pixel from yiq_rgb's saturated RGB: the luma code and the
@@ -541,6 +580,67 @@ __device__ __forceinline__ void nv12_store_quad(uint8_t *outp, const Geo &g, int
         const unsigned c4 = nv12_ccode(b0.x, g.nv.cbo) | nv12_ccode(b0.y, g.nv.cro) << 8 |
                             nv12_ccode(b1.x, g.nv.cbo) << 16 | nv12_ccode(b1.y, g.nv.cro) << 24;
         st_stream<uint32_t>(outp + (size_t)(unsigned)((g.H + (i >> 1)) * g.W), (unsigned)X, c4);
+    }
+}
+// MM_P010: the same with 10-bit codes (nv12_ycode's is in 0 .. 1023 by the
+// range's yo_scale), each stored as code << 6 in a 16-bit word
+__device__ __forceinline__ unsigned p010_ccode(float sum4, float k)
+{
+    return (unsigned)fminf(sum4 * k + 512.5f, 1023.0f);     // >= 1: |C'| <= 1/2
+}
+// A quad's row is four words, 8 bytes, at a multiple of 8 from the frame base
+// (X % 4 == 0, W % 8 == 0, frames 3 W H bytes); the contract aligns the base to
+// 4 bytes only, so `wide` (workgroup-uniform: the base is 8-byte aligned) picks
+// one 8-byte store, else two 4-byte stores.
+__device__ __forceinline__ void p010_st4(uint8_t *row, unsigned X, bool wide, unsigned lo, unsigned hi)
+{
+    if (wide) {
+        st_stream<uint2>(row, X * 2u, make_uint2(lo, hi));
+    } else {
+        st_stream<uint32_t>(row, X * 2u, lo);
+        st_stream<uint32_t>(row, X * 2u + 4u, hi);
+    }
+}
+__device__ __forceinline__ void p010_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
+                                                bool wide, const float (&rr)[4], const float (&gg)[4],
+                                                const float (&bb)[4], c2 (&cd0)[4])
+{
+    c2 cd[4];
+    unsigned y[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = nv12_ycode(rr[k], gg[k], bb[k], g, cd[k]) << 6;
+    p010_st4(outp + (size_t)(unsigned)(i * g.W) * 2u, (unsigned)X, wide, y[0] | y[1] << 16, y[2] | y[3] << 16);
+    if (!odd) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) cd0[k] = cd[k];
+    } else {
+        const c2 b0 = (cd0[0] + cd[0]) + (cd0[1] + cd[1]), b1 = (cd0[2] + cd[2]) + (cd0[3] + cd[3]);
+        const unsigned c0 = p010_ccode(b0.x, g.nv.cbo) << 6 | p010_ccode(b0.y, g.nv.cro) << 22;
+        const unsigned c1 = p010_ccode(b1.x, g.nv.cbo) << 6 | p010_ccode(b1.y, g.nv.cro) << 22;
+        p010_st4(outp + (size_t)(unsigned)((g.H + (i >> 1)) * g.W) * 2u, (unsigned)X, wide, c0, c1);
+    }
+}
+// the fused kernels' quad store for a 4:2:0 format
+template <int FMT>
+__device__ __forceinline__ void c420_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
+                                                [[maybe_unused]] bool wide, const float (&rr)[4],
+                                                const float (&gg)[4], const float (&bb)[4], c2 (&cd0)[4])
+{
+    if constexpr (kP010<FMT>) p010_store_quad(outp, g, i, X, odd, wide, rr, gg, bb, cd0);
+    else nv12_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
+}
+// the fused kernels' load of the two (Cb, Cr) pairs of the quad X .. X+3 in
+// source row `row`
+template <int FMT>
+__device__ __forceinline__ void c420_quad_pairs(const uint8_t *img, const Geo &g, int row, unsigned X,
+                                                unsigned &p0, unsigned &p1)
+{
+    if constexpr (kP010<FMT>) {   // two 4-byte loads: the base is 4-byte aligned only
+        p0 = ld_off<uint32_t>(img, c420_off<FMT>(g, row, X));
+        p1 = ld_off<uint32_t>(img, c420_off<FMT>(g, row, X) + 4u);
+    } else {
+        p0 = ld_off<uint32_t>(img, nv12_c_off(g, row, X));
+        p1 = p0 >> 16;
     }
 }
 
@@ -2284,7 +2384,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     // offset addressing, no 64-bit address math per access
     // (NV12: the pixel's (Cb, Cr) pair, shared with its 2x2 neighbours)
     auto src_off = [&](int row, unsigned col) {
-        if constexpr (kNV12<FMT>) return nv12_c_off(g, row, col);
+        if constexpr (k420<FMT>) return c420_off<FMT>(g, row, col);
         else return (unsigned)(row * g.W + col) * Pix<FMT>::bpp;
     };
     const unsigned colA = (unsigned)wrap_near(min(c0 - 1 + tid, g.W), g.W, g.edge);
@@ -2341,7 +2441,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                              bv.w2 * (yv[r] + yv[r + 4]);
             float rr, gg, bb;
             yiq_rgb<FMT>(yb, cc, rr, gg, bb);
-            if constexpr (kNV12<FMT>) {
+            if constexpr (k420<FMT>) {
                 // One luma byte per pixel.  The 2x2 chroma mean: this column's
                 // two rows (i0 and TR even: r even starts a block; H even: both
                 // rows are inside), plus the neighbour column's from the lane
@@ -2352,7 +2452,9 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 static_assert(TR % 2 == 0 && TC % 2 == 0, "NV12: tiles of whole 2x2 blocks");
                 c2 cd;
                 const unsigned yc = nv12_ycode(rr, gg, bb, g, cd);
-                if (MM_NV12_K4_PACK && g.W % 4 == 0 && frame_bytes % 4 == 0) {
+                if constexpr (kP010<FMT>) {   // one 16-bit word per lane (always aligned)
+                    st_off<uint16_t>(outp, (unsigned)(i * g.W + X) * 2u, (uint16_t)(yc << 6));
+                } else if (MM_NV12_K4_PACK && g.W % 4 == 0 && frame_bytes % 4 == 0) {
                     // diagnostic: the four lanes of a quad gather their codes
                     // (quad-perm broadcasts) and lane 0 stores one dword
                     auto bc = [&](int ctrl) {
@@ -2374,8 +2476,13 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                     const float mine = X & 1 ? v.y : v.x, send = X & 1 ? v.x : v.y;
                     const float theirs = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
                         __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
-                    const unsigned cc8 = nv12_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
-                    st_off<uint8_t>(outp, (unsigned)((g.H + (i >> 1)) * g.W + X), (uint8_t)cc8);
+                    if constexpr (kP010<FMT>) {
+                        const unsigned cc10 = p010_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
+                        st_off<uint16_t>(outp, (unsigned)((g.H + (i >> 1)) * g.W + X) * 2u, (uint16_t)(cc10 << 6));
+                    } else {
+                        const unsigned cc8 = nv12_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
+                        st_off<uint8_t>(outp, (unsigned)((g.H + (i >> 1)) * g.W + X), (uint8_t)cc8);
+                    }
                 }
             } else {
                 out_store<FMT>(outp + (unsigned)(i * g.W * Pix<FMT>::bpp), (unsigned)X, rr, gg, bb);
@@ -2434,6 +2541,8 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     const c2 *Qf = Q + (size_t)frame * q_stride;
     const uint8_t *img = frames_in + (size_t)frame * frame_bytes;
     uint8_t *outp = frames_out + (size_t)frame * frame_bytes;
+    // P010: 8-byte quad stores only from an 8-byte aligned frame (workgroup-uniform)
+    [[maybe_unused]] const bool wide8 = (reinterpret_cast<uintptr_t>(outp) & 7u) == 0;
 
     const int q = threadIdx.x;
     const bool vq = 4 * q < g.W;
@@ -2446,18 +2555,20 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     auto chroma_row = [&](int i, c2 (&hc)[4]) {
         const int row = wrap_near(min(i, g.H), g.H, g.edge);
         c2 a[6];
-        if constexpr (kNV12<FMT>) {
+        if constexpr (k420<FMT>) {
             // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
             // outer two wrapped or clamped as pixels, then halved): the quad's
             // own two pairs as one dword (W % 8 == 0, X % 4 == 0: aligned in
             // every frame of a stream), the outer two as 2-byte loads
-            const unsigned pl = ld_off<uint16_t>(img, nv12_c_off(g, row, cl));
-            const unsigned pm = ld_off<uint32_t>(img, nv12_c_off(g, row, (unsigned)X));
-            const unsigned pr = ld_off<uint16_t>(img, nv12_c_off(g, row, cr));
-            a[0] = nv12_iq2(pl, g);
-            a[1] = a[2] = nv12_iq2(pm, g);
-            a[3] = a[4] = nv12_iq2(pm >> 16, g);
-            a[5] = nv12_iq2(pr, g);
+            // (P010: pairs are dwords, the quad's own two as two dword loads)
+            const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
+            unsigned pm0, pm1;
+            c420_quad_pairs<FMT>(img, g, row, (unsigned)X, pm0, pm1);
+            const unsigned pr = ld_off<raw_t>(img, c420_off<FMT>(g, row, cr));
+            a[0] = c420_iq2<FMT>(pl, g);
+            a[1] = a[2] = c420_iq2<FMT>(pm0, g);
+            a[3] = a[4] = c420_iq2<FMT>(pm1, g);
+            a[5] = c420_iq2<FMT>(pr, g);
         } else {
             const unsigned base = (unsigned)(row * g.W);
             raw_t p[6];
@@ -2575,7 +2686,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
         if (s > 0) {
             // ---- K4 on output rows i0+4s-4 .. i0+4s-1, two at a time ----
 #ifndef MM_K34_ROWS2   // the 4 chroma rows' loads first (one memory round trip)
-            if constexpr (kNV12<FMT>) {
+            if constexpr (k420<FMT>) {
                 // source rows 2j and 2j+1 share a chroma row (i0 % 4 == 0, H
                 // even): row i0+4s-3 has the kept row i0+4s-4's samples, row
                 // i0+4s-1 those of i0+4s-2; two loads per step, not four
@@ -2614,8 +2725,8 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         yiq_rgb<FMT>(yb, cc, rr[k], gg[k], bb[k]);
                     }
                     [[maybe_unused]] const unsigned o = (unsigned)(i * g.W + X);
-                    if constexpr (kNV12<FMT>) {
-                        nv12_store_quad(outp, g, i, X, r & 1, rr, gg, bb, cd0);
+                    if constexpr (k420<FMT>) {
+                        c420_store_quad<FMT>(outp, g, i, X, r & 1, wide8, rr, gg, bb, cd0);
                     } else if constexpr (bpp == 4) {
                         uint4 px;
                         px.x = out_pack<FMT>(rr[0], gg[0], bb[0]);
@@ -2687,6 +2798,8 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     const c2 *Qf = Q + (size_t)frame * q_stride;
     const uint8_t *img = frames_in + (size_t)frame * frame_bytes;
     uint8_t *outp = frames_out + (size_t)frame * frame_bytes;
+    // P010: 8-byte quad stores only from an 8-byte aligned frame (workgroup-uniform)
+    [[maybe_unused]] const bool wide8 = (reinterpret_cast<uintptr_t>(outp) & 7u) == 0;
 
     // ---- K3 on list-row pair i0/2 + grp (zero beyond Hn) ----
     {
@@ -2732,18 +2845,20 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     auto chroma_row = [&](int i, c2 (&hc)[4]) {   // k_rows_inv_compose's
         const int row = wrap_near(min(i, g.H), g.H, g.edge);
         c2 a[6];
-        if constexpr (kNV12<FMT>) {
+        if constexpr (k420<FMT>) {
             // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
             // outer two wrapped or clamped as pixels, then halved): the quad's
             // own two pairs as one dword (W % 8 == 0, X % 4 == 0: aligned in
             // every frame of a stream), the outer two as 2-byte loads
-            const unsigned pl = ld_off<uint16_t>(img, nv12_c_off(g, row, cl));
-            const unsigned pm = ld_off<uint32_t>(img, nv12_c_off(g, row, (unsigned)X));
-            const unsigned pr = ld_off<uint16_t>(img, nv12_c_off(g, row, cr));
-            a[0] = nv12_iq2(pl, g);
-            a[1] = a[2] = nv12_iq2(pm, g);
-            a[3] = a[4] = nv12_iq2(pm >> 16, g);
-            a[5] = nv12_iq2(pr, g);
+            // (P010: pairs are dwords, the quad's own two as two dword loads)
+            const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
+            unsigned pm0, pm1;
+            c420_quad_pairs<FMT>(img, g, row, (unsigned)X, pm0, pm1);
+            const unsigned pr = ld_off<raw_t>(img, c420_off<FMT>(g, row, cr));
+            a[0] = c420_iq2<FMT>(pl, g);
+            a[1] = a[2] = c420_iq2<FMT>(pm0, g);
+            a[3] = a[4] = c420_iq2<FMT>(pm1, g);
+            a[5] = c420_iq2<FMT>(pr, g);
         } else {
             const unsigned base = (unsigned)(row * g.W);
             raw_t p[6];
@@ -2767,7 +2882,7 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     };
     const int r0 = i0 + 2 * hh;   // first output row of this half
     c2 hc[4][4];                  // combined (I, Q) of source rows r0-1 .. r0+2
-    if constexpr (kNV12<FMT>) {   // rows r0, r0+1 (r0 even) share a chroma row
+    if constexpr (k420<FMT>) {   // rows r0, r0+1 (r0 even) share a chroma row
         chroma_row(r0 - 1, hc[0]);
         chroma_row(r0, hc[1]);
 #pragma unroll
@@ -2804,8 +2919,8 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                 yiq_rgb<FMT>(yb, cc, rr[k], gg[k], bb[k]);
             }
             [[maybe_unused]] const unsigned o = (unsigned)(i * g.W + X);
-            if constexpr (kNV12<FMT>) {
-                nv12_store_quad(outp, g, i, X, r & 1, rr, gg, bb, cd0);
+            if constexpr (k420<FMT>) {
+                c420_store_quad<FMT>(outp, g, i, X, r & 1, wide8, rr, gg, bb, cd0);
             } else if constexpr (bpp == 4) {
                 uint4 px;
                 px.x = out_pack<FMT>(rr[0], gg[0], bb[0]);

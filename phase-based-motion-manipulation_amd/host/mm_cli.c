@@ -8,7 +8,7 @@
  *
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
- *          [--full-range] [--srgb] [--nv12] [--standard] [--show-magnitude] [--show-phase]
+ *          [--full-range] [--srgb] [--nv12] [--p010] [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
  *          [--ring-local G [--compare]]
@@ -44,6 +44,13 @@
  * on the way in and split on the way out (a C420 .y4m; any other extension:
  * the raw NV12 frames), and no colour arithmetic runs on the host.  Not with
  * --srgb, the debug views, the ring modes, 4:4:4 / mono input or odd sizes.
+ * --p010: the same for a 10-bit 4:2:0 .y4m input (C420p10), sent as MM_P010
+ * frames (MM_P010_FULL with --full-range): the chroma planes are interleaved
+ * and every sample shifted left by 6 on the way in, the reverse on the way out
+ * (a C420p10 .y4m; any other extension: the raw P010 frames).  Refused with
+ * what --nv12 is refused with, and with --nv12.  Bit depths are never
+ * converted silently: an 8-bit input with --p010 and a 10-bit input without it
+ * are refused.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -390,7 +397,7 @@ int main(int argc, char **argv)
     int W = 1920, H = 1080, F = 300, L = 5, B = 30, dev = 0;
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
-    int nv12 = 0, srgb = 0;
+    int nv12 = 0, p010 = 0, srgb = 0;
     float S = 25.0f;
     const char *in_path = NULL, *out_path = NULL, *ring_id_path = NULL;
     for (int i = 1; i < argc; ++i) {
@@ -398,6 +405,7 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--full-range")) { full_range = 1; continue; }
         if (!strcmp(a, "--srgb")) { g_fmt = MM_RGBA8_SRGB; srgb = 1; continue; }
         if (!strcmp(a, "--nv12")) { nv12 = 1; continue; }
+        if (!strcmp(a, "--p010")) { p010 = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
         if (!strcmp(a, "--show-magnitude")) { show_mag = 1; continue; }
         if (!strcmp(a, "--show-phase")) { show_phase = 1; continue; }
@@ -433,10 +441,38 @@ int main(int argc, char **argv)
     y4m_info yi = {0};
     yi.fps_num = 25;
     yi.fps_den = 1;
+    int depth = 8;
     if (y4m_in) {
-        if (y4m_read_header(fi, &yi)) { fprintf(stderr, "%s: unsupported Y4M\n", in_path); return 1; }
+        if (y4m_read_header_depth(fi, &yi, &depth)) { fprintf(stderr, "%s: unsupported Y4M\n", in_path); return 1; }
         W = yi.width;
         H = yi.height;
+    }
+    if (p010) {
+        if (nv12) {
+            fprintf(stderr, "--p010 does not go with --nv12\n");
+            return 2;
+        }
+        if (srgb || show_mag || show_phase || ring_local > 0 || ring_world > 0) {
+            fprintf(stderr, "--p010 does not go with --srgb, the debug views or the ring modes\n");
+            return 2;
+        }
+        if (!y4m_in || yi.chroma != Y4M_420) {
+            fprintf(stderr, "--p010 needs a 10-bit 4:2:0 .y4m input (-i, C420p10)\n");
+            return 2;
+        }
+        if (depth != 10) {
+            fprintf(stderr, "--p010 needs a 10-bit input (C420p10); %s is 8-bit (--nv12 takes it as it is)\n",
+                    in_path);
+            return 2;
+        }
+        if ((W | H) & 1) {
+            fprintf(stderr, "--p010 needs even width and height (%dx%d)\n", W, H);
+            return 2;
+        }
+        g_fmt = full_range ? MM_P010_FULL : MM_P010;
+    } else if (depth != 8) {
+        fprintf(stderr, "%s is a 10-bit stream (C420p10): it needs --p010\n", in_path);
+        return 2;
     }
     if (nv12) {
         if (srgb || show_mag || show_phase || ring_local > 0 || ring_world > 0) {
@@ -493,7 +529,7 @@ int main(int argc, char **argv)
     }
 
     size_t fb = (size_t)W * H * 4;
-    if (nv12) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
+    if (nv12 || p010) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
     void *d_in = NULL, *d_out = NULL;
     if (hipMalloc(&d_in, fb * B) != hipSuccess || hipMalloc(&d_out, fb * B) != hipSuccess) {
         fprintf(stderr, "hipMalloc failed\n");
@@ -506,8 +542,10 @@ int main(int argc, char **argv)
                                                ? y4m_frame_bytes(&yi) : 3 * (size_t)W * H)
                                          : 3 * (size_t)W * H)
         : NULL;
-    if (y4m_out && (nv12 ? y4m_write_header_420(fo, W, H, yi.fps_num, yi.fps_den)
-                         : y4m_write_header(fo, W, H, yi.fps_num, yi.fps_den))) {
+    /* (planes: 3 W H bytes hold a C420p10 frame, 2 bytes per sample, exactly) */
+    if (y4m_out && (p010   ? y4m_write_header_420p10(fo, W, H, yi.fps_num, yi.fps_den)
+                    : nv12 ? y4m_write_header_420(fo, W, H, yi.fps_num, yi.fps_den)
+                           : y4m_write_header(fo, W, H, yi.fps_num, yi.fps_den))) {
         fprintf(stderr, "write failed\n");
         return 1;
     }
@@ -522,10 +560,11 @@ int main(int argc, char **argv)
         if (fi && y4m_in) {
             int got = 0;
             for (; got < n; ++got) {
-                const int r = y4m_read_frame(fi, &yi, planes);
+                const int r = y4m_read_frame_depth(fi, &yi, depth, planes);
                 if (r < 0) { fprintf(stderr, "%s: malformed frame\n", in_path); return 1; }
                 if (r == 0) break;
-                if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
+                if (p010) y4m_420p10_to_p010(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
+                else if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
                 else y4m_to_rgba(&yi, planes, host + fb * got, full_range);
             }
             if (got == 0) break;
@@ -551,9 +590,12 @@ int main(int argc, char **argv)
             hipMemcpy(host, d_out, fb * n, hipMemcpyDeviceToHost);
             if (y4m_out) {
                 for (int k = 0; k < n; ++k) {
-                    if (nv12) y4m_nv12_to_420(W, H, host + fb * k, planes);
+                    if (p010) y4m_p010_to_420p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
+                    else if (nv12) y4m_nv12_to_420(W, H, host + fb * k, planes);
                     else y4m_from_rgba(W, H, host + fb * k, planes, full_range);
-                    if (nv12 ? y4m_write_frame_420(fo, W, H, planes) : y4m_write_frame(fo, W, H, planes)) {
+                    if (p010   ? y4m_write_frame_420p10(fo, W, H, (const uint16_t *)planes)
+                        : nv12 ? y4m_write_frame_420(fo, W, H, planes)
+                               : y4m_write_frame(fo, W, H, planes)) {
                         fprintf(stderr, "write failed\n");
                         return 1;
                     }

@@ -16,7 +16,8 @@ static int parse_ratio(const char *s, int *a, int *b)
     return sscanf(s, "%d:%d", a, b) == 2 ? 0 : -1;
 }
 
-int y4m_read_header(FILE *f, y4m_info *info)
+/* depth: NULL refuses the high-bit-depth tags (y4m_read_header) */
+static int read_header(FILE *f, y4m_info *info, int *depth)
 {
     char line[512];
     size_t n = 0;
@@ -32,6 +33,7 @@ int y4m_read_header(FILE *f, y4m_info *info)
     info->aspect_num = info->aspect_den = 1;
     info->chroma = Y4M_420;
     info->interlace = 'p';
+    if (depth) *depth = 8;
     char *save = NULL;
     for (char *tok = strtok_r(line + 9, " ", &save); tok; tok = strtok_r(NULL, " ", &save)) {
         const char *v = tok + 1;
@@ -45,7 +47,10 @@ int y4m_read_header(FILE *f, y4m_info *info)
             if (!strcmp(v, "420") || !strcmp(v, "420jpeg") || !strcmp(v, "420paldv") ||
                 !strcmp(v, "420mpeg2"))
                 info->chroma = Y4M_420;
-            else if (!strcmp(v, "444")) info->chroma = Y4M_444;
+            else if (depth && !strcmp(v, "420p10")) {
+                info->chroma = Y4M_420;
+                *depth = 10;
+            } else if (!strcmp(v, "444")) info->chroma = Y4M_444;
             else if (!strcmp(v, "mono")) info->chroma = Y4M_MONO;
             else return -1;   /* 422, 411, high bit depth, alpha: unsupported */
             break;
@@ -54,6 +59,16 @@ int y4m_read_header(FILE *f, y4m_info *info)
     }
     if (info->width <= 0 || info->height <= 0) return -1;
     return 0;
+}
+
+int y4m_read_header(FILE *f, y4m_info *info)
+{
+    return read_header(f, info, NULL);
+}
+
+int y4m_read_header_depth(FILE *f, y4m_info *info, int *bit_depth)
+{
+    return bit_depth ? read_header(f, info, bit_depth) : -1;
 }
 
 size_t y4m_frame_bytes(const y4m_info *info)
@@ -65,7 +80,12 @@ size_t y4m_frame_bytes(const y4m_info *info)
     return w * h + 2 * cw * ch;
 }
 
-int y4m_read_frame(FILE *f, const y4m_info *info, uint8_t *planes)
+size_t y4m_frame_bytes_depth(const y4m_info *info, int bit_depth)
+{
+    return y4m_frame_bytes(info) * (bit_depth > 8 ? 2 : 1);
+}
+
+static int read_frame(FILE *f, size_t nb, void *planes)
 {
     char tag[6];
     if (fread(tag, 1, 5, f) != 5) return 0;
@@ -74,8 +94,17 @@ int y4m_read_frame(FILE *f, const y4m_info *info, uint8_t *planes)
     int c;
     while ((c = fgetc(f)) != EOF && c != '\n') {}   /* frame parameters: ignored */
     if (c != '\n') return -1;
-    const size_t nb = y4m_frame_bytes(info);
     return fread(planes, 1, nb, f) == nb ? 1 : -1;
+}
+
+int y4m_read_frame(FILE *f, const y4m_info *info, uint8_t *planes)
+{
+    return read_frame(f, y4m_frame_bytes(info), planes);
+}
+
+int y4m_read_frame_depth(FILE *f, const y4m_info *info, int bit_depth, void *planes)
+{
+    return read_frame(f, y4m_frame_bytes_depth(info, bit_depth), planes);
 }
 
 void y4m_to_rgba(const y4m_info *info, const uint8_t *planes, uint8_t *rgba, int full_range)
@@ -163,5 +192,39 @@ int y4m_write_frame_420(FILE *f, int W, int H, const uint8_t *planes420)
 {
     if (fputs("FRAME\n", f) < 0) return -1;
     const size_t nb = (size_t)W * H * 3 / 2;
+    return fwrite(planes420, 1, nb, f) == nb ? 0 : -1;
+}
+
+void y4m_420p10_to_p010(int W, int H, const uint16_t *planes420, uint16_t *p010)
+{
+    const size_t ny = (size_t)W * H, nc = ny / 4;
+    const uint16_t *Cb = planes420 + ny, *Cr = Cb + nc;
+    for (size_t i = 0; i < ny; ++i) p010[i] = (uint16_t)(planes420[i] << 6);
+    for (size_t i = 0; i < nc; ++i) {
+        p010[ny + 2 * i] = (uint16_t)(Cb[i] << 6);
+        p010[ny + 2 * i + 1] = (uint16_t)(Cr[i] << 6);
+    }
+}
+
+void y4m_p010_to_420p10(int W, int H, const uint16_t *p010, uint16_t *planes420)
+{
+    const size_t ny = (size_t)W * H, nc = ny / 4;
+    uint16_t *Cb = planes420 + ny, *Cr = Cb + nc;
+    for (size_t i = 0; i < ny; ++i) planes420[i] = (uint16_t)(p010[i] >> 6);
+    for (size_t i = 0; i < nc; ++i) {
+        Cb[i] = (uint16_t)(p010[ny + 2 * i] >> 6);
+        Cr[i] = (uint16_t)(p010[ny + 2 * i + 1] >> 6);
+    }
+}
+
+int y4m_write_header_420p10(FILE *f, int W, int H, int fps_num, int fps_den)
+{
+    return fprintf(f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420p10\n", W, H, fps_num, fps_den) > 0 ? 0 : -1;
+}
+
+int y4m_write_frame_420p10(FILE *f, int W, int H, const uint16_t *planes420)
+{
+    if (fputs("FRAME\n", f) < 0) return -1;
+    const size_t nb = (size_t)W * H * 3;
     return fwrite(planes420, 1, nb, f) == nb ? 0 : -1;
 }

@@ -7,7 +7,8 @@
  * replication (each 4:2:0 sample covers its 2x2 block).  Colour matrix BT.601,
  * limited range (Y 16..235, C 16..240) unless `full_range` (JPEG-style 0..255).
  * Host-side only: the frames then go through mm_process_stream as RGBA8, or,
- * 4:2:0 streams re-interleaved to NV12, as MM_NV12 without any conversion.
+ * 4:2:0 streams re-interleaved to NV12, as MM_NV12 without any conversion;
+ * 10-bit 4:2:0 (C420p10) streams likewise as MM_P010 (the last section).
  */
 #ifndef MM355_Y4M_H
 #define MM355_Y4M_H
@@ -60,6 +61,32 @@ void y4m_nv12_to_420(int width, int height, const uint8_t *nv12, uint8_t *planes
 /* Write a C420 header / one C420 frame (planes Y, Cb, Cr). */
 int y4m_write_header_420(FILE *f, int width, int height, int fps_num, int fps_den);
 int y4m_write_frame_420(FILE *f, int width, int height, const uint8_t *planes420);
+
+/* ---- 10-bit 4:2:0 (C420p10), for the MM_P010 path -------------------------
+ * Samples are 16-bit little-endian words holding 0 .. 1023, planes Y, Cb, Cr
+ * (this module reads and writes them as uint16_t: little-endian hosts).
+ * y4m_read_header keeps refusing the tag; these entry points stand beside it
+ * and y4m_info keeps its layout (the depth travels separately). */
+
+/* y4m_read_header that also accepts C420p10: *bit_depth is 10 for it (chroma
+ * Y4M_420), 8 for every tag y4m_read_header accepts. */
+int y4m_read_header_depth(FILE *f, y4m_info *info, int *bit_depth);
+
+/* Bytes of one frame's planes at `bit_depth` (2 bytes per sample above 8), and
+ * y4m_read_frame for that many bytes. */
+size_t y4m_frame_bytes_depth(const y4m_info *info, int bit_depth);
+int y4m_read_frame_depth(FILE *f, const y4m_info *info, int bit_depth, void *planes);
+
+/* 10-bit 4:2:0 planes (even width and height) <-> one P010 frame (Y words,
+ * then rows of interleaved Cb, Cr words; 3 * width * height bytes either way):
+ * interleave / de-interleave and a shift by 6 (word = sample << 6; sample =
+ * word >> 6), no other arithmetic. */
+void y4m_420p10_to_p010(int width, int height, const uint16_t *planes420, uint16_t *p010);
+void y4m_p010_to_420p10(int width, int height, const uint16_t *p010, uint16_t *planes420);
+
+/* Write a C420p10 header / one C420p10 frame (planes Y, Cb, Cr). */
+int y4m_write_header_420p10(FILE *f, int width, int height, int fps_num, int fps_den);
+int y4m_write_frame_420p10(FILE *f, int width, int height, const uint16_t *planes420);
 
 #ifdef __cplusplus
 }

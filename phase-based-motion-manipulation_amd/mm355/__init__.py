@@ -17,7 +17,7 @@ There is no CPU fallback.  If the library or a gfx950 device is missing,
 construction/Start raises ``MMError`` — loudly, never silently.
 """
 from .binding import (MMError, lib, load_library, LIB_PATH, RGBA8, RGBA32F, RGBA16F, RGBA8_SRGB,
-                      NV12, NV12_FULL, FORMAT_BPP, frame_bytes, nv12_chroma_matrix,
+                      NV12, NV12_FULL, P010, P010_FULL, FORMAT_BPP, frame_bytes, nv12_chroma_matrix,
                       EDGE_REPEAT, EDGE_CLAMP, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       FILTER_DIFF, FILTER_IIR, Params, Handle,
                       abi_symbols, resample_table, strerror)
@@ -26,7 +26,8 @@ from .stream import ShardedStream, shard_range
 from .ring import Ring, new_ring_id, ring_lib
 
 __all__ = ["MMError", "lib", "load_library", "LIB_PATH", "RGBA8", "RGBA32F", "RGBA16F",
-           "RGBA8_SRGB", "NV12", "NV12_FULL", "FORMAT_BPP", "frame_bytes", "nv12_chroma_matrix",
+           "RGBA8_SRGB", "NV12", "NV12_FULL", "P010", "P010_FULL", "FORMAT_BPP", "frame_bytes",
+           "nv12_chroma_matrix",
            "EDGE_REPEAT", "EDGE_CLAMP", "MODE_PYRAMID", "MODE_STANDARD", "MODE_STEERABLE",
            "FILTER_DIFF", "FILTER_IIR", "Params", "Handle", "abi_symbols",
            "resample_table", "strerror", "MotionMagnificationProcessor",

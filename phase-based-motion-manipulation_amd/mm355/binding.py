@@ -19,6 +19,10 @@ FORMAT_BPP = {RGBA8: 4, RGBA32F: 16, RGBA16F: 8, RGBA8_SRGB: 4}
 # of W interleaved Cb, Cr bytes; W and H even): frame_bytes() gives W*H*3/2
 NV12 = 16           # BT.601 limited ("video") range
 NV12_FULL = 17      # full ("JPEG") range
+# 10-bit video frames, the same layout in little-endian 16-bit words (10-bit code
+# << 6; a P016 surface's low bits are honoured): frame_bytes() gives W*H*3
+P010 = 18           # BT.601 matrix, limited range (Y 64..940, C 64..960)
+P010_FULL = 19      # full range (0..1023)
 EDGE_REPEAT = 0
 EDGE_CLAMP = 1
 MODE_PYRAMID = 0

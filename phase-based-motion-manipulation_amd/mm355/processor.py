@@ -7,7 +7,7 @@ snake_case; methods keep the reference's Unity callback names.
 import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
-                      NV12, NV12_FULL, RGBA8, RGBA8_SRGB, RGBA16F, RGBA32F, Handle, MMError,
+                      NV12, NV12_FULL, P010, P010_FULL, RGBA8, RGBA8_SRGB, RGBA16F, RGBA32F, Handle, MMError,
                       Params)
 
 
@@ -159,5 +159,7 @@ class MotionMagnificationProcessor:
 def host_frames(n, h, w, fmt):
     if fmt in (NV12, NV12_FULL):    # h luma rows, then h/2 rows of interleaved Cb, Cr
         return np.zeros((n, h * 3 // 2, w), np.uint8)
+    if fmt in (P010, P010_FULL):    # the same rows in 16-bit words (10-bit code << 6)
+        return np.zeros((n, h * 3 // 2, w), np.uint16)
     dt = {RGBA8: np.uint8, RGBA8_SRGB: np.uint8, RGBA16F: np.float16}.get(fmt, np.float32)
     return np.zeros((n, h, w, 4), dt)

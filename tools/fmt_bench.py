@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""RGBA8 against NV12 frames on one GPU, same process, alternating legs.
+"""RGBA8 against NV12 and P010 frames on one GPU, same process, alternating legs.
 
 The flagship stream (1920x1080, 5 levels, phase scale 25, batches of 150
-frames as bench.py) in both frame formats.  Frames are generated on the device
-(mm_synth_frames) and converted to NV12 with torch ops once, outside the
-timing.  Every launch shape is warmed up; a leg is `calls` back-to-back
+frames as bench.py) in the three frame formats.  Frames are generated on the
+device (mm_synth_frames) and converted to NV12 and P010 with torch ops once,
+outside the timing.  Every launch shape is warmed up; a leg is `calls` back-to-back
 mm_process_stream calls (>= --leg-seconds of device work) between two events
 on the handle's stream, synchronised at its end; the formats alternate
 --rounds times.  Reports each format's median frames/s and spread, and the
@@ -22,21 +22,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "phase-based-motion-manipulation_amd"))
 
 
-def to_nv12(torch, rgba):
-    """[n][H][W][4] uint8 (device) -> [n][H*3/2][W] NV12, BT.601 limited range,
-    chroma the mean of each 2 x 2 block (y4m_from_rgba's formulas)."""
+def to_420(torch, rgba, ten_bit=False):
+    """[n][H][W][4] uint8 (device) -> [n][H*3/2][W] NV12 (uint8), BT.601 limited
+    range, chroma the mean of each 2 x 2 block (y4m_from_rgba's formulas); or,
+    ten_bit, P010: the same with 10-bit codes (Y 64 .. 940, C 64 .. 960), each
+    stored as code << 6 in an int16 word (the bit pattern of the uint16)."""
     n, H, W, _ = rgba.shape
-    out = torch.empty((n, H * 3 // 2, W), dtype=torch.uint8, device=rgba.device)
+    ys, y0, cs, c0, top = (876.0, 64.0, 896.0, 512.0, 1023) if ten_bit else (219.0, 16.0, 224.0, 128.0, 255)
+    out = torch.empty((n, H * 3 // 2, W), dtype=torch.int16 if ten_bit else torch.uint8, device=rgba.device)
     for k in range(n):       # frame by frame: float planes of one frame at a time
         f = rgba[k, ..., :3].float() / 255.0
         r, g, b = f[..., 0], f[..., 1], f[..., 2]
         yl = 0.299 * r + 0.587 * g + 0.114 * b
         cb = ((b - yl) * (0.5 / 0.886)).reshape(H // 2, 2, W // 2, 2).mean(dim=(1, 3))
         cr = ((r - yl) * (0.5 / 0.701)).reshape(H // 2, 2, W // 2, 2).mean(dim=(1, 3))
-        code = lambda v: torch.clamp(torch.floor(v + 0.5), 0, 255).to(torch.uint8)
-        out[k, :H] = code(yl * 219.0 + 16.0)
-        out[k, H:, 0::2] = code(cb * 224.0 + 128.0)
-        out[k, H:, 1::2] = code(cr * 224.0 + 128.0)
+        if ten_bit:          # code << 6 as int16: codes >= 512 wrap to the negative half
+            code = lambda v: ((torch.clamp(torch.floor(v + 0.5), 0, top).to(torch.int32) << 6) & 0xFFFF
+                              ).to(torch.int16)
+        else:
+            code = lambda v: torch.clamp(torch.floor(v + 0.5), 0, top).to(torch.uint8)
+        out[k, :H] = code(yl * ys + y0)
+        out[k, H:, 0::2] = code(cb * cs + c0)
+        out[k, H:, 1::2] = code(cr * cs + c0)
     return out
 
 
@@ -56,7 +63,7 @@ def main():
     p = mm355.Params.make(levels=5, phase_scale=25.0)
     legs = {}
     rgba = torch.empty((B, H, W, 4), dtype=torch.uint8, device="cuda")
-    for name, fmt in (("rgba8", mm355.RGBA8), ("nv12", mm355.NV12)):
+    for name, fmt in (("rgba8", mm355.RGBA8), ("nv12", mm355.NV12), ("p010", mm355.P010)):
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
         if name == "rgba8":
@@ -64,7 +71,7 @@ def main():
             torch.cuda.synchronize()
             src = rgba
         else:
-            src = to_nv12(torch, rgba)
+            src = to_420(torch, rgba, ten_bit=name == "p010")
         legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[],
                           bytes_per_frame=mm355.frame_bytes(W, H, fmt))
     st = torch.cuda.Stream()
@@ -105,8 +112,9 @@ def main():
             "kernel_us_per_frame": {k: round(1e3 * ms / fr, 3) for k, (ms, n, fr) in prof.items() if n},
         }
         L["h"].close()
-    r, v = out["formats"]["rgba8"], out["formats"]["nv12"]
-    out["nv12_over_rgba8"] = round(v["fps_median"] / r["fps_median"], 4)
+    r = out["formats"]["rgba8"]
+    for name in ("nv12", "p010"):
+        out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
     txt = json.dumps(out, indent=1)
     print(txt)
     if a.out:
