@@ -12,7 +12,9 @@
  *   - Every function returns MM_OK (0) or a negative MM_ERR_* code; nothing
  *     throws or aborts across the ABI.  mm_strerror() names a code.
  *   - Frames are caller-owned, row-major, H rows of W RGBA pixels, tightly
- *     packed (pitch = W * bytes-per-pixel, mm_frame_bytes).  RGBA8 is UNORM
+ *     packed (pitch = W * bytes-per-pixel, mm_frame_bytes) or, through the
+ *     mm_surface entry points, with a row pitch, a chroma-plane offset and a
+ *     frame stride of the caller's.  RGBA8 is UNORM
  *     (v = byte/255); RGBA32F and RGBA16F are linear float; RGBA8_SRGB is an
  *     8-bit sRGB target as Unity's Linear colour space sees it (decoded to
  *     linear light on read, encoded on write).  MM_NV12 / MM_NV12_FULL are
@@ -131,8 +133,7 @@ extern "C" {
  * through bitwise, low bits included.
  * The matrix stays BT.601 because its luma weights are RGBToYIQ's own (what
  * lets the transform read the luma plane alone).  Out of scope: BT.709 /
- * BT.2020 matrices, PQ / HLG transfer curves, 4:2:2 and 4:4:4, and pitched
- * surfaces (rows padded beyond W words). */
+ * BT.2020 matrices, PQ / HLG transfer curves, 4:2:2 and 4:4:4. */
 #define MM_P010      18   /* 10-bit 4:2:0, BT.601 matrix, limited range */
 #define MM_P010_FULL 19   /* the same, full range                        */
 
@@ -219,6 +220,71 @@ int mm_padded_size(const mm_handle *h, int *n);
  * ABI 10. */
 int mm_frame_bytes(int width, int height, int format, size_t *bytes);
 
+/* Pitched surfaces (backward-compatible addition to ABI 10: a caller detects it
+ * by the presence of mm_surface_bytes).  Frames as a decoder, an encoder or an
+ * engine really stores them: rows padded to a pitch, the 4:2:0 (Cb, Cr) plane
+ * at an offset of its own (a VCN / VA-API 1080p NV12 surface: pitch 2048, luma
+ * padded to 1088 rows), frames of a stream a stride apart; a region of interest
+ * inside a larger frame is such a view too (base = its first sample, pitch =
+ * the parent's).  Every format, mode and entry point, the input and the output
+ * side independently, no repack.
+ *   - A pitched frame IS the tight frame of its W x H samples: padding (row
+ *     tails, the gap between the planes and between frames, anything past the
+ *     last row's W samples) is never read and never written.  The first frame
+ *     and apply_magnification = 0 pass the W x H samples through bitwise and
+ *     leave the destination's padding alone.
+ *   - in_layout and out_layout may differ (decoder surface in, encoder surface
+ *     out); their `format` must be equal (MM_ERR_INVALID).
+ *   - The temporal state G_{t-1} does not depend on any layout: consecutive
+ *     calls of one handle may use different layouts.
+ *   - mm_process / mm_process_stream / mm_compute_state are these calls with
+ *     mm_surface_tight on both sides: one code path, one set of kernels.
+ *     Everything else (debug views, modes, odd sizes of the RGBA formats, edge
+ *     modes, host-memory frames, stream ordering, aliasing) follows them.
+ * Validation (mm_surface_bytes; every frame entry point applies it before it
+ * queues anything; no GPU needed).  With the unit u = the pixel size of an RGBA
+ * format (4, 16, 8, 4), 2 for NV12 (a (Cb, Cr) pair) and 4 for P010:
+ *   - unknown format: MM_ERR_INVALID; 4:2:0 with odd W or H: MM_ERR_UNSUPPORTED;
+ *   - pitch (4:2:0: and chroma_pitch) at least the row's sample bytes (W pixels;
+ *     4:2:0: W samples) and a multiple of u; chroma_offset a multiple of u and
+ *     at or past the end of the last luma row's samples; RGBA formats:
+ *     chroma_offset = chroma_pitch = 0; else MM_ERR_INVALID;
+ *   - extent = the byte after the last sample of the last row of the last
+ *     plane (not pitch * H: a region of interest at the bottom of its parent
+ *     is valid).  The kernels address a frame with 32-bit byte offsets from
+ *     its base, so extent <= 2^32 (4 GiB per frame), else MM_ERR_UNSUPPORTED;
+ *     an overflow of size_t: MM_ERR_INVALID;
+ *   - device frame pointers are aligned to u (MM_ERR_INVALID; host-memory
+ *     frames are staged and need no alignment).  (The tight NV12 layout
+ *     puts odd frames of a 98 x 62 stream at 2 mod 4, so NV12 asks for the
+ *     pair's 2 bytes; 4-byte aligned NV12 surfaces with pitches that are
+ *     multiples of 4 get the dword accesses.)  With count > 1, frame_stride is
+ *     at least extent and a multiple of u.
+ * Wide accesses (RGBA8's 16-byte quads, NV12's dword quads, P010's 8-byte
+ * quads) are decided per frame from base, pitch and chroma offset and pitch;
+ * an unaligned frame takes the narrower access, never another kernel: a layout
+ * aligned like a decoder's runs exactly the tight layout's kernels. */
+typedef struct {
+    int    format;         /* MM_RGBA8 ... MM_P010_FULL */
+    size_t pitch;          /* bytes from one row to the next: RGBA rows, or luma rows */
+    size_t chroma_offset;  /* 4:2:0: bytes from the frame's base to the (Cb,Cr) plane; else 0 */
+    size_t chroma_pitch;   /* 4:2:0: bytes from one (Cb,Cr) row to the next; else 0 */
+    size_t frame_stride;   /* streams: bytes from frame k to frame k+1 (ignored for one frame) */
+} mm_surface;
+
+/* The packed layout of mm_frame_bytes (pitch = row bytes, the chroma plane
+ * right after row H - 1, frame_stride = mm_frame_bytes). */
+int mm_surface_tight(int width, int height, int format, mm_surface *s);
+/* pitch = row bytes rounded up to pitch_align (a multiple of u, >= 1),
+ * chroma_pitch = pitch, chroma_offset = pitch x (H rounded up to rows_align;
+ * even for 4:2:0), frame_stride = the whole padded planes (4:2:0: pitch x 3/2
+ * of the padded rows).  (256, 16) is a hardware decoder's layout: 1080p NV12
+ * gives pitch 2048, chroma_offset 2048 x 1088, frame_stride 2048 x 1632. */
+int mm_surface_aligned(int width, int height, int format, size_t pitch_align, int rows_align,
+                       mm_surface *s);
+/* Validates a layout for W x H frames (rules above) and returns its extent. */
+int mm_surface_bytes(int width, int height, const mm_surface *s, size_t *extent);
+
 /* OnRenderImage (.cs:101-143): one frame in, one frame out.
  * flags & MM_FRAMES_ON_DEVICE: in/out are device pointers and the call is
  * asynchronous on `hip_stream` (NULL = the default stream, as everywhere in
@@ -237,6 +303,12 @@ int mm_process(mm_handle *h, const void *in, void *out, int format, int flags,
  * mm_process calls; batches the launches. Asynchronous on hip_stream. */
 int mm_process_stream(mm_handle *h, const void *in, void *out, int count,
                       int format, void *hip_stream);
+
+/* mm_process / mm_process_stream on pitched surfaces (see mm_surface). */
+int mm_process_surface(mm_handle *h, const void *in, const mm_surface *in_layout,
+                       void *out, const mm_surface *out_layout, int flags, void *hip_stream);
+int mm_process_stream_surfaces(mm_handle *h, const void *in, const mm_surface *in_layout,
+                               void *out, const mm_surface *out_layout, int count, void *hip_stream);
 
 /* isFirstFrame = true (.cs:75): the next frame is passed through.  The same
  * happens after a MM_MODE_STEERABLE mm_set_state followed by a switch to
@@ -260,6 +332,8 @@ int mm_set_state(mm_handle *h, const void *dev_buf, size_t bytes, void *hip_stre
  * to hand the chunk-boundary state to the next rank). */
 int mm_compute_state(mm_handle *h, const void *in_dev, int format, void *dev_buf,
                      size_t bytes, void *hip_stream);
+int mm_compute_state_surface(mm_handle *h, const void *in_dev, const mm_surface *in_layout,
+                             void *dev_buf, size_t bytes, void *hip_stream);
 
 /* The handle's HIP stream (hipStream_t). */
 void *mm_stream(mm_handle *h);

@@ -33,14 +33,14 @@ MM_SIZE_ENTRIES(MM_ONLY_LOG2N)
 #endif
 
 static int do_set_attrs(mm_handle *h) { MM_DISPATCH(mm_size_set_attrs_, h) }
-static int do_stream(mm_handle *h, const uint8_t *in, uint8_t *out, int count, int fmt,
+static int do_stream(mm_handle *h, const uint8_t *in, uint8_t *out, int count, const Frames &fr,
                      hipStream_t s)
 {
-    MM_DISPATCH(mm_size_stream_, h, in, out, count, fmt, s)
+    MM_DISPATCH(mm_size_stream_, h, in, out, count, fr, s)
 }
-static int do_compute_state(mm_handle *h, const uint8_t *in, int fmt, void *dst, hipStream_t s)
+static int do_compute_state(mm_handle *h, const uint8_t *in, const Frames &fr, void *dst, hipStream_t s)
 {
-    MM_DISPATCH(mm_size_compute_state_, h, in, fmt, dst, s)
+    MM_DISPATCH(mm_size_compute_state_, h, in, fr, dst, s)
 }
 
 // ------------------------------------------------------------------------
@@ -432,30 +432,103 @@ int mm_get_batch(const mm_handle *h, int *frames)
     return MM_OK;
 }
 
-int mm_process_stream(mm_handle *h, const void *in, void *out, int count, int format,
-                      void *hip_stream)
+int mm_surface_tight(int width, int height, int format, mm_surface *s)
 {
-    if (!h || !in || !out || count < 0) return MM_ERR_INVALID;
-    if (int rc = fmt_check(h->W, h->H, format, &h->p)) return rc;
+    return surf_tight(width, height, format, s);
+}
+
+int mm_surface_aligned(int width, int height, int format, size_t pitch_align, int rows_align, mm_surface *s)
+{
+    mm_surface t;
+    if (!s || pitch_align < 1 || rows_align < 1) return MM_ERR_INVALID;
+    if (int rc = surf_tight(width, height, format, &t)) return rc;
+    const size_t u = fmt_unit(format);
+    if (pitch_align % u || (fmt_420(format) && (rows_align & 1))) return MM_ERR_INVALID;
+    size_t pitch, rows, planes;
+    if (__builtin_add_overflow(t.pitch, pitch_align - 1, &pitch) ||
+        __builtin_add_overflow((size_t)height, (size_t)rows_align - 1, &rows))
+        return MM_ERR_INVALID;
+    pitch = pitch / pitch_align * pitch_align;
+    rows = rows / (size_t)rows_align * (size_t)rows_align;
+    if (__builtin_mul_overflow(pitch, rows, &planes)) return MM_ERR_INVALID;
+    t.pitch = pitch;
+    t.frame_stride = planes;
+    if (fmt_420(format)) {
+        t.chroma_offset = planes;
+        t.chroma_pitch = pitch;
+        if (__builtin_add_overflow(planes, planes / 2, &t.frame_stride)) return MM_ERR_INVALID;
+    }
+    if (int rc = surf_check(width, height, &t, nullptr)) return rc;
+    *s = t;
+    return MM_OK;
+}
+
+int mm_surface_bytes(int width, int height, const mm_surface *s, size_t *extent)
+{
+    if (!extent) return MM_ERR_INVALID;
+    return surf_check(width, height, s, extent);
+}
+
+int mm_process_stream_surfaces(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                               const mm_surface *out_layout, int count, void *hip_stream)
+{
+    if (!h || !in || !out || !in_layout || !out_layout || count < 0) return MM_ERR_INVALID;
+    if (int rc = fmt_check(h->W, h->H, in_layout->format, &h->p)) return rc;
+    if (in_layout->format != out_layout->format) return MM_ERR_INVALID;
+    int rc;
+    if ((rc = surf_check_frames(h->W, h->H, in, in_layout, count)) ||
+        (rc = surf_check_frames(h->W, h->H, out, out_layout, count)))
+        return rc;
     if (count == 0) return MM_OK;
+    const Frames fr = frames_of(h->W, h->H, *in_layout, *out_layout);
     hipStream_t s = (hipStream_t)hip_stream;   // NULL: the default stream (HIP convention)
     DEVICE_SCOPE(h);
     int ro = order_after_last(h, s);
     if (ro) return ro;
     // last_ev also after a failed call: kernels it launched before failing may
     // still read the handle's buffers
-    const int rc = do_stream(h, (const uint8_t *)in, (uint8_t *)out, count, format, s);
+    rc = do_stream(h, (const uint8_t *)in, (uint8_t *)out, count, fr, s);
     const int rn = note_work(h, s);
     return rc ? rc : rn;
 }
 
-int mm_process(mm_handle *h, const void *in, void *out, int format, int flags, void *hip_stream)
+int mm_process_stream(mm_handle *h, const void *in, void *out, int count, int format,
+                      void *hip_stream)
 {
-    if (!h || !in || !out) return MM_ERR_INVALID;
-    if (int rc = fmt_check(h->W, h->H, format, &h->p)) return rc;
-    if (flags & MM_FRAMES_ON_DEVICE) return mm_process_stream(h, in, out, 1, format, hip_stream);
-    // host frames: stage through device buffers and synchronise
-    const size_t fb = fmt_frame_bytes(h->W, h->H, format);
+    mm_surface t;
+    if (!h || !in || !out || count < 0) return MM_ERR_INVALID;
+    if (int rc = surf_tight(h->W, h->H, format, &t)) return rc;
+    return mm_process_stream_surfaces(h, in, &t, out, &t, count, hip_stream);
+}
+
+// One plane (or RGBA frame) between a pitched host frame and the tight staging buffer
+static hipError_t stage_plane(void *dst, size_t dpitch, const void *src, size_t spitch, size_t row_bytes,
+                              size_t rows, hipMemcpyKind kind, hipStream_t s)
+{
+    if (dpitch == row_bytes && spitch == row_bytes) return hipMemcpyAsync(dst, src, row_bytes * rows, kind, s);
+    return hipMemcpy2DAsync(dst, dpitch, src, spitch, row_bytes, rows, kind, s);
+}
+
+int mm_process_surface(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                       const mm_surface *out_layout, int flags, void *hip_stream)
+{
+    if (!h || !in || !out || !in_layout || !out_layout) return MM_ERR_INVALID;
+    if (flags & MM_FRAMES_ON_DEVICE)
+        return mm_process_stream_surfaces(h, in, in_layout, out, out_layout, 1, hip_stream);
+    if (int rc = fmt_check(h->W, h->H, in_layout->format, &h->p)) return rc;
+    if (in_layout->format != out_layout->format) return MM_ERR_INVALID;
+    int rc;
+    if ((rc = surf_check_frames(h->W, h->H, in, in_layout, 1, false)) ||
+        (rc = surf_check_frames(h->W, h->H, out, out_layout, 1, false)))
+        return rc;
+    // host frames: stage through tight device buffers and synchronise; the 2D
+    // copies move the W x H samples only (the host frames' padding is neither
+    // read nor written)
+    const int format = in_layout->format;
+    mm_surface t;
+    (void)surf_tight(h->W, h->H, format, &t);
+    const Frames fr = frames_of(h->W, h->H, t, t);
+    const size_t fb = fr.fb, rb = t.pitch, luma = rb * (size_t)h->H;
     DEVICE_SCOPE(h);
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     int ro = order_after_last(h, s);
@@ -469,13 +542,39 @@ int mm_process(mm_handle *h, const void *in, void *out, int format, int flags, v
             return MM_ERR_OOM;
         h->stage_bytes = fb;
     }
-    HIPCHK(hipMemcpyAsync(h->d_stage_in, in, fb, hipMemcpyHostToDevice, s));
-    int rc = do_stream(h, h->d_stage_in, h->d_stage_out, 1, format, s);
+    const bool in_tight = in_layout->pitch == rb && (!fmt_420(format) || (in_layout->chroma_offset == luma &&
+                                                                          in_layout->chroma_pitch == rb));
+    const bool out_tight = out_layout->pitch == rb && (!fmt_420(format) || (out_layout->chroma_offset == luma &&
+                                                                            out_layout->chroma_pitch == rb));
+    if (in_tight) {
+        HIPCHK(hipMemcpyAsync(h->d_stage_in, in, fb, hipMemcpyHostToDevice, s));
+    } else {
+        HIPCHK(stage_plane(h->d_stage_in, rb, in, in_layout->pitch, rb, h->H, hipMemcpyHostToDevice, s));
+        if (fmt_420(format))
+            HIPCHK(stage_plane(h->d_stage_in + luma, rb, (const uint8_t *)in + in_layout->chroma_offset,
+                               in_layout->chroma_pitch, rb, h->H / 2, hipMemcpyHostToDevice, s));
+    }
+    rc = do_stream(h, h->d_stage_in, h->d_stage_out, 1, fr, s);
     const int rn = note_work(h, s);
     if (rc || (rc = rn)) return rc;
-    HIPCHK(hipMemcpyAsync(out, h->d_stage_out, fb, hipMemcpyDeviceToHost, s));
+    if (out_tight) {
+        HIPCHK(hipMemcpyAsync(out, h->d_stage_out, fb, hipMemcpyDeviceToHost, s));
+    } else {
+        HIPCHK(stage_plane(out, out_layout->pitch, h->d_stage_out, rb, rb, h->H, hipMemcpyDeviceToHost, s));
+        if (fmt_420(format))
+            HIPCHK(stage_plane((uint8_t *)out + out_layout->chroma_offset, out_layout->chroma_pitch,
+                               h->d_stage_out + luma, rb, rb, h->H / 2, hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(hipStreamSynchronize(s));
     return MM_OK;
+}
+
+int mm_process(mm_handle *h, const void *in, void *out, int format, int flags, void *hip_stream)
+{
+    mm_surface t;
+    if (!h || !in || !out) return MM_ERR_INVALID;
+    if (int rc = surf_tight(h->W, h->H, format, &t)) return rc;
+    return mm_process_surface(h, in, &t, out, &t, flags, hip_stream);
 }
 
 int mm_reset(mm_handle *h)
@@ -540,12 +639,14 @@ int mm_set_state(mm_handle *h, const void *dev_buf, size_t bytes, void *hip_stre
     return note_work(h, s);
 }
 
-int mm_compute_state(mm_handle *h, const void *in_dev, int format, void *dev_buf, size_t bytes,
-                     void *hip_stream)
+int mm_compute_state_surface(mm_handle *h, const void *in_dev, const mm_surface *in_layout, void *dev_buf,
+                             size_t bytes, void *hip_stream)
 {
     size_t need = 0;
-    if (!h || !in_dev || !dev_buf || mm_state_size(h, &need) || bytes < need) return MM_ERR_INVALID;
-    if (int rc = fmt_check(h->W, h->H, format, nullptr)) return rc;   // (computes no view)
+    if (!h || !in_dev || !in_layout || !dev_buf || mm_state_size(h, &need) || bytes < need)
+        return MM_ERR_INVALID;
+    if (int rc = surf_check_frames(h->W, h->H, in_dev, in_layout, 1)) return rc;   // (computes no view)
+    const Frames fr = frames_of(h->W, h->H, *in_layout, *in_layout);
     hipStream_t s = (hipStream_t)hip_stream;   // NULL: the default stream (HIP convention)
     DEVICE_SCOPE(h);
     // the IIR state is a history of frames, not a function of one input frame
@@ -553,9 +654,19 @@ int mm_compute_state(mm_handle *h, const void *in_dev, int format, void *dev_buf
         return MM_ERR_UNSUPPORTED;
     int ro = order_after_last(h, s);
     if (ro) return ro;
-    const int rc = do_compute_state(h, (const uint8_t *)in_dev, format, dev_buf, s);
+    const int rc = do_compute_state(h, (const uint8_t *)in_dev, fr, dev_buf, s);
     const int rn = note_work(h, s);
     return rc ? rc : rn;
+}
+
+int mm_compute_state(mm_handle *h, const void *in_dev, int format, void *dev_buf, size_t bytes,
+                     void *hip_stream)
+{
+    mm_surface t;
+    size_t need = 0;
+    if (!h || !in_dev || !dev_buf || mm_state_size(h, &need) || bytes < need) return MM_ERR_INVALID;
+    if (int rc = surf_tight(h->W, h->H, format, &t)) return rc;
+    return mm_compute_state_surface(h, in_dev, &t, dev_buf, bytes, hip_stream);
 }
 
 void mm_destroy(mm_handle *h)

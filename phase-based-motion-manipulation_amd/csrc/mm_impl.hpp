@@ -237,6 +237,99 @@ static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
     if (fmt_420(fmt) && p && (p->show_magnitude || p->show_phase)) return MM_ERR_UNSUPPORTED;
     return MM_OK;
 }
+// ---- surfaces (mm_surface, include/mm.h) ----------------------------------
+// u: what pitches, offsets, strides and frame pointers are multiples of
+static inline size_t fmt_unit(int fmt) { return fmt_nv12(fmt) ? 2 : fmt_p010(fmt) ? 4 : fmt_bpp(fmt); }
+// sample bytes of one row (4:2:0: of a luma row and of a (Cb, Cr) row alike)
+static inline size_t fmt_row_bytes(int W, int fmt)
+{
+    return (size_t)W * (fmt_p010(fmt) ? 2 : fmt_nv12(fmt) ? 1 : fmt_bpp(fmt));
+}
+static inline int surf_tight(int W, int H, int fmt, mm_surface *s)
+{
+    if (!s || W < 1 || H < 1 || !fmt_valid(fmt)) return MM_ERR_INVALID;
+    if (int rc = fmt_check(W, H, fmt, nullptr)) return rc;
+    s->format = fmt;
+    s->pitch = fmt_row_bytes(W, fmt);
+    s->chroma_offset = fmt_420(fmt) ? s->pitch * (size_t)H : 0;
+    s->chroma_pitch = fmt_420(fmt) ? s->pitch : 0;
+    s->frame_stride = fmt_frame_bytes(W, H, fmt);
+    return MM_OK;
+}
+// The largest extent the kernels' 32-bit byte offsets from a frame's base
+// reach (ld_off / st_off / st_stream take `unsigned`): every sample below 2^32.
+static constexpr unsigned long long kSurfMaxExtent = 1ull << 32;
+// mm_surface_bytes: the layout's validation and its extent (host only)
+static inline int surf_check(int W, int H, const mm_surface *s, size_t *extent)
+{
+    if (!s || W < 1 || H < 1 || !fmt_valid(s->format)) return MM_ERR_INVALID;
+    const int fmt = s->format;
+    if (int rc = fmt_check(W, H, fmt, nullptr)) return rc;
+    const size_t u = fmt_unit(fmt), rb = fmt_row_bytes(W, fmt);
+    if (s->pitch < rb || s->pitch % u) return MM_ERR_INVALID;
+    size_t end;   // the byte after the last sample of the RGBA / luma plane
+    if (__builtin_mul_overflow(s->pitch, (size_t)(H - 1), &end) || __builtin_add_overflow(end, rb, &end))
+        return MM_ERR_INVALID;
+    if (fmt_420(fmt)) {
+        if (s->chroma_pitch < rb || s->chroma_pitch % u || s->chroma_offset % u || s->chroma_offset < end)
+            return MM_ERR_INVALID;
+        if (__builtin_mul_overflow(s->chroma_pitch, (size_t)(H / 2 - 1), &end) ||
+            __builtin_add_overflow(end, s->chroma_offset, &end) || __builtin_add_overflow(end, rb, &end))
+            return MM_ERR_INVALID;
+    } else if (s->chroma_offset || s->chroma_pitch) {
+        return MM_ERR_INVALID;
+    }
+    if (end > kSurfMaxExtent) return MM_ERR_UNSUPPORTED;
+    if (extent) *extent = end;
+    return MM_OK;
+}
+// What a frame entry point asks of `count` frames at `p` in layout `s`
+// (host-memory frames go through copies into aligned staging buffers: their
+// pointers need no alignment, as before)
+static inline int surf_check_frames(int W, int H, const void *p, const mm_surface *s, int count,
+                                    bool on_device = true)
+{
+    size_t extent;
+    if (int rc = surf_check(W, H, s, &extent)) return rc;
+    const size_t u = fmt_unit(s->format);
+    if (on_device && reinterpret_cast<uintptr_t>(p) % u) return MM_ERR_INVALID;
+    if (count > 1 && (s->frame_stride < extent || s->frame_stride % u)) return MM_ERR_INVALID;
+    return MM_OK;
+}
+static inline Geo::Lay surf_lay(const mm_surface &s)
+{
+    Geo::Lay l;
+    l.pitch = (unsigned)s.pitch;            // (< 2^32 wherever a second row exists: extent <= 2^32)
+    l.c_off = (unsigned)s.chroma_offset;
+    l.c_pitch = (unsigned)s.chroma_pitch;
+    l.pad_ = 0;
+    l.stride = s.frame_stride;
+    return l;
+}
+// The frames of one call: their format and where the two sides lie.
+struct Frames {
+    int fmt;
+    Geo::Lay in, out;
+    size_t fb;       // mm_frame_bytes
+    bool packed;     // both sides tight, frames back to back: a passthrough is one plain copy
+};
+static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surface &lo)
+{
+    Frames f;
+    f.fmt = li.format;
+    f.in = surf_lay(li);
+    f.out = surf_lay(lo);
+    f.fb = fmt_frame_bytes(W, H, f.fmt);
+    mm_surface t;
+    (void)surf_tight(W, H, f.fmt, &t);
+    auto tight = [&](const mm_surface &s) {
+        return s.pitch == t.pitch && s.chroma_offset == t.chroma_offset && s.chroma_pitch == t.chroma_pitch &&
+               s.frame_stride == t.frame_stride;
+    };
+    f.packed = tight(li) && tight(lo);
+    return f;
+}
+
 static_assert(kFmtNV12 == MM_NV12, "the kernels' NV12 template argument is the format code");
 static_assert(kFmtP010 == MM_P010, "the kernels' P010 template argument is the format code");
 // Runs the statement with the compile-time format FMT_ of the runtime `fmt`
@@ -278,13 +371,17 @@ static inline void nv12_chroma_matrix(double m[4])
         }
     }
 }
-// The launch geometry for frames of `fmt`: the handle's, plus the NV12 range's
+// The launch geometry for frames of `fmt`: the handle's, the two sides'
+// layouts, plus the NV12 range's
 // scales and offsets (limited: Y 16 .. 235, C 16 .. 240; full: 0 .. 255) or
 // the P010 range's (limited: Y 64 .. 940, C 64 .. 960; full: 0 .. 1023; the
 // input side in units of the 16-bit word, 64 per code: u = 64).
-static inline Geo geo_of(const mm_handle *h, int fmt)
+static inline Geo geo_of(const mm_handle *h, const Frames &fr)
 {
     Geo g = h->geo;
+    const int fmt = fr.fmt;
+    g.li = fr.in;
+    g.lo = fr.out;
     if (fmt_420(fmt)) {
         const bool full = fmt == MM_NV12_FULL || fmt == MM_P010_FULL, p10 = fmt_p010(fmt);
         const double ys = p10 ? (full ? 1023.0 : 876.0) : (full ? 255.0 : 219.0);
@@ -575,13 +672,13 @@ static int set_attrs(int W)
 }
 
 template <int LOG2N>
-static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, int fmt, hipStream_t s, c2 *G)
+static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, const Frames &fr, hipStream_t s, c2 *G)
 {
+    const int fmt = fr.fmt;
     const int ppf = (h->H + 1) / 2;   // odd H: the last pair's second row is zero
     const int total = ppf * nframes;
     // fewer than 2 workgroups per CU at the batch form: the one-pair form
     const bool lat = (total + k1_groups<LOG2N>() - 1) / k1_groups<LOG2N>() < 512;
-    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     ProfScope ps(h, s, MM_K_ROWS_FWD, nframes);
 #define MM_K1_LAUNCH(F, GEN, LAT)                                                                  \
     do {                                                                                           \
@@ -591,11 +688,11 @@ static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, int fmt, hipS
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_fwd<LOG2N, F, GEN, LAT>), \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
         hipLaunchKernelGGL((k_rows_fwd<LOG2N, F, GEN, LAT>), dim3((total + gpw - 1) / gpw),         \
-                           dim3(gpw * fft_T<LOG2N>()), lds, s, in, fb, ppf, total, g,              \
+                           dim3(gpw * fft_T<LOG2N>()), lds, s, in, ppf, total, g,                  \
                            h->d_col3, h->d_row3, h->d_col, h->d_row, h->d_tw, G, h->g_stride);     \
     } while (0)
     const bool gen = h->geo.ox || h->geo.oy;   // odd W/H: taps span i-2 .. i+1
-    const Geo g = geo_of(h, fmt);
+    const Geo g = geo_of(h, fr);
     if (gen) {   // (no NV12 / P010 instance: odd sizes are not 4:2:0)
         MM_FMT_SWITCH_RGBA(fmt, MM_K1_LAUNCH(FMT_, true, false))
     } else {
@@ -716,13 +813,31 @@ static int place_batch(mm_handle *h, int n, hipStream_t s, int *base)
 }
 
 static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, int nframes,
-                     int fmt, hipStream_t s);
+                     const Frames &fr, hipStream_t s);
 
 // k_rows_inv_compose's geometry: even sizes whose quads tile the rows (W % 8 == 0
 // puts x0 on a multiple of 4), the horizontal blur's float4 taps inside the
 // canvas, and no vertical blur tap wrapping (list row of output row i + v is i + v)
-static bool k34_fits(const mm_handle *h)
+// ... and, for NV12, layouts whose quads are dwords: the fused kernels read
+// two (Cb, Cr) pairs and store four luma codes or two pairs as ONE dword at
+// column X % 4 == 0 of a row, so every row they touch must start on a multiple
+// of 4: both frame pointers, the output pitch, both chroma planes' offsets and
+// pitches, and, with more than one frame in the launch, both frame strides
+// (a stream whose frames are 2 mod 4 apart alternates alignment: decided for
+// all its frames here, not from its first one).  NV12's unit is 2, so a valid
+// layout may fail this: it takes the unfused pair, same results.  (RGBA8's and
+// P010's quads are multi-dword accesses at dword-aligned addresses, which the
+// unit, 4, gives every layout: mm_kernels.hpp ld_quad_a4.)
+static bool nv12_quads_aligned(const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in) + fr.in.c_off, b = reinterpret_cast<uintptr_t>(out);
+    uintptr_t m = a | fr.in.c_pitch | b | fr.out.pitch | (b + fr.out.c_off) | fr.out.c_pitch;
+    if (nframes > 1) m |= fr.in.stride | fr.out.stride;
+    return (m & 3u) == 0;
+}
+static bool k34_fits(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
+{
+    if (fmt_nv12(fr.fmt) && !nv12_quads_aligned(in, out, fr, nframes)) return false;
     const Geo &g = h->geo;
     return g.N <= 4096 &&   // two transforms per workgroup: 2 N / 8 <= 1024 threads
            !g.ox && !g.oy && g.W % 8 == 0 && g.x0 >= 4 && g.x0 % 4 == 0 &&
@@ -753,11 +868,11 @@ static int k34_strip_rows(const mm_handle *h, int nout)
 
 template <int LOG2N>
 static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, int nframes,
-                     int fmt, hipStream_t s)
+                     const Frames &fr, hipStream_t s)
 {
     const int nout = nframes - frame0;
     if (nout <= 0) return MM_OK;
-    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
+    const int fmt = fr.fmt;
     const int R = k34_strip_rows(h, nout);
     // Short launches (the one-frame call) at N <= 1024 whose strips fit one
     // workgroup round (4 waves per SIMD at <= 128 VGPRs: 1024 / 4T workgroups
@@ -769,7 +884,7 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
     // 270 strips take two rounds (48.0 -> 54.4 us): K3 -> K4 there
     // (MM_K34_ONESHOT=2 forces it, 0 disables it).
     constexpr int k34o_per_cu = 4 * fft_T<LOG2N>() <= 1024 ? 1024 / (4 * fft_T<LOG2N>()) : 0;
-    if constexpr (LOG2N <= 11) if (R == 0 && h->k34_rows < 0 && h->k34_oneshot && k34_fits(h) &&
+    if constexpr (LOG2N <= 11) if (R == 0 && h->k34_rows < 0 && h->k34_oneshot && k34_fits(h, in, out, fr, nframes) &&
                                    ((LOG2N <= 10 && (h->H + 3) / 4 * nout <= k34o_per_cu * h->num_cu) ||
                                     h->k34_oneshot == 2)) {
         const int strips = (h->H + 3) / 4;
@@ -777,18 +892,18 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
         const dim3 grid((unsigned)(strips * nout)), block(4 * fft_T<LOG2N>());
         ProfScope ps(h, s, MM_K_ROWS_INV_COMPOSE, nout);
         MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_rows_inv_compose4<LOG2N, FMT_>), grid, block, lds, s, h->d_Q,
-                                              h->q_stride, in, out, fb, frame0, strips, geo_of(h, fmt), h->blur,
+                                              h->q_stride, in, out, frame0, strips, geo_of(h, fr), h->blur,
                                               h->d_col3, h->d_row3, h->d_tw))
         HIPCHK(hipGetLastError());
         return MM_OK;
     }
-    if (R >= 4 && k34_fits(h)) {   // K3 + K4 fused: Yh stays on chip
+    if (R >= 4 && k34_fits(h, in, out, fr, nframes)) {   // K3 + K4 fused: Yh stays on chip
         const int strips = (h->H + R - 1) / R, steps = R / 4 + 1;
         const size_t lds = sizeof(c2) * 2 * lds_complex<(1 << LOG2N)>();
         const dim3 grid((unsigned)(strips * nout)), block(2 * fft_T<LOG2N>());
         ProfScope ps(h, s, MM_K_ROWS_INV_COMPOSE, nout);
         MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_rows_inv_compose<LOG2N, FMT_>), grid, block, lds, s, h->d_Q,
-                                              h->q_stride, in, out, fb, frame0, strips, steps, geo_of(h, fmt),
+                                              h->q_stride, in, out, frame0, strips, steps, geo_of(h, fr),
                                               h->blur, h->d_col3, h->d_row3, h->d_tw))
         HIPCHK(hipGetLastError());
         return MM_OK;
@@ -807,22 +922,22 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
                            h->blur, h->d_tw);
         HIPCHK(hipGetLastError());
     }
-    return launch_k4(h, in, out, frame0, nframes, fmt, s);
+    return launch_k4(h, in, out, frame0, nframes, fr, s);
 }
 
 // K4 k_compose over chunk frames [frame0, nframes) (Yh of those frames ready)
 static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, int nframes,
-                     int fmt, hipStream_t s)
+                     const Frames &fr, hipStream_t s)
 {
     const int nout = nframes - frame0;
     if (nout <= 0) return MM_OK;
-    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
+    const int fmt = fr.fmt;
     if (h->geo.ox || h->geo.oy) {   // odd W/H: the crop samples between texels
         const size_t tot = (size_t)nout * h->W * h->H;
         ProfScope ps(h, s, MM_K_COMPOSE, nout);
         const dim3 grid((unsigned)((tot + 255) / 256));
         MM_FMT_SWITCH_RGBA(fmt, hipLaunchKernelGGL((k_compose_odd<FMT_>), grid, dim3(256), 0, s, h->d_Yh,
-                                              h->yh_stride, in, out, fb, frame0, nout, h->geo, h->blur,
+                                              h->yh_stride, in, out, frame0, nout, geo_of(h, fr), h->blur,
                                               h->d_col, h->d_row))
         HIPCHK(hipGetLastError());
         return MM_OK;
@@ -831,9 +946,34 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
     const dim3 grid(rt * ct * nout);
     ProfScope ps(h, s, MM_K_COMPOSE, nout);
     MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_compose<FMT_>), grid, dim3(kTileCols), 0, s, h->d_Yh,
-                                          h->yh_stride, in, out, fb, frame0, rt, ct, geo_of(h, fmt), h->blur,
+                                          h->yh_stride, in, out, frame0, rt, ct, geo_of(h, fr), h->blur,
                                           h->d_col3, h->d_row3))
     HIPCHK(hipGetLastError());
+    return MM_OK;
+}
+
+// Passthrough of n frames (the first frame, apply_magnification = 0): the
+// W x H samples bitwise, the destination's padding untouched.  Tight frames
+// back to back on both sides are one device copy; any other layout goes
+// through k_copy_rows, one launch for the n frames.
+static int copy_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const Frames &fr, hipStream_t s)
+{
+    if (n <= 0) return MM_OK;
+    if (fr.packed) {
+        HIPCHK(hipMemcpyAsync(out, in, fr.fb * n, hipMemcpyDeviceToDevice, s));
+        return MM_OK;
+    }
+    const unsigned rb = (unsigned)fmt_row_bytes(h->W, fr.fmt);
+    const int rows = fmt_420(fr.fmt) ? h->H + h->H / 2 : h->H;
+    const Geo g = geo_of(h, fr);
+    for (int f0 = 0; f0 < n; f0 += 32768) {   // (grid y <= 65535)
+        const dim3 grid((unsigned)rows, (unsigned)std::min(32768, n - f0));
+        const uint8_t *src = in + fr.in.stride * f0;
+        uint8_t *dst = out + fr.out.stride * f0;
+        if (fmt_nv12(fr.fmt)) hipLaunchKernelGGL((k_copy_rows<uint16_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
+        else hipLaunchKernelGGL((k_copy_rows<uint32_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
+        HIPCHK(hipGetLastError());
+    }
     return MM_OK;
 }
 
@@ -896,7 +1036,7 @@ static int steer_alloc(mm_handle *h, hipStream_t s)
 // (mm_compute_state) is always seeded).  write == false: outputs pass through,
 // the state keeps following the input.
 template <int LOG2N>
-static int run_steer(mm_handle *h, const uint8_t *in, uint8_t *out, int n, int fmt, float *sst,
+static int run_steer(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const Frames &fr, float *sst,
                      bool write, hipStream_t s, const c2 *G)
 {
     constexpr int N = 1 << LOG2N;
@@ -994,22 +1134,19 @@ static int run_steer(mm_handle *h, const uint8_t *in, uint8_t *out, int n, int f
         }
     }
     if (sst == h->d_sst) h->steer_valid = true;
-    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
-    if (!write) {
-        if (out) HIPCHK(hipMemcpyAsync(out, in, fb * n, hipMemcpyDeviceToDevice, s));
-        return MM_OK;
-    }
-    if (seed) HIPCHK(hipMemcpyAsync(out, in, fb, hipMemcpyDeviceToDevice, s));
-    return launch_k4(h, in, out, seed, n, fmt, s);
+    if (!write) return out ? copy_frames(h, in, out, n, fr, s) : MM_OK;
+    if (seed && (rc = copy_frames(h, in, out, 1, fr, s))) return rc;
+    return launch_k4(h, in, out, seed, n, fr, s);
 }
 
 // ProcessDebugView (.cs:119-123, :234-257) for batch frames [first, n) whose
 // row spectra are in G: k_dbg_cols (view textures) -> k_dbg_out (crop or split
 // screen).  The state follows the input (.cs:122): the caller's slot update.
 template <int LOG2N>
-static int run_debug(mm_handle *h, uint8_t *out, int n, int first, int fmt, hipStream_t s,
+static int run_debug(mm_handle *h, uint8_t *out, int n, int first, const Frames &fr, hipStream_t s,
                      const c2 *G)
 {
+    const int fmt = fr.fmt;
     constexpr int N = 1 << LOG2N;
     if (n <= first) return MM_OK;
     const size_t tex_stride = (size_t)2 * N * N;
@@ -1034,21 +1171,19 @@ static int run_debug(mm_handle *h, uint8_t *out, int n, int first, int fmt, hipS
                        tex_stride, first, h->p.show_magnitude, h->p.show_phase, h->geo,
                        h->d_tw_half);
     HIPCHK(hipGetLastError());
-    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     const size_t tot = (size_t)m * h->W * h->H;
     const dim3 grid((unsigned)((tot + 255) / 256));
     MM_FMT_SWITCH_RGBA(fmt, hipLaunchKernelGGL((k_dbg_out<FMT_>), grid, dim3(256), 0, s, h->d_dbg, tex_stride,
-                                          out, fb, first, m, h->p.show_magnitude, h->p.show_phase, h->geo))
+                                          out, first, m, h->p.show_magnitude, h->p.show_phase, geo_of(h, fr)))
     HIPCHK(hipGetLastError());
     return MM_OK;
 }
 
 // One batch of `n` consecutive frames (n <= chunk), all on the device.
 template <int LOG2N>
-static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, int fmt,
+static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const Frames &fr,
                      hipStream_t s)
 {
-    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     const bool mag = h->p.apply_magnification != 0;
     const bool dbg = h->p.show_magnitude || h->p.show_phase;
     // the steerable path's state is its local-phase planes; every other path
@@ -1058,7 +1193,7 @@ static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, int f
     const bool have = h->has_state && (steer || h->g_valid);
     const int first = have ? 0 : 1;
     int rc, base;
-    if (first) HIPCHK(hipMemcpyAsync(out, in, fb, hipMemcpyDeviceToDevice, s));
+    if (first && (rc = copy_frames(h, in, out, 1, fr, s))) return rc;
     if ((rc = place_batch(h, n, s, &base))) return rc;
     c2 *G = h->d_G + h->g_stride * base;
     // G_{t-1}: the state slot; a stream's first frame primes with itself (its
@@ -1069,26 +1204,26 @@ static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, int f
         // but previousSourceTexture still follows the input (.cs:142): K1 of
         // the batch's last frame only.
         const int from = first ? 1 : 0;
-        if (n > from)
-            HIPCHK(hipMemcpyAsync(out + fb * from, in + fb * from, fb * (n - from),
-                                  hipMemcpyDeviceToDevice, s));
-        if ((rc = launch_k1<LOG2N>(h, in + fb * (n - 1), 1, fmt, s, G))) return rc;
+        if (n > from &&
+            (rc = copy_frames(h, in + fr.in.stride * from, out + fr.out.stride * from, n - from, fr, s)))
+            return rc;
+        if ((rc = launch_k1<LOG2N>(h, in + fr.in.stride * (n - 1), 1, fr, s, G))) return rc;
         h->gs = base;
         h->has_state = h->g_valid = true;
         return MM_OK;
     }
-    if ((rc = launch_k1<LOG2N>(h, in, n, fmt, s, G))) return rc;
+    if ((rc = launch_k1<LOG2N>(h, in, n, fr, s, G))) return rc;
     if (dbg) {
         h->steer_valid = false;   // the debug path does not advance the local-phase state
-        rc = run_debug<LOG2N>(h, out, n, first, fmt, s, G);
+        rc = run_debug<LOG2N>(h, out, n, first, fr, s, G);
     } else if (h->p.mode == MM_MODE_STEERABLE) {
         if (first) h->steer_valid = false;
         // two transforms per band workgroup: N <= 4096 (mm_create refuses more)
-        if constexpr (LOG2N <= 12) rc = run_steer<LOG2N>(h, in, out, n, fmt, nullptr, mag, s, G);
+        if constexpr (LOG2N <= 12) rc = run_steer<LOG2N>(h, in, out, n, fr, nullptr, mag, s, G);
         else rc = MM_ERR_UNSUPPORTED;
     } else {
         if ((rc = launch_k2<LOG2N>(h, n, Gprev, G, s))) return rc;
-        rc = launch_k3<LOG2N>(h, in, out, first, n, fmt, s);
+        rc = launch_k3<LOG2N>(h, in, out, first, n, fr, s);
     }
     if (rc) return rc;
     h->gs = base + n - 1;   // the state follows the input in every mode (.cs:142)
@@ -1097,13 +1232,12 @@ static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, int f
 }
 
 template <int LOG2N>
-static int run_stream(mm_handle *h, const uint8_t *in, uint8_t *out, int count, int fmt,
+static int run_stream(mm_handle *h, const uint8_t *in, uint8_t *out, int count, const Frames &fr,
                       hipStream_t s)
 {
-    const size_t fb = fmt_frame_bytes(h->W, h->H, fmt);
     for (int f0 = 0; f0 < count; f0 += h->chunk) {
         const int n = std::min(h->chunk, count - f0);
-        int rc = run_chunk<LOG2N>(h, in + fb * f0, out + fb * f0, n, fmt, s);
+        int rc = run_chunk<LOG2N>(h, in + fr.in.stride * f0, out + fr.out.stride * f0, n, fr, s);
         if (rc) return rc;
     }
     return MM_OK;
@@ -1112,20 +1246,20 @@ static int run_stream(mm_handle *h, const uint8_t *in, uint8_t *out, int count, 
 // The state frame `in` leaves behind: its row spectra (K1) straight into dst;
 // steerable DIFF: its local phases (K1 to a free G slot, then the band path).
 template <int LOG2N>
-static int compute_state(mm_handle *h, const uint8_t *in, int fmt, void *dst, hipStream_t s)
+static int compute_state(mm_handle *h, const uint8_t *in, const Frames &fr, void *dst, hipStream_t s)
 {
     int rc;
     if (h->p.mode == MM_MODE_STEERABLE) {
         int base;
         if ((rc = place_batch(h, 1, s, &base))) return rc;
         c2 *G = h->d_G + h->g_stride * base;
-        if ((rc = launch_k1<LOG2N>(h, in, 1, fmt, s, G))) return rc;
+        if ((rc = launch_k1<LOG2N>(h, in, 1, fr, s, G))) return rc;
         if constexpr (LOG2N <= 12)
-            return run_steer<LOG2N>(h, in, nullptr, 1, fmt, reinterpret_cast<float *>(dst), false, s, G);
+            return run_steer<LOG2N>(h, in, nullptr, 1, fr, reinterpret_cast<float *>(dst), false, s, G);
         else
             return MM_ERR_UNSUPPORTED;
     }
-    return launch_k1<LOG2N>(h, in, 1, fmt, s, reinterpret_cast<c2 *>(dst));
+    return launch_k1<LOG2N>(h, in, 1, fr, s, reinterpret_cast<c2 *>(dst));
 }
 
 // MM_ONLY_LOG2N=n (experiment builds only): instantiate one padded size, so an
@@ -1135,20 +1269,22 @@ static int compute_state(mm_handle *h, const uint8_t *in, int fmt, void *dst, hi
 // or in mm_api.hip itself for a one-size experiment build, MM_ONLY_LOG2N)
 #define MM_SIZE_DECLS(L)                                                                            \
     int mm_size_set_attrs_##L(mm_handle *h);                                                        \
-    int mm_size_stream_##L(mm_handle *h, const uint8_t *in, uint8_t *out, int count, int fmt,       \
-                           hipStream_t s);                                                          \
-    int mm_size_compute_state_##L(mm_handle *h, const uint8_t *in, int fmt, void *dst, hipStream_t s);
+    int mm_size_stream_##L(mm_handle *h, const uint8_t *in, uint8_t *out, int count,                \
+                           const Frames &fr, hipStream_t s);                                        \
+    int mm_size_compute_state_##L(mm_handle *h, const uint8_t *in, const Frames &fr, void *dst,     \
+                                  hipStream_t s);
 #define MM_SIZE_ENTRIES(L) MM_SIZE_ENTRIES_(L)
 #define MM_SIZE_ENTRIES_(L)                                                                         \
     int mm_size_set_attrs_##L(mm_handle *h) { return set_attrs<L>(h->W); }                          \
-    int mm_size_stream_##L(mm_handle *h, const uint8_t *in, uint8_t *out, int count, int fmt,       \
-                           hipStream_t s)                                                           \
+    int mm_size_stream_##L(mm_handle *h, const uint8_t *in, uint8_t *out, int count,                \
+                           const Frames &fr, hipStream_t s)                                         \
     {                                                                                               \
-        return run_stream<L>(h, in, out, count, fmt, s);                                            \
+        return run_stream<L>(h, in, out, count, fr, s);                                             \
     }                                                                                               \
-    int mm_size_compute_state_##L(mm_handle *h, const uint8_t *in, int fmt, void *dst, hipStream_t s) \
+    int mm_size_compute_state_##L(mm_handle *h, const uint8_t *in, const Frames &fr, void *dst,     \
+                                  hipStream_t s)                                                    \
     {                                                                                               \
-        return compute_state<L>(h, in, fmt, dst, s);                                                \
+        return compute_state<L>(h, in, fr, dst, s);                                                 \
     }
 MM_SIZE_DECLS(4)
 MM_SIZE_DECLS(5)

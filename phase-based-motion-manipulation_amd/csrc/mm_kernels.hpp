@@ -56,6 +56,16 @@ struct Geo {
         float yo_scale, yo_bias;    // out: luma code = floor(Yl * yo_scale + yo_bias), bias = offset + 0.5
         float cbo, cro;             // out: chroma code = floor(sum of four (B - Yl) * cbo + 128.5), Cr: R - Yl
     } nv;
+    // Where the caller's frames lie (mm_surface, include/mm.h), in bytes, the
+    // input side (li) and the output side (lo) apart; filled per launch by
+    // geo_of.  Row r of the RGBA / luma plane at r * pitch, (Cb, Cr) row j at
+    // c_off + j * c_pitch, frame k at k * stride.  Every offset inside a frame
+    // fits 32 bits (extent <= 2^32, mm_surface_bytes): workgroup-uniform row
+    // bases plus 32-bit lane offsets, as with the tight layout's W * bpp.
+    struct Lay {
+        unsigned pitch, c_off, c_pitch, pad_;
+        size_t stride;
+    } li, lo;
 };
 
 struct Spec {
@@ -200,6 +210,35 @@ __device__ __forceinline__ void st_stream(void *base, unsigned byte_off, T v)
         __builtin_memcpy(&w, &v, 4);
         __builtin_nontemporal_store(w, reinterpret_cast<unsigned *>(p));
     }
+}
+
+// The fused kernels' RGBA8 quads (16 bytes) and P010 quads (four words, 8
+// bytes) at a dword-aligned address.  A surface's rows start on multiples of
+// its unit, 4 bytes, and not always on multiples of 16 or 8 (a pitch of row
+// bytes + 4, a region of interest at an odd column, a stream whose frames are
+// 4 mod 8 apart); gfx9 global memory takes a multi-dword access at any
+// dword-aligned address, so the quad stays one access in every layout, typed
+// with the alignment it really has.
+typedef unsigned u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ uint4 ld_quad_a4(const void *base, unsigned byte_off)
+{
+    const u32x4_a4 w = *reinterpret_cast<const u32x4_a4 *>(reinterpret_cast<const uint8_t *>(base) + byte_off);
+    return make_uint4(w.x, w.y, w.z, w.w);
+}
+__device__ __forceinline__ void st_stream_quad_a4(void *base, unsigned byte_off, uint4 v)
+{
+    u32x4_a4 w;
+    __builtin_memcpy(&w, &v, 16);
+    __builtin_nontemporal_store(w, reinterpret_cast<u32x4_a4 *>(reinterpret_cast<uint8_t *>(base) + byte_off));
+}
+
+typedef unsigned u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+__device__ __forceinline__ void st_stream_pair_a4(void *base, unsigned byte_off, unsigned lo, unsigned hi)
+{
+    u32x2_a4 w;
+    w.x = lo;
+    w.y = hi;
+    __builtin_nontemporal_store(w, reinterpret_cast<u32x2_a4 *>(reinterpret_cast<uint8_t *>(base) + byte_off));
 }
 
 // |z| rows of the row IFFTs (K3 four-wide path, K34, K34o) start kZShift
@@ -459,20 +498,25 @@ template <int FMT> __device__ __forceinline__ void out_store(uint8_t *base, unsi
 // kernels the half-resolution chroma plane alone, and neither goes through
 // Pix<FMT> (one interleaved pixel per raw_t).  MM_NV12 and MM_NV12_FULL share
 // the instances (FMT = kFmtNV12); their scales and offsets are Geo::nv.
-// Alignment: rows are W bytes and a frame W H 3/2, both only even, so the
-// luma plane is read bytewise and a (Cb, Cr) pair as one 2-byte load; dword
-// accesses only where W % 8 == 0 (the fused kernels' quads).
+// Alignment: frame base, pitches and the chroma offset are only even
+// (mm_surface's unit; tight: rows of W bytes, a frame W H 3/2), so the luma
+// plane is read bytewise and a (Cb, Cr) pair as one 2-byte load; dword
+// accesses only in the fused kernels' quads, which the host launches for NV12
+// only where every row they touch, in every frame of the launch, starts on a
+// multiple of 4 (nv12_quads_aligned, mm_impl.hpp: frame bases, strides,
+// pitches and chroma offsets of both sides); any other layout takes the
+// unfused pair, whose accesses are single samples and pairs.
 //
 // MM_P010 / MM_P010_FULL (FMT = kFmtP010) are the same layout in little-endian
 // 16-bit words, the 10-bit code in the word's high bits (v = word / 64; the low
 // 6 bits of a P016 surface are honoured): 2 W bytes per row, 3 W H per frame.
 // Every NV12 statement above holds with the word as the sample, Geo::nv in
 // word units on input and 10-bit code units on output, and k420<FMT> selects
-// the shared 4:2:0 structure of the kernels.  Alignment: frames are 4-byte
-// aligned (include/mm.h), rows 2 W bytes with W even, so 2-byte luma loads,
-// 4-byte (Cb, Cr) pair loads and 4-byte stores of two words are always
-// aligned; the fused kernels' 8-byte quad stores only if the frame base is
-// 8-byte aligned too (W % 8 == 0 there), which they test per workgroup.
+// the shared 4:2:0 structure of the kernels.  Alignment: frame base, pitches
+// and the chroma offset are multiples of 4 (mm_surface's unit), so 2-byte luma
+// loads, 4-byte (Cb, Cr) pair loads and 4-byte stores of two words are always
+// aligned, and so are the fused kernels' 8-byte quad stores as multi-dword
+// accesses (st_stream_pair_a4).
 constexpr int kFmtNV12 = 16;   // MM_NV12
 constexpr int kFmtP010 = 18;   // MM_P010
 template <int FMT> constexpr bool kNV12 = FMT == kFmtNV12;
@@ -512,7 +556,7 @@ template <int FMT> __device__ __forceinline__ float k1_unit(const Geo &g)
 // REPEAT / CLAMP behaviour exactly)
 __device__ __forceinline__ unsigned nv12_c_off(const Geo &g, int row, unsigned col)
 {
-    return (unsigned)((g.H + (row >> 1)) * g.W) + (col & ~1u);
+    return g.li.c_off + (unsigned)(row >> 1) * g.li.c_pitch + (col & ~1u);
 }
 // (I, Q) of a (Cb, Cr) pair: exact zero for neutral chroma (128, 128)
 __device__ __forceinline__ c2 nv12_iq2(unsigned u, const Geo &g)
@@ -529,7 +573,7 @@ __device__ __forceinline__ c2 p010_iq2(unsigned u, const Geo &g)
 // both for a 4:2:0 format's sample size
 template <int FMT> __device__ __forceinline__ unsigned c420_off(const Geo &g, int row, unsigned col)
 {
-    if constexpr (kP010<FMT>) return nv12_c_off(g, row, col) * 2u;
+    if constexpr (kP010<FMT>) return g.li.c_off + (unsigned)(row >> 1) * g.li.c_pitch + (col & ~1u) * 2u;
     else return nv12_c_off(g, row, col);
 }
 template <int FMT> __device__ __forceinline__ c2 c420_iq2(unsigned u, const Geo &g)
@@ -559,8 +603,8 @@ __device__ __forceinline__ unsigned nv12_ccode(float sum4, float k)
 {
     return (unsigned)fminf(sum4 * k + 128.5f, 255.0f);      // >= 1: |C'| <= 1/2
 }
-// The fused kernels' store of output row i of the quad X .. X+3 (X % 4 == 0,
-// W % 8 == 0: dword aligned): four luma codes as one dword; the even row of a
+// The fused kernels' store of output row i of the quad X .. X+3 (X % 4 == 0;
+// rows dword aligned: nv12_quads_aligned): four luma codes as one dword; the even row of a
 // row pair leaves its chroma differences in cd0, the odd row adds its own and
 // stores the two 2x2 blocks' (Cb, Cr) codes as one dword of chroma row i/2.
 __device__ __forceinline__ void nv12_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
@@ -571,7 +615,7 @@ __device__ __forceinline__ void nv12_store_quad(uint8_t *outp, const Geo &g, int
     unsigned y4 = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) y4 |= nv12_ycode(rr[k], gg[k], bb[k], g, cd[k]) << (8 * k);
-    st_stream<uint32_t>(outp + (size_t)(unsigned)(i * g.W), (unsigned)X, y4);
+    st_stream<uint32_t>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, y4);
     if (!odd) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) cd0[k] = cd[k];
@@ -579,7 +623,7 @@ __device__ __forceinline__ void nv12_store_quad(uint8_t *outp, const Geo &g, int
         const c2 b0 = (cd0[0] + cd[0]) + (cd0[1] + cd[1]), b1 = (cd0[2] + cd[2]) + (cd0[3] + cd[3]);
         const unsigned c4 = nv12_ccode(b0.x, g.nv.cbo) | nv12_ccode(b0.y, g.nv.cro) << 8 |
                             nv12_ccode(b1.x, g.nv.cbo) << 16 | nv12_ccode(b1.y, g.nv.cro) << 24;
-        st_stream<uint32_t>(outp + (size_t)(unsigned)((g.H + (i >> 1)) * g.W), (unsigned)X, c4);
+        st_stream<uint32_t>(outp + (size_t)(g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch), (unsigned)X, c4);
     }
 }
 // MM_P010: the same with 10-bit codes (nv12_ycode's is in 0 .. 1023 by the
@@ -588,28 +632,22 @@ __device__ __forceinline__ unsigned p010_ccode(float sum4, float k)
 {
     return (unsigned)fminf(sum4 * k + 512.5f, 1023.0f);     // >= 1: |C'| <= 1/2
 }
-// A quad's row is four words, 8 bytes, at a multiple of 8 from the frame base
-// (X % 4 == 0, W % 8 == 0, frames 3 W H bytes); the contract aligns the base to
-// 4 bytes only, so `wide` (workgroup-uniform: the base is 8-byte aligned) picks
-// one 8-byte store, else two 4-byte stores.
-__device__ __forceinline__ void p010_st4(uint8_t *row, unsigned X, bool wide, unsigned lo, unsigned hi)
+// A quad's row is four words, 8 bytes, at a multiple of 8 from the row's start
+// (X % 4 == 0); the layout aligns rows to 4 bytes only: one 8-byte store at a
+// dword-aligned address (st_stream_pair_a4), in every layout.
+__device__ __forceinline__ void p010_st4(uint8_t *row, unsigned X, unsigned lo, unsigned hi)
 {
-    if (wide) {
-        st_stream<uint2>(row, X * 2u, make_uint2(lo, hi));
-    } else {
-        st_stream<uint32_t>(row, X * 2u, lo);
-        st_stream<uint32_t>(row, X * 2u + 4u, hi);
-    }
+    st_stream_pair_a4(row, X * 2u, lo, hi);
 }
 __device__ __forceinline__ void p010_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
-                                                bool wide, const float (&rr)[4], const float (&gg)[4],
+                                                const float (&rr)[4], const float (&gg)[4],
                                                 const float (&bb)[4], c2 (&cd0)[4])
 {
     c2 cd[4];
     unsigned y[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) y[k] = nv12_ycode(rr[k], gg[k], bb[k], g, cd[k]) << 6;
-    p010_st4(outp + (size_t)(unsigned)(i * g.W) * 2u, (unsigned)X, wide, y[0] | y[1] << 16, y[2] | y[3] << 16);
+    p010_st4(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, y[0] | y[1] << 16, y[2] | y[3] << 16);
     if (!odd) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) cd0[k] = cd[k];
@@ -617,16 +655,16 @@ __device__ __forceinline__ void p010_store_quad(uint8_t *outp, const Geo &g, int
         const c2 b0 = (cd0[0] + cd[0]) + (cd0[1] + cd[1]), b1 = (cd0[2] + cd[2]) + (cd0[3] + cd[3]);
         const unsigned c0 = p010_ccode(b0.x, g.nv.cbo) << 6 | p010_ccode(b0.y, g.nv.cro) << 22;
         const unsigned c1 = p010_ccode(b1.x, g.nv.cbo) << 6 | p010_ccode(b1.y, g.nv.cro) << 22;
-        p010_st4(outp + (size_t)(unsigned)((g.H + (i >> 1)) * g.W) * 2u, (unsigned)X, wide, c0, c1);
+        p010_st4(outp + (size_t)(g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch), (unsigned)X, c0, c1);
     }
 }
 // the fused kernels' quad store for a 4:2:0 format
 template <int FMT>
 __device__ __forceinline__ void c420_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
-                                                [[maybe_unused]] bool wide, const float (&rr)[4],
+                                                const float (&rr)[4],
                                                 const float (&gg)[4], const float (&bb)[4], c2 (&cd0)[4])
 {
-    if constexpr (kP010<FMT>) p010_store_quad(outp, g, i, X, odd, wide, rr, gg, bb, cd0);
+    if constexpr (kP010<FMT>) p010_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
     else nv12_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
 }
 // the fused kernels' load of the two (Cb, Cr) pairs of the quad X .. X+3 in
@@ -635,10 +673,10 @@ template <int FMT>
 __device__ __forceinline__ void c420_quad_pairs(const uint8_t *img, const Geo &g, int row, unsigned X,
                                                 unsigned &p0, unsigned &p1)
 {
-    if constexpr (kP010<FMT>) {   // two 4-byte loads: the base is 4-byte aligned only
+    if constexpr (kP010<FMT>) {   // two 4-byte loads: rows are 4-byte aligned only
         p0 = ld_off<uint32_t>(img, c420_off<FMT>(g, row, X));
         p1 = ld_off<uint32_t>(img, c420_off<FMT>(g, row, X) + 4u);
-    } else {
+    } else {                      // one dword (rows dword aligned: nv12_quads_aligned)
         p0 = ld_off<uint32_t>(img, nv12_c_off(g, row, X));
         p1 = p0 >> 16;
     }
@@ -654,7 +692,7 @@ __device__ __forceinline__ void c420_quad_pairs(const uint8_t *img, const Geo &g
 #endif
 template <int LOG2N, int FMT, bool GEN = false, bool LAT = false>
 __global__ __launch_bounds__((k1_gpw<LOG2N, LAT>() * fft_T<LOG2N>()))
-void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pairs_per_frame,
+void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
                 int total_pairs, Geo g, const float4 *__restrict__ colW3,
                 const float4 *__restrict__ rowW3, const Tap4 *__restrict__ colT,
                 const Tap4 *__restrict__ rowT, const c2 *__restrict__ tw,
@@ -672,7 +710,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
     const bool valid = logical < total_pairs;
     const int frame = valid ? logical / pairs_per_frame : 0;
     const int ra = valid ? 2 * (logical % pairs_per_frame) : 0;  // image row of pair
-    const uint8_t *img = frames + (size_t)frame * frame_bytes;
+    const uint8_t *img = frames + (size_t)frame * g.li.stride;
 
     // vertical part of the separable resample: V_a, V_b over all source columns.
     // Taps of image row r lie on source rows r-1..r+1 (w3 tables), so the pair
@@ -708,8 +746,8 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
             unsigned pa[4], pb[4];   // source row byte offsets
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                pa[m] = (unsigned)(wrap_near(ta.idx[m], g.H, g.edge) * g.W * BPP);
-                pb[m] = (unsigned)(wrap_near(tb.idx[m], g.H, g.edge) * g.W * BPP);
+                pa[m] = (unsigned)wrap_near(ta.idx[m], g.H, g.edge) * g.li.pitch;
+                pb[m] = (unsigned)wrap_near(tb.idx[m], g.H, g.edge) * g.li.pitch;
             }
             for (int i = t; i < g.W; i += T) {
                 float va = 0.0f, vb = 0.0f;
@@ -743,7 +781,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
             }
             const uint8_t *rowp[6];   // workgroup-uniform source row pointers
 #pragma unroll
-            for (int d = 0; d < 6; ++d) rowp[d] = img + (unsigned)(wrap_near(r0 - 1 + d, g.H, g.edge) * g.W * BPP);
+            for (int d = 0; d < 6; ++d) rowp[d] = img + (unsigned)wrap_near(r0 - 1 + d, g.H, g.edge) * g.li.pitch;
             constexpr int CT = N / (2 * T);          // columns per thread (W <= N)
             constexpr int CB = BPP == 16 ? 1 : CT;   // columns per load batch
             c2 *V2g1 = lds_all + lds_complex<N>();
@@ -781,7 +819,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, size_t frame_bytes, int pair
         const c2 w0 = mk(wa.x, wb.x), w1 = mk(wa.y, wb.y), w2 = mk(wa.z, wb.z);
         const uint8_t *rowp[4];   // workgroup-uniform source row pointers
 #pragma unroll
-        for (int d = 0; d < 4; ++d) rowp[d] = img + (unsigned)(wrap_near(ra - 1 + d, g.H, g.edge) * g.W * BPP);
+        for (int d = 0; d < 4; ++d) rowp[d] = img + (unsigned)wrap_near(ra - 1 + d, g.H, g.edge) * g.li.pitch;
         // W <= N = 8T: at most 8 columns per thread
 #pragma unroll
         for (int h = 0; h < 8 / UB; ++h) {
@@ -2360,7 +2398,7 @@ constexpr int kTileRows = MM_K4_ROWS, kTileCols = MM_K4_COLS;
 template <int FMT>
 __global__ __launch_bounds__(kTileCols)
 void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__restrict__ frames_in,
-               uint8_t *__restrict__ frames_out, size_t frame_bytes, int frame0, int row_tiles,
+               uint8_t *__restrict__ frames_out, int frame0, int row_tiles,
                int col_tiles, Geo g, Blur5 bw, const float4 *__restrict__ colW3,
                const float4 *__restrict__ rowW3)
 {
@@ -2373,7 +2411,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     const int rt = b % row_tiles;
     const int frame = frame0 + b / row_tiles;
     const int i0 = rt * TR, c0 = ct * TC;
-    const uint8_t *img = frames_in + (size_t)frame * frame_bytes;
+    const uint8_t *img = frames_in + (size_t)frame * g.li.stride;
 
     // Staged entry (sr, j) is source pixel (row i0-1+sr, column c0-1+j), wrapped
     // or clamped like the resample's sampler.  Rows are workgroup-uniform (scalar
@@ -2385,7 +2423,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     // (NV12: the pixel's (Cb, Cr) pair, shared with its 2x2 neighbours)
     auto src_off = [&](int row, unsigned col) {
         if constexpr (k420<FMT>) return c420_off<FMT>(g, row, col);
-        else return (unsigned)(row * g.W + col) * Pix<FMT>::bpp;
+        else return (unsigned)row * g.li.pitch + col * Pix<FMT>::bpp;
     };
     const unsigned colA = (unsigned)wrap_near(min(c0 - 1 + tid, g.W), g.W, g.edge);
     raw_t pa[TR + 2];
@@ -2428,7 +2466,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
         const c2 a = iq[sr * WC + tid], m = iq[sr * WC + tid + 1], c = iq[sr * WC + tid + 2];
         hc[sr] = wc.x * a + wc.y * m + wc.z * c;
     }
-    uint8_t *outp = frames_out + (size_t)frame * frame_bytes;
+    uint8_t *outp = frames_out + (size_t)frame * g.lo.stride;
     const Blur5 bv = vblur_w<FMT>(bw);
     [[maybe_unused]] c2 cd0;   // NV12: the even row's chroma differences
 #pragma unroll
@@ -2453,8 +2491,9 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 c2 cd;
                 const unsigned yc = nv12_ycode(rr, gg, bb, g, cd);
                 if constexpr (kP010<FMT>) {   // one 16-bit word per lane (always aligned)
-                    st_off<uint16_t>(outp, (unsigned)(i * g.W + X) * 2u, (uint16_t)(yc << 6));
-                } else if (MM_NV12_K4_PACK && g.W % 4 == 0 && frame_bytes % 4 == 0) {
+                    st_off<uint16_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X * 2u, (uint16_t)(yc << 6));
+                } else if (MM_NV12_K4_PACK && g.W % 4 == 0 &&
+                           ((reinterpret_cast<uintptr_t>(outp) | g.lo.pitch) & 3u) == 0) {
                     // diagnostic: the four lanes of a quad gather their codes
                     // (quad-perm broadcasts) and lane 0 stores one dword
                     auto bc = [&](int ctrl) {
@@ -2464,9 +2503,9 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                                                          : __builtin_amdgcn_mov_dpp((int)yc, 0xFF, 0xF, 0xF, true));
                     };
                     const unsigned y4 = bc(0x00) | bc(0x55) << 8 | bc(0xAA) << 16 | bc(0xFF) << 24;
-                    if ((X & 3) == 0) st_off<uint32_t>(outp, (unsigned)(i * g.W + X), y4);
+                    if ((X & 3) == 0) st_off<uint32_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X, y4);
                 } else {
-                    st_off<uint8_t>(outp, (unsigned)(i * g.W + X), (uint8_t)yc);
+                    st_off<uint8_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X, (uint8_t)yc);
                 }
                 if (r % 2 == 0) {
                     cd0 = cd;
@@ -2478,14 +2517,15 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                         __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
                     if constexpr (kP010<FMT>) {
                         const unsigned cc10 = p010_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
-                        st_off<uint16_t>(outp, (unsigned)((g.H + (i >> 1)) * g.W + X) * 2u, (uint16_t)(cc10 << 6));
+                        st_off<uint16_t>(outp, g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch + (unsigned)X * 2u,
+                                         (uint16_t)(cc10 << 6));
                     } else {
                         const unsigned cc8 = nv12_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
-                        st_off<uint8_t>(outp, (unsigned)((g.H + (i >> 1)) * g.W + X), (uint8_t)cc8);
+                        st_off<uint8_t>(outp, g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch + (unsigned)X, (uint8_t)cc8);
                     }
                 }
             } else {
-                out_store<FMT>(outp + (unsigned)(i * g.W * Pix<FMT>::bpp), (unsigned)X, rr, gg, bb);
+                out_store<FMT>(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
             }
         }
     }
@@ -2522,7 +2562,7 @@ template <int LOG2N, int FMT>
 __global__ __launch_bounds__(2 * fft_T<LOG2N>()) __attribute__((amdgpu_waves_per_eu(4)))
 void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         const uint8_t *__restrict__ frames_in, uint8_t *__restrict__ frames_out,
-                        size_t frame_bytes, int frame0, int strips, int steps, Geo g, Blur5 bw,
+                        int frame0, int strips, int steps, Geo g, Blur5 bw,
                         const float4 *__restrict__ colW3, const float4 *__restrict__ rowW3,
                         const c2 *__restrict__ tw)
 {
@@ -2539,10 +2579,8 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     const int frame = frame0 + b / strips;
     const int i0 = (b % strips) * 4 * (steps - 1);
     const c2 *Qf = Q + (size_t)frame * q_stride;
-    const uint8_t *img = frames_in + (size_t)frame * frame_bytes;
-    uint8_t *outp = frames_out + (size_t)frame * frame_bytes;
-    // P010: 8-byte quad stores only from an 8-byte aligned frame (workgroup-uniform)
-    [[maybe_unused]] const bool wide8 = (reinterpret_cast<uintptr_t>(outp) & 7u) == 0;
+    const uint8_t *img = frames_in + (size_t)frame * g.li.stride;
+    uint8_t *outp = frames_out + (size_t)frame * g.lo.stride;
 
     const int q = threadIdx.x;
     const bool vq = 4 * q < g.W;
@@ -2558,8 +2596,8 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
         if constexpr (k420<FMT>) {
             // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
             // outer two wrapped or clamped as pixels, then halved): the quad's
-            // own two pairs as one dword (W % 8 == 0, X % 4 == 0: aligned in
-            // every frame of a stream), the outer two as 2-byte loads
+            // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
+            // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
             // (P010: pairs are dwords, the quad's own two as two dword loads)
             const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
             unsigned pm0, pm1;
@@ -2570,11 +2608,12 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
             a[3] = a[4] = c420_iq2<FMT>(pm1, g);
             a[5] = c420_iq2<FMT>(pr, g);
         } else {
-            const unsigned base = (unsigned)(row * g.W);
+            // (in pixels: an RGBA pitch is a multiple of the pixel size)
+            const unsigned base = (unsigned)row * (g.li.pitch / bpp);
             raw_t p[6];
             p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
-            if constexpr (bpp == 4) {
-                const uint4 m = ld_off<uint4>(img, (base + (unsigned)X) * bpp);
+            if constexpr (bpp == 4) {   // one 16-byte load (dword aligned: ld_quad_a4)
+                const uint4 m = ld_quad_a4(img, (base + (unsigned)X) * bpp);
                 p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
             } else {
 #pragma unroll
@@ -2724,9 +2763,10 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                                          bv.w2 * (yw[r][k] + yw[r + 4][k]);
                         yiq_rgb<FMT>(yb, cc, rr[k], gg[k], bb[k]);
                     }
-                    [[maybe_unused]] const unsigned o = (unsigned)(i * g.W + X);
+                    // (in pixels: an RGBA pitch is a multiple of the pixel size)
+                    [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
                     if constexpr (k420<FMT>) {
-                        c420_store_quad<FMT>(outp, g, i, X, r & 1, wide8, rr, gg, bb, cd0);
+                        c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
                     } else if constexpr (bpp == 4) {
                         uint4 px;
                         px.x = out_pack<FMT>(rr[0], gg[0], bb[0]);
@@ -2735,7 +2775,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         px.w = out_pack<FMT>(rr[3], gg[3], bb[3]);
                         // scalar row base + the thread's column offset: one
                         // live VGPR, not a hoisted offset per row
-                        st_stream<uint4>(outp + (size_t)(unsigned)(i * g.W) * 4u, (unsigned)X * 4u, px);
+                        st_stream_quad_a4(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 4u, px);
                     } else {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) out_store<FMT>(outp, o + k, rr[k], gg[k], bb[k]);
@@ -2779,7 +2819,7 @@ template <int LOG2N, int FMT>
 __global__ __launch_bounds__(4 * fft_T<LOG2N>())
 void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                          const uint8_t *__restrict__ frames_in, uint8_t *__restrict__ frames_out,
-                         size_t frame_bytes, int frame0, int strips, Geo g, Blur5 bw,
+                         int frame0, int strips, Geo g, Blur5 bw,
                          const float4 *__restrict__ colW3, const float4 *__restrict__ rowW3,
                          const c2 *__restrict__ tw)
 {
@@ -2796,10 +2836,8 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     const int frame = frame0 + b / strips;
     const int i0 = (b % strips) * 4;
     const c2 *Qf = Q + (size_t)frame * q_stride;
-    const uint8_t *img = frames_in + (size_t)frame * frame_bytes;
-    uint8_t *outp = frames_out + (size_t)frame * frame_bytes;
-    // P010: 8-byte quad stores only from an 8-byte aligned frame (workgroup-uniform)
-    [[maybe_unused]] const bool wide8 = (reinterpret_cast<uintptr_t>(outp) & 7u) == 0;
+    const uint8_t *img = frames_in + (size_t)frame * g.li.stride;
+    uint8_t *outp = frames_out + (size_t)frame * g.lo.stride;
 
     // ---- K3 on list-row pair i0/2 + grp (zero beyond Hn) ----
     {
@@ -2848,8 +2886,8 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
         if constexpr (k420<FMT>) {
             // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
             // outer two wrapped or clamped as pixels, then halved): the quad's
-            // own two pairs as one dword (W % 8 == 0, X % 4 == 0: aligned in
-            // every frame of a stream), the outer two as 2-byte loads
+            // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
+            // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
             // (P010: pairs are dwords, the quad's own two as two dword loads)
             const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
             unsigned pm0, pm1;
@@ -2860,11 +2898,12 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
             a[3] = a[4] = c420_iq2<FMT>(pm1, g);
             a[5] = c420_iq2<FMT>(pr, g);
         } else {
-            const unsigned base = (unsigned)(row * g.W);
+            // (in pixels: an RGBA pitch is a multiple of the pixel size)
+            const unsigned base = (unsigned)row * (g.li.pitch / bpp);
             raw_t p[6];
             p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
-            if constexpr (bpp == 4) {
-                const uint4 m = ld_off<uint4>(img, (base + (unsigned)X) * bpp);
+            if constexpr (bpp == 4) {   // one 16-byte load (dword aligned: ld_quad_a4)
+                const uint4 m = ld_quad_a4(img, (base + (unsigned)X) * bpp);
                 p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
             } else {
 #pragma unroll
@@ -2918,16 +2957,16 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                                  bv.w2 * (yw[r][k] + yw[r + 4][k]);
                 yiq_rgb<FMT>(yb, cc, rr[k], gg[k], bb[k]);
             }
-            [[maybe_unused]] const unsigned o = (unsigned)(i * g.W + X);
+            [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
             if constexpr (k420<FMT>) {
-                c420_store_quad<FMT>(outp, g, i, X, r & 1, wide8, rr, gg, bb, cd0);
+                c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
             } else if constexpr (bpp == 4) {
                 uint4 px;
                 px.x = out_pack<FMT>(rr[0], gg[0], bb[0]);
                 px.y = out_pack<FMT>(rr[1], gg[1], bb[1]);
                 px.z = out_pack<FMT>(rr[2], gg[2], bb[2]);
                 px.w = out_pack<FMT>(rr[3], gg[3], bb[3]);
-                st_stream<uint4>(outp, o * 4u, px);
+                st_stream_quad_a4(outp, o * 4u, px);
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) out_store<FMT>(outp, o + k, rr[k], gg[k], bb[k]);
@@ -2947,7 +2986,7 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
 template <int FMT>
 __global__ __launch_bounds__(256)
 void k_compose_odd(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__restrict__ frames_in,
-                   uint8_t *__restrict__ frames_out, size_t frame_bytes, int frame0, int nframes, Geo g,
+                   uint8_t *__restrict__ frames_out, int frame0, int nframes, Geo g,
                    Blur5 bw, const Tap4 *__restrict__ colT, const Tap4 *__restrict__ rowT)
 {
     const size_t npx = (size_t)g.W * g.H;
@@ -2957,7 +2996,7 @@ void k_compose_odd(const float *__restrict__ Yh, size_t yh_stride, const uint8_t
     const int p = (int)(e - (size_t)k * npx);
     const int Y = p / g.W, X = p - Y * g.W;
     const int frame = frame0 + k;
-    const uint8_t *img = frames_in + (size_t)frame * frame_bytes;
+    const uint8_t *img = frames_in + (size_t)frame * g.li.stride;
     const float *Yf = Yh + (size_t)frame * yh_stride;
     const float wt = (g.ox ? 0.5f : 1.0f) * (g.oy ? 0.5f : 1.0f);
     float acc[3] = {0.0f, 0.0f, 0.0f};
@@ -2981,7 +3020,8 @@ void k_compose_odd(const float *__restrict__ Yh, size_t yh_stride, const uint8_t
                     float hi = 0.0f, hq = 0.0f;
                     for (int b = 0; b < 4; ++b) {
                         const int sc = wrap_near(tc.idx[b], g.W, g.edge);
-                        const float2 iq = chroma_iq<FMT>(Pix<FMT>::raw(img, (size_t)sr * g.W + sc));
+                        const float2 iq = chroma_iq<FMT>(ld_off<typename Pix<FMT>::raw_t>(
+                            img, (unsigned)sr * g.li.pitch + (unsigned)sc * Pix<FMT>::bpp));
                         hi += tc.w[b] * iq.x;
                         hq += tc.w[b] * iq.y;
                     }
@@ -2993,7 +3033,8 @@ void k_compose_odd(const float *__restrict__ Yh, size_t yh_stride, const uint8_t
             acc[1] += wt * sat(1.0f * yb + -0.272f * ci + -0.647f * cq);
             acc[2] += wt * sat(1.0f * yb + -1.106f * ci + 1.703f * cq);
         }
-    Pix<FMT>::store(frames_out + (size_t)frame * frame_bytes, (unsigned)p, acc[0], acc[1], acc[2]);
+    Pix<FMT>::store(frames_out + (size_t)frame * g.lo.stride + (size_t)((unsigned)Y * g.lo.pitch), (unsigned)X,
+                    acc[0], acc[1], acc[2]);
 }
 
 // =========================================================================
@@ -3053,7 +3094,7 @@ void k_dbg_cols(const c2 *__restrict__ G, size_t g_stride, float *__restrict__ t
 template <int FMT>
 __global__ __launch_bounds__(256)
 void k_dbg_out(const float *__restrict__ tex, size_t tex_stride, uint8_t *__restrict__ frames_out,
-               size_t frame_bytes, int frame0, int nframes, int show_mag, int show_phase, Geo g)
+               int frame0, int nframes, int show_mag, int show_phase, Geo g)
 {
     const size_t npx = (size_t)g.W * g.H;
     const size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -3082,7 +3123,29 @@ void k_dbg_out(const float *__restrict__ tex, size_t tex_stride, uint8_t *__rest
         v = (show_mag ? mag : pha)[(size_t)(g.y0 + Y) * g.N + g.x0 + X];
     }
     if (kUnorm<FMT>) v = sat(v);   // UNORM destination
-    Pix<FMT>::store(frames_out + (size_t)(frame0 + k) * frame_bytes, (unsigned)p, v, 0.0f, 0.0f);
+    Pix<FMT>::store(frames_out + (size_t)(frame0 + k) * g.lo.stride + (size_t)((unsigned)Y * g.lo.pitch), (unsigned)X,
+                    v, 0.0f, 0.0f);
+}
+
+// =========================================================================
+// passthrough of pitched frames (the first frame, apply_magnification = 0)
+// =========================================================================
+// One workgroup per (plane row, frame): the row's samples and nothing else, in
+// words of U (NV12: 2 bytes, its unit; every other format: 4, which divides
+// its unit).  `rows_y` RGBA / luma rows, then the (Cb, Cr) rows of a 4:2:0
+// frame.  Tight frames on both sides are one plain device copy instead.
+template <class U>
+__global__ __launch_bounds__(256)
+void k_copy_rows(const uint8_t *__restrict__ frames_in, uint8_t *__restrict__ frames_out, Geo g,
+                 unsigned row_bytes, int rows_y)
+{
+    const int r = blockIdx.x, c = r - rows_y;
+    const uint8_t *src = frames_in + (size_t)blockIdx.y * g.li.stride +
+                         (c < 0 ? (size_t)((unsigned)r * g.li.pitch) : (size_t)(g.li.c_off + (unsigned)c * g.li.c_pitch));
+    uint8_t *dst = frames_out + (size_t)blockIdx.y * g.lo.stride +
+                   (c < 0 ? (size_t)((unsigned)r * g.lo.pitch) : (size_t)(g.lo.c_off + (unsigned)c * g.lo.c_pitch));
+    for (unsigned o = threadIdx.x * (unsigned)sizeof(U); o < row_bytes; o += 256u * (unsigned)sizeof(U))
+        st_off<U>(dst, o, ld_off<U>(src, o));
 }
 
 // =========================================================================

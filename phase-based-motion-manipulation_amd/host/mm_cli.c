@@ -9,7 +9,7 @@
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
  *          [--full-range] [--srgb] [--nv12] [--p010] [--standard] [--show-magnitude] [--show-phase]
- *          [--orientations O] [--iir] [--halo K]
+ *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
  *          [--ring-local G [--compare]]
  *
@@ -51,6 +51,11 @@
  * what --nv12 is refused with, and with --nv12.  Bit depths are never
  * converted silently: an 8-bit input with --p010 and a 10-bit input without it
  * are refused.
+ * --surface-align P,R: the device frames, input and output, are held in
+ * mm_surface_aligned(W, H, format, P, R) surfaces (256,16: a hardware
+ * decoder's layout) and go through mm_process_stream_surfaces; for every input
+ * format, --nv12 and --p010 included.  Files and checksums are those of the
+ * run without the flag, byte for byte.  Not with the ring modes.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -123,6 +128,29 @@ static void print_checksums(const unsigned char *dev, size_t fb, int n, int t0)
     if (hs && !hash_frames(dev, fb, n, hs))
         for (int k = 0; k < n; ++k) printf("frame %d %llu\n", t0 + k, (unsigned long long)hs[k]);
     free(hs);
+}
+
+/* n frames between two layouts, the W x H samples only (2D copies per plane) */
+static int surf_copy(void *dst, const mm_surface *dl, const void *src, const mm_surface *sl, int W, int H, int n,
+                     hipMemcpyKind kind, hipStream_t s)
+{
+    mm_surface t;
+    if (mm_surface_tight(W, H, dl->format, &t)) return 1;
+    const size_t rb = t.pitch;   /* sample bytes of a row */
+    if (dl->pitch == rb && sl->pitch == rb && dl->chroma_offset == t.chroma_offset &&
+        sl->chroma_offset == t.chroma_offset && dl->chroma_pitch == t.chroma_pitch &&
+        sl->chroma_pitch == t.chroma_pitch && dl->frame_stride == t.frame_stride &&
+        sl->frame_stride == t.frame_stride)   /* tight on both sides: one copy */
+        return hipMemcpyAsync(dst, src, t.frame_stride * (size_t)n, kind, s) != hipSuccess;
+    for (int k = 0; k < n; ++k) {
+        unsigned char *d = (unsigned char *)dst + dl->frame_stride * (size_t)k;
+        const unsigned char *a = (const unsigned char *)src + sl->frame_stride * (size_t)k;
+        if (hipMemcpy2DAsync(d, dl->pitch, a, sl->pitch, rb, (size_t)H, kind, s) != hipSuccess) return 1;
+        if (t.chroma_pitch && hipMemcpy2DAsync(d + dl->chroma_offset, dl->chroma_pitch, a + sl->chroma_offset,
+                                               sl->chroma_pitch, rb, (size_t)H / 2, kind, s) != hipSuccess)
+            return 1;
+    }
+    return 0;
 }
 
 /* Ring id out of band: rank 0 writes FILE (atomically), the others wait for it. */
@@ -398,6 +426,7 @@ int main(int argc, char **argv)
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
     int nv12 = 0, p010 = 0, srgb = 0;
+    const char *surf_arg = NULL;
     float S = 25.0f;
     const char *in_path = NULL, *out_path = NULL, *ring_id_path = NULL;
     for (int i = 1; i < argc; ++i) {
@@ -429,6 +458,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--ring-local")) ring_local = atoi(v);
         else if (!strcmp(a, "--orientations")) orientations = atoi(v);
         else if (!strcmp(a, "--halo")) halo = atoi(v);
+        else if (!strcmp(a, "--surface-align")) surf_arg = v;
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         ++i;
     }
@@ -498,6 +528,10 @@ int main(int argc, char **argv)
     p.temporal_filter = iir ? MM_FILTER_IIR : MM_FILTER_DIFF;
     p.show_magnitude = show_mag;
     p.show_phase = show_phase;
+    if (surf_arg && (ring_local > 0 || ring_world > 0)) {
+        fprintf(stderr, "--surface-align does not go with the ring modes (they take tight frames)\n");
+        return 2;
+    }
     if (ring_local > 0) {
         if (fi || fo) {
             fprintf(stderr, "--ring-local needs a synthetic stream\n");
@@ -530,8 +564,27 @@ int main(int argc, char **argv)
 
     size_t fb = (size_t)W * H * 4;
     if (nv12 || p010) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
-    void *d_in = NULL, *d_out = NULL;
-    if (hipMalloc(&d_in, fb * B) != hipSuccess || hipMalloc(&d_out, fb * B) != hipSuccess) {
+    /* --surface-align: the frames the operator sees live in `lay` surfaces
+     * (d_in, d_out); d_tin / d_tout are tight device frames for the synthetic
+     * source and for the checksums and files */
+    mm_surface tight, lay;
+    CHECK(mm_surface_tight(W, H, g_fmt, &tight));
+    lay = tight;
+    if (surf_arg) {
+        unsigned long long pa = 0;
+        int ra = 0, rc;
+        if (sscanf(surf_arg, "%llu,%d", &pa, &ra) != 2 ||
+            (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK) {
+            fprintf(stderr, "--surface-align %s: want P,R with P a multiple of the format's unit "
+                            "(pixel size; NV12 2, P010 4) and R >= 1 (4:2:0: even)\n", surf_arg);
+            return 2;
+        }
+        printf("surfaces: pitch %zu  chroma offset %zu  frame stride %zu\n", lay.pitch, lay.chroma_offset,
+               lay.frame_stride);
+    }
+    void *d_in = NULL, *d_out = NULL, *d_tin = NULL, *d_tout = NULL;
+    if (hipMalloc(&d_in, lay.frame_stride * B) != hipSuccess || hipMalloc(&d_out, lay.frame_stride * B) != hipSuccess ||
+        (surf_arg && (hipMalloc(&d_tin, fb * B) != hipSuccess || hipMalloc(&d_tout, fb * B) != hipSuccess))) {
         fprintf(stderr, "hipMalloc failed\n");
         return 1;
     }
@@ -569,25 +622,34 @@ int main(int argc, char **argv)
             }
             if (got == 0) break;
             n = got;
-            hipMemcpyAsync(d_in, host, fb * n, hipMemcpyHostToDevice, s);
+            if (surf_copy(d_in, &lay, host, &tight, W, H, n, hipMemcpyHostToDevice, s)) return 1;
         } else if (fi) {
             size_t got = fread(host, fb, (size_t)n, fi);
             if (got == 0) break;
             n = (int)got;
-            hipMemcpyAsync(d_in, host, fb * n, hipMemcpyHostToDevice, s);
+            if (surf_copy(d_in, &lay, host, &tight, W, H, n, hipMemcpyHostToDevice, s)) return 1;
         } else {
-            CHECK(mm_synth_frames(d_in, W, H, done, n, 0x5EED0000ull, 0, s));
+            CHECK(mm_synth_frames(surf_arg ? d_tin : d_in, W, H, done, n, 0x5EED0000ull, 0, s));
+            if (surf_arg && surf_copy(d_in, &lay, d_tin, &tight, W, H, n, hipMemcpyDeviceToDevice, s)) return 1;
         }
         hipEventRecord(e0, s);
-        CHECK(mm_process_stream(h, d_in, d_out, n, g_fmt, s));
+        if (surf_arg) CHECK(mm_process_stream_surfaces(h, d_in, &lay, d_out, &lay, n, s));
+        else CHECK(mm_process_stream(h, d_in, d_out, n, g_fmt, s));
         hipEventRecord(e1, s);
         hipEventSynchronize(e1);
         float ms = 0.0f;
         hipEventElapsedTime(&ms, e0, e1);
         if (done > 0) t_proc += ms * 1e-3;      /* first call holds the passthrough frame */
-        if (checksum) print_checksums((const unsigned char *)d_out, fb, n, done);
+        const void *d_res = d_out;   /* the output frames, tight */
+        if (surf_arg && (checksum || fo)) {
+            if (surf_copy(d_tout, &tight, d_out, &lay, W, H, n, hipMemcpyDeviceToDevice, s) ||
+                hipStreamSynchronize(s) != hipSuccess)
+                return 1;
+            d_res = d_tout;
+        }
+        if (checksum) print_checksums((const unsigned char *)d_res, fb, n, done);
         if (fo) {
-            hipMemcpy(host, d_out, fb * n, hipMemcpyDeviceToHost);
+            hipMemcpy(host, d_res, fb * n, hipMemcpyDeviceToHost);
             if (y4m_out) {
                 for (int k = 0; k < n; ++k) {
                     if (p010) y4m_p010_to_420p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
@@ -618,6 +680,8 @@ int main(int argc, char **argv)
     free(planes);
     hipFree(d_in);
     hipFree(d_out);
+    hipFree(d_tin);
+    hipFree(d_tout);
     mm_destroy(h);
     return 0;
 }

@@ -19,9 +19,9 @@ construction/Start raises ``MMError`` — loudly, never silently.
 from .binding import (MMError, lib, load_library, LIB_PATH, RGBA8, RGBA32F, RGBA16F, RGBA8_SRGB,
                       NV12, NV12_FULL, P010, P010_FULL, FORMAT_BPP, frame_bytes, nv12_chroma_matrix,
                       EDGE_REPEAT, EDGE_CLAMP, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
-                      FILTER_DIFF, FILTER_IIR, Params, Handle,
+                      FILTER_DIFF, FILTER_IIR, Params, Handle, Surface, has_surfaces,
                       abi_symbols, resample_table, strerror)
-from .processor import MotionMagnificationProcessor
+from .processor import MotionMagnificationProcessor, frame_layout
 from .stream import ShardedStream, shard_range
 from .ring import Ring, new_ring_id, ring_lib
 
@@ -29,6 +29,7 @@ __all__ = ["MMError", "lib", "load_library", "LIB_PATH", "RGBA8", "RGBA32F", "RG
            "RGBA8_SRGB", "NV12", "NV12_FULL", "P010", "P010_FULL", "FORMAT_BPP", "frame_bytes",
            "nv12_chroma_matrix",
            "EDGE_REPEAT", "EDGE_CLAMP", "MODE_PYRAMID", "MODE_STANDARD", "MODE_STEERABLE",
-           "FILTER_DIFF", "FILTER_IIR", "Params", "Handle", "abi_symbols",
+           "FILTER_DIFF", "FILTER_IIR", "Params", "Handle", "Surface", "has_surfaces",
+           "frame_layout", "abi_symbols",
            "resample_table", "strerror", "MotionMagnificationProcessor",
            "ShardedStream", "shard_range", "Ring", "new_ring_id", "ring_lib"]

@@ -85,6 +85,59 @@ class Params(ctypes.Structure):
         return p
 
 
+class Surface(ctypes.Structure):
+    """mm_surface — where the frames of one side of a call lie: row pitch, the
+    4:2:0 (Cb, Cr) plane's offset and pitch, the stride between the frames of a
+    stream, all in bytes (include/mm.h)."""
+    _fields_ = [("format", ctypes.c_int), ("pitch", ctypes.c_size_t),
+                ("chroma_offset", ctypes.c_size_t), ("chroma_pitch", ctypes.c_size_t),
+                ("frame_stride", ctypes.c_size_t)]
+
+    @classmethod
+    def tight(cls, width, height, fmt):
+        """mm_surface_tight: the packed layout of frame_bytes()."""
+        s = cls()
+        check(_surface_fn("mm_surface_tight")(width, height, fmt, ctypes.byref(s)), "mm_surface_tight")
+        return s
+
+    @classmethod
+    def aligned(cls, width, height, fmt, pitch_align=256, rows_align=16):
+        """mm_surface_aligned: pitch rounded up to pitch_align, planes padded to
+        rows_align rows ((256, 16): a hardware decoder's surface)."""
+        s = cls()
+        check(_surface_fn("mm_surface_aligned")(width, height, fmt, pitch_align, rows_align,
+                                                ctypes.byref(s)), "mm_surface_aligned")
+        return s
+
+    def bytes(self, width, height):
+        """mm_surface_bytes: validates the layout for W x H frames; the byte
+        after the last sample of the last row of the last plane."""
+        n = ctypes.c_size_t()
+        check(_surface_fn("mm_surface_bytes")(width, height, ctypes.byref(self), ctypes.byref(n)),
+              "mm_surface_bytes")
+        return n.value
+
+    def __repr__(self):
+        return (f"Surface(format={self.format}, pitch={self.pitch}, chroma_offset={self.chroma_offset}, "
+                f"chroma_pitch={self.chroma_pitch}, frame_stride={self.frame_stride})")
+
+
+SURFACE_SYMBOLS = ("mm_surface_tight", "mm_surface_aligned", "mm_surface_bytes", "mm_process_surface",
+                   "mm_process_stream_surfaces", "mm_compute_state_surface")
+
+
+def has_surfaces():
+    """The loaded library takes pitched surfaces (detected, as include/mm.h
+    says, by the presence of mm_surface_bytes)."""
+    return hasattr(lib(), "mm_surface_bytes")
+
+
+def _surface_fn(name):
+    if not has_surfaces():
+        raise MMError(-2, f"{library_path()} has no {name} (a build from before the pitched surfaces)")
+    return getattr(lib(), name)
+
+
 _lib = None
 _lib_path = None
 ABI_VERSION = 10  # include/mm.h MM_ABI_VERSION
@@ -102,7 +155,14 @@ def load_library(path=None):
     L = ctypes.CDLL(path)
     vp, ci, cf, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
     pp = ctypes.POINTER(Params)
+    ps = ctypes.POINTER(Surface)
     sigs = {
+        "mm_surface_tight": (ci, [ci, ci, ci, ps]),
+        "mm_surface_aligned": (ci, [ci, ci, ci, sz, ci, ps]),
+        "mm_surface_bytes": (ci, [ci, ci, ps, ctypes.POINTER(sz)]),
+        "mm_process_surface": (ci, [vp, vp, ps, vp, ps, ci, vp]),
+        "mm_process_stream_surfaces": (ci, [vp, vp, ps, vp, ps, ci, vp]),
+        "mm_compute_state_surface": (ci, [vp, vp, ps, vp, sz, vp]),
         "mm_abi_version": (ci, []),
         "mm_strerror": (ctypes.c_char_p, [ci]),
         "mm_params_default": (ci, [pp]),
@@ -143,6 +203,8 @@ def load_library(path=None):
             continue
         if name == "mm_nv12_chroma_matrix" and not hasattr(L, name):
             continue    # an A/B build from before the NV12 formats (same ABI version)
+        if name in SURFACE_SYMBOLS and not hasattr(L, name):
+            continue    # ... or from before the pitched surfaces
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -279,6 +341,19 @@ class Handle:
         check(lib().mm_process_stream(self.h, _ptr(src), _ptr(dst), count, fmt, _ptr(stream)),
               "mm_process_stream")
 
+    def process_surface(self, src, src_layout, dst, dst_layout, on_device=True, stream=None):
+        """mm_process_surface: one frame, each side in its own Surface."""
+        check(_surface_fn("mm_process_surface")(self.h, _ptr(src), ctypes.byref(src_layout), _ptr(dst),
+                                                ctypes.byref(dst_layout),
+                                                FRAMES_ON_DEVICE if on_device else 0, _ptr(stream)),
+              "mm_process_surface")
+
+    def process_stream_surfaces(self, src, src_layout, dst, dst_layout, count, stream=None):
+        """mm_process_stream_surfaces: frame k at k * frame_stride of its side."""
+        check(_surface_fn("mm_process_stream_surfaces")(self.h, _ptr(src), ctypes.byref(src_layout),
+                                                        _ptr(dst), ctypes.byref(dst_layout), count,
+                                                        _ptr(stream)), "mm_process_stream_surfaces")
+
     def reset(self):
         check(lib().mm_reset(self.h), "mm_reset")
 
@@ -293,6 +368,11 @@ class Handle:
     def compute_state(self, src, fmt, dev_buf, stream=None):
         check(lib().mm_compute_state(self.h, _ptr(src), fmt, _ptr(dev_buf), self.state_bytes,
                                      _ptr(stream)), "mm_compute_state")
+
+    def compute_state_surface(self, src, src_layout, dev_buf, stream=None):
+        check(_surface_fn("mm_compute_state_surface")(self.h, _ptr(src), ctypes.byref(src_layout),
+                                                      _ptr(dev_buf), self.state_bytes, _ptr(stream)),
+              "mm_compute_state_surface")
 
     def profile_begin(self):
         check(lib().mm_profile_begin(self.h), "mm_profile_begin")

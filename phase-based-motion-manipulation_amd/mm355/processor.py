@@ -8,7 +8,7 @@ import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       NV12, NV12_FULL, P010, P010_FULL, RGBA8, RGBA8_SRGB, RGBA16F, RGBA32F, Handle, MMError,
-                      Params)
+                      Params, Surface)
 
 
 def _fmt_of(frame, srgb=False):
@@ -26,6 +26,28 @@ def _fmt_of(frame, srgb=False):
 
 def _is_device(frame):
     return bool(getattr(frame, "is_cuda", False))
+
+
+def frame_layout(frame, width, height, fmt):
+    """The mm_surface of a row-strided [H, W, 4] frame (torch tensor or numpy
+    array): channels and pixels packed, rows any valid pitch apart, so that a
+    region of interest is ``parent[y:y+H, x:x+W]``.  None for a contiguous
+    frame (the tight entry point); MMError for any other striding.  Needs no GPU."""
+    if tuple(frame.shape) != (height, width, 4):
+        raise MMError(-1, f"frame shape {tuple(frame.shape)} (want {(height, width, 4)})")
+    if isinstance(frame, np.ndarray):
+        item = frame.itemsize
+        strides = tuple(frame.strides)                       # bytes
+    else:
+        item = frame.element_size()
+        strides = tuple(s * item for s in frame.stride())    # elements -> bytes
+    if strides[2] != item or strides[1] != 4 * item or strides[0] <= 0:
+        raise MMError(-1, "frames must be contiguous or row-strided (pixels and channels packed)")
+    if strides[0] == 4 * item * width:
+        return None
+    lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
+    lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation
+    return lay
 
 
 class MotionMagnificationProcessor:
@@ -125,16 +147,20 @@ class MotionMagnificationProcessor:
         on_dev = _is_device(source)
         if on_dev != _is_device(destination):
             raise MMError(-1, "source and destination must both be device or host")
-        if not on_dev:
-            if not (source.flags.c_contiguous and destination.flags.c_contiguous):
-                raise MMError(-1, "frames must be C-contiguous")
-        elif not (source.is_contiguous() and destination.is_contiguous()):
-            raise MMError(-1, "frames must be contiguous")
+        # contiguous frames, or row-strided views (a region of interest of a
+        # larger frame): the layout follows the strides, each side its own
+        src_lay = frame_layout(source, self.width, self.height, fmt)
+        dst_lay = frame_layout(destination, self.width, self.height, fmt)
         stream = None
         if on_dev:   # order after whatever produced `source` on torch's current stream
             import torch
             stream = torch.cuda.current_stream(source.device).cuda_stream
-        self._handle.process(source, destination, fmt, on_device=on_dev, stream=stream)
+        if src_lay is None and dst_lay is None:
+            self._handle.process(source, destination, fmt, on_device=on_dev, stream=stream)
+            return
+        tight = Surface.tight(self.width, self.height, fmt)
+        self._handle.process_surface(source, src_lay or tight, destination, dst_lay or tight,
+                                     on_device=on_dev, stream=stream)
 
     def OnDestroy(self):
         """OnDestroy -> ReleaseResources (.cs:96-99, :344-356)."""

@@ -10,7 +10,13 @@ on the handle's stream, synchronised at its end; the formats alternate
 --rounds times.  Reports each format's median frames/s and spread, and the
 per-kernel device time (mm_profile_begin/end) of one call of each.
 
-usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--out FILE.json]
+Pitched legs (<format>_pitched): the same frames held in decoder-layout
+surfaces, mm_surface_aligned(256, 16), on both sides, through
+mm_process_stream_surfaces; in the same rounds, next to the tight legs.  A
+library from before the pitched surfaces (MM355_LIB, A/B runs) runs the tight
+legs only.
+
+usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--out FILE.json]
 """
 import argparse
 import json
@@ -47,6 +53,20 @@ def to_420(torch, rgba, ten_bit=False):
     return out
 
 
+def to_surface(torch, src, lay, W, H, planar):
+    """Tight frames [n][...] (device) -> one uint8 buffer holding them in layout
+    `lay` (padding zero), with strided views of the planes."""
+    n = src.shape[0]
+    flat = src.contiguous().view(torch.uint8).reshape(n, -1)
+    buf = torch.zeros(n * lay.frame_stride, dtype=torch.uint8, device=src.device)
+    rb = flat.shape[1] // (H * 3 // 2 if planar else H)
+    buf.as_strided((n, H, rb), (lay.frame_stride, lay.pitch, 1)).copy_(flat[:, :H * rb].reshape(n, H, rb))
+    if planar:
+        buf.as_strided((n, H // 2, rb), (lay.frame_stride, lay.chroma_pitch, 1), lay.chroma_offset).copy_(
+            flat[:, H * rb:].reshape(n, H // 2, rb))
+    return buf
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -54,6 +74,7 @@ def main():
     ap.add_argument("--batch", type=int, default=150)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--leg-seconds", type=float, default=0.6)
+    ap.add_argument("--no-pitched", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -72,16 +93,29 @@ def main():
             src = rgba
         else:
             src = to_420(torch, rgba, ten_bit=name == "p010")
-        legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[],
+        legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[], lay=None,
                           bytes_per_frame=mm355.frame_bytes(W, H, fmt))
+        if not a.no_pitched and mm355.has_surfaces():
+            lay = mm355.Surface.aligned(W, H, fmt, 256, 16)
+            h = mm355.Handle(W, H, p)
+            h.set_batch(B)
+            buf = to_surface(torch, src, lay, W, H, name != "rgba8")
+            legs[name + "_pitched"] = dict(h=h, fmt=fmt, src=buf, dst=torch.zeros_like(buf), fps=[], lay=lay,
+                                           bytes_per_frame=lay.frame_stride)
     st = torch.cuda.Stream()
+
+    def call(L):
+        if L["lay"] is None:
+            L["h"].process_stream(L["src"], L["dst"], B, L["fmt"], stream=st.cuda_stream)
+        else:
+            L["h"].process_stream_surfaces(L["src"], L["lay"], L["dst"], L["lay"], B, stream=st.cuda_stream)
 
     def leg(L, calls):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(st):
             e0.record(st)
             for _ in range(calls):
-                L["h"].process_stream(L["src"], L["dst"], B, L["fmt"], stream=st.cuda_stream)
+                call(L)
             e1.record(st)
         e1.synchronize()
         return e0.elapsed_time(e1) * 1e-3
@@ -96,15 +130,17 @@ def main():
             t = leg(L, L["calls"])
             L["fps"].append(L["calls"] * B / t)
     out = {"workload": f"{W}x{H}, 5 levels, phase scale 25, mm_process_stream of {B} frames, batch {B}",
-           "device": torch.cuda.get_device_name(0), "rounds": a.rounds, "formats": {}}
+           "device": torch.cuda.get_device_name(0), "rounds": a.rounds,
+           "library": "MM355_LIB override" if os.environ.get("MM355_LIB") else "the tree's build", "formats": {}}
     for name, L in legs.items():
         L["h"].profile_begin()
-        L["h"].process_stream(L["src"], L["dst"], B, L["fmt"], stream=st.cuda_stream)
+        call(L)
         st.synchronize()
         prof = L["h"].profile_end()
         f = L["fps"]
         out["formats"][name] = {
             "bytes_per_frame": L["bytes_per_frame"], "calls_per_leg": L["calls"],
+            **({"pitch": L["lay"].pitch, "chroma_offset": L["lay"].chroma_offset} if L["lay"] is not None else {}),
             "leg_seconds": round(L["calls"] * B / statistics.median(f), 3),
             "fps_legs": [round(x, 1) for x in f], "fps_median": round(statistics.median(f), 1),
             "fps_min": round(min(f), 1), "fps_max": round(max(f), 1),
@@ -115,6 +151,10 @@ def main():
     r = out["formats"]["rgba8"]
     for name in ("nv12", "p010"):
         out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
+    for name in ("rgba8", "nv12", "p010"):
+        if name + "_pitched" in out["formats"]:
+            out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
+                                                      out["formats"][name]["fps_median"], 4)
     txt = json.dumps(out, indent=1)
     print(txt)
     if a.out:
