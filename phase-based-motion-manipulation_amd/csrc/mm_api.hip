@@ -277,7 +277,6 @@ int mm_create(int width, int height, const mm_params *p, int hip_device, mm_hand
     g.edge = p->edge_mode;
     build_spec(*p, N, h->spec);
     h->k2_tab = bands_fit_table(h->spec) && !getenv("MM_K2_NOTAB");
-    h->k2_sp = k2_power_exponent(h->spec, h->N);
     h->k2_tab2 = h->k2_tab && bands_overlap(h->spec) && h->N <= 4096;   // (N = 8192: LDS, set_attrs)
     h->ktab_mode = -1;
     h->blur = build_blur();
@@ -285,22 +284,11 @@ int mm_create(int width, int height, const mm_params *p, int hip_device, mm_hand
     // became its own instance (same-call 1080p k_cols 7.92-8.00 -> 7.81-7.82 us;
     // 50 / 60 %: 7.83-7.88 / 7.80-7.90), 30 % at N = 4096 (C3 33.7 vs 34.3 at 40 %)
     h->k2_tail_pct = getenv("MM_K2_TAIL") ? atoi(getenv("MM_K2_TAIL")) : (N >= 4096 ? 30 : 40);
-    // every packed-block frame in k_cols_tail (MM_K2_PKALL=1): what lets a
-    // one-column N = 4096 build (-DMM_K2_GROUPS_4K=1) fit two workgroups per
-    // CU; same-call no faster at the default shapes (1080p 8.54 vs 8.58 us,
-    // C3 within noise), so off by default
-    h->k2_pk_all = getenv("MM_K2_PKALL") && atoi(getenv("MM_K2_PKALL")) != 0;
-    // dedicated Q staging: 2 barriers per frame fewer, but same-call K2 +1 %
-    // at 1080p (r04d); opt-in (MM_K2_STGD=1)
-    h->k2_stg_ded = getenv("MM_K2_STGD") && atoi(getenv("MM_K2_STGD")) == 1;
     h->k2_tail2_pct = getenv("MM_K2_TAIL2") ? atoi(getenv("MM_K2_TAIL2")) : 10;
     h->k34_rows = getenv("MM_K34_ROWS") ? atoi(getenv("MM_K34_ROWS")) / 4 * 4 : -1;
     h->k34_oneshot = getenv("MM_K34_ONESHOT") ? atoi(getenv("MM_K34_ONESHOT")) : 1;
     h->sb_nf = getenv("MM_SB_NF") ? atoi(getenv("MM_SB_NF")) : 2;
     h->sb_cf = getenv("MM_SB_CF") ? atoi(getenv("MM_SB_CF")) : 8;
-    h->sb_cf4k = getenv("MM_SB_CF4K") ? atoi(getenv("MM_SB_CF4K")) : 2;
-    h->sb_rg = getenv("MM_SB_RG") ? atoi(getenv("MM_SB_RG")) != 0 : true;
-    h->sb_stg_own = getenv("MM_SB_STG") ? atoi(getenv("MM_SB_STG")) != 0 : true;
 
     h->chunk = default_batch(width, height, N);
     h->g_stride = (size_t)(N / 2 + 1) * g.Hg;
@@ -377,7 +365,6 @@ int mm_set_params(mm_handle *h, const mm_params *p)
     h->geo.edge = p->edge_mode;
     build_spec(*p, h->N, h->spec);
     h->k2_tab = bands_fit_table(h->spec) && !getenv("MM_K2_NOTAB");
-    h->k2_sp = k2_power_exponent(h->spec, h->N);
     h->k2_tab2 = h->k2_tab && bands_overlap(h->spec) && h->N <= 4096;   // (N = 8192: LDS, set_attrs)
     h->ktab_mode = -1;
     if (edge_changed) return upload_tables(h);

@@ -66,9 +66,6 @@ struct mm_handle {
     int steer_planes;           // state planes allocated (1: DIFF, 3: IIR)
     int sb_nf;                  // frames per k_sb_rows launch (MM_SB_NF; 2: pairs)
     int sb_cf;                  // frames per k_sb_cols launch at N <= 2048 (MM_SB_CF)
-    int sb_cf4k;                // frames per column chunk at N = 4096 (MM_SB_CF4K; launches stay per frame)
-    int sb_rg;                  // k_sb_rows: a chunk's frame groups in one launch (MM_SB_RG)
-    bool sb_stg_own;            // k_sb_cols stages in its own LDS area where it fits (MM_SB_STG)
     bool steer_valid;           // d_sst holds the state after the previous frame
     // G: chunk + 1 slots of K1's row spectra.  Slot gs holds G_{t-1}, the row
     // spectra of the previous input frame: the temporal state
@@ -85,16 +82,13 @@ struct mm_handle {
     bool last_ev_set;
     hipStream_t last_s;         // the stream last_ev was recorded on
     bool k2_tab;                // pyramid masks from the per-bin LDS table (<= 2 bands/bin)
-    int k2_sp;                  // ... and the phase factor as z^S, |S| == k2_sp (k_cols SP; 0: atan2)
     bool k2_tab2;               // ... with overlapping middle bands (MM_K2_PYR_TAB2)
-    bool k2_stg_ded;            // k_cols stages Q in its own LDS area where it fits (MM_K2_STGD=1)
     uint8_t *d_stage_in, *d_stage_out;
     size_t stage_bytes;
     bool has_state;
     bool g_valid;               // the G slot gs holds G_{t-1} (K1 or a non-steerable mm_set_state
                                 // wrote it; a steerable mm_set_state sets only the local phases)
     int k2_tail_pct;            // share of a batch's frames of k_cols's packed block run by k_cols_tail
-    bool k2_pk_all;             // ... all of them (batches >= 24 frames): block 0 leaves k_cols
     int k2_tail2_pct;           // share of the second-half blocks' frames run by k_cols's tail blocks
     int k34_rows;               // output rows per k_rows_inv_compose strip (0: K3 + K4 unfused;
                                 // -1: by the launch's frame count, k34_strip_rows)
@@ -483,10 +477,6 @@ static void build_spec(const mm_params &p, int N, Spec &sp)
     sp.tau2 = p.magnitude_threshold * p.magnitude_threshold;
     sp.inv_nn = 1.0f / ((float)N * (float)N);
     sp.S_rev = (float)((double)p.phase_scale / (2.0 * 3.14159265358979323846));
-    // integer phase scale (the reference default 10, BASELINE's 25): the power form
-    const float aS = fabsf(p.phase_scale);
-    sp.S_pow = (aS == floorf(aS) && aS <= 4096.0f) ? (int)aS : -1;
-    sp.S_sgn = p.phase_scale < 0.0f ? -1.0f : 1.0f;
     sp.tau2_nn = sp.tau2 * sp.inv_nn * sp.inv_nn;   // exact: inv_nn is a power of two
     sp.hp_lo = p.max_freq * 0.8f;             // PyramidOperations.compute:36-41
     sp.hp_inv = 1.0f / (p.max_freq * 0.2f);
@@ -540,16 +530,6 @@ static bool bands_overlap(const Spec &sp)
             if (hi - lo > 1e-5f * hi) return true;   // NaN bands (L = 3) compare false
         }
     return false;
-}
-
-// k_cols' power-form instance for this handle (mm_kernels.hpp cpow_x2), opt-in
-// with MM_K2_POW=1 (measured slower than the atan2 form): |S| for an integer
-// phase scale with a compiled instance (|S| 25 and 10, the configurations'
-// values, at N >= 2048), else 0 (the atan2 form).
-static int k2_power_exponent(const Spec &sp, int N)
-{
-    if (!getenv("MM_K2_POW") || atoi(getenv("MM_K2_POW")) == 0) return 0;
-    return N >= 2048 && (sp.S_pow == 25 || sp.S_pow == 10) ? sp.S_pow : 0;
 }
 
 // GaussianBlur.shader:47-60 at _BlurSize 0.5 (.cs:427): bilinear taps at
@@ -618,23 +598,10 @@ static int set_attrs(int W)
         for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
-        // k_sb_cols: exchange buffers (73.7 KB) + its own staging (run_steer)
+        // k_sb_cols: exchange buffer (36.9 KB) + its own staging, past 64 KB for
+        // frames taller than ~3,570 rows (run_steer's bound)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sb_cols<12>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        // k_sb_rows: sb_rows_groups<12>() 4096-point transforms (73.7 KB at two)
-        if constexpr (sb_rows_groups<12>() > 1) {
-            const int rl = (int)(sizeof(c2) * sb_rows_groups<12>() * lds_complex<4096>());
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sb_rows<12, false, 1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sb_rows<12, false, 2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sb_rows<12, false, 4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sb_rows<12, true, 1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sb_rows<12, true, 2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-        }
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 81920));
     }
     if constexpr (LOG2N == 13) {   // N = 8192: one 8192-point transform per workgroup, 73.7 KB and more
         auto set = [](const void *f, size_t b) {
@@ -645,14 +612,12 @@ static int set_attrs(int W)
         HIPCHK(set(reinterpret_cast<const void *>(&k_rows_inv<13>), sizeof(c2) * k3_groups<13>() * lds_complex<8192>()));
         HIPCHK(set(reinterpret_cast<const void *>(&k_dbg_cols<13>), 2 * sizeof(c2) * lds_complex<4096>()));
         (void)x;
-#define MM_SET_K2(MODE, SP)                                                                                       \
-        HIPCHK(set(reinterpret_cast<const void *>(&k_cols<13, MODE, SP>), k2_lds_bytes<13, MODE>()));            \
-        HIPCHK(set(reinterpret_cast<const void *>(&k_cols_tail<13, MODE, SP>), k2_lds_bytes<13, MODE>()))
-        MM_SET_K2(MM_MODE_PYRAMID, 0);
-        MM_SET_K2(MM_MODE_STANDARD, 0);
-        MM_SET_K2(MM_K2_PYR_TAB, 0);
-        MM_SET_K2(MM_K2_PYR_TAB, 25);
-        MM_SET_K2(MM_K2_PYR_TAB, 10);
+#define MM_SET_K2(MODE)                                                                                  \
+        HIPCHK(set(reinterpret_cast<const void *>(&k_cols<13, MODE>), k2_lds_bytes<13, MODE>()));        \
+        HIPCHK(set(reinterpret_cast<const void *>(&k_cols_tail<13, MODE>), k2_lds_bytes<13, MODE>()))
+        MM_SET_K2(MM_MODE_PYRAMID);
+        MM_SET_K2(MM_MODE_STANDARD);
+        MM_SET_K2(MM_K2_PYR_TAB);
         // (no two-band instance: its mask-sum arrays would take K2 past 160 KB
         // of LDS at N = 8192; overlapping bands run the generic op there)
 #undef MM_SET_K2
@@ -662,11 +627,6 @@ static int set_attrs(int W)
         for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
-        // k_sb_cols with four columns per workgroup (MM_SB_MIN_GROUPS = 4):
-        // exchange buffers (73.7 KB) + its own staging
-        if constexpr (sb_groups<11>() == 4)
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sb_cols<11>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     return MM_OK;
 }
@@ -728,44 +688,29 @@ static int launch_k2(mm_handle *h, int nframes, const c2 *Gprev, const c2 *G, hi
         h->ktab_mode = tab_mode;
     }
     ProfScope ps(h, s, MM_K_COLS, nframes);
-    // the packed block's last k frames go to k_cols_tail (k_cols's critical
-    // path); all of them (k = nframes, block 0 not in k_cols) where
-    // k2_pk_all is set: k_cols's LDS then omits the packed group's arrays
-    const bool pk_all = h->k2_pk_all && nframes >= 24 && blocks >= 2;
+    // the packed block's last k frames go to k_cols_tail (k_cols's critical path)
     int k = nframes >= 24 ? nframes * h->k2_tail_pct / 100 : 0;
-    k = pk_all ? nframes : std::max(0, std::min(k, nframes - 2));
-    const int pk_off = pk_all ? 1 : 0, cb = blocks - pk_off;   // column blocks of k_cols
+    k = std::max(0, std::min(k, nframes - 2));
     // second-half tails (k_cols): the last k2 frames of each second-half block's
     // columns in extra blocks (MM_K2_TAIL2 percent)
-    const int k2t = nframes >= 24 && cb >= 2 ? std::min(nframes * h->k2_tail2_pct / 100, nframes - 2) : 0;
-    const int tb = k2t > 0 ? cb / 2 : 0;
-#define MM_K2_LAUNCH(MODE, SP)                                                                       \
+    const int k2t = nframes >= 24 && blocks >= 2 ? std::min(nframes * h->k2_tail2_pct / 100, nframes - 2) : 0;
+    const int tb = k2t > 0 ? blocks / 2 : 0;
+#define MM_K2_LAUNCH(MODE)                                                                           \
     do {                                                                                             \
-        const int sc2 = h->k2_stg_ded ? k2_stg_c2<LOG2N, MODE>(h->geo.Hq, !pk_all) : 0; /* dedicated staging */ \
-        /* (dedicated staging +) exchange buffers + per-bin tables (+ the packed group's) */       \
-        const size_t lds = k2_lds_bytes<LOG2N, MODE>(!pk_all) + sizeof(c2) * (size_t)sc2;           \
-        hipLaunchKernelGGL((k_cols<LOG2N, MODE, SP>), dim3(cb + tb), dim3(k2_threads<LOG2N>()), lds, s, G, \
+        /* exchange buffers + per-bin tables + the packed group's */                                 \
+        const size_t lds = k2_lds_bytes<LOG2N, MODE>();                                              \
+        hipLaunchKernelGGL((k_cols<LOG2N, MODE>), dim3(blocks + tb), dim3(k2_threads<LOG2N>()), lds, s, G, \
                            h->g_stride, Gprev, h->d_Q, h->q_stride, nframes, h->geo, h->spec, h->d_tw, h->d_ktab, \
-                           h->d_kmsum, sc2, nframes - k, tb, k2t, pk_off);                           \
-        if (k) {                                                                                     \
-            const int sct = h->k2_stg_ded ? k2_stg_c2<LOG2N, MODE>(h->geo.Hq) : 0;                  \
-            const size_t ldt = k2_lds_bytes<LOG2N, MODE>() + sizeof(c2) * (size_t)sct;              \
-            hipLaunchKernelGGL((k_cols_tail<LOG2N, MODE, SP>), dim3(k), dim3(k2_threads<LOG2N>()),  \
-                               ldt, s, G, h->g_stride, Gprev,                                       \
-                               h->d_Q, h->q_stride, nframes - k, h->geo, h->spec, h->d_tw, h->d_ktab,   \
-                               h->d_kmsum, sct);                                                     \
-        }                                                                                            \
+                           h->d_kmsum, nframes - k, tb, k2t);                                        \
+        if (k)                                                                                       \
+            hipLaunchKernelGGL((k_cols_tail<LOG2N, MODE>), dim3(k), dim3(k2_threads<LOG2N>()), lds, s, G, \
+                               h->g_stride, Gprev, h->d_Q, h->q_stride, nframes - k, h->geo, h->spec, h->d_tw, \
+                               h->d_ktab, h->d_kmsum);                                               \
     } while (0)
-    // the power-form instances (k2_power_exponent): 1080p and 2160p, |S| 25, 10
-    constexpr bool pow_ok = LOG2N >= 11;
-    if (h->spec.mode == MM_MODE_STANDARD) MM_K2_LAUNCH(MM_MODE_STANDARD, 0);
-    else if (pow_ok && h->k2_tab2 && h->k2_sp == 25) MM_K2_LAUNCH(MM_K2_PYR_TAB2, (pow_ok ? 25 : 0));
-    else if (pow_ok && h->k2_tab2 && h->k2_sp == 10) MM_K2_LAUNCH(MM_K2_PYR_TAB2, (pow_ok ? 10 : 0));
-    else if (h->k2_tab2) MM_K2_LAUNCH(MM_K2_PYR_TAB2, 0);
-    else if (pow_ok && h->k2_tab && h->k2_sp == 25) MM_K2_LAUNCH(MM_K2_PYR_TAB, (pow_ok ? 25 : 0));
-    else if (pow_ok && h->k2_tab && h->k2_sp == 10) MM_K2_LAUNCH(MM_K2_PYR_TAB, (pow_ok ? 10 : 0));
-    else if (h->k2_tab) MM_K2_LAUNCH(MM_K2_PYR_TAB, 0);
-    else MM_K2_LAUNCH(MM_MODE_PYRAMID, 0);
+    if (h->spec.mode == MM_MODE_STANDARD) MM_K2_LAUNCH(MM_MODE_STANDARD);
+    else if (h->k2_tab2) MM_K2_LAUNCH(MM_K2_PYR_TAB2);
+    else if (h->k2_tab) MM_K2_LAUNCH(MM_K2_PYR_TAB);
+    else MM_K2_LAUNCH(MM_MODE_PYRAMID);
 #undef MM_K2_LAUNCH
     HIPCHK(hipGetLastError());
     return MM_OK;
@@ -997,10 +942,11 @@ static size_t steer_state_bytes(const mm_handle *h)
 // orientations.  Reallocated (state invalid) only when those change, never
 // by mm_set_batch: the per-batch spectra Fb grow separately (ensure_frames).
 // frames of one k_sb_cols launch chunk (MM_SB_CF, 2 .. 16: k_sb_rows' write
-// mask holds a bit per frame of its launch; per-frame launches at N = 4096)
+// mask holds a bit per frame of its launch; N = 4096: chunks of 2, launched
+// per frame)
 static int sb_cols_frames(const mm_handle *h)
 {
-    return std::min(16, std::max(2, h->N >= 4096 ? h->sb_cf4k : h->sb_cf));
+    return h->N >= 4096 ? 2 : std::min(16, std::max(2, h->sb_cf));
 }
 static int steer_alloc(mm_handle *h, hipStream_t s)
 {
@@ -1018,9 +964,9 @@ static int steer_alloc(mm_handle *h, hipStream_t s)
     h->d_sst = nullptr;
     h->steer_nb = -1;
     h->steer_valid = false;
-    // band rows of the frames one k_sb_cols launch chunk covers (sb_cols_frames;
-    // at least the k_sb_rows group: pairs, MM_SB_NF=4: DIFF in fours)
-    const int tfr = std::max(sb_cols_frames(h), h->sb_nf >= 4 ? 4 : 2);
+    // band rows of the frames one k_sb_cols launch chunk covers (sb_cols_frames:
+    // at least the k_sb_rows group, a pair)
+    const int tfr = sb_cols_frames(h);
     if (h_alloc(h, &h->d_T, sizeof(c2) * tfr * (size_t)(nb + 1) * h->N * t_rows(h->geo.Hn)) != hipSuccess ||
         h_alloc(h, &h->d_sst, steer_state_bytes(h) + sizeof(float)) != hipSuccess)
         return MM_ERR_OOM;
@@ -1063,10 +1009,10 @@ static int run_steer(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const
     // whose workgroups carry the first frame's new state to the second in
     // registers (MM_SB_NF=1: one frame per launch)
     const size_t t_stride = band_stride * (size_t)(steer_bands(h) + 1);
-    // frames of this k_sb_rows launch: 4 (MM_SB_NF=4, DIFF; opt-in: C3
-    // k_sb_rows -1.3 % but k_sb_cols +2.3 %, 1080p k_sb_rows +16 % at 4
-    // waves per SIMD, profiles/r06h_sb_rows_layout_ab.txt), 2 or 1
-    const int nfm = h->sb_nf >= 4 && h->spec.filt != MM_FILTER_IIR ? 4 : h->sb_nf >= 2 ? 2 : 1;
+    // frames of a k_sb_rows group: 2 or 1 (fours: C3 k_sb_rows -1.3 % but
+    // k_sb_cols +2.3 %, 1080p k_sb_rows +16 % at 4 waves per SIMD,
+    // profiles/r06h_sb_rows_layout_ab.txt)
+    const int nfm = h->sb_nf >= 2 ? 2 : 1;
     // k_sb_cols runs the band columns of sb_cf (MM_SB_CF, default 8) frames per
     // launch at N <= 2048 (blockIdx.y: frame), then the chunk's k_sb_rows
     // groups: the kernel boundaries are what it saves (1080p O = 8 DIFF, same
@@ -1074,24 +1020,20 @@ static int run_steer(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const
     // frames/s; 1.85 GB of band rows at 8); per frame at N = 4096, whose
     // 2,048-workgroup launches gain nothing from it (C3 k_sb_cols 424 -> 430
     // us at 2; profiles/r06h_sb_rows_layout_ab.txt)
-    const int cf = std::max(sb_cols_frames(h), nfm);
+    const int cf = sb_cols_frames(h);   // >= nfm
     for (int c0 = 0; c0 < n; c0 += cf) {
         const int cn = std::min(cf, n - c0);
         {
             ProfScope ps(h, s, MM_K_COLS, 0);
             const int g2 = sb_groups<LOG2N>();
             // the staging [Hn][GPW] gets its own LDS area where it costs no
-            // residency: two workgroups per CU at N <= 2048 (1080p: 54 KB
-            // each), and at N = 4096, whose 1,024-thread workgroups are alone
-            // on their CU anyway (126 VGPRs: 4 waves per SIMD), within the
-            // CU's 160 KB (2160p: 73.7 + 34.6 KB); else it aliases the
-            // exchange buffers (one more barrier per band, and a band's
-            // stores cannot overlap the next band's transform)
-            // (one column per workgroup, sb_direct: two exchange buffers, no staging)
-            const size_t lx = sizeof(c2) * (size_t)(sb_direct<LOG2N>() ? 2 : g2) * lds_complex<N>(),
+            // residency: two workgroups per CU, 80 KB each (1080p: 18.4 +
+            // 8.8 KB, 2160p: 36.9 + 17.5 KB); else it aliases the exchange
+            // buffers (one more barrier per band, and a band's stores cannot
+            // overlap the next band's transform)
+            const size_t lx = sizeof(c2) * (size_t)g2 * lds_complex<N>(),
                          ls = sizeof(c2) * (size_t)g2 * sb_stg_stride(h->geo.Hn, N);   // (whole row groups)
-            const size_t own_cap = sb_threads<LOG2N>() >= 1024 ? 160 * 1024 : 81920;
-            const int own = !sb_direct<LOG2N>() && h->sb_stg_own && lx + ls <= own_cap ? 1 : 0;
+            const int own = lx + ls <= 81920 ? 1 : 0;
             const int per = LOG2N >= 12 ? 1 : cn;
             for (int f = 0; f < cn; f += per) {
                 hipLaunchKernelGGL((k_sb_cols<LOG2N>), dim3((N + g2 - 1) / g2, per), dim3(sb_threads<LOG2N>()),
@@ -1102,11 +1044,10 @@ static int run_steer(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const
         }
         for (int k = c0; k < c0 + cn;) {
             const int left = c0 + cn - k;
-            const int nf = left >= nfm ? nfm : (nfm >= 2 && left >= 2 ? 2 : 1);
+            const int nf = left >= nfm ? nfm : 1;
             // the chunk's whole groups of nf frames in one launch, each
-            // workgroup running them one after the other (MM_SB_RG=0: a launch
-            // per group)
-            const int ng = h->sb_rg && h->spec.filt != MM_FILTER_IIR ? left / nf : 1;
+            // workgroup running them one after the other (IIR: a launch per group)
+            const int ng = h->spec.filt != MM_FILTER_IIR ? left / nf : 1;
             const int reset = k < seed;
             // bit f: frame k + f's Yh (the stream's first frame passes through)
             const int wmask = write ? (((1 << (ng * nf)) - 1) & ~(reset ? 1 : 0)) : 0;
@@ -1124,8 +1065,7 @@ static int run_steer(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const
                 if (nf == 2) MM_SB_ROWS(true, 2);
                 else MM_SB_ROWS(true, 1);
             } else {
-                if (nf == 4) MM_SB_ROWS(false, 4);
-                else if (nf == 2) MM_SB_ROWS(false, 2);
+                if (nf == 2) MM_SB_ROWS(false, 2);
                 else MM_SB_ROWS(false, 1);
             }
 #undef MM_SB_ROWS

@@ -77,8 +77,6 @@ struct Spec {
     int L;
     float minF, maxF, S, tau2, inv_nn;
     float S_rev;            // S / (2 pi): phase scale in revolutions (v_sin/v_cos)
-    int S_pow;              // |S| when S is an integer, else -1 (k_cols SP: the power form)
-    float S_sgn;            // sign of S (+1 / -1) for the power form
     float tau2_nn;          // tau2 * inv_nn^2 (gate on masks pre-scaled by inv_nn)
     float hp_lo, hp_inv;    // high-pass ramp start maxF*0.8, 1/(maxF*0.2)
     float lp_hi, lp_inv;    // low-pass ramp end minF*1.2, 1/(minF*0.2)
@@ -287,14 +285,6 @@ template <> struct Pix<0> {           // RGBA8 UNORM
     {
         st_stream<uint32_t>(base, i * 4u, pack(r, g, b));
     }
-    // r, g, b in code units (255 x the UNORM value), unclamped: three
-    // v_cvt_pk_u8_f32, each rounding to nearest and clamping to 0 .. 255 into
-    // its byte lane (the compose kernels' pack, kOut255)
-    __device__ static uint32_t pack255(float r, float g, float b)
-    {
-        const uint32_t a = __builtin_amdgcn_cvt_pk_u8_f32(r, 0u, 0xff000000u);
-        return __builtin_amdgcn_cvt_pk_u8_f32(b, 2u, __builtin_amdgcn_cvt_pk_u8_f32(g, 1u, a));
-    }
 };
 template <> struct Pix<1> {           // RGBA32F
     static constexpr int bpp = 16;
@@ -380,30 +370,6 @@ template <> struct Pix<3> {
 };
 // saturated before the store: the UNORM destinations (RGBA8, RGBA8 sRGB)
 template <int FMT> constexpr bool kUnorm = FMT == 0 || FMT == 3;
-// MM_OUT255=1 (diagnostic): RGBA8 compose in code units.  The chroma
-// conversion drops its 1/255, the vertical luma blur carries 255 in its
-// weights, and YIQToRGB's saturate and the x255 + round of the UNORM write
-// become the clamp and round-to-nearest-even of v_cvt_pk_u8_f32
-// (Pix<0>::pack255; tools/cvtpk_probe.hip): 3 VALU per pixel instead of 10,
-// K34 -10 % VALU, parity green, but 4 spills at its 128-VGPR bound at
-// N = 2048: same-call K34 6.09 -> 6.24 us per frame at 1080p, equal at 2160p
-// (profiles/r06f_out255_ab.txt).  Off by default.
-#ifndef MM_OUT255
-#define MM_OUT255 0
-#endif
-template <int FMT> constexpr bool kOut255 = MM_OUT255 && FMT == 0;
-// the vertical blur weights of the compose (255 x for kOut255; scalar
-// registers like the kernel argument they come from, not 3 VGPRs)
-__device__ __forceinline__ float uniform_f(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-template <int FMT> __device__ __forceinline__ Blur5 vblur_w(Blur5 b)
-{
-    if constexpr (kOut255<FMT>)
-        return Blur5{uniform_f(b.w0 * 255.0f), uniform_f(b.w1 * 255.0f), uniform_f(b.w2 * 255.0f)};
-    else return b;
-}
 
 // RGBToYIQ.shader:46-50 rows
 __device__ __forceinline__ float luma(float4 c) { return 0.299f * c.x + 0.587f * c.y + 0.114f * c.z; }
@@ -453,7 +419,7 @@ template <int FMT>
 __device__ __forceinline__ c2 chroma_iq2(typename Pix<FMT>::raw_t u)
 {
     if constexpr (FMT == 0) {
-        constexpr float k = kOut255<FMT> ? 1.0f : 1.0f / 255.0f;
+        constexpr float k = 1.0f / 255.0f;
         const float r = (float)(u & 255u), gg = (float)((u >> 8) & 255u), b = (float)((u >> 16) & 255u);
         return mk(0.596f * k, 0.211f * k) * r + mk(-0.274f * k, -0.523f * k) * gg + mk(-0.322f * k, 0.312f * k) * b;
     } else {
@@ -465,28 +431,11 @@ __device__ __forceinline__ c2 chroma_iq2(typename Pix<FMT>::raw_t u)
 // YIQToRGB.shader:51-76 + saturate for one pixel: R and G as one pair, B alone
 // (B as two FMAs: written as 1 yb + ..., the contraction fused the 1 yb
 // product and left a multiply and a subtract)
-// (kOut255: yb, cc and the result in code units, the saturate left to the pack)
-template <int FMT>
 __device__ __forceinline__ void yiq_rgb(float yb, c2 cc, float &rr, float &gg, float &bb)
 {
     const c2 rg = mk(yb, yb) + mk(0.956f, -0.272f) * cc.x + mk(0.621f, -0.647f) * cc.y;
     const float b = fmaf(1.703f, cc.y, fmaf(-1.106f, cc.x, yb));
-    if constexpr (kOut255<FMT>) {
-        rr = rg.x; gg = rg.y; bb = b;
-    } else {
-        rr = sat(rg.x); gg = sat(rg.y); bb = sat(b);
-    }
-}
-// the compose kernels' packed pixel and single-pixel store of yiq_rgb's result
-template <int FMT> __device__ __forceinline__ uint32_t out_pack(float r, float g, float b)
-{
-    if constexpr (kOut255<FMT>) return Pix<FMT>::pack255(r, g, b);
-    else return Pix<FMT>::pack(r, g, b);
-}
-template <int FMT> __device__ __forceinline__ void out_store(uint8_t *base, unsigned i, float r, float g, float b)
-{
-    if constexpr (kOut255<FMT>) st_stream<uint32_t>(base, i * 4u, Pix<FMT>::pack255(r, g, b));
-    else Pix<FMT>::store(base, i, r, g, b);
+    rr = sat(rg.x); gg = sat(rg.y); bb = sat(b);
 }
 
 // ---- NV12 (planar 4:2:0) access ------------------------------------------
@@ -687,9 +636,6 @@ __device__ __forceinline__ void c420_quad_pairs(const uint8_t *img, const Geo &g
 // =========================================================================
 // GEN (odd W or H): the composite taps of a pixel span i-2 .. i+1 and are
 // read as unmerged Tap4 entries (colT / rowT) instead of the 3-tap tables.
-#ifndef MM_K1_COOP
-#define MM_K1_COOP 1   // batch form: the two row pairs' source rows loaded once
-#endif
 template <int LOG2N, int FMT, bool GEN = false, bool LAT = false>
 __global__ __launch_bounds__((k1_gpw<LOG2N, LAT>() * fft_T<LOG2N>()))
 void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
@@ -760,7 +706,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
                 V[g.W + i] = vb;
             }
         }
-    } else if (MM_K1_COOP && GPW == 2 && !LAT && pairs_per_frame % 2 == 0) {
+    } else if (GPW == 2 && !LAT && pairs_per_frame % 2 == 0) {
         // Batch form, the two groups' row pairs in one frame (uniform test):
         // the workgroup's 4 rows r0 .. r0+3 read the 6 source rows r0-1 ..
         // r0+4 once, shared (each group alone read 4: 8 row loads for 4
@@ -1332,89 +1278,6 @@ __device__ __forceinline__ c2 pyramid_op_2band(c2 c, c2 p, const Spec &sp, float
     return mul(c, mk(mmag * cw + mpass, mmag * sw));
 }
 
-// The power form of the phase factor (k_cols SP > 0: an integer phase scale
-// S with |S| == SP fixed at compile time).  For an integer S
-//   e^{i S wrap(arg p - arg c)} = e^{i S (arg p - arg c)} = z^S,
-//   z = p conj(c) / (|p| |c|)
-// (wrap subtracts a multiple of 2 pi, which an integer S maps to a multiple of
-// 2 pi: PyramidPhaseDifference.compute:47-54, 92-98), so the atan2 polynomial,
-// its octant logic and sin / cos become one rsq and a fixed chain of complex
-// squarings and products, two bins per packed op: |S| = 25 is 4 squarings + 2
-// products, 10 is 3 + 1.  S < 0: conj(z)^|S| (the sign on z's imaginary part).
-// Same value up to fp32 rounding (tests/test_k2_pow.py against the atan2 form
-// and the oracle).  Opt-in (MM_K2_POW=1): it trades the atan2 polynomial and
-// 3 transcendentals per bin for 1 rsq and 12 packed ops per bin (|S| = 25),
-// +15 VALU per 8 bins at 16 fewer transcendental issue slots, and measured
-// slower same-call (1080p k_cols 8.38 -> 8.58-8.61 us, C3 38.6-39.0 ->
-// 39.1-39.4: the squaring chain is one long dependency per bin pair).  Range: |p| |c| < 2^64 (the product of the squared norms is
-// scaled by 2^-64 before the rsq; any RGBA8 frame is below 2^25 per bin), and
-// a bin with |p|^2 |c|^2 < 2^-62 gets z = u 2^31 instead of u / |u| (such a bin
-// is gated unless tau < 2^-31 / (m N M)).
-
-// (x + i y)^E for two bins at once (one per lane of x and y)
-template <int E>
-__device__ __forceinline__ void cpow_x2(c2 &x, c2 &y)
-{
-    static_assert(E >= 1, "exponent");
-    if constexpr (E % 2 == 0) {
-        cpow_x2<E / 2>(x, y);
-        const c2 xx = x * x - y * y, yy = (x + x) * y;
-        x = xx;
-        y = yy;
-    } else if constexpr (E > 1) {
-        c2 rx = x, ry = y;
-        cpow_x2<E - 1>(rx, ry);
-        const c2 xx = rx * x - ry * y, yy = rx * y + ry * x;
-        x = xx;
-        y = yy;
-    }
-}
-
-// pyramid_op_1band_x2 (TWO: pyramid_op_2band_x2, with the bins' mask sums
-// ms0, ms1) in the power form, E = |S|
-template <int E, bool TWO>
-__device__ __forceinline__ void pyramid_op_pow_x2(c2 &v0, c2 &p0, float2 mt0, float ms0, c2 &v1, c2 &p1,
-                                                  float2 mt1, float ms1, const Spec &sp)
-{
-    const c2 c0 = v0, c1 = v1;
-    const float cn0 = c0.x * c0.x + c0.y * c0.y, pn0 = p0.x * p0.x + p0.y * p0.y;
-    const float cn1 = c1.x * c1.x + c1.y * c1.y, pn1 = p1.x * p1.x + p1.y * p1.y;
-    const float mn0 = fminf(cn0, pn0), mn1 = fminf(cn1, pn1);
-    float mmag0, mmag1, mpass0, mpass1;
-    if constexpr (TWO) {
-        const float mb0 = fmaxf(mt0.y, 0.0f), mb1 = fmaxf(mt1.y, 0.0f);
-        mmag0 = (mt0.x * mt0.x * mn0 < sp.tau2_nn ? 0.0f : mt0.x) + (mb0 * mb0 * mn0 < sp.tau2_nn ? 0.0f : mb0);
-        mmag1 = (mt1.x * mt1.x * mn1 < sp.tau2_nn ? 0.0f : mt1.x) + (mb1 * mb1 * mn1 < sp.tau2_nn ? 0.0f : mb1);
-        mpass0 = ms0 - mmag0;
-        mpass1 = ms1 - mmag1;
-    } else {
-        mmag0 = mt0.x * mt0.x * mn0 < sp.tau2_nn ? 0.0f : mt0.x;
-        mmag1 = mt1.x * mt1.x * mn1 < sp.tau2_nn ? 0.0f : mt1.x;
-        mpass0 = -mt0.y - mmag0;
-        mpass1 = -mt1.y - mmag1;
-    }
-    const c2 u0 = mul_conj(p0, c0), u1 = mul_conj(p1, c1);
-    // 1 / (|u| 2^-32) = rsq(|c|^2 |p|^2 2^-64), then the 2^-32 back
-    const c2 q = (mk(cn0, cn1) * mk(0x1p-64f, 0x1p-64f)) * mk(pn0, pn1);
-    const c2 r = mk(__builtin_amdgcn_rsqf(fmaxf(q.x, 0x1p-126f)), __builtin_amdgcn_rsqf(fmaxf(q.y, 0x1p-126f))) *
-                 mk(0x1p-32f, 0x1p-32f);
-    c2 x = mk(u0.x, u1.x) * r, y = mk(u0.y, u1.y) * (r * mk(sp.S_sgn, sp.S_sgn));
-    cpow_x2<E>(x, y);
-    v0 = mul(c0, mk(mmag0 * x.x + mpass0, mmag0 * y.x));
-    v1 = mul(c1, mk(mmag1 * x.y + mpass1, mmag1 * y.y));
-    p0 = c0;
-    p1 = c1;
-}
-
-// one bin (the packed group's one-at-a-time ops): the two-bin form with the
-// second lane a copy
-template <int E, bool TWO>
-__device__ __forceinline__ c2 pyramid_op_pow1(c2 c, c2 p, const Spec &sp, float2 mt, float ms)
-{
-    c2 v0 = c, p0 = p, v1 = c, p1 = p;
-    pyramid_op_pow_x2<E, TWO>(v0, p0, mt, ms, v1, p1, mt, ms, sp);
-    return v0;
-}
 template <int MODE>
 __device__ __forceinline__ c2 standard_op_t(c2 c, c2 p, const Spec &sp, float2 mt)
 {
@@ -1454,20 +1317,14 @@ __device__ __forceinline__ c2 k2_op(c2 c, c2 p, int fx, int fy, const Spec &sp, 
     }
 }
 
-// k_cols runs at least two columns per workgroup, so that a Q row receives one
-// 16-B (or wider) piece per workgroup instead of one 8-B value per column
-// two columns per k_cols workgroup (whole 32-B Q pieces per tile row).  At
-// N = 4096 that is 16 waves with 123-148 KB of LDS, one workgroup per CU for
-// the whole launch; one column per workgroup there (8 waves, <= 62 KB without
-// the packed group's arrays, MM_K2_PKALL: two per CU) measured slower
-// same-call (C3 k_cols 37.5 -> 38.6-39.0 us per frame: 16-B Q pieces), so it
-// is a build option only (-DMM_K2_GROUPS_4K=1).
-#ifndef MM_K2_GROUPS_4K
-#define MM_K2_GROUPS_4K 2
-#endif
+// k_cols runs two columns per workgroup (whole 32-B Q pieces per tile row
+// instead of one 8-B value per column).  At N = 4096 that is 16 waves with
+// 123-148 KB of LDS, one workgroup per CU for the whole launch; one column per
+// workgroup there (8 waves, two per CU) measured slower same-call (C3 k_cols
+// 37.5 -> 38.6-39.0 us per frame: 16-B Q pieces).
 template <int LOG2N> constexpr int k2_groups()
 {
-    return LOG2N >= 13 ? 1 : LOG2N >= 12 ? MM_K2_GROUPS_4K : groups_at_least<LOG2N, MM_K2_GROUPS>();
+    return LOG2N >= 13 ? 1 : LOG2N >= 12 ? 2 : groups_at_least<LOG2N, MM_K2_GROUPS>();
 }
 // the steerable band-column kernel: one column per workgroup where one
 // transform fills a workgroup (N >= 2048), else the transforms a 256-thread
@@ -1475,70 +1332,20 @@ template <int LOG2N> constexpr int k2_groups()
 // groups of 4 (MM_SB_RROWS, mm_steer.hpp), and the workgroups of a CU run
 // independently (two columns in one 1,024-thread workgroup synchronised 16
 // waves per barrier: C3 O = 8 k_sb_cols 434 -> 380 us, 1080p 81.7 -> 69.4,
-// profiles/r06h_sb_rows_layout_ab.txt).  MM_SB_MIN_GROUPS = 2 / 4: two / four
-// columns per workgroup (four at N = 2048: 130 us, one workgroup per CU in
-// two rounds).  MM_SB_GPW1 = 1: one column with direct 8-B stores and a
-// double-buffered exchange (no staging: C3 1,020 us).
-#ifndef MM_SB_GPW1
-#define MM_SB_GPW1 0
-#endif
-#ifndef MM_SB_MIN_GROUPS
-#define MM_SB_MIN_GROUPS 1
-#endif
-template <int LOG2N> constexpr int sb_groups() { return groups_at_least<LOG2N, MM_SB_GPW1 ? 1 : MM_SB_MIN_GROUPS>(); }
-// k_sb_cols with one column per workgroup: the band loop alternates two
-// exchange buffers (the next band's transform never waits for this one's
-// cross-wave reads) and stores from registers (no staging)
-// the steerable band-row kernel: row transforms per workgroup (MM_SB_ROWS2_4K
-// = 1: two at N = 4096, rows k, k+1 of one band-row group reading the same
-// 32-B sectors in one 1,024-thread workgroup: C3 k_sb_rows 465 -> 568 us,
-// profiles/r06h_sb_rows_layout_ab.txt; off)
-#ifndef MM_SB_ROWS2_4K
-#define MM_SB_ROWS2_4K 0
-#endif
-template <int LOG2N> constexpr int sb_rows_groups()
-{
-    return LOG2N == 12 && MM_SB_ROWS2_4K ? 2 : groups_per_wg<LOG2N>();
-}
+// profiles/r06h_sb_rows_layout_ab.txt).
+template <int LOG2N> constexpr int sb_groups() { return groups_per_wg<LOG2N>(); }
+// the steerable band-row kernel: row transforms per workgroup
+template <int LOG2N> constexpr int sb_rows_groups() { return groups_per_wg<LOG2N>(); }
 template <int LOG2N> constexpr int sb_rows_threads() { return sb_rows_groups<LOG2N>() * fft_T<LOG2N>(); }
-template <int LOG2N> constexpr bool sb_direct() { return MM_SB_GPW1 && sb_groups<LOG2N>() == 1 && fft_c_v(LOG2N) > 1; }
 template <int LOG2N> constexpr int sb_threads() { return sb_groups<LOG2N>() * fft_T<LOG2N>(); }
 // K2's Q staging buffer (c2 slots written by rows, read back as float4
 // pieces): slot i lives at i ^ (((i >> 4) & 1) << 1), i.e. float4 r at
 // r ^ ((r >> 3) & 1).  The row writes of a 16-lane group (every other float4
 // of a 16-float4 span) then cover all 32 banks once (linear: 2-way), and the
 // ds_read_b128 groups still read 16 distinct 4-bank slots (tools/lds_banks.py).
-#ifndef MM_K2_NOSWZ
 __device__ __forceinline__ int k2_stg_swz(int i) { return i ^ (((i >> 4) & 1) << 1); }
 __device__ __forceinline__ int k2_stg_swz4(int r) { return r ^ ((r >> 3) & 1); }
-#else   // diagnostic: linear staging
-__device__ __forceinline__ int k2_stg_swz(int i) { return i; }
-__device__ __forceinline__ int k2_stg_swz4(int r) { return r; }
-#endif
 template <int LOG2N> constexpr int k2_threads() { return k2_groups<LOG2N>() * fft_T<LOG2N>(); }
-// dynamic LDS of k_cols: per group the FFT exchange buffer and its column's
-// per-bin table, plus for column N/2 (packed group only) its table, its
-// previous spectrum (bins 0..N/2) and its staged Q values (one float per row).
-// Above 64 KiB at N = 2048 (77.8 KiB): two workgroups still fit a CU's 160 KiB.
-// The inner 512-point passes of k_cols's column FFTs take their twiddle
-// powers from an LDS table (tw_tab_build) instead of 6 products per pass
-// (MM_K2_TWTAB=1; default 0: same-call K2 8.08 -> 8.21 us/frame with the
-// table, profiles/r03k_k2_twtab_ab.txt: the LDS reads cost more than the
-// 48 VALU products per wave-frame they replace)
-#ifndef MM_K2_TWTAB
-#define MM_K2_TWTAB 0
-#endif
-template <int LOG2N> constexpr bool k2_twtab() { return MM_K2_TWTAB && fft_c_v(LOG2N) > 1; }
-// Dedicated Q staging (k_cols_body stg_c2): the list rows [0, Hq) of the
-// workgroup's GPW columns, [Hq/TK][GPW][TK] c2 (k2_stg_swz stays inside
-// 32-slot blocks), when it fits beside two workgroups per CU (1080p: 17 KB);
-// else 0 (aliased with the exchange buffers).
-template <int LOG2N, int MODE> constexpr size_t k2_lds_bytes(bool with_packed = true);
-template <int LOG2N, int MODE> inline int k2_stg_c2(int Hq, bool with_packed = true)
-{
-    const int c = (Hq * k2_groups<LOG2N>() + 31) / 32 * 32;
-    return k2_lds_bytes<LOG2N, MODE>(with_packed) + sizeof(c2) * (size_t)c <= 81920 ? c : 0;
-}
 
 // bytes of n columns' mask-sum arrays ([TS] floats each, rounded up to 16 B;
 // pyramid tables with overlapping bands only)
@@ -1547,17 +1354,16 @@ template <int LOG2N, int MODE> constexpr size_t k2_msum_bytes(int n)
     return k2_msum<MODE>() ? ((sizeof(float) * (size_t)n * k2_tab_slots<LOG2N>()) + 15) / 16 * 16 : 0;
 }
 // k_cols' dynamic LDS, in layout order: the GPW exchange buffers, the GPW
-// columns' tables and mask sums, the inner twiddle table (TT); then what only
-// the packed group (block 0) uses: column N/2's table and mask sums and ldsX.
-// A launch without block 0 (its frames all in k_cols_tail) omits that last part.
-template <int LOG2N, int MODE> constexpr size_t k2_lds_bytes(bool with_packed)
+// columns' tables and mask sums; then what only the packed group (block 0)
+// uses: column N/2's table and mask sums and ldsX.  The staged Q pieces alias
+// the exchange buffers.  Above 64 KiB at N = 2048 (77.8 KiB): two workgroups
+// still fit a CU's 160 KiB.
+template <int LOG2N, int MODE> constexpr size_t k2_lds_bytes()
 {
     return (size_t)k2_groups<LOG2N>() *
                (sizeof(c2) * lds_complex<(1 << LOG2N)>() + sizeof(float2) * k2_tab_slots<LOG2N>()) +
            k2_msum_bytes<LOG2N, MODE>(k2_groups<LOG2N>()) +
-           (k2_twtab<LOG2N>() ? sizeof(float4) * tw_tab_float4() : 0) +
-           (with_packed ? sizeof(float2) * k2_tab_slots<LOG2N>() + k2_msum_bytes<LOG2N, MODE>(1) + sizeof(c2) * 4
-                        : 0);
+           sizeof(float2) * k2_tab_slots<LOG2N>() + k2_msum_bytes<LOG2N, MODE>(1) + sizeof(c2) * 4;
 }
 
 // Columns f = 1..N/2-1 get one FFT group each.  The two real columns f = 0 and
@@ -1573,8 +1379,8 @@ template <int LOG2N, int MODE> constexpr size_t k2_lds_bytes(bool with_packed)
 // A second exchange recombines A = A0 + i AN per bin.
 // (The packed block is the kernel's critical path: every block is resident at
 // once, so its extra work is the kernel's.)
-#ifndef MM_K2_OPG
-#define MM_K2_OPG 2   // bins of the branch-free op interleaved per scheduling group (8, 4: K2 +1.6 %, +0.9 %)
+#ifndef MM_K2_OPX2G
+#define MM_K2_OPX2G 8   // bins per scheduling group of the two-bin op (2, 4: K2 +3 %, +1 %)
 #endif
 #ifdef MM_K2_STAMPS
 // Diagnostic build only: per-wave cycle totals of the frame-loop phases
@@ -1609,12 +1415,12 @@ __device__ __forceinline__ float2 tab_ld(const float2 *p)
     return make_float2(v.x, v.y);
 }
 
-template <int LOG2N, int MODE, bool BLK0, int SP = 0>
+template <int LOG2N, int MODE, bool BLK0>
 __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q,
                                             size_t q_stride, int nframes, const Geo &g,
                                             const Spec &sp, const c2 *__restrict__ tw,
                                             const float2 *__restrict__ ktab, const float *__restrict__ kmsum,
-                                            int stg_c2, int blk, int nb_prio = 0)
+                                            int blk, int nb_prio = 0)
 {
     constexpr int N = 1 << LOG2N, T = fft_T<LOG2N>(), GPW = k2_groups<LOG2N>();
     constexpr int TS = k2_tab_slots<LOG2N>();
@@ -1625,13 +1431,14 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
     // group index: wave-uniform (scalar) when a group spans whole waves
     const int grp = T % 64 == 0 ? __builtin_amdgcn_readfirstlane(threadIdx.x / T) : threadIdx.x / T;
     const int t0 = threadIdx.x % T;
-    // stg_c2 > 0: a dedicated Q staging area of that many c2 at the start of
-    // the LDS (k2_stg_c2, when it fits beside two workgroups per CU), the FFT
-    // exchange buffers and tables after it; 0: the staging aliases the
-    // exchange buffers (two more workgroup barriers per frame)
-    c2 *xbase = lds_all + stg_c2;
-    c2 *lds = xbase + grp * lds_complex<N>();
-    float2 *tabs = reinterpret_cast<float2 *>(xbase + GPW * lds_complex<N>());
+    c2 *lds = lds_all + grp * lds_complex<N>();
+    // (N = 8192: the tables start past a DS instruction's 16-bit offset field;
+    // as an opaque scalar the offset stays in one register, where the constant
+    // cost a v_add per table read.  Not at N = 4096, whose tables start as far
+    // in: there it cost the two-band instance 7 VALU.)
+    int tab_off = GPW * lds_complex<N>();
+    if constexpr (LOG2N == 13) asm volatile("" : "+s"(tab_off));
+    float2 *tabs = reinterpret_cast<float2 *>(lds_all + tab_off);
     float2 *tab0 = tabs + grp * TS;
     // column N/2: F_{t-1} at its real bins 0 and N/2 and their results (two
     // threads of the packed group).  Its Q values are staged with column 0's:
@@ -1639,11 +1446,9 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
     // A0 + i AN; both real), split into the two columns' pieces at the store.
     // the bins' whole mask sums (tabled pyramid modes; two-band waves read them)
     float *ms0 = reinterpret_cast<float *>(tabs + GPW * TS) + grp * TS;
-    uint8_t *lds_tail = reinterpret_cast<uint8_t *>(tabs + GPW * TS) + k2_msum_bytes<LOG2N, MODE>(GPW);
-    float4 *ttab = reinterpret_cast<float4 *>(lds_tail);   // inner passes' twiddle powers (TT)
-    if constexpr (k2_twtab<LOG2N>()) lds_tail += sizeof(float4) * tw_tab_float4();
-    // packed group only (k2_lds_bytes with_packed): column N/2's table, mask sums, ldsX
-    float2 *tabN = reinterpret_cast<float2 *>(lds_tail);
+    // packed group only: column N/2's table, mask sums, ldsX
+    float2 *tabN = reinterpret_cast<float2 *>(reinterpret_cast<uint8_t *>(tabs + GPW * TS) +
+                                              k2_msum_bytes<LOG2N, MODE>(GPW));
     float *msN = reinterpret_cast<float *>(tabN + TS);
     c2 *ldsX = reinterpret_cast<c2 *>(reinterpret_cast<uint8_t *>(msN) + k2_msum_bytes<LOG2N, MODE>(1));
     const int f_raw = blk * GPW + grp;
@@ -1685,25 +1490,15 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                 gb[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(nrs, o0 + (unsigned)(j * T * 8), 0, 0));
         }
     };
-#ifndef MM_K2_NOGAHEAD
     // the prime's G_{t-1} loads first: their HBM latency overlaps the twiddle
     // loads and the table copy instead of following its barrier (one-frame
     // calls pay the prologue and the prime on every call)
     load_g(-1, t0);
-#endif
     // twiddle bases of both FFTs, loaded once (issued under the table copy): no loads inside a frame but G's
-    constexpr bool TT = k2_twtab<LOG2N>();
     c2 wtw[kTwSlots];
 #pragma unroll
     for (int i = 0; i < kTwSlots; ++i) wtw[i] = mk(1.0f, 0.0f);
-    if constexpr (TT) {   // outer-stage bases only; the inner passes read ttab
-#pragma unroll
-        for (int h = 0; h < 8 / fft_c_v(LOG2N); ++h) wtw[12 + h] = tw[t0 + 64 * fft_c_v(LOG2N) * h];
-        tw_tab_build(ttab, threadIdx.x, GPW * T, tw, fft_c_v(LOG2N));
-        if constexpr (MODE == MM_MODE_PYRAMID) __syncthreads();
-    } else {
-        preload_twiddles_wl<LOG2N>(wtw, t0, tw);
-    }
+    preload_twiddles_wl<LOG2N>(wtw, t0, tw);
     if constexpr (MODE != MM_MODE_PYRAMID) {
         // the column's table, evaluated once per parameter set by k_k2_table
         // (slot order): a copy instead of N/2+1 bin_static per group and launch
@@ -1763,15 +1558,14 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
     constexpr int TK = q_tile<LOG2N>(), BLK = GPW * TK / 2;   // float4 per tile row
     constexpr int NST = (N * GPW / 2 + GPW * T - 1) / (GPW * T);   // store slots per thread (Hq <= N)
     const int fb = blk * GPW, nq = (g.Hq / TK) * BLK;
-    c2 *stg = lds_all;   // staged Q pieces of a frame: [row pair][GPW][TK]
-    const bool stg_ded = stg_c2 > 0;
+    c2 *stg = lds_all;   // staged Q pieces of a frame: [row pair][GPW][TK], over the exchange buffers
     bool staged = false;   // stg holds the previous frame's pieces (uniform)
     // Canvas-row staging (TK == 2, rb even, no list row wrapping: every
     // geometry but H close to N): the inverse transform's rows n = t + jT go
     // to LDS unconditionally at slot(n) = ((n/2) GPW + grp) TK + n%2 (one base
     // + immediates, no per-row checks), and the Q stores read list row pair kt
     // at canvas pair kt + rb/2.  Otherwise list-row staging (rows of [0, Hq)).
-    const bool cstage = !stg_ded && TK == 2 && (g.rb & 1) == 0 && g.rb >= 0 && g.rb + g.Hq <= N;
+    const bool cstage = TK == 2 && (g.rb & 1) == 0 && g.rb >= 0 && g.rb + g.Hq <= N;
     const int rd_off = cstage ? (g.rb / 2) * GPW : 0;   // float4 pieces
     // frame-invariant per-thread Q store offsets (loop invariant: computed
     // from t0, not the opaque t below); a frame with nothing staged stores
@@ -1829,19 +1623,15 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
         if (blk0) __builtin_amdgcn_s_setprio(3);
         else if ((fr ^ ((int)blockIdx.x >= nb_prio / 2 ? 1 : 0)) & 1) __builtin_amdgcn_s_setprio(2);
         else __builtin_amdgcn_s_setprio(1);
-#ifdef MM_K2_NOGAHEAD
-        load_g(fr < nframes ? fr : nframes - 1, t);
-#else
-        // (Gprev: issued before the prologue; later frames' loads mid-iteration)
-#endif
+        // (Gprev's loads: issued before the prologue; later frames' mid-iteration)
         K2_STAMP(0);
         __builtin_amdgcn_sched_barrier(0);   // keep the stores behind the loads
         {
             float4 sv[NST];
 #pragma unroll
             for (int i = 0; i < NST; ++i) sv[i] = rd_base[i * GPW * T];   // (slots past the staging: unused)
-            // (aliased staging) staging read before this frame's FFT rewrites the buffers
-            if (!stg_ded) __syncthreads();
+            // staging read before this frame's FFT rewrites the buffers
+            __syncthreads();
             const int qfr = __builtin_amdgcn_readfirstlane(fr > 0 ? fr - 1 : 0);   // uniform
             const auto qrs = __builtin_amdgcn_make_buffer_rsrc(
                 Q + (size_t)qfr * q_stride, 0, staged ? (int)(q_stride * sizeof(c2)) : 0, 0x00020000);
@@ -1884,23 +1674,21 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
         for (int j = 0; j < 8; ++j)   // G[0][r], G[N/2][r] are real (exact zero imaginary parts)
             v[j] = packed ? mk(ga[j].x, gb[j]) : ga[j];
         const bool pass_frame = fr < 0;   // the prime (fr = -1)
-#ifndef MM_K2_NOGAHEAD
         // the prime's successor (frame 0) loads now, under the prime's transform
         // (the prime has no op, so its "after the op" slot below came one
         // transform later; a one-frame call waits on these loads next)
         if (pass_frame) load_g(nframes > 0 ? 0 : -1, t);
-#endif
         // opaque per-iteration copy of the twiddle bases (same reason as t: the
         // products of their powers must not be hoisted into live registers)
         c2 wt[kTwSlots];
 #pragma unroll
         for (int i = 0; i < kTwSlots; ++i) {
             wt[i] = wtw[i];
-            if (tw_slot_used_wl(LOG2N, i) && !(TT && i < 12)) asm volatile("" : "+v"(wt[i]));
+            if (tw_slot_used_wl(LOG2N, i)) asm volatile("" : "+v"(wt[i]));
         }
         K2_STAMP(2);
         MM_MARK("M1_fwd_start");
-        fft_dif<LOG2N, -1, TT>(v, t, lds, wt, ttab);
+        fft_dif<LOG2N, -1>(v, t, lds, wt);
         MM_MARK("M2_fwd_end");
         K2_STAMP(3);
         // the spectral op of a regular group (all groups but the packed one)
@@ -1909,8 +1697,8 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
 #pragma unroll
                 for (int j = 0; j < 8; ++j) prev[j] = v[j];
             } else if (k2_one_band_op<MODE>() && (OPK == 1 || (OPK < 0 && !wave_two_band))) {
-                // no bin of this wave has two middle bands: branch-free op, bins
-                // interleaved MM_K2_OPG at a time
+                // no bin of this wave has two middle bands: branch-free op, two
+                // bins per packed op
                 // bin j: fy = fy0 + j N/8 (fy0 = fft_bin(t, 0)), table entry fy
                 // for j < 4, N - fy for j >= 4 (fy <= N/2 exactly for j < 4).
                 // N/8 is a multiple of C, so both are slots of two per-frame
@@ -1922,30 +1710,13 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                 const int w = fy0 % C;
                 const float2 *tlo = HOIST ? tlo0 : tab0 + k2_tix<LOG2N>(fy0);
                 const float2 *thi = HOIST ? thi0 : tab0 + (w ? k2_tix<LOG2N>(C - w) - 1 : 0) - fy0 / C;
-#ifndef MM_K2_OPX1
 #pragma unroll
-#ifndef MM_K2_OPX2G
-#define MM_K2_OPX2G 8   // bins per scheduling group of the two-bin op (2, 4: K2 +3 %, +1 %)
-#endif
                 for (int j = 0; j < 8; j += 2) {   // two bins per packed op
                     if (j % MM_K2_OPX2G == 0) __builtin_amdgcn_sched_barrier(0);
                     const float2 mt0 = tab_ld(j < 4 ? tlo + j * (N / 8) / C : thi + (N - j * (N / 8)) / C);
                     const float2 mt1 = tab_ld(j + 1 < 4 ? tlo + (j + 1) * (N / 8) / C : thi + (N - (j + 1) * (N / 8)) / C);
-                    if constexpr (SP > 0)
-                        pyramid_op_pow_x2<SP, false>(v[j], prev[j], mt0, 0.0f, v[j + 1], prev[j + 1], mt1, 0.0f, sp);
-                    else
-                        pyramid_op_1band_x2(v[j], prev[j], mt0, v[j + 1], prev[j + 1], mt1, sp);
+                    pyramid_op_1band_x2(v[j], prev[j], mt0, v[j + 1], prev[j + 1], mt1, sp);
                 }
-#else
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    if (j % MM_K2_OPG == 0) __builtin_amdgcn_sched_barrier(0);
-                    const float2 mt = j < 4 ? tlo[j * (N / 8) / C] : thi[(N - j * (N / 8)) / C];
-                    const c2 a = pyramid_op_1band(v[j], prev[j], sp, mt);
-                    prev[j] = v[j];
-                    v[j] = a;
-                }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             } else if (MODE == MM_K2_PYR_TAB2) {
                 // a bin of this wave has two middle bands (L = 6 layouts): the
@@ -1963,10 +1734,7 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                     const int i1 = j + 1 < 4 ? (j + 1) * (N / 8) / C : (N - (j + 1) * (N / 8)) / C;
                     const float2 mt0 = tab_ld(j < 4 ? tlo + i0 : thi + i0), mt1 = tab_ld(j + 1 < 4 ? tlo + i1 : thi + i1);
                     const float s0 = j < 4 ? mlo[i0] : mhi[i0], s1 = j + 1 < 4 ? mlo[i1] : mhi[i1];
-                    if constexpr (SP > 0)
-                        pyramid_op_pow_x2<SP, true>(v[j], prev[j], mt0, s0, v[j + 1], prev[j + 1], mt1, s1, sp);
-                    else
-                        pyramid_op_2band_x2(v[j], prev[j], mt0, s0, v[j + 1], prev[j + 1], mt1, s1, sp);
+                    pyramid_op_2band_x2(v[j], prev[j], mt0, s0, v[j + 1], prev[j + 1], mt1, s1, sp);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             } else {
@@ -2009,10 +1777,7 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                             const int fy = fft_bin<LOG2N>(t, j);
                             const c2 c = v[j];
                             const float2 mt = pk_col0(j, fy) ? tab0[k2_tix<LOG2N>(fy)] : tabN[k2_tix<LOG2N>(N - fy)];
-                            if constexpr (SP > 0)
-                                v[j] = pyramid_op_pow1<SP, false>(c, prev[j], sp, mt, 0.0f);
-                            else
-                                v[j] = pyramid_op_1band(c, prev[j], sp, mt);
+                            v[j] = pyramid_op_1band(c, prev[j], sp, mt);
                             prev[j] = c;
                         }
                     } else if (MODE == MM_K2_PYR_TAB2) {   // two-band waves
@@ -2023,12 +1788,7 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                             const bool c0 = pk_col0(j, fy);
                             const int ix = k2_tix<LOG2N>(c0 ? fy : N - fy);
                             const c2 c = v[j];
-                            if constexpr (SP > 0)
-                                v[j] = pyramid_op_pow1<SP, true>(c, prev[j], sp, c0 ? tab0[ix] : tabN[ix],
-                                                                 c0 ? ms0[ix] : msN[ix]);
-                            else
-                                v[j] = pyramid_op_2band(c, prev[j], sp, c0 ? tab0[ix] : tabN[ix],
-                                                        c0 ? ms0[ix] : msN[ix]);
+                            v[j] = pyramid_op_2band(c, prev[j], sp, c0 ? tab0[ix] : tabN[ix], c0 ? ms0[ix] : msN[ix]);
                             prev[j] = c;
                         }
                     } else {
@@ -2098,21 +1858,19 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
             __syncthreads();   // the inverse FFT rewrites the buffer
         }
         if constexpr (!blk0) regular_op();
-#ifndef MM_K2_NOGAHEAD
         // next frame's G loads now: they land during this frame's inverse
         // transform, staging and Q stores instead of stalling the next frame
         // at its top (same-call K2 8.94 -> 8.33 us/frame, profiles/r03_abv.txt;
         // the op's registers are free again here: no spill at 123 VGPRs)
         if (!pass_frame) load_g(fr + 1 < nframes ? fr + 1 : nframes - 1, t);
-#endif
         staged = !pass_frame;
         if (!pass_frame) {
         K2_STAMP(4);
         MM_MARK("M3_inv_start");
-        fft_dit<LOG2N, +1, TT>(v, t, lds, wt, ttab);   // natural row order again
+        fft_dit<LOG2N, +1>(v, t, lds, wt);   // natural row order again
         MM_MARK("M4_inv_end");
         K2_STAMP(5);
-        if (!stg_ded) __syncthreads();   // (aliased) every wave past its exchange reads: the staging overwrites them
+        __syncthreads();   // every wave past its exchange reads: the staging overwrites them
         // Q is stored by row pairs (q_index) so that K3 reads each of its two
         // rows' values as one 16-B piece per bin, contiguous across the wave (a
         // column-major Q made K3's 16-B gathers cost it 4 of its 7 us/frame at
@@ -2148,26 +1906,14 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
         K2_STAMP(6);
         return true;
     };
-#ifndef MM_K2_UNROLL
-#define MM_K2_UNROLL 1
-#endif
     auto run_frames = [&](auto opk_c) __attribute__((always_inline)) {
         {
             int fr_prime = -1;   // opaque: the prime instance keeps the runtime passthrough test
             asm volatile("" : "+s"(fr_prime));
             frame_iter(fr_prime, opk_c);
         }
-#if MM_K2_UNROLL == 2
-        // two frames per trip: F_{t-1} alternates between the two bodies'
-        // registers instead of being copied back at the loop's end
-        for (int fr = 0;; fr += 2) {
-            if (!frame_iter(fr, opk_c)) break;
-            if (!frame_iter(fr + 1, opk_c)) break;
-        }
-#else
         for (int fr = 0;; ++fr)
             if (!frame_iter(fr, opk_c)) break;   // (fr >= 0 here: no passthrough branch)
-#endif
     };
     if constexpr (blk0 || !k2_one_band_op<MODE>()) run_frames(std::integral_constant<int, -1>());
     else if (!wave_two_band) run_frames(std::integral_constant<int, 1>());
@@ -2191,12 +1937,11 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
 #define MM_K2_WAVES 4
 #endif
 
-template <int LOG2N, int MODE, int SP = 0>
+template <int LOG2N, int MODE>
 __global__ __launch_bounds__(k2_threads<LOG2N>()) __attribute__((amdgpu_waves_per_eu(MM_K2_WAVES)))
 void k_cols(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_stride,   // not restrict: G loads must stay ahead of Q stores
             int nframes, Geo g, Spec sp, const c2 *__restrict__ tw, const float2 *__restrict__ ktab,
-            const float *__restrict__ kmsum, int stg_c2, int nframes_blk0, int tail_blocks, int ktail,
-            int pk_off)
+            const float *__restrict__ kmsum, int nframes_blk0, int tail_blocks, int ktail)
 {
     // Blocks nb .. nb + tail_blocks - 1 (tail_blocks <= nb / 2) are tails: the
     // last ktail frames of the columns of second-half block nb/2 + i, which
@@ -2205,24 +1950,20 @@ void k_cols(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_strid
     // (phase stamps: first half done at ~825 us, second at ~1,045 us per 100
     // frames); its tail starts in the slot the first one frees, primed with the
     // frame before its first (the state is a pure function of that frame).
-    // pk_off = 1: block 0 (the packed group) is not in this launch (all its
-    // frames run in k_cols_tail): the column blocks are 1 .. nb
     const int nb = gridDim.x - tail_blocks;
     const bool tail = (int)blockIdx.x >= nb;
     const int p = tail ? nb / 2 + ((int)blockIdx.x - nb) : (int)blockIdx.x;
     // same-XCD blocks own consecutive columns, so the pieces of one 128-B Q line
     // are merged in one L2 (split over XCDs they left as partial-line writes)
-    const int blk = xcd_remap(p, nb) + pk_off;
+    const int blk = xcd_remap(p, nb);
     if (blk == 0) {   // the packed block stops nframes_blk0 frames in (k_cols_tail)
-        k_cols_body<LOG2N, MODE, true, SP>(G, g_stride, Gprev, Q, q_stride, nframes_blk0, g, sp, tw, ktab, kmsum, stg_c2,
-                                       blk, nb);
+        k_cols_body<LOG2N, MODE, true>(G, g_stride, Gprev, Q, q_stride, nframes_blk0, g, sp, tw, ktab, kmsum, blk, nb);
     } else {
         const int f0 = tail ? nframes - ktail : 0;
         const int nf = tail ? ktail : (p >= nb / 2 && p - nb / 2 < tail_blocks ? nframes - ktail : nframes);
-        k_cols_body<LOG2N, MODE, false, SP>(G + (size_t)f0 * g_stride, g_stride,
+        k_cols_body<LOG2N, MODE, false>(G + (size_t)f0 * g_stride, g_stride,
                                         tail ? G + (size_t)(f0 - 1) * g_stride : Gprev,
-                                        Q + (size_t)f0 * q_stride, q_stride, nf, g, sp, tw, ktab, kmsum, stg_c2,
-                                        blk, nb);
+                                        Q + (size_t)f0 * q_stride, q_stride, nf, g, sp, tw, ktab, kmsum, blk, nb);
     }
 }
 
@@ -2235,16 +1976,15 @@ void k_cols(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_strid
 // function of the previous input frame (.cs:142), so workgroup i primes with
 // frame f0 + i - 1 (its passthrough frame sets F_{t-1} exactly as the frame
 // loop would: bitwise the same outputs) and then runs frame f0 + i.
-template <int LOG2N, int MODE, int SP = 0>
+template <int LOG2N, int MODE>
 __global__ __launch_bounds__(k2_threads<LOG2N>()) __attribute__((amdgpu_waves_per_eu(MM_K2_WAVES)))
 void k_cols_tail(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_stride, int f0, Geo g, Spec sp,
-                 const c2 *__restrict__ tw, const float2 *__restrict__ ktab, const float *__restrict__ kmsum,
-                 int stg_c2)
+                 const c2 *__restrict__ tw, const float2 *__restrict__ ktab, const float *__restrict__ kmsum)
 {
     const int fr = f0 + (int)blockIdx.x;   // frame 0 primes with the state slot
-    k_cols_body<LOG2N, MODE, true, SP>(G + (size_t)fr * g_stride, g_stride,
-                                       fr > 0 ? G + (size_t)(fr - 1) * g_stride : Gprev,
-                                       Q + (size_t)fr * q_stride, q_stride, 1, g, sp, tw, ktab, kmsum, stg_c2, 0);
+    k_cols_body<LOG2N, MODE, true>(G + (size_t)fr * g_stride, g_stride,
+                                   fr > 0 ? G + (size_t)(fr - 1) * g_stride : Gprev,
+                                   Q + (size_t)fr * q_stride, q_stride, 1, g, sp, tw, ktab, kmsum, 0);
 }
 
 // K2's per-bin tables of every column in LDS slot order ([N/2+1][k2_tab_slots]):
@@ -2388,13 +2128,6 @@ void k_rows_inv(const c2 *__restrict__ Q, size_t q_stride, float *__restrict__ Y
 #define MM_K4_COLS 256
 #endif
 constexpr int kTileRows = MM_K4_ROWS, kTileCols = MM_K4_COLS;
-// MM_NV12_K4_PACK=1 (diagnostic): k_compose's NV12 luma codes gathered over the
-// four lanes of a quad and stored as one dword (W % 4 == 0), instead of one
-// byte store per lane.
-#ifndef MM_NV12_K4_PACK
-#define MM_NV12_K4_PACK 0
-#endif
-
 template <int FMT>
 __global__ __launch_bounds__(kTileCols)
 void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__restrict__ frames_in,
@@ -2467,7 +2200,6 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
         hc[sr] = wc.x * a + wc.y * m + wc.z * c;
     }
     uint8_t *outp = frames_out + (size_t)frame * g.lo.stride;
-    const Blur5 bv = vblur_w<FMT>(bw);
     [[maybe_unused]] c2 cd0;   // NV12: the even row's chroma differences
 #pragma unroll
     for (int r = 0; r < TR; ++r) {
@@ -2475,10 +2207,10 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
         if (i < g.H) {
             const float4 wr = rowW3[i];                        // source rows i-1, i, i+1
             const c2 cc = wr.x * hc[r] + wr.y * hc[r + 1] + wr.z * hc[r + 2];   // (ci, cq)
-            const float yb = bv.w0 * yv[r + 2] + bv.w1 * (yv[r + 1] + yv[r + 3]) +
-                             bv.w2 * (yv[r] + yv[r + 4]);
+            const float yb = bw.w0 * yv[r + 2] + bw.w1 * (yv[r + 1] + yv[r + 3]) +
+                             bw.w2 * (yv[r] + yv[r + 4]);
             float rr, gg, bb;
-            yiq_rgb<FMT>(yb, cc, rr, gg, bb);
+            yiq_rgb(yb, cc, rr, gg, bb);
             if constexpr (k420<FMT>) {
                 // One luma byte per pixel.  The 2x2 chroma mean: this column's
                 // two rows (i0 and TR even: r even starts a block; H even: both
@@ -2492,18 +2224,6 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 const unsigned yc = nv12_ycode(rr, gg, bb, g, cd);
                 if constexpr (kP010<FMT>) {   // one 16-bit word per lane (always aligned)
                     st_off<uint16_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X * 2u, (uint16_t)(yc << 6));
-                } else if (MM_NV12_K4_PACK && g.W % 4 == 0 &&
-                           ((reinterpret_cast<uintptr_t>(outp) | g.lo.pitch) & 3u) == 0) {
-                    // diagnostic: the four lanes of a quad gather their codes
-                    // (quad-perm broadcasts) and lane 0 stores one dword
-                    auto bc = [&](int ctrl) {
-                        return (unsigned)(ctrl == 0x00   ? __builtin_amdgcn_mov_dpp((int)yc, 0x00, 0xF, 0xF, true)
-                                          : ctrl == 0x55 ? __builtin_amdgcn_mov_dpp((int)yc, 0x55, 0xF, 0xF, true)
-                                          : ctrl == 0xAA ? __builtin_amdgcn_mov_dpp((int)yc, 0xAA, 0xF, 0xF, true)
-                                                         : __builtin_amdgcn_mov_dpp((int)yc, 0xFF, 0xF, 0xF, true));
-                    };
-                    const unsigned y4 = bc(0x00) | bc(0x55) << 8 | bc(0xAA) << 16 | bc(0xFF) << 24;
-                    if ((X & 3) == 0) st_off<uint32_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X, y4);
                 } else {
                     st_off<uint8_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X, (uint8_t)yc);
                 }
@@ -2525,7 +2245,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                     }
                 }
             } else {
-                out_store<FMT>(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
+                Pix<FMT>::store(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
             }
         }
     }
@@ -2589,7 +2309,6 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     const unsigned cr = (unsigned)wrap_near(X + 4, g.W, g.edge);
     // horizontally combined I/Q of one source row for the quad (k_compose's
     // staged 3-tap combine over columns X-1 .. X+4)
-    const Blur5 bv = vblur_w<FMT>(bw);   // the compose's vertical blur
     auto chroma_row = [&](int i, c2 (&hc)[4]) {
         const int row = wrap_near(min(i, g.H), g.H, g.edge);
         c2 a[6];
@@ -2640,11 +2359,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     unsigned long long st_prev = __builtin_amdgcn_s_memtime();
     st_acc[7] = __builtin_amdgcn_s_memrealtime();
 #endif
-    // Q rows of step s: list-row pair i0/2 + 2s + grp (zero beyond Hn).
-    // MM_K34_QPF=1 (diagnostic) issues step s+1's Q loads after step s's blur,
-    // to land under its compose: +32 live VGPRs, 120 B of spills at the
-    // 128-VGPR bound (4 waves per SIMD) even with the compose two rows at a
-    // time (MM_K34_ROWS2), so off by default.
+    // Q rows of step s: list-row pair i0/2 + 2s + grp (zero beyond Hn)
     float4 qv[8];
     auto load_q = [&](int s_) {
         const int ka_ = i0 + 4 * s_ + 2 * grp;
@@ -2660,14 +2375,10 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
             else qv[j] = (Qp + (size_t)(N - j * T - (T - 1)) * (TK / 2))[dn];
         }
     };
-#ifndef MM_K34_QPF
-#define MM_K34_QPF 0
-#endif
-    if (MM_K34_QPF) load_q(0);
     for (int s = 0; s < steps; ++s) {
         const int ka = i0 + 4 * s + 2 * grp;
         const bool valid = ka < g.Hn;
-        if (!MM_K34_QPF) load_q(s);
+        load_q(s);
         c2 v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -2682,11 +2393,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
         K34_STAMP(0);
         fft_regs<LOG2N, +1>(v, t, lds, tw);
         K34_STAMP(1);
-#ifndef MM_K34_BLUR_R3
         float *raw = reinterpret_cast<float *>(lds) + kZShift;   // [2][N] |z| of rows ka, ka+1
-#else
-        float *raw = reinterpret_cast<float *>(lds);
-#endif
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             raw[t + j * T] = fabsf(v[j].x);
@@ -2701,19 +2408,11 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
         // ds_read2_b64 of 8-B aligned halves (2-way conflicts on every one,
         // tools/lds_banks.py "k34"); same expressions and order as k_rows_inv
         // one base address; the rows are immediate offsets
-#ifndef MM_K34_BLUR_R3
         const float4 *b4 = reinterpret_cast<const float4 *>(raw_all) + ((g.x0 + X) >> 2);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float4 *r4 = b4 + ((r >> 1) * GROUP_FLOATS + (r & 1) * N) / 4;
             const float4 P = r4[0], Z = r4[1];   // z[c-2 .. c+1], z[c+2 .. c+5]
-#else   // diagnostic: round 3's unshifted rows (taps read by the compiler's ds_read2_b64)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float4 *r4 = reinterpret_cast<const float4 *>(raw_all + (r >> 1) * GROUP_FLOATS + (r & 1) * N + g.x0 + X);
-            const float4 A = r4[-1], B = r4[0], C = r4[1];
-            const float4 P = make_float4(A.z, A.w, B.x, B.y), Z = make_float4(B.z, B.w, C.x, C.y);
-#endif
             yw[4 + r][0] = bw.w0 * P.z + bw.w1 * (P.y + P.w) + bw.w2 * (P.x + Z.x);
             yw[4 + r][1] = bw.w0 * P.w + bw.w1 * (P.z + Z.x) + bw.w2 * (P.y + Z.y);
             yw[4 + r][2] = bw.w0 * Z.x + bw.w1 * (P.w + Z.y) + bw.w2 * (P.z + Z.z);
@@ -2721,10 +2420,9 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
         }
         __syncthreads();   // LDS free for the next step's FFT
         K34_STAMP(3);
-        if (MM_K34_QPF && s + 1 < steps) load_q(s + 1);
         if (s > 0) {
             // ---- K4 on output rows i0+4s-4 .. i0+4s-1, two at a time ----
-#ifndef MM_K34_ROWS2   // the 4 chroma rows' loads first (one memory round trip)
+            // the 4 chroma rows' loads first (one memory round trip)
             if constexpr (k420<FMT>) {
                 // source rows 2j and 2j+1 share a chroma row (i0 % 4 == 0, H
                 // even): row i0+4s-3 has the kept row i0+4s-4's samples, row
@@ -2739,18 +2437,8 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
 #pragma unroll
                 for (int r = 0; r < 4; ++r) chroma_row(i0 + 4 * s - 3 + r, hc[2 + r]);
             }
-#endif
             [[maybe_unused]] c2 cd0[4];   // NV12: the even row's chroma differences
-#ifdef MM_K34_ROWS2
-#pragma unroll
-#endif
             for (int r = 0; r < 4; ++r) {
-#ifdef MM_K34_ROWS2   // diagnostic: two rows at a time (120 VGPRs; same-call K34 +8 %, r04d)
-                if (r % 2 == 0) {
-                    chroma_row(i0 + 4 * s - 3 + r, hc[2 + r]);
-                    chroma_row(i0 + 4 * s - 2 + r, hc[3 + r]);
-                }
-#endif
                 K34_STAMP(4);
                 const int i = i0 + 4 * s - 4 + r;
                 if (vq && i < g.H) {
@@ -2759,9 +2447,9 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const c2 cc = wr.x * hc[r][k] + wr.y * hc[r + 1][k] + wr.z * hc[r + 2][k];
-                        const float yb = bv.w0 * yw[r + 2][k] + bv.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
-                                         bv.w2 * (yw[r][k] + yw[r + 4][k]);
-                        yiq_rgb<FMT>(yb, cc, rr[k], gg[k], bb[k]);
+                        const float yb = bw.w0 * yw[r + 2][k] + bw.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
+                                         bw.w2 * (yw[r][k] + yw[r + 4][k]);
+                        yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
                     }
                     // (in pixels: an RGBA pitch is a multiple of the pixel size)
                     [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
@@ -2769,16 +2457,16 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
                     } else if constexpr (bpp == 4) {
                         uint4 px;
-                        px.x = out_pack<FMT>(rr[0], gg[0], bb[0]);
-                        px.y = out_pack<FMT>(rr[1], gg[1], bb[1]);
-                        px.z = out_pack<FMT>(rr[2], gg[2], bb[2]);
-                        px.w = out_pack<FMT>(rr[3], gg[3], bb[3]);
+                        px.x = Pix<FMT>::pack(rr[0], gg[0], bb[0]);
+                        px.y = Pix<FMT>::pack(rr[1], gg[1], bb[1]);
+                        px.z = Pix<FMT>::pack(rr[2], gg[2], bb[2]);
+                        px.w = Pix<FMT>::pack(rr[3], gg[3], bb[3]);
                         // scalar row base + the thread's column offset: one
                         // live VGPR, not a hoisted offset per row
                         st_stream_quad_a4(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 4u, px);
                     } else {
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) out_store<FMT>(outp, o + k, rr[k], gg[k], bb[k]);
+                        for (int k = 0; k < 4; ++k) Pix<FMT>::store(outp, o + k, rr[k], gg[k], bb[k]);
                     }
                 }
             }
@@ -2879,7 +2567,6 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     const int X = vq ? 4 * q : g.W - 4;
     const unsigned cl = (unsigned)wrap_near(X - 1, g.W, g.edge);
     const unsigned cr = (unsigned)wrap_near(X + 4, g.W, g.edge);
-    const Blur5 bv = vblur_w<FMT>(bw);   // the compose's vertical blur
     auto chroma_row = [&](int i, c2 (&hc)[4]) {   // k_rows_inv_compose's
         const int row = wrap_near(min(i, g.H), g.H, g.edge);
         c2 a[6];
@@ -2953,23 +2640,23 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const c2 cc = wr.x * hc[r][k] + wr.y * hc[r + 1][k] + wr.z * hc[r + 2][k];
-                const float yb = bv.w0 * yw[r + 2][k] + bv.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
-                                 bv.w2 * (yw[r][k] + yw[r + 4][k]);
-                yiq_rgb<FMT>(yb, cc, rr[k], gg[k], bb[k]);
+                const float yb = bw.w0 * yw[r + 2][k] + bw.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
+                                 bw.w2 * (yw[r][k] + yw[r + 4][k]);
+                yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
             }
             [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
             if constexpr (k420<FMT>) {
                 c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
             } else if constexpr (bpp == 4) {
                 uint4 px;
-                px.x = out_pack<FMT>(rr[0], gg[0], bb[0]);
-                px.y = out_pack<FMT>(rr[1], gg[1], bb[1]);
-                px.z = out_pack<FMT>(rr[2], gg[2], bb[2]);
-                px.w = out_pack<FMT>(rr[3], gg[3], bb[3]);
+                px.x = Pix<FMT>::pack(rr[0], gg[0], bb[0]);
+                px.y = Pix<FMT>::pack(rr[1], gg[1], bb[1]);
+                px.z = Pix<FMT>::pack(rr[2], gg[2], bb[2]);
+                px.w = Pix<FMT>::pack(rr[3], gg[3], bb[3]);
                 st_stream_quad_a4(outp, o * 4u, px);
             } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) out_store<FMT>(outp, o + k, rr[k], gg[k], bb[k]);
+                for (int k = 0; k < 4; ++k) Pix<FMT>::store(outp, o + k, rr[k], gg[k], bb[k]);
             }
         }
     }

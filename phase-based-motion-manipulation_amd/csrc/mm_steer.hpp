@@ -112,19 +112,16 @@ template <int N> __device__ __forceinline__ size_t t_row(int k)   // offset of (
 constexpr int t_col_stride() { return kSbR; }                     // between (k, kx) and (k, kx+1)
 // rows per band in T (whole row groups)
 __host__ __device__ constexpr int t_rows(int hn) { return (hn + kSbR - 1) / kSbR * kSbR; }
-// k_sb_cols staging: column c's rows at c S + k (MM_SB_STG_CM = 1), S = the
+// k_sb_cols staging: column c's rows at c S + k, S = the
 // rows rounded up to 16 mod 32 entries from N = 1024 on: the rows' 8-B
 // writes (16 consecutive rows per lane group) are conflict-free, and so are
 // the float4 reads of a row group's columns (S 2 = 32 mod 64 dwords puts
 // column 1 on the other half of the banks; tools/lds_banks.py "sb_stg").
-// MM_SB_STG_CM = 0: row-group-major (k / R) R GPW + R c + k % R (2-way
-// conflicted writes).
-#ifndef MM_SB_STG_CM
-#define MM_SB_STG_CM 1
-#endif
+// (Row-group-major staging, (k / R) R GPW + R c + k % R: 2-way conflicted
+// writes.)
 __host__ __device__ constexpr int sb_stg_stride(int hn, int n)
 {
-    return MM_SB_STG_CM && n >= 1024 ? (t_rows(hn) + 15) / 32 * 32 + 16 : t_rows(hn);
+    return n >= 1024 ? (t_rows(hn) + 15) / 32 * 32 + 16 : t_rows(hn);
 }
 
 // -------------------------------------------------------------------------
@@ -138,9 +135,6 @@ __host__ __device__ constexpr int sb_stg_stride(int hn, int n)
 // workgroup) / 16 B (R = 1) / 32 B (R = 2) per lane: C3 O = 8 k_sb_cols 1,020 /
 // 594 / 434 us per frame (profiles/r06h_sb_rows_layout_ab.txt).  The band loop
 // issues no loads (twiddle bases hoisted), so its stores are never waited for.
-#ifndef MM_SB_COLS_WL
-#define MM_SB_COLS_WL 1
-#endif
 template <int LOG2N>
 __global__ __launch_bounds__(sb_threads<LOG2N>()) __attribute__((amdgpu_waves_per_eu(4)))
 void k_sb_cols(const c2 *__restrict__ Fb, c2 *__restrict__ Tb, size_t band_stride, Geo g, Spec sp,
@@ -151,8 +145,7 @@ void k_sb_cols(const c2 *__restrict__ Fb, c2 *__restrict__ Tb, size_t band_strid
     Fb += blockIdx.y * f_stride;
     Tb += blockIdx.y * t_stride;
     constexpr int N = 1 << LOG2N, T = fft_T<LOG2N>(), GPW = sb_groups<LOG2N>();
-    constexpr bool SB_WL = MM_SB_COLS_WL && fft_c_v(LOG2N) > 1;
-    constexpr bool DIRECT = SB_WL && sb_direct<LOG2N>();
+    constexpr bool SB_WL = fft_c_v(LOG2N) > 1;
     extern __shared__ __attribute__((aligned(16))) c2 lds_all[];
     const int grp = T % 64 == 0 ? __builtin_amdgcn_readfirstlane(threadIdx.x / T) : threadIdx.x / T;
     const int t0 = threadIdx.x % T;
@@ -226,7 +219,6 @@ void k_sb_cols(const c2 *__restrict__ Fb, c2 *__restrict__ Tb, size_t band_strid
     // add the angular factor (the same expressions per band: bitwise the
     // band-major loop's values).  The residual band (b = nb) runs last.
     float rm[8];
-    int nbuf = 0;   // DIRECT: exchange buffer of the next band run
     for (int lb = 0; lb <= nb; ++lb) {
         const int i = lb < nb ? 1 + lb / (sp.O / 2) : 0, o = lb < nb ? lb % (sp.O / 2) : 0;
         const int b = lb < nb ? o * nmid + (i - 1) : nb;
@@ -262,20 +254,6 @@ void k_sb_cols(const c2 *__restrict__ Fb, c2 *__restrict__ Tb, size_t band_strid
             }
             v[j] = scale(v0[j], m);
         }
-        if constexpr (DIRECT) {
-            // one column: rows t + jT leave from registers as 8-B values;
-            // the two exchange buffers alternate, so no barrier guards the
-            // next band's writes against this band's cross-wave reads
-            fft_dit<LOG2N, +1>(v, t, lds_all + nbuf * lds_complex<N>(), wt);
-            nbuf ^= 1;
-            c2 *out = Tb + (size_t)b * band_stride + (size_t)kx * t_col_stride();
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int k = (t + j * T - g.rb + 2 * N) & (N - 1);
-                if (valid && k < g.Hn) out[t_row<N>(k)] = v[j];
-            }
-            continue;
-        }
         if constexpr (SB_WL) {
             fft_dit<LOG2N, +1>(v, t, lds, wt);
             // staging over the exchange buffers: every wave past its reads first
@@ -283,19 +261,17 @@ void k_sb_cols(const c2 *__restrict__ Fb, c2 *__restrict__ Tb, size_t band_strid
         } else {
             fft_regs_w<LOG2N, +1>(v, t, lds, wt);   // ends with a barrier after its last exchange read
         }
-        // staging: column-major (c S + k, MM_SB_STG_CM) or in T's order (row
-        // group m's GPW columns x R rows at m R GPW)
+        // staging: column-major (c S + k)
         const int S = sb_stg_stride(g.Hn, N);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int k = (t + j * T - g.rb + 2 * N) & (N - 1);
-            if (k < g.Hn)
-                stg[MM_SB_STG_CM ? grp * S + k : (k / kSbR) * (kSbR * GPW) + kSbR * grp + k % kSbR] = v[j];
+            if (k < g.Hn) stg[grp * S + k] = v[j];
         }
         __syncthreads();
         c2 *out = Tb + (size_t)b * band_stride;
         const int groups = t_rows(g.Hn) / kSbR;
-        if constexpr (MM_SB_STG_CM && kSbR > 1 && GPW <= N) {   // R GPW / 2 float4 per row group
+        if constexpr (kSbR > 1 && GPW <= N) {   // R GPW / 2 float4 per row group
             // float4 q of row group m: column q / (R/2), rows 2 (q % (R/2)) ..
             // +1 of the group (a last partial group's missing rows are stale
             // staging, written to T's pad rows, which k_sb_rows never reads)
@@ -305,36 +281,10 @@ void k_sb_cols(const c2 *__restrict__ Fb, c2 *__restrict__ Tb, size_t band_strid
                 *reinterpret_cast<float4 *>(out + (size_t)m * (kSbR * N) + kSbR * kx0 + 2 * q) =
                     *reinterpret_cast<const float4 *>(stg + c * S + m * kSbR + 2 * h);
             }
-        } else if constexpr (MM_SB_STG_CM) {    // R = 1, or tiny N (fewer columns than groups)
+        } else {    // R = 1, or tiny N (fewer columns than groups)
             for (int e = grp * T + t; e < groups * kSbR * GPW; e += GPW * T) {
                 const int m = e / (kSbR * GPW), o = e - m * (kSbR * GPW), c = o / kSbR, kk = o - c * kSbR;
                 if (kx0 + c < N) out[(size_t)m * (kSbR * N) + kSbR * (kx0 + c) + kk] = stg[c * S + m * kSbR + kk];
-            }
-        } else if constexpr (kSbR > 1 && GPW <= N) {   // whole pieces: R GPW / 2 float4 per row group
-            // (a last partial group's missing rows are stale staging, written
-            // to T's pad rows, which k_sb_rows never reads)
-            constexpr int PW = kSbR * GPW / 2;
-            for (int e = grp * T + t; e < groups * PW; e += GPW * T) {
-                const int m = e / PW, part = e - m * PW;
-                *reinterpret_cast<float4 *>(out + (size_t)m * (kSbR * N) + kSbR * kx0 + 2 * part) =
-                    reinterpret_cast<const float4 *>(stg)[e];
-            }
-        } else if constexpr (kSbR > 1) {       // tiny N: fewer columns than groups
-            for (int e = grp * T + t; e < groups * kSbR * GPW; e += GPW * T) {
-                const int m = e / (kSbR * GPW), c = (e / kSbR) % GPW, kk = e % kSbR;
-                if (kx0 + c < N) out[(size_t)m * (kSbR * N) + kSbR * (kx0 + c) + kk] = stg[e];
-            }
-        } else if constexpr (GPW >= 2 && GPW <= N) {   // whole pieces: GPW / 2 float4 per row
-            constexpr int PW = GPW / 2;
-            for (int e = grp * T + t; e < g.Hn * PW; e += GPW * T) {
-                const int k = e / PW, part = e - k * PW;
-                *reinterpret_cast<float4 *>(out + (size_t)k * N + kx0 + 2 * part) =
-                    reinterpret_cast<const float4 *>(stg)[e];
-            }
-        } else {                    // tiny N: fewer columns than groups
-            for (int e = grp * T + t; e < g.Hn * GPW; e += GPW * T) {
-                const int k = e / GPW, c = e - k * GPW;
-                if (kx0 + c < N) out[(size_t)k * N + kx0 + c] = stg[e];
             }
         }
         // the next band's FFT rewrites the buffers (an own staging area: the
@@ -369,27 +319,14 @@ void k_sb_cols(const c2 *__restrict__ Fb, c2 *__restrict__ Tb, size_t band_strid
 // its Yh at Yh + f * yh_stride; reset applies to frame 0 (the stream's first
 // frame: it seeds the state and passes through); write_mask bit f: frame f's
 // Yh is wanted.
-#ifndef MM_SB_OFF32
-#define MM_SB_OFF32 1
-#endif
-#ifndef MM_SB_IIR_GROUPS
-#define MM_SB_IIR_GROUPS 0
-#endif
-// k_sb_rows' twiddle bases loaded per band from the (L1-resident) table
-// instead of ~20 VGPRs held across the band loop: IIR (its band loop then
-// fits 128 VGPRs without spills: 1080p O = 8 IIR 4.43k -> 4.52k frames/s,
-// profiles/r06h_sb_rows_layout_ab.txt); MM_SB_TWLD_DIFF for DIFF (at 6 waves
-// per SIMD, 80 VGPRs, it spills 18)
-#ifndef MM_SB_TWLD_IIR
-#define MM_SB_TWLD_IIR 1
-#endif
-#ifndef MM_SB_TWLD_DIFF
-#define MM_SB_TWLD_DIFF 0
-#endif
-template <bool IIR> constexpr bool kSbRowsTwLd = IIR ? MM_SB_TWLD_IIR : MM_SB_TWLD_DIFF;
+// IIR loads its twiddle bases per band from the (L1-resident) table instead
+// of holding ~20 VGPRs across the band loop (its band loop then fits 128 VGPRs
+// without spills: 1080p O = 8 IIR 4.43k -> 4.52k frames/s,
+// profiles/r06h_sb_rows_layout_ab.txt); DIFF keeps them in registers (loading
+// them at 6 waves per SIMD, 80 VGPRs, spills 18).
 template <int LOG2N, bool IIR, int NF>
 __global__ __launch_bounds__(sb_rows_threads<LOG2N>())
-__attribute__((amdgpu_waves_per_eu(IIR || NF > 2 || sb_rows_threads<LOG2N>() >= 1024 ? 4 : 5)))
+__attribute__((amdgpu_waves_per_eu(IIR || sb_rows_threads<LOG2N>() >= 1024 ? 4 : 5)))
 void k_sb_rows(const c2 *Tb, size_t band_stride, size_t t_stride, float *__restrict__ Yh, size_t yh_stride,
                float *st_phi, float *st_uh, float *st_ul,
                int reset, int write_mask, Geo g, Spec sp, Blur5 bw, const c2 *__restrict__ tw, int ngroups)
@@ -412,7 +349,7 @@ void k_sb_rows(const c2 *Tb, size_t band_stride, size_t t_stride, float *__restr
     c2 wtw[kTwSlots];
 #pragma unroll
     for (int i = 0; i < kTwSlots; ++i) wtw[i] = mk(1.0f, 0.0f);
-    if constexpr (!kSbRowsTwLd<IIR>) preload_twiddles<LOG2N>(wtw, t0, tw);   // forward bases; fft_regs_w conjugates
+    if constexpr (!IIR) preload_twiddles<LOG2N>(wtw, t0, tw);   // forward bases; fft_regs_w conjugates
     // row k of band b of frame f (contiguous) and its state: loaded one row ahead
     c2 v[8];
     float pp[8], puh[8], pul[8];
@@ -425,14 +362,13 @@ void k_sb_rows(const c2 *Tb, size_t band_stride, size_t t_stride, float *__restr
     int rz = reset;
     auto load_row = [&](int f, int b, int t) {
         // (row base per workgroup, 32-bit lane offsets: no 64-bit address
-        // math per element, MM_SB_OFF32)
+        // math per element)
         const c2 *row = Tg + (size_t)f * t_stride + (size_t)b * band_stride + t_row<N>(k);
 #pragma unroll
         for (int j = 0; j < 8; ++j)   // band_col_zero columns were never written: 0
             v[j] = band_col_zero<N>(b, nb, nmid, t + j * T, sp)
                        ? mk(0.0f, 0.0f)
-                       : (MM_SB_OFF32 ? ld_off<c2>(row, (unsigned)((t + j * T) * t_col_stride()) * 8u)
-                                      : row[(t + j * T) * t_col_stride()]);
+                       : ld_off<c2>(row, (unsigned)((t + j * T) * t_col_stride()) * 8u);
     };
     auto load_state = [&](int b, int t) {
         if (b < nb && !rz) {
@@ -440,25 +376,17 @@ void k_sb_rows(const c2 *Tb, size_t band_stride, size_t t_stride, float *__restr
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int xi = min((t + j * T - xs + N) & (N - 1), Wc - 1);
-                if (MM_SB_OFF32) {
-                    pp[j] = ld_off<float>(st_phi + rs, (unsigned)xi * 4u);
-                    if (iir) {
-                        puh[j] = ld_off<float>(st_uh + rs, (unsigned)xi * 4u);
-                        pul[j] = ld_off<float>(st_ul + rs, (unsigned)xi * 4u);
-                    }
-                } else {
-                    pp[j] = st_phi[rs + xi];
-                    if (iir) {
-                        puh[j] = st_uh[rs + xi];
-                        pul[j] = st_ul[rs + xi];
-                    }
+                pp[j] = ld_off<float>(st_phi + rs, (unsigned)xi * 4u);
+                if (iir) {
+                    puh[j] = ld_off<float>(st_uh + rs, (unsigned)xi * 4u);
+                    pul[j] = ld_off<float>(st_ul + rs, (unsigned)xi * 4u);
                 }
             }
         }
     };
     // (IIR: one group per launch; its three state planes leave no registers
     // for the loop: 34 B of spills inside the band loop, k_sb_rows +6 %)
-    const int ngr = IIR && !MM_SB_IIR_GROUPS ? 1 : ngroups;
+    const int ngr = IIR ? 1 : ngroups;
     for (int gi = 0; gi < ngr; ++gi) {
     Tg = Tb + (size_t)gi * NF * t_stride;
     rz = gi == 0 ? reset : 0;
@@ -482,7 +410,7 @@ void k_sb_rows(const c2 *Tb, size_t band_stride, size_t t_stride, float *__restr
             int t = t0;
             asm volatile("" : "+v"(t));
             c2 wt[kTwSlots];
-            if constexpr (kSbRowsTwLd<IIR>) {
+            if constexpr (IIR) {
                 // (IIR: the twiddle bases from the L1-resident table per band
                 // instead of ~20 VGPRs held across the band loop)
 #pragma unroll
@@ -561,18 +489,10 @@ void k_sb_rows(const c2 *Tb, size_t band_stride, size_t t_stride, float *__restr
                 for (int j = 0; j < 8; ++j) {
                     const int xi = (t + j * T - xs + N) & (N - 1);
                     if (xi < Wc) {
-                        if (MM_SB_OFF32) {
-                            st_off<float>(st_phi + rs, (unsigned)xi * 4u, nph[j]);
-                            if (iir) {
-                                st_off<float>(st_uh + rs, (unsigned)xi * 4u, nuh[j]);
-                                st_off<float>(st_ul + rs, (unsigned)xi * 4u, nul[j]);
-                            }
-                        } else {
-                            st_phi[rs + xi] = nph[j];
-                            if (iir) {
-                                st_uh[rs + xi] = nuh[j];
-                                st_ul[rs + xi] = nul[j];
-                            }
+                        st_off<float>(st_phi + rs, (unsigned)xi * 4u, nph[j]);
+                        if (iir) {
+                            st_off<float>(st_uh + rs, (unsigned)xi * 4u, nuh[j]);
+                            st_off<float>(st_ul + rs, (unsigned)xi * 4u, nul[j]);
                         }
                     }
                 }

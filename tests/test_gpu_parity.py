@@ -457,22 +457,22 @@ def test_k2_tail_bitwise_equals_single_launch(W, H, n, batch, tail, monkeypatch)
         assert np.array_equal(x, y)
 
 
-# ---- round 4: K2 staging area and the two-band op -----------------------------
+# ---- K2's Q staging: run-to-run bitwise repeatability ---------------------------
 @pytest.mark.parametrize("W,H,n,batch", [(1920, 1080, 40, 20), (640, 360, 30, 10), (200, 120, 20, 7)])
-def test_k2_dedicated_staging_bitwise_equals_aliased(W, H, n, batch, monkeypatch):
-    """k_cols with its own Q staging area in LDS (MM_K2_STGD=1: 2 barriers per
-    frame fewer, where it fits beside two workgroups per CU; opt-in) gives
-    bitwise the outputs of the default staging that aliases the FFT exchange
-    buffers."""
+def test_k2_dedicated_staging_bitwise_equals_aliased(W, H, n, batch):
+    """Two runs of the same stream on fresh handles are bitwise equal: k_cols's
+    staged Q pieces alias its FFT exchange buffers, guarded by two workgroup
+    barriers per frame, and a missing guard shows as run-to-run differences.
+    (The name is from the A/B of a removed dedicated staging area, whose two
+    legs these runs were.)"""
     fr = T.synth(W, H, n, fmt="u8")
-    monkeypatch.setenv("MM_K2_STGD", "0")
     a = T.gpu_run(W, H, fr, 5, 25.0, mode="stream", batch=batch)
-    monkeypatch.setenv("MM_K2_STGD", "1")
     b = T.gpu_run(W, H, fr, 5, 25.0, mode="stream", batch=batch)
     for x, y in zip(a, b):
         assert np.array_equal(x, y)
 
 
+# ---- round 4: the two-band op -------------------------------------------------
 @pytest.mark.parametrize("W,H,S", [(256, 192, 25.0), (320, 200, 9.7)])
 def test_two_band_op_l6_vs_oracle(W, H, S):
     """L = 6 (neighbouring middle bands overlap: MM_K2_PYR_TAB2, the branch-
@@ -503,24 +503,46 @@ def test_two_band_op_tail_and_batch_bitwise(monkeypatch):
         assert np.array_equal(x, y) and np.array_equal(x, z)
 
 
-# ---- round 4: the packed block entirely in k_cols_tail (MM_K2_PKALL) --------------
+# ---- batches >= 24 frames (k_cols_tail, tail blocks) against one-frame calls -----
 @pytest.mark.parametrize("W,H,L,n,batch", [(1920, 1080, 5, 30, 30), (1920, 1080, 6, 30, 30),
                                            (640, 360, 5, 60, 25), (2100, 64, 6, 50, 25)])
-def test_k2_packed_all_in_tail_bitwise(W, H, L, n, batch, monkeypatch):
-    """Batches >= 24 frames with block 0 (the packed group) out of k_cols and
-    every one of its frames a k_cols_tail workgroup (frame 0 primed from the
-    state slot, the others from the previous input frame): bitwise the
-    outputs with block 0 in k_cols and of one-frame calls (2100 x 64: N =
-    4096).  Opt-in (MM_K2_PKALL=1): same-call no faster at the default shapes."""
+def test_k2_packed_all_in_tail_bitwise(W, H, L, n, batch):
+    """Batches >= 24 frames, whose packed block hands its last frames to
+    k_cols_tail workgroups (each primed from the previous input frame) and
+    whose second-half blocks run tail blocks: bitwise the outputs of one-frame
+    calls (2100 x 64: N = 4096).  (The name is from a removed variant that ran
+    every packed-block frame in k_cols_tail; this is its default-path leg.)"""
     fr = T.synth(W, H, n, fmt="u8")
-    monkeypatch.setenv("MM_K2_PKALL", "0")
     a = T.gpu_run(W, H, fr, L, 25.0, mode="stream", batch=batch)
-    monkeypatch.setenv("MM_K2_PKALL", "1")
-    b = T.gpu_run(W, H, fr, L, 25.0, mode="stream", batch=batch)
-    monkeypatch.delenv("MM_K2_PKALL")
     c = T.gpu_run(W, H, fr, L, 25.0, mode="frame", batch=1)
-    for x, y, z in zip(a, b, c):
-        assert np.array_equal(x, y) and np.array_equal(x, z)
+    for x, z in zip(a, c):
+        assert np.array_equal(x, z)
+
+
+# ---- K2's phase factor at N = 2048: integer S of both signs, one- and two-band ------
+@pytest.mark.parametrize("S,L", [(25.0, 5), (10.0, 5), (-25.0, 5), (25.0, 6), (-10.0, 6)])
+def test_k2_n2048_integer_scales_vs_oracle(S, L):
+    """1100 x 48 (N = 2048) at the configurations' phase scales and their
+    negatives, one-band (L = 5) and two-band (L = 6) layouts: k_cols's atan2 +
+    sin/cos phase factor against the oracle's literal atan2f path."""
+    W, H = 1100, 48
+    fr = T.synth(W, H, 5)
+    at = T.gpu_run(W, H, fr, L, S, mode="stream", batch=3)
+    ref = T.oracle_run(W, H, fr, L, S)
+    assert np.array_equal(at[0], fr[0])
+    for k in range(1, 5):
+        T.assert_close_f32(at[k], ref[k])
+
+
+def test_k2_n2048_stream_equals_frame_calls_bitwise():
+    """frame-at-a-time (the packed group's one-bin ops every call) and a long
+    batch whose last frames run in k_cols_tail: both equal the stream."""
+    W, H = 1100, 48
+    fr = T.synth(W, H, 30)
+    st = T.gpu_run(W, H, fr, 5, 25.0, mode="stream", batch=30)
+    fm = T.gpu_run(W, H, fr, 5, 25.0, mode="frame", batch=3)
+    for a, b in zip(st, fm):
+        assert np.array_equal(a, b)
 
 
 # ---- K2's generic per-bin op (MM_MODE_PYRAMID instance) ---------------------------
