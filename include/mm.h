@@ -19,7 +19,8 @@
  *     8-bit sRGB target as Unity's Linear colour space sees it (decoded to
  *     linear light on read, encoded on write).  MM_NV12 / MM_NV12_FULL are
  *     video frames, planar Y'CbCr 4:2:0, and MM_P010 / MM_P010_FULL their
- *     10-bit form (see the format list).  The handle
+ *     10-bit form, BT.601 or with a matrix bit BT.709 / BT.2020 (see the
+ *     format list).  The handle
  *     owns all device scratch and the one-frame temporal state.
  *   - A handle is not thread-safe: one handle per video stream, calls in frame
  *     order (Unity calls OnRenderImage serially on its render thread).
@@ -131,11 +132,49 @@ extern "C" {
  * a quarter of an 8-bit source's luma quantisation noise for phase_scale to
  * amplify.  The first frame and apply_magnification = 0 pass all 3 W H bytes
  * through bitwise, low bits included.
- * The matrix stays BT.601 because its luma weights are RGBToYIQ's own (what
- * lets the transform read the luma plane alone).  Out of scope: BT.709 /
- * BT.2020 matrices, PQ / HLG transfer curves, 4:2:2 and 4:4:4. */
+ * These four codes are BT.601, whose luma weights are RGBToYIQ's own (what
+ * lets the transform read the luma plane alone); the matrix bits below select
+ * BT.709 or BT.2020. */
 #define MM_P010      18   /* 10-bit 4:2:0, BT.601 matrix, limited range */
 #define MM_P010_FULL 19   /* the same, full range                        */
+
+/* HD and UHD video frames (backward-compatible addition to ABI 10: a caller
+ * detects it by mm_frame_bytes(W, H, MM_NV12 | MM_MATRIX_BT709, &n) == MM_OK).
+ * One matrix bit, OR-ed onto one of the four 4:2:0 codes above, names the
+ * Y'CbCr matrix of the content: H.264 / HEVC / AV1 at 720p and above is
+ * BT.709, 10-bit HEVC Main10 / AV1 BT.709 or BT.2020.  The valid formats are
+ * then 16..19 (BT.601, unchanged), 48..51 and 80..83 (8-bit BT.2020 included).
+ * A matrix bit on an RGBA format, both bits together or any other unknown bit
+ * is MM_ERR_INVALID from mm_frame_bytes, mm_surface_* and every frame entry
+ * point, before anything is queued; the handle stays usable.  Layout, sizes,
+ * surface units (2 and 4), even W and H, no debug views, in_layout->format ==
+ * out_layout->format and the bitwise passthrough of the first frame and of
+ * apply_magnification = 0 are the base code's.
+ * With (Kr, Kb) the bit's and Kg = 1 - Kr - Kb, the frame IS the RGBA32F frame
+ * of this decode and the result the reference's result on it:
+ *   in:  y, cb, cr from the codes by the range's scales exactly as above
+ *        (limited / _FULL; P010 in word units); R = y + 2 (1 - Kr) cr,
+ *        B = y + 2 (1 - Kb) cb, G = y - (2 Kb (1 - Kb) / Kg) cb -
+ *        (2 Kr (1 - Kr) / Kg) cr, alpha 1, NOT clamped, every chroma sample
+ *        shared by its 2 x 2 pixels;
+ *   out: of the saturated RGB, Y' = Kr R + Kg G + Kb B, Cb' = (B - Y') /
+ *        (2 (1 - Kb)), Cr' = (R - Y') / (2 (1 - Kr)); codes, the mean of the
+ *        2 x 2 pixels' C', rounding and clamps exactly as NV12 / P010 above.
+ * No shortcut: Y' is not the reference's luma here.  RGBToYIQ's luma of the
+ * decoded pixel is Yq = y + a cb + b cr with
+ *   a = 0.114 x 2 (1 - Kb) - 0.587 x 2 Kb (1 - Kb) / Kg,
+ *   b = 0.299 x 2 (1 - Kr) - 0.587 x 2 Kr (1 - Kr) / Kg
+ * (BT.709: a = 0.10158, b = 0.19608; BT.601: both 0, by this header's
+ * definition), so these frames cost the forward row kernel a read of the
+ * half-resolution chroma plane next to the luma plane (1.5 samples per pixel
+ * instead of 1).  The I and Q rows of RGBToYIQ sum to 0, so (I, Q) stays a
+ * 2 x 2 matrix of (cb, cr) (mm_ycbcr_matrix); neutral chroma still gives
+ * exactly zero I and Q and luma = y.
+ * Out of scope: PQ / HLG transfer curves (the samples are taken as they are,
+ * like every other format's), constant-luminance BT.2020, 4:2:2 and 4:4:4,
+ * chroma siting other than the shared 2 x 2 sample, odd sizes. */
+#define MM_MATRIX_BT709   32   /* Kr 0.2126, Kb 0.0722 */
+#define MM_MATRIX_BT2020  64   /* Kr 0.2627, Kb 0.0593, non-constant luminance */
 
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0   /* usePyramidDecomposition = true (.cs:18, :128-131) */
@@ -265,7 +304,7 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  * an unaligned frame takes the narrower access, never another kernel: a layout
  * aligned like a decoder's runs exactly the tight layout's kernels. */
 typedef struct {
-    int    format;         /* MM_RGBA8 ... MM_P010_FULL */
+    int    format;         /* MM_RGBA8 ... MM_P010_FULL, 4:2:0: | MM_MATRIX_* */
     size_t pitch;          /* bytes from one row to the next: RGBA rows, or luma rows */
     size_t chroma_offset;  /* 4:2:0: bytes from the frame's base to the (Cb,Cr) plane; else 0 */
     size_t chroma_pitch;   /* 4:2:0: bytes from one (Cb,Cr) row to the next; else 0 */
@@ -421,6 +460,12 @@ int mm_resample_table(int width, int height, int axis, int edge_mode,
  * Q_cr}: RGBToYIQ's I and Q rows times the BT.601 conversion above, derived
  * in double (the kernels take it divided by the range's chroma scale). */
 int mm_nv12_chroma_matrix(double m[4]);
+/* The (cb, cr) -> (Y, I, Q) matrix of a 4:2:0 format, m = {Y_cb, I_cb, Q_cb,
+ * Y_cr, I_cr, Q_cr}: RGBToYIQ's rows times the format's decode (its matrix
+ * bit's; the range does not enter), derived in double.  Y_cb, Y_cr are the a,
+ * b of Yq above; for the BT.601 codes they are exactly 0 and the I, Q entries
+ * mm_nv12_chroma_matrix's.  MM_ERR_INVALID for any other format. */
+int mm_ycbcr_matrix(int format, double m[6]);
 
 #ifdef __cplusplus
 }

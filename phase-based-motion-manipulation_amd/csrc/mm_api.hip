@@ -400,6 +400,13 @@ int mm_nv12_chroma_matrix(double m[4])
     return MM_OK;
 }
 
+int mm_ycbcr_matrix(int format, double m[6])
+{
+    if (!m || !fmt_valid(format) || !fmt_420(format)) return MM_ERR_INVALID;
+    ycbcr_matrix(format, m);
+    return MM_OK;
+}
+
 void *mm_stream(mm_handle *h) { return h ? (void *)h->stream : nullptr; }
 
 int mm_set_batch(mm_handle *h, int frames)

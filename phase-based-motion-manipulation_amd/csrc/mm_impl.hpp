@@ -206,13 +206,21 @@ static inline size_t fmt_bpp(int fmt)
 {
     return fmt == MM_RGBA32F ? 16 : fmt == MM_RGBA16F ? 8 : 4;
 }
-static inline bool fmt_nv12(int fmt) { return fmt == MM_NV12 || fmt == MM_NV12_FULL; }
-static inline bool fmt_p010(int fmt) { return fmt == MM_P010 || fmt == MM_P010_FULL; }
+// A 4:2:0 code may carry one matrix bit (MM_MATRIX_BT709 / MM_MATRIX_BT2020):
+// layout, sizes and units are its base code's, the bit changes coefficients
+// (geo_of) and K1's instance (MM_FMT_SWITCH_K1).
+static constexpr int kMatrixBits = MM_MATRIX_BT709 | MM_MATRIX_BT2020;
+static inline int fmt_base(int fmt) { return fmt & ~kMatrixBits; }
+static inline int fmt_matrix(int fmt) { return fmt & kMatrixBits; }
+static inline bool fmt_nv12(int fmt) { return fmt_base(fmt) == MM_NV12 || fmt_base(fmt) == MM_NV12_FULL; }
+static inline bool fmt_p010(int fmt) { return fmt_base(fmt) == MM_P010 || fmt_base(fmt) == MM_P010_FULL; }
 static inline bool fmt_420(int fmt) { return fmt_nv12(fmt) || fmt_p010(fmt); }   // planar, not Pix<FMT>
+static inline bool fmt_full(int fmt) { return fmt_base(fmt) == MM_NV12_FULL || fmt_base(fmt) == MM_P010_FULL; }
 static inline bool fmt_valid(int fmt)
 {
-    return fmt == MM_RGBA8 || fmt == MM_RGBA32F || fmt == MM_RGBA16F || fmt == MM_RGBA8_SRGB ||
-           fmt_420(fmt);
+    if (fmt == MM_RGBA8 || fmt == MM_RGBA32F || fmt == MM_RGBA16F || fmt == MM_RGBA8_SRGB) return true;
+    // (any other bit, a negative code included, leaves a base that is no 4:2:0 code)
+    return fmt_420(fmt) && fmt_matrix(fmt) != kMatrixBits;
 }
 // Bytes of one W x H frame (the planar 4:2:0 formats: W H luma samples and half
 // as many chroma samples, of 1 byte (NV12) or 2 (P010); W and H even, fmt_check).
@@ -326,11 +334,13 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
 
 static_assert(kFmtNV12 == MM_NV12, "the kernels' NV12 template argument is the format code");
 static_assert(kFmtP010 == MM_P010, "the kernels' P010 template argument is the format code");
+static_assert(kFmtNV12M == (MM_NV12 | MM_MATRIX_BT709) && kFmtP010M == (MM_P010 | MM_MATRIX_BT709),
+              "K1's matrixed template arguments are the BT.709 limited-range codes");
 // Runs the statement with the compile-time format FMT_ of the runtime `fmt`
 // (both NV12 ranges run the MM_NV12 instances, both P010 ranges the MM_P010
-// instances; geo_of sets their uniforms).
+// instances, whatever the matrix bit; geo_of sets their uniforms).
 #define MM_FMT_SWITCH(fmt, ...)                                                \
-    switch (fmt) {                                                             \
+    switch (fmt_base(fmt)) {                                                   \
     case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
     case MM_RGBA32F: { constexpr int FMT_ = MM_RGBA32F; __VA_ARGS__; } break;  \
     case MM_RGBA16F: { constexpr int FMT_ = MM_RGBA16F; __VA_ARGS__; } break;  \
@@ -338,6 +348,12 @@ static_assert(kFmtP010 == MM_P010, "the kernels' P010 template argument is the f
     case MM_P010: case MM_P010_FULL: { constexpr int FMT_ = MM_P010; __VA_ARGS__; } break; \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
+// ... K1's: a code with a matrix bit runs the matrixed NV12 / P010 instance,
+// which reads the chroma plane too (BT.709 and BT.2020, both ranges, share it)
+#define MM_FMT_SWITCH_K1(fmt, ...)                                             \
+    if (fmt_matrix(fmt) && fmt_nv12(fmt)) { constexpr int FMT_ = kFmtNV12M; __VA_ARGS__; }      \
+    else if (fmt_matrix(fmt)) { constexpr int FMT_ = kFmtP010M; __VA_ARGS__; }                  \
+    else MM_FMT_SWITCH(fmt, __VA_ARGS__)
 // ... and the kernels that have no NV12 / P010 instance (odd sizes and the debug
 // views, refused by fmt_check before any launch)
 #define MM_FMT_SWITCH_RGBA(fmt, ...)                                           \
@@ -353,6 +369,43 @@ static_assert(kFmtP010 == MM_P010, "the kernels' P010 template argument is the f
 // BT.601 conversion R = y + 1.402 cr, G = y - 0.344136 cb - 0.714136 cr,
 // B = y + 1.772 cb, in double: m = {I_cb, Q_cb, I_cr, Q_cr}.  (The y column
 // of the product is the rows' sums, 0 for I and Q.)
+// (Kr, Kb) of a matrix bit (include/mm.h)
+static inline void matrix_krkb(int fmt, double *kr, double *kb)
+{
+    const int mx = fmt_matrix(fmt);
+    *kr = mx == MM_MATRIX_BT709 ? 0.2126 : mx == MM_MATRIX_BT2020 ? 0.2627 : 0.299;
+    *kb = mx == MM_MATRIX_BT709 ? 0.0722 : mx == MM_MATRIX_BT2020 ? 0.0593 : 0.114;
+}
+static inline void nv12_chroma_matrix(double m[4]);
+// mm_ycbcr_matrix: (cb, cr) -> (Y, I, Q), m = {Y_cb, I_cb, Q_cb, Y_cr, I_cr,
+// Q_cr}: RGBToYIQ's three rows (RGBToYIQ.shader:46-50) times the decode of the
+// format's matrix, R = y + 2 (1 - Kr) cr, B = y + 2 (1 - Kb) cb, G = y -
+// (2 Kb (1 - Kb) / Kg) cb - (2 Kr (1 - Kr) / Kg) cr, in double.  BT.601 keeps
+// its standing definition: the Y entries exactly 0 (its luma weights ARE
+// RGBToYIQ's) and nv12_chroma_matrix's I and Q (six-digit decode).
+static inline void ycbcr_matrix(int fmt, double m[6])
+{
+    if (!fmt_matrix(fmt)) {
+        double q[4];
+        nv12_chroma_matrix(q);
+        m[0] = m[3] = 0.0;
+        m[1] = q[0], m[2] = q[1], m[4] = q[2], m[5] = q[3];
+        return;
+    }
+    double kr, kb;
+    matrix_krkb(fmt, &kr, &kb);
+    const double kg = 1.0 - kr - kb;
+    const double yiq[3][3] = {{0.299, 0.587, 0.114}, {0.596, -0.274, -0.322}, {0.211, -0.523, 0.312}};
+    const double rgb_cb[3] = {0.0, -2.0 * kb * (1.0 - kb) / kg, 2.0 * (1.0 - kb)};
+    const double rgb_cr[3] = {2.0 * (1.0 - kr), -2.0 * kr * (1.0 - kr) / kg, 0.0};
+    for (int q = 0; q < 3; ++q) {
+        m[q] = m[3 + q] = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            m[q] += yiq[q][c] * rgb_cb[c];
+            m[3 + q] += yiq[q][c] * rgb_cr[c];
+        }
+    }
+}
 static inline void nv12_chroma_matrix(double m[4])
 {
     const double yiq[2][3] = {{0.596, -0.274, -0.322}, {0.211, -0.523, 0.312}};
@@ -377,23 +430,32 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
     g.li = fr.in;
     g.lo = fr.out;
     if (fmt_420(fmt)) {
-        const bool full = fmt == MM_NV12_FULL || fmt == MM_P010_FULL, p10 = fmt_p010(fmt);
+        const bool full = fmt_full(fmt), p10 = fmt_p010(fmt);
         const double ys = p10 ? (full ? 1023.0 : 876.0) : (full ? 255.0 : 219.0);
         const double cs = p10 ? (full ? 1023.0 : 896.0) : (full ? 255.0 : 224.0);
         const double y0 = full ? 0.0 : p10 ? 64.0 : 16.0, u = p10 ? 64.0 : 1.0;
-        double m[4];
-        nv12_chroma_matrix(m);
+        double m[6], kr, kb;
+        ycbcr_matrix(fmt, m);
+        matrix_krkb(fmt, &kr, &kb);
         g.nv.y_off = (float)(y0 * u);
         g.nv.y_unit = (float)(1.0 / (ys * u));
-        g.nv.icb = (float)(m[0] / (cs * u));
-        g.nv.qcb = (float)(m[1] / (cs * u));
-        g.nv.icr = (float)(m[2] / (cs * u));
-        g.nv.qcr = (float)(m[3] / (cs * u));
+        // K1 adds la (Cb - mid) + lb (Cr - mid) to (Y - y_off) before y_unit
+        // scales the sum: Yq's a, b over the chroma scale, times the luma scale
+        g.nv.la = (float)(m[0] * ys / cs);
+        g.nv.lb = (float)(m[3] * ys / cs);
+        g.nv.icb = (float)(m[1] / (cs * u));
+        g.nv.qcb = (float)(m[2] / (cs * u));
+        g.nv.icr = (float)(m[4] / (cs * u));
+        g.nv.qcr = (float)(m[5] / (cs * u));
+        g.nv.kr = (float)kr;
+        g.nv.kg = (float)(1.0 - kr - kb);
+        g.nv.kb = (float)kb;
         g.nv.yo_scale = (float)ys;
         g.nv.yo_bias = (float)(y0 + 0.5);
-        // C' = (B - Yl) 0.5 / 0.886, (R - Yl) 0.5 / 0.701; the mean of four; the code scale
-        g.nv.cbo = (float)(0.25 * cs * 0.5 / 0.886);
-        g.nv.cro = (float)(0.25 * cs * 0.5 / 0.701);
+        // C' = (B - Yl) 0.5 / (1 - Kb), (R - Yl) 0.5 / (1 - Kr) (BT.601: 0.886,
+        // 0.701); the mean of four; the code scale
+        g.nv.cbo = (float)(0.25 * cs * 0.5 / (1.0 - kb));
+        g.nv.cro = (float)(0.25 * cs * 0.5 / (1.0 - kr));
     }
     return g;
 }
@@ -656,8 +718,8 @@ static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, const Frames 
     if (gen) {   // (no NV12 / P010 instance: odd sizes are not 4:2:0)
         MM_FMT_SWITCH_RGBA(fmt, MM_K1_LAUNCH(FMT_, true, false))
     } else {
-        MM_FMT_SWITCH(fmt, if (lat) MM_K1_LAUNCH(FMT_, false, true);
-                           else MM_K1_LAUNCH(FMT_, false, false))
+        MM_FMT_SWITCH_K1(fmt, if (lat) MM_K1_LAUNCH(FMT_, false, true);
+                              else MM_K1_LAUNCH(FMT_, false, false))
     }
 #undef MM_K1_LAUNCH
     HIPCHK(hipGetLastError());

@@ -49,10 +49,15 @@ struct Geo {
     // MM_P010 / MM_P010_FULL use it the same way, in units of the 16-bit word
     // on input (64 per 10-bit code: y_off 64 x, y_unit and the matrix 1/64 x)
     // and of the 10-bit code on output (chroma bias 512.5, not 128.5).
+    // A matrix bit (MM_MATRIX_BT709 / _BT2020) changes values only, except in
+    // K1, whose matrixed instances add the chroma term of RGBToYIQ's luma.
     struct Nv12 {
         float y_off, y_unit;        // K1: luma = ((float)Yb - y_off) * y_unit
+        float la, lb;               // K1, matrixed: ... + la (Cb - mid) + lb (Cr - mid) inside the bracket:
+                                    // Yq's a, b times luma / chroma code scale (BT.601: 0, never read)
         float icb, qcb, icr, qcr;   // compose: (I, Q) = (icb, qcb) (Cb - 128) + (icr, qcr) (Cr - 128),
                                     // RGBToYIQ x BT.601 with the code scale folded in
+        float kr, kg, kb;           // out: Yl = kr R + kg G + kb B, the matrix's luma weights
         float yo_scale, yo_bias;    // out: luma code = floor(Yl * yo_scale + yo_bias), bias = offset + 0.5
         float cbo, cro;             // out: chroma code = floor(sum of four (B - Yl) * cbo + 128.5), Cr: R - Yl
     } nv;
@@ -466,11 +471,22 @@ __device__ __forceinline__ void yiq_rgb(float yb, c2 cc, float &rr, float &gg, f
 // loads, 4-byte (Cb, Cr) pair loads and 4-byte stores of two words are always
 // aligned, and so are the fused kernels' 8-byte quad stores as multi-dword
 // accesses (st_stream_pair_a4).
+//
+// Matrixed frames (a code with MM_MATRIX_BT709 or MM_MATRIX_BT2020): the
+// decode's luma weights are not RGBToYIQ's, so the luma of the decoded pixel
+// is Yq = y + a cb + b cr (include/mm.h) and K1 reads the pixel's (Cb, Cr) pair
+// too.  That is K1's only difference, and its alone: FMT = kFmtNV12M /
+// kFmtP010M are K1 instances (both matrices and both ranges share them, a and
+// b travel in Geo::nv); the compose kernels read every weight of every 4:2:0
+// format from Geo::nv and run the kFmtNV12 / kFmtP010 instances.
 constexpr int kFmtNV12 = 16;   // MM_NV12
 constexpr int kFmtP010 = 18;   // MM_P010
-template <int FMT> constexpr bool kNV12 = FMT == kFmtNV12;
-template <int FMT> constexpr bool kP010 = FMT == kFmtP010;
+constexpr int kFmtNV12M = 48;  // MM_NV12 | MM_MATRIX_BT709 (K1 only: any matrixed NV12)
+constexpr int kFmtP010M = 50;  // MM_P010 | MM_MATRIX_BT709 (K1 only: any matrixed P010)
+template <int FMT> constexpr bool kNV12 = FMT == kFmtNV12 || FMT == kFmtNV12M;
+template <int FMT> constexpr bool kP010 = FMT == kFmtP010 || FMT == kFmtP010M;
 template <int FMT> constexpr bool k420 = kNV12<FMT> || kP010<FMT>;
+template <int FMT> constexpr bool kMatrixed = FMT == kFmtNV12M || FMT == kFmtP010M;
 // the raw sample K1 loads per pixel
 template <int FMT> struct LumaSrc {
     using raw_t = typename Pix<FMT>::raw_t;
@@ -488,6 +504,10 @@ template <> struct LumaSrc<kFmtP010> {
     static constexpr int bpp = 2;
 };
 template <> struct ChromaSrc<kFmtP010> { using raw_t = uint32_t; };   // Cb | Cr << 16
+template <> struct LumaSrc<kFmtNV12M> : LumaSrc<kFmtNV12> {};
+template <> struct LumaSrc<kFmtP010M> : LumaSrc<kFmtP010> {};
+template <> struct ChromaSrc<kFmtNV12M> : ChromaSrc<kFmtNV12> {};
+template <> struct ChromaSrc<kFmtP010M> : ChromaSrc<kFmtP010> {};
 // K1's luma of a raw sample and its unit (folded into the resample weights)
 template <int FMT>
 __device__ __forceinline__ float k1_luma(typename LumaSrc<FMT>::raw_t u, const Geo &g)
@@ -499,6 +519,27 @@ template <int FMT> __device__ __forceinline__ float k1_unit(const Geo &g)
 {
     if constexpr (k420<FMT>) return g.nv.y_unit;
     else return kLumaUnit<FMT>;
+}
+// K1, matrixed frames: what a (Cb, Cr) pair adds to the luma of its 2x2
+// pixels, in k1_luma's units; exactly 0 for neutral chroma.  One expression
+// for the three load forms, so their lumas are bitwise equal.
+template <int FMT>
+__device__ __forceinline__ float k1_chroma(typename ChromaSrc<FMT>::raw_t u, const Geo &g)
+{
+    float cb, cr;
+    if constexpr (kP010<FMT>) cb = (float)(u & 0xFFFFu) - 32768.0f, cr = (float)(u >> 16) - 32768.0f;
+    else cb = (float)(u & 255u) - 128.0f, cr = (float)((unsigned)u >> 8) - 128.0f;
+    return fmaf(g.nv.lb, cr, g.nv.la * cb);
+}
+// K1's chroma plane: row `row` (wrapped or clamped on PIXEL coordinates, then
+// halved, as c420_off) and the byte offset of pixel column col's pair in it
+template <int FMT> __device__ __forceinline__ const uint8_t *k1_crow(const uint8_t *img, const Geo &g, int row)
+{
+    return img + (g.li.c_off + (unsigned)(row >> 1) * g.li.c_pitch);
+}
+template <int FMT> __device__ __forceinline__ unsigned k1_ccol(unsigned col)
+{
+    return (col & ~1u) * (unsigned)LumaSrc<FMT>::bpp;
 }
 // byte offset of the (Cb, Cr) pair of source pixel (row, col), both already
 // wrapped or clamped on PIXEL coordinates (then halved: the decoded frame's
@@ -544,7 +585,7 @@ __device__ __forceinline__ c2 src_iq2(typename ChromaSrc<FMT>::raw_t u, const Ge
 // fused and unfused outputs stay bitwise equal.
 __device__ __forceinline__ unsigned nv12_ycode(float r, float gg, float b, const Geo &g, c2 &c)
 {
-    const float yl = 0.299f * r + 0.587f * gg + 0.114f * b;
+    const float yl = g.nv.kr * r + g.nv.kg * gg + g.nv.kb * b;
     c = mk(b - yl, r - yl);
     return (unsigned)(yl * g.nv.yo_scale + g.nv.yo_bias);   // in 0 .. 255: yl in [0, 1]
 }
@@ -728,6 +769,16 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
             const uint8_t *rowp[6];   // workgroup-uniform source row pointers
 #pragma unroll
             for (int d = 0; d < 6; ++d) rowp[d] = img + (unsigned)wrap_near(r0 - 1 + d, g.H, g.edge) * g.li.pitch;
+            // matrixed 4:2:0: the 6 source rows lie on 4 chroma rows (r0 is
+            // even: rows r0, r0+1 and r0+2, r0+3 share one each), loaded once
+            // per column in the same batch as the lumas
+            [[maybe_unused]] const uint8_t *crowp[4];
+            if constexpr (kMatrixed<FMT>) {
+                crowp[0] = k1_crow<FMT>(img, g, wrap_near(r0 - 1, g.H, g.edge));
+                crowp[1] = k1_crow<FMT>(img, g, r0);
+                crowp[2] = k1_crow<FMT>(img, g, r0 + 2);
+                crowp[3] = k1_crow<FMT>(img, g, wrap_near(r0 + 4, g.H, g.edge));
+            }
             constexpr int CT = N / (2 * T);          // columns per thread (W <= N)
             constexpr int CB = BPP == 16 ? 1 : CT;   // columns per load batch
             c2 *V2g1 = lds_all + lds_complex<N>();
@@ -735,11 +786,18 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
             for (int h = 0; h < CT / CB; ++h) {
                 __builtin_amdgcn_sched_barrier(0);
                 raw_t px[CB][6];
+                [[maybe_unused]] typename ChromaSrc<FMT>::raw_t cx[CB][4];
 #pragma unroll
                 for (int u = 0; u < CB; ++u) {
-                    const unsigned off = (unsigned)min((int)threadIdx.x + (h * CB + u) * 2 * T, g.W - 1) * BPP;
+                    const unsigned col = (unsigned)min((int)threadIdx.x + (h * CB + u) * 2 * T, g.W - 1);
+                    const unsigned off = col * BPP;
 #pragma unroll
                     for (int d = 0; d < 6; ++d) px[u][d] = ld_off<raw_t>(rowp[d], off);
+                    if constexpr (kMatrixed<FMT>) {
+#pragma unroll
+                        for (int d = 0; d < 4; ++d)
+                            cx[u][d] = ld_off<typename ChromaSrc<FMT>::raw_t>(crowp[d], k1_ccol<FMT>(col));
+                    }
                 }
 #pragma unroll
                 for (int u = 0; u < CB; ++u) {
@@ -747,6 +805,10 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
                     float l[6];
 #pragma unroll
                     for (int d = 0; d < 6; ++d) l[d] = k1_luma<FMT>(px[u][d], g);
+                    if constexpr (kMatrixed<FMT>) {
+#pragma unroll
+                        for (int d = 0; d < 6; ++d) l[d] += k1_chroma<FMT>(cx[u][(d + 1) >> 1], g);
+                    }
                     if (i < g.W) {
                         lds_all[i] = w[0][0] * mk(l[0], l[1]) + w[0][1] * mk(l[1], l[2]) + w[0][2] * mk(l[2], l[3]);
                         V2g1[i] = w[1][0] * mk(l[2], l[3]) + w[1][1] * mk(l[3], l[4]) + w[1][2] * mk(l[4], l[5]);
@@ -766,16 +828,32 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
         const uint8_t *rowp[4];   // workgroup-uniform source row pointers
 #pragma unroll
         for (int d = 0; d < 4; ++d) rowp[d] = img + (unsigned)wrap_near(ra - 1 + d, g.H, g.edge) * g.li.pitch;
+        // matrixed 4:2:0 (H even, so ra + 1 < H): the 4 source rows lie on 3
+        // chroma rows (ra and ra + 1 share one), loaded once per column in the
+        // same batch as the lumas
+        [[maybe_unused]] const uint8_t *crowp[3];
+        if constexpr (kMatrixed<FMT>) {
+            crowp[0] = k1_crow<FMT>(img, g, wrap_near(ra - 1, g.H, g.edge));
+            crowp[1] = k1_crow<FMT>(img, g, ra);
+            crowp[2] = k1_crow<FMT>(img, g, wrap_near(ra + 2, g.H, g.edge));
+        }
         // W <= N = 8T: at most 8 columns per thread
 #pragma unroll
         for (int h = 0; h < 8 / UB; ++h) {
             __builtin_amdgcn_sched_barrier(0);
             raw_t px[UB][4];
+            [[maybe_unused]] typename ChromaSrc<FMT>::raw_t cx[UB][3];
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
-                const unsigned off = (unsigned)min(t + (h * UB + u) * T, g.W - 1) * BPP;
+                const unsigned col = (unsigned)min(t + (h * UB + u) * T, g.W - 1);
+                const unsigned off = col * BPP;
 #pragma unroll
                 for (int d = 0; d < 4; ++d) px[u][d] = ld_off<raw_t>(rowp[d], off);
+                if constexpr (kMatrixed<FMT>) {
+#pragma unroll
+                    for (int d = 0; d < 3; ++d)
+                        cx[u][d] = ld_off<typename ChromaSrc<FMT>::raw_t>(crowp[d], k1_ccol<FMT>(col));
+                }
             }
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
@@ -783,6 +861,10 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
                 float l[4];
 #pragma unroll
                 for (int d = 0; d < 4; ++d) l[d] = k1_luma<FMT>(px[u][d], g);
+                if constexpr (kMatrixed<FMT>) {
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) l[d] += k1_chroma<FMT>(cx[u][(d + 1) >> 1], g);
+                }
                 if (i < g.W) V2[i] = w0 * mk(l[0], l[1]) + w1 * mk(l[1], l[2]) + w2 * mk(l[2], l[3]);
             }
         }

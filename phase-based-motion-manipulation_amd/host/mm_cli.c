@@ -8,7 +8,8 @@
  *
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
- *          [--full-range] [--srgb] [--nv12] [--p010] [--standard] [--show-magnitude] [--show-phase]
+ *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020]
+ *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
  *          [--ring-local G [--compare]]
@@ -51,6 +52,11 @@
  * what --nv12 is refused with, and with --nv12.  Bit depths are never
  * converted silently: an 8-bit input with --p010 and a 10-bit input without it
  * are refused.
+ * --matrix 601|709|2020 (default 601): the Y'CbCr matrix of an --nv12 or
+ * --p010 clip (HD content is BT.709, UHD BT.709 or BT.2020), OR-ed onto the
+ * frame format as MM_MATRIX_BT709 / MM_MATRIX_BT2020.  A .y4m header has no
+ * matrix tag, so files are the same whatever the value.  Only with --nv12 or
+ * --p010: the host's own RGBA conversion of a .y4m is BT.601.
  * --surface-align P,R: the device frames, input and output, are held in
  * mm_surface_aligned(W, H, format, P, R) surfaces (256,16: a hardware
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
@@ -426,6 +432,7 @@ int main(int argc, char **argv)
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
     int nv12 = 0, p010 = 0, srgb = 0;
+    const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
     const char *in_path = NULL, *out_path = NULL, *ring_id_path = NULL;
@@ -459,6 +466,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--orientations")) orientations = atoi(v);
         else if (!strcmp(a, "--halo")) halo = atoi(v);
         else if (!strcmp(a, "--surface-align")) surf_arg = v;
+        else if (!strcmp(a, "--matrix")) matrix_arg = v;
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         ++i;
     }
@@ -518,6 +526,18 @@ int main(int argc, char **argv)
             return 2;
         }
         g_fmt = full_range ? MM_NV12_FULL : MM_NV12;
+    }
+    if (matrix_arg) {
+        if (!nv12 && !p010) {
+            fprintf(stderr, "--matrix needs --nv12 or --p010 (the RGBA conversion of a .y4m is BT.601)\n");
+            return 2;
+        }
+        if (!strcmp(matrix_arg, "709")) g_fmt |= MM_MATRIX_BT709;
+        else if (!strcmp(matrix_arg, "2020")) g_fmt |= MM_MATRIX_BT2020;
+        else if (strcmp(matrix_arg, "601")) {
+            fprintf(stderr, "--matrix takes 601, 709 or 2020, not %s\n", matrix_arg);
+            return 2;
+        }
     }
     mm_params p;
     mm_params_default(&p);

@@ -23,6 +23,10 @@ NV12_FULL = 17      # full ("JPEG") range
 # << 6; a P016 surface's low bits are honoured): frame_bytes() gives W*H*3
 P010 = 18           # BT.601 matrix, limited range (Y 64..940, C 64..960)
 P010_FULL = 19      # full range (0..1023)
+# one matrix bit, OR-ed onto a 4:2:0 code above (HD / UHD content): the layout
+# and sizes stay the base code's (base_format)
+MATRIX_BT709 = 32   # Kr 0.2126, Kb 0.0722
+MATRIX_BT2020 = 64  # Kr 0.2627, Kb 0.0593, non-constant luminance
 EDGE_REPEAT = 0
 EDGE_CLAMP = 1
 MODE_PYRAMID = 0
@@ -172,6 +176,7 @@ def load_library(path=None):
         "mm_padded_size": (ci, [vp, ctypes.POINTER(ci)]),
         "mm_frame_bytes": (ci, [ci, ci, ci, ctypes.POINTER(sz)]),
         "mm_nv12_chroma_matrix": (ci, [ctypes.POINTER(ctypes.c_double)]),
+        "mm_ycbcr_matrix": (ci, [ci, ctypes.POINTER(ctypes.c_double)]),
         "mm_process": (ci, [vp, vp, vp, ci, ci, vp]),
         "mm_process_stream": (ci, [vp, vp, vp, ci, ci, vp]),
         "mm_reset": (ci, [vp]),
@@ -201,8 +206,8 @@ def load_library(path=None):
             continue
         if abi < 10 and name == "mm_frame_bytes":
             continue
-        if name == "mm_nv12_chroma_matrix" and not hasattr(L, name):
-            continue    # an A/B build from before the NV12 formats (same ABI version)
+        if name in ("mm_nv12_chroma_matrix", "mm_ycbcr_matrix") and not hasattr(L, name):
+            continue    # an A/B build from before the NV12 formats or the matrix bits (same ABI version)
         if name in SURFACE_SYMBOLS and not hasattr(L, name):
             continue    # ... or from before the pitched surfaces
         fn = getattr(L, name)
@@ -256,6 +261,22 @@ def nv12_chroma_matrix():
     m = (ctypes.c_double * 4)()
     check(lib().mm_nv12_chroma_matrix(m), "mm_nv12_chroma_matrix")
     return np.array([[m[0], m[2]], [m[1], m[3]]])
+
+
+def base_format(fmt):
+    """The format without its matrix bit: what decides a frame's size and shape."""
+    return fmt & ~(MATRIX_BT709 | MATRIX_BT2020)
+
+
+def ycbcr_matrix(fmt):
+    """mm_ycbcr_matrix: a 4:2:0 format's (cb, cr) -> (Y, I, Q) matrix,
+    [[Y_cb, Y_cr], [I_cb, I_cr], [Q_cb, Q_cr]] (float64); the Y row is what the
+    decoded pixel's RGBToYIQ luma adds to y (zero for the BT.601 codes)."""
+    if not hasattr(lib(), "mm_ycbcr_matrix"):
+        raise MMError(-2, f"{library_path()} has no mm_ycbcr_matrix (a build from before the matrix bits)")
+    m = (ctypes.c_double * 6)()
+    check(lib().mm_ycbcr_matrix(fmt, m), "mm_ycbcr_matrix")
+    return np.array([[m[0], m[3]], [m[1], m[4]], [m[2], m[5]]])
 
 
 def resample_table(width, height, axis, edge_mode=EDGE_REPEAT):

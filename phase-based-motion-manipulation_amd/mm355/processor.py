@@ -8,7 +8,7 @@ import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       NV12, NV12_FULL, P010, P010_FULL, RGBA8, RGBA8_SRGB, RGBA16F, RGBA32F, Handle, MMError,
-                      Params, Surface)
+                      Params, Surface, base_format)
 
 
 def _fmt_of(frame, srgb=False):
@@ -183,6 +183,7 @@ class MotionMagnificationProcessor:
 
 
 def host_frames(n, h, w, fmt):
+    fmt = base_format(fmt)          # a matrix bit changes no size or shape
     if fmt in (NV12, NV12_FULL):    # h luma rows, then h/2 rows of interleaved Cb, Cr
         return np.zeros((n, h * 3 // 2, w), np.uint8)
     if fmt in (P010, P010_FULL):    # the same rows in 16-bit words (10-bit code << 6)

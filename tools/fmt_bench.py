@@ -16,6 +16,13 @@ mm_process_stream_surfaces; in the same rounds, next to the tight legs.  A
 library from before the pitched surfaces (MM355_LIB, A/B runs) runs the tight
 legs only.
 
+Matrixed legs (nv12_bt709, p010_bt2020, and their _pitched forms): the NV12 and
+P010 legs' own bytes taken as MM_NV12 | MM_MATRIX_BT709 and MM_P010 |
+MM_MATRIX_BT2020 (the timing does not depend on the sample values), whose K1
+reads the chroma plane too; in the same rounds, so that their K1 stands next to
+the luma-only K1 and to RGBA8's.  A library from before the matrix bits runs
+without them.
+
 usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--out FILE.json]
 """
 import argparse
@@ -84,13 +91,21 @@ def main():
     p = mm355.Params.make(levels=5, phase_scale=25.0)
     legs = {}
     rgba = torch.empty((B, H, W, 4), dtype=torch.uint8, device="cuda")
-    for name, fmt in (("rgba8", mm355.RGBA8), ("nv12", mm355.NV12), ("p010", mm355.P010)):
+    fmts = [("rgba8", mm355.RGBA8), ("nv12", mm355.NV12), ("p010", mm355.P010)]
+    try:
+        mm355.frame_bytes(W, H, mm355.NV12 | mm355.MATRIX_BT709)
+        fmts += [("nv12_bt709", mm355.NV12 | mm355.MATRIX_BT709), ("p010_bt2020", mm355.P010 | mm355.MATRIX_BT2020)]
+    except mm355.MMError:
+        pass    # a build from before the matrix bits
+    for name, fmt in fmts:
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
         if name == "rgba8":
             h.synth(rgba, 0, B, stream=torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
             src = rgba
+        elif name in ("nv12_bt709", "p010_bt2020"):
+            src = legs[name.split("_")[0]]["src"]
         else:
             src = to_420(torch, rgba, ten_bit=name == "p010")
         legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[], lay=None,
@@ -151,7 +166,13 @@ def main():
     r = out["formats"]["rgba8"]
     for name in ("nv12", "p010"):
         out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
-    for name in ("rgba8", "nv12", "p010"):
+    for name, base in (("nv12_bt709", "nv12"), ("p010_bt2020", "p010")):
+        if name in out["formats"]:
+            out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                out["formats"][base]["fps_median"], 4)
+            k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
+            out[name + "_k1_us"] = {"matrixed": k1(name), base: k1(base), "rgba8": k1("rgba8")}
+    for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020"):
         if name + "_pitched" in out["formats"]:
             out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
                                                       out["formats"][name]["fps_median"], 4)
