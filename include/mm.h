@@ -62,7 +62,8 @@ extern "C" {
 #define MM_ERR_NO_STATE    -6  /* mm_get_state before any frame was seen */
 
 /* frame formats (every entry point that takes frames takes each of them;
- * the NV12 and P010 pairs for even W and H and without the debug views) */
+ * the NV12 and P010 pairs for even W and H and without the debug views; the
+ * single-plane grayscale formats MM_Y8 .. MM_Y16 further down) */
 #define MM_RGBA8   0       /* 4 B/px, UNORM: v = byte / 255; out round(saturate(v) * 255) */
 #define MM_RGBA32F 1       /* 16 B/px, linear float                                       */
 /* The frames the reference actually receives (since ABI 10): its camera
@@ -176,8 +177,51 @@ extern "C" {
 #define MM_MATRIX_BT709   32   /* Kr 0.2126, Kb 0.0722 */
 #define MM_MATRIX_BT2020  64   /* Kr 0.2627, Kb 0.0593, non-constant luminance */
 
+/* Grayscale camera frames (backward-compatible addition to ABI 10: a caller
+ * detects it by mm_frame_bytes(W, H, MM_Y8, &n) == MM_OK).  One plane, one
+ * sample per pixel, as a machine-vision camera (GenICam Mono8 / Mono10 /
+ * Mono12 / Mono16), a thermal imager or a grayscale decoder stores it, tightly
+ * packed: H rows of W bytes (MM_Y8, W H bytes in all) or of W little-endian
+ * 16-bit words with the code in the LOW bits (MM_Y10 / MM_Y12 / MM_Y16, 2 W H
+ * bytes: ffmpeg's gray10le / gray12le / gray16le); frame k of a stream at
+ * k * mm_frame_bytes.  With max = 255, 1023, 4095 or 65535:
+ *   in:  the frame IS the RGBA32F frame R = G = B = v = sample / max, alpha 1.
+ *        v is NOT clamped: a Y10 / Y12 word above max gives v > 1, which
+ *        passes until the reference's saturate, like an HDR value.
+ *        RGBToYIQ's luma row sums to 1 and its I and Q rows to 0, so the luma
+ *        of the pixel is the sample and (I, Q) is zero;
+ *   out: of the reference's saturated RGB, Yl = 0.299 R + 0.587 G + 0.114 B,
+ *        code = floor(Yl max + 0.5) clamped to 0..max (for the kernels: the
+ *        code of the saturated magnified luma, since R = G = B); the bits of
+ *        a Y10 / Y12 output word above the code are zero.
+ * The first frame after mm_create / mm_reset and apply_magnification = 0 pass
+ * the W x H samples through bitwise, stray high bits of Y10 / Y12 words
+ * included; padding stays untouched.  There is no chroma subsampling, so odd W
+ * and H are supported, in every mode (pyramid, standard, steerable), and so
+ * are show_magnitude / show_phase, split screen included: the views are
+ * R-channel pictures and the output code is the view's R value, encoded as
+ * above.  A matrix bit on these codes is MM_ERR_INVALID (there is no matrix);
+ * in_layout->format == out_layout->format holds as everywhere.
+ * Surfaces: the unit u is 1 for MM_Y8 and 2 for the word formats;
+ * chroma_offset = chroma_pitch = 0 (else MM_ERR_INVALID); device frame
+ * pointers, pitch and frame stride are multiples of u; the extent and 4 GiB
+ * rules are unchanged.  The fused kernels' wide stores (four bytes as a dword,
+ * four words as 8 bytes) run where every output row of the call is 4-byte
+ * aligned; any other layout takes the unfused pair, same results.
+ * The operator changes luma only, so this is the cheapest path of the
+ * library: the forward kernel reads the plane as it reads a 4:2:0 frame's
+ * luma plane, the compose stage reads nothing from the input at all, and 1 or
+ * 2 bytes per pixel travel each way.
+ * Out of scope: packed Mono10p / Mono12p; MSB-aligned words (a P016-style mono
+ * plane); limited-range mono; Bayer mosaics; the ring entry points
+ * (include/mm_ring.h), which stay RGBA8 / RGBA32F as for NV12; the Unity shim. */
+#define MM_Y8   8    /* 1 B/px, full range: v = byte / 255                          */
+#define MM_Y10  9    /* 2 B/px, little-endian word, code in the LOW 10 bits: v = word / 1023 */
+#define MM_Y12  10   /* ... low 12 bits: v = word / 4095                            */
+#define MM_Y16  11   /* ... v = word / 65535                                        */
+
 /* mm_params.mode */
-#define MM_MODE_PYRAMID   0   /* usePyramidDecomposition = true (.cs:18, :128-131) */
+#define MM_MODE_PYRAMID   0  /* usePyramidDecomposition = true (.cs:18, :128-131) */
 #define MM_MODE_STANDARD  1   /* usePyramidDecomposition = false (.cs:132-135, :208-232) */
 #define MM_MODE_STEERABLE 2  /* extension f2: oriented local-phase subbands + temporal filter */
 #define MM_FILTER_DIFF 0      /* steerable: the reference's 2-tap phase difference per coefficient */
@@ -282,12 +326,13 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  *     modes, host-memory frames, stream ordering, aliasing) follows them.
  * Validation (mm_surface_bytes; every frame entry point applies it before it
  * queues anything; no GPU needed).  With the unit u = the pixel size of an RGBA
- * format (4, 16, 8, 4), 2 for NV12 (a (Cb, Cr) pair) and 4 for P010:
+ * format (4, 16, 8, 4), 2 for NV12 (a (Cb, Cr) pair), 4 for P010 and the sample
+ * size of a single-plane format (1 for MM_Y8, 2 for MM_Y10 / Y12 / Y16):
  *   - unknown format: MM_ERR_INVALID; 4:2:0 with odd W or H: MM_ERR_UNSUPPORTED;
  *   - pitch (4:2:0: and chroma_pitch) at least the row's sample bytes (W pixels;
  *     4:2:0: W samples) and a multiple of u; chroma_offset a multiple of u and
- *     at or past the end of the last luma row's samples; RGBA formats:
- *     chroma_offset = chroma_pitch = 0; else MM_ERR_INVALID;
+ *     at or past the end of the last luma row's samples; RGBA and single-plane
+ *     formats: chroma_offset = chroma_pitch = 0; else MM_ERR_INVALID;
  *   - extent = the byte after the last sample of the last row of the last
  *     plane (not pitch * H: a region of interest at the bottom of its parent
  *     is valid).  The kernels address a frame with 32-bit byte offsets from
@@ -304,7 +349,7 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  * an unaligned frame takes the narrower access, never another kernel: a layout
  * aligned like a decoder's runs exactly the tight layout's kernels. */
 typedef struct {
-    int    format;         /* MM_RGBA8 ... MM_P010_FULL, 4:2:0: | MM_MATRIX_* */
+    int    format;         /* MM_RGBA8 ... MM_P010_FULL, MM_Y8 ... MM_Y16; 4:2:0: | MM_MATRIX_* */
     size_t pitch;          /* bytes from one row to the next: RGBA rows, or luma rows */
     size_t chroma_offset;  /* 4:2:0: bytes from the frame's base to the (Cb,Cr) plane; else 0 */
     size_t chroma_pitch;   /* 4:2:0: bytes from one (Cb,Cr) row to the next; else 0 */

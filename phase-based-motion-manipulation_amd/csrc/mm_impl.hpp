@@ -204,7 +204,7 @@ struct ProfScope {
 // argument is the format code itself (Pix<FMT>, mm_kernels.hpp).
 static inline size_t fmt_bpp(int fmt)
 {
-    return fmt == MM_RGBA32F ? 16 : fmt == MM_RGBA16F ? 8 : 4;
+    return fmt == MM_RGBA32F ? 16 : fmt == MM_RGBA16F ? 8 : fmt == MM_Y8 ? 1 : fmt >= MM_Y10 && fmt <= MM_Y16 ? 2 : 4;
 }
 // A 4:2:0 code may carry one matrix bit (MM_MATRIX_BT709 / MM_MATRIX_BT2020):
 // layout, sizes and units are its base code's, the bit changes coefficients
@@ -216,8 +216,12 @@ static inline bool fmt_nv12(int fmt) { return fmt_base(fmt) == MM_NV12 || fmt_ba
 static inline bool fmt_p010(int fmt) { return fmt_base(fmt) == MM_P010 || fmt_base(fmt) == MM_P010_FULL; }
 static inline bool fmt_420(int fmt) { return fmt_nv12(fmt) || fmt_p010(fmt); }   // planar, not Pix<FMT>
 static inline bool fmt_full(int fmt) { return fmt_base(fmt) == MM_NV12_FULL || fmt_base(fmt) == MM_P010_FULL; }
+// single-plane grayscale: one sample per pixel, a byte (MM_Y8) or a 16-bit word
+static inline bool fmt_mono(int fmt) { return fmt >= MM_Y8 && fmt <= MM_Y16; }
+static inline int mono_max(int fmt) { return fmt == MM_Y8 ? 255 : fmt == MM_Y10 ? 1023 : fmt == MM_Y12 ? 4095 : 65535; }
 static inline bool fmt_valid(int fmt)
 {
+    if (fmt_mono(fmt)) return true;   // (a matrix bit on these codes: no 4:2:0 base, invalid below)
     if (fmt == MM_RGBA8 || fmt == MM_RGBA32F || fmt == MM_RGBA16F || fmt == MM_RGBA8_SRGB) return true;
     // (any other bit, a negative code included, leaves a base that is no 4:2:0 code)
     return fmt_420(fmt) && fmt_matrix(fmt) != kMatrixBits;
@@ -231,7 +235,8 @@ static inline size_t fmt_frame_bytes(int W, int H, int fmt)
 }
 // What every frame entry point asks of (format, geometry, parameters) before
 // it queues anything.  NV12 and P010 are 4:2:0: even sizes only; the debug
-// views are R-channel pictures, which they cannot hold.
+// views are R-channel pictures, which they cannot hold.  (The single-plane
+// formats hold them, and have no subsampling: every size, every view.)
 static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
 {
     if (!fmt_valid(fmt)) return MM_ERR_INVALID;
@@ -241,6 +246,7 @@ static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
 }
 // ---- surfaces (mm_surface, include/mm.h) ----------------------------------
 // u: what pitches, offsets, strides and frame pointers are multiples of
+// (the single-plane formats: their sample, 1 or 2 bytes)
 static inline size_t fmt_unit(int fmt) { return fmt_nv12(fmt) ? 2 : fmt_p010(fmt) ? 4 : fmt_bpp(fmt); }
 // sample bytes of one row (4:2:0: of a luma row and of a (Cb, Cr) row alike)
 static inline size_t fmt_row_bytes(int W, int fmt)
@@ -333,12 +339,14 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
 }
 
 static_assert(kFmtNV12 == MM_NV12, "the kernels' NV12 template argument is the format code");
+static_assert(kFmtY8 == MM_Y8 && kFmtY16 == MM_Y16, "the kernels' single-plane template arguments are the format codes");
 static_assert(kFmtP010 == MM_P010, "the kernels' P010 template argument is the format code");
 static_assert(kFmtNV12M == (MM_NV12 | MM_MATRIX_BT709) && kFmtP010M == (MM_P010 | MM_MATRIX_BT709),
               "K1's matrixed template arguments are the BT.709 limited-range codes");
 // Runs the statement with the compile-time format FMT_ of the runtime `fmt`
 // (both NV12 ranges run the MM_NV12 instances, both P010 ranges the MM_P010
-// instances, whatever the matrix bit; geo_of sets their uniforms).
+// instances, whatever the matrix bit, and the three word depths of the
+// single-plane formats the MM_Y16 instances; geo_of sets their uniforms).
 #define MM_FMT_SWITCH(fmt, ...)                                                \
     switch (fmt_base(fmt)) {                                                   \
     case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
@@ -346,6 +354,8 @@ static_assert(kFmtNV12M == (MM_NV12 | MM_MATRIX_BT709) && kFmtP010M == (MM_P010 
     case MM_RGBA16F: { constexpr int FMT_ = MM_RGBA16F; __VA_ARGS__; } break;  \
     case MM_NV12: case MM_NV12_FULL: { constexpr int FMT_ = MM_NV12; __VA_ARGS__; } break; \
     case MM_P010: case MM_P010_FULL: { constexpr int FMT_ = MM_P010; __VA_ARGS__; } break; \
+    case MM_Y8: { constexpr int FMT_ = MM_Y8; __VA_ARGS__; } break;            \
+    case MM_Y10: case MM_Y12: case MM_Y16: { constexpr int FMT_ = MM_Y16; __VA_ARGS__; } break; \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
 // ... K1's: a code with a matrix bit runs the matrixed NV12 / P010 instance,
@@ -354,10 +364,18 @@ static_assert(kFmtNV12M == (MM_NV12 | MM_MATRIX_BT709) && kFmtP010M == (MM_P010 
     if (fmt_matrix(fmt) && fmt_nv12(fmt)) { constexpr int FMT_ = kFmtNV12M; __VA_ARGS__; }      \
     else if (fmt_matrix(fmt)) { constexpr int FMT_ = kFmtP010M; __VA_ARGS__; }                  \
     else MM_FMT_SWITCH(fmt, __VA_ARGS__)
-// ... and the kernels that have no NV12 / P010 instance (odd sizes and the debug
-// views, refused by fmt_check before any launch)
-#define MM_FMT_SWITCH_RGBA(fmt, ...)                                           \
+// K1's instance of a format: a single-plane frame IS a luma plane and runs the
+// NV12 (bytes) or P010 (words) luma-plane instance with its own uniforms
+// (geo_of: y_off 0, y_unit 1 / max), bit for bit what an instance of its own
+// would compute (mm_kernels.hpp)
+template <int F> constexpr int kK1Fmt = F == MM_Y8 ? kFmtNV12 : F == MM_Y16 ? kFmtP010 : F;
+// ... and the kernels of the odd sizes and the debug views, which the 4:2:0
+// formats cannot have (refused by fmt_check before any launch): the RGBA and
+// the single-plane instances
+#define MM_FMT_SWITCH_FULLRES(fmt, ...)                                        \
     switch (fmt) {                                                             \
+    case MM_Y8: { constexpr int FMT_ = MM_Y8; __VA_ARGS__; } break;            \
+    case MM_Y10: case MM_Y12: case MM_Y16: { constexpr int FMT_ = MM_Y16; __VA_ARGS__; } break; \
     case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
     case MM_RGBA32F: { constexpr int FMT_ = MM_RGBA32F; __VA_ARGS__; } break;  \
     case MM_RGBA16F: { constexpr int FMT_ = MM_RGBA16F; __VA_ARGS__; } break;  \
@@ -456,6 +474,15 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
         // 0.701); the mean of four; the code scale
         g.nv.cbo = (float)(0.25 * cs * 0.5 / (1.0 - kb));
         g.nv.cro = (float)(0.25 * cs * 0.5 / (1.0 - kr));
+    } else if (fmt_mono(fmt)) {
+        // v = sample / max in, code = floor(v max + 0.5) clamped to max out:
+        // K1 runs the luma-plane instances (no offset), the compose instances
+        // read the scale (also their clamp) and the rounding bias
+        const double mx = (double)mono_max(fmt);
+        g.nv.y_off = 0.0f;
+        g.nv.y_unit = (float)(1.0 / mx);
+        g.nv.yo_scale = (float)mx;
+        g.nv.yo_bias = 0.5f;
     }
     return g;
 }
@@ -657,7 +684,7 @@ static int set_attrs(int W)
     (void)W;   // every other kernel stays within the default 64 KiB dynamic LDS
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 2 * lds_complex<4096>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         // k_sb_cols: exchange buffer (36.9 KB) + its own staging, past 64 KB for
@@ -686,7 +713,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 11) {   // k_rows_inv_compose4: four 2048-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 4 * lds_complex<2048>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
     }
@@ -715,11 +742,11 @@ static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, const Frames 
     } while (0)
     const bool gen = h->geo.ox || h->geo.oy;   // odd W/H: taps span i-2 .. i+1
     const Geo g = geo_of(h, fr);
-    if (gen) {   // (no NV12 / P010 instance: odd sizes are not 4:2:0)
-        MM_FMT_SWITCH_RGBA(fmt, MM_K1_LAUNCH(FMT_, true, false))
+    if (gen) {   // (4:2:0 frames have even sizes; single-plane ones run the luma-plane instances here too)
+        MM_FMT_SWITCH_FULLRES(fmt, MM_K1_LAUNCH(kK1Fmt<FMT_>, true, false))
     } else {
-        MM_FMT_SWITCH_K1(fmt, if (lat) MM_K1_LAUNCH(FMT_, false, true);
-                              else MM_K1_LAUNCH(FMT_, false, false))
+        MM_FMT_SWITCH_K1(fmt, if (lat) MM_K1_LAUNCH(kK1Fmt<FMT_>, false, true);
+                              else MM_K1_LAUNCH(kK1Fmt<FMT_>, false, false))
     }
 #undef MM_K1_LAUNCH
     HIPCHK(hipGetLastError());
@@ -842,9 +869,22 @@ static bool nv12_quads_aligned(const uint8_t *in, const uint8_t *out, const Fram
     if (nframes > 1) m |= fr.in.stride | fr.out.stride;
     return (m & 3u) == 0;
 }
+// The single-plane formats' quads are stores only (their compose reads no
+// input): four bytes as one dword, four words as one 8-byte store at a
+// dword-aligned address, so every output row of every frame of the launch
+// starts on a multiple of 4.  Their units are 1 and 2: a valid layout may fail
+// this (98 x 62 MM_Y8: rows 98 bytes apart) and takes the unfused pair, whose
+// stores are single samples.  Same arithmetic, same results.
+static bool mono_quads_aligned(const uint8_t *out, const Frames &fr, int nframes)
+{
+    uintptr_t m = reinterpret_cast<uintptr_t>(out) | fr.out.pitch;
+    if (nframes > 1) m |= fr.out.stride;
+    return (m & 3u) == 0;
+}
 static bool k34_fits(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
     if (fmt_nv12(fr.fmt) && !nv12_quads_aligned(in, out, fr, nframes)) return false;
+    if (fmt_mono(fr.fmt) && !mono_quads_aligned(out, fr, nframes)) return false;
     const Geo &g = h->geo;
     return g.N <= 4096 &&   // two transforms per workgroup: 2 N / 8 <= 1024 threads
            !g.ox && !g.oy && g.W % 8 == 0 && g.x0 >= 4 && g.x0 % 4 == 0 &&
@@ -932,6 +972,12 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
     return launch_k4(h, in, out, frame0, nframes, fr, s);
 }
 
+// k_compose's instance of a format (the single-plane formats': k_compose_mono)
+template <int FMT> static constexpr auto k4_kernel()
+{
+    if constexpr (kMono<FMT>) return &k_compose_mono<FMT>;
+    else return &k_compose<FMT>;
+}
 // K4 k_compose over chunk frames [frame0, nframes) (Yh of those frames ready)
 static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, int nframes,
                      const Frames &fr, hipStream_t s)
@@ -943,7 +989,7 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
         const size_t tot = (size_t)nout * h->W * h->H;
         ProfScope ps(h, s, MM_K_COMPOSE, nout);
         const dim3 grid((unsigned)((tot + 255) / 256));
-        MM_FMT_SWITCH_RGBA(fmt, hipLaunchKernelGGL((k_compose_odd<FMT_>), grid, dim3(256), 0, s, h->d_Yh,
+        MM_FMT_SWITCH_FULLRES(fmt, hipLaunchKernelGGL((k_compose_odd<FMT_>), grid, dim3(256), 0, s, h->d_Yh,
                                               h->yh_stride, in, out, frame0, nout, geo_of(h, fr), h->blur,
                                               h->d_col, h->d_row))
         HIPCHK(hipGetLastError());
@@ -952,7 +998,7 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
     const int rt = (h->H + kTileRows - 1) / kTileRows, ct = (h->W + kTileCols - 1) / kTileCols;
     const dim3 grid(rt * ct * nout);
     ProfScope ps(h, s, MM_K_COMPOSE, nout);
-    MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_compose<FMT_>), grid, dim3(kTileCols), 0, s, h->d_Yh,
+    MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k4_kernel<FMT_>()), grid, dim3(kTileCols), 0, s, h->d_Yh,
                                           h->yh_stride, in, out, frame0, rt, ct, geo_of(h, fr), h->blur,
                                           h->d_col3, h->d_row3))
     HIPCHK(hipGetLastError());
@@ -977,7 +1023,8 @@ static int copy_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, con
         const dim3 grid((unsigned)rows, (unsigned)std::min(32768, n - f0));
         const uint8_t *src = in + fr.in.stride * f0;
         uint8_t *dst = out + fr.out.stride * f0;
-        if (fmt_nv12(fr.fmt)) hipLaunchKernelGGL((k_copy_rows<uint16_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
+        if (fmt_unit(fr.fmt) == 1) hipLaunchKernelGGL((k_copy_rows<uint8_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
+        else if (fmt_unit(fr.fmt) == 2) hipLaunchKernelGGL((k_copy_rows<uint16_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
         else hipLaunchKernelGGL((k_copy_rows<uint32_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
         HIPCHK(hipGetLastError());
     }
@@ -1175,7 +1222,7 @@ static int run_debug(mm_handle *h, uint8_t *out, int n, int first, const Frames 
     HIPCHK(hipGetLastError());
     const size_t tot = (size_t)m * h->W * h->H;
     const dim3 grid((unsigned)((tot + 255) / 256));
-    MM_FMT_SWITCH_RGBA(fmt, hipLaunchKernelGGL((k_dbg_out<FMT_>), grid, dim3(256), 0, s, h->d_dbg, tex_stride,
+    MM_FMT_SWITCH_FULLRES(fmt, hipLaunchKernelGGL((k_dbg_out<FMT_>), grid, dim3(256), 0, s, h->d_dbg, tex_stride,
                                           out, first, m, h->p.show_magnitude, h->p.show_phase, geo_of(h, fr)))
     HIPCHK(hipGetLastError());
     return MM_OK;

@@ -672,6 +672,57 @@ __device__ __forceinline__ void c420_quad_pairs(const uint8_t *img, const Geo &g
     }
 }
 
+// ---- single-plane grayscale (MM_Y8 .. MM_Y16) ------------------------------
+// A frame is H rows of W samples, bytes (MM_Y8) or little-endian 16-bit words
+// with the code in the low bits (MM_Y10 / MM_Y12 / MM_Y16).  It IS the RGBA32F
+// frame R = G = B = v = sample / max, alpha 1 (include/mm.h): the luma of the
+// pixel is the sample and (I, Q) is zero.  So K1 is the luma-plane path of the
+// 4:2:0 formats with other uniforms, and it runs THEIR instances (kFmtNV12 for
+// bytes, kFmtP010 for words, the GEN form included, which the 4:2:0 formats
+// themselves never launch): with y_off = 0 their (float)sample - y_off is
+// (float)sample bit for bit, and y_unit = 1 / max folds into the resample
+// weights as NV12's 1 / 219 does.  The compose kernels have instances of their
+// own (FMT = kFmtY8, kFmtY16; the three word depths share one, Geo::nv.yo_scale
+// = max tells them apart) that never read the input frame: with zero (I, Q)
+// YIQToRGB gives R = G = B = sat(Y'), whose luma is sat(Y') itself, so a pixel
+// is vertical blur -> sat -> code -> store, the blur written as in every other
+// instance.  No chroma subsampling: odd sizes and the debug views (the view's
+// R value is the sample) are supported.
+// Alignment: frame base, pitch and stride are multiples of the sample size
+// only, so the unfused kernels store single samples; the fused kernels' quad
+// (four bytes as one dword, four words as one 8-byte store at a dword-aligned
+// address) runs only where every output row of the launch starts on a multiple
+// of 4 (mono_quads_aligned, mm_impl.hpp).
+constexpr int kFmtY8 = 8;     // MM_Y8
+constexpr int kFmtY16 = 11;   // MM_Y16 (and MM_Y10, MM_Y12)
+template <int FMT> constexpr bool kMono = FMT == kFmtY8 || FMT == kFmtY16;
+template <> struct LumaSrc<kFmtY8> : LumaSrc<kFmtNV12> {};
+template <> struct LumaSrc<kFmtY16> : LumaSrc<kFmtP010> {};
+template <> struct ChromaSrc<kFmtY8> { using raw_t = uint32_t; };    // (never loaded)
+template <> struct ChromaSrc<kFmtY16> { using raw_t = uint32_t; };
+// code of a saturated value v in [0, 1]: floor(v max + 0.5), at most max
+__device__ __forceinline__ unsigned mono_code(float v, const Geo &g)
+{
+    return (unsigned)fminf(v * g.nv.yo_scale + g.nv.yo_bias, g.nv.yo_scale);
+}
+// one sample of row `row` (the unfused, odd-size and debug kernels)
+template <int FMT>
+__device__ __forceinline__ void mono_store(uint8_t *row, unsigned X, float v, const Geo &g)
+{
+    if constexpr (FMT == kFmtY8) st_off<uint8_t>(row, X, (uint8_t)mono_code(v, g));
+    else st_off<uint16_t>(row, X * 2u, (uint16_t)mono_code(v, g));
+}
+// the fused kernels' quad X .. X+3 (X % 4 == 0) of a dword-aligned row
+template <int FMT>
+__device__ __forceinline__ void mono_store_quad(uint8_t *row, unsigned X, const float (&v)[4], const Geo &g)
+{
+    unsigned c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = mono_code(v[k], g);
+    if constexpr (FMT == kFmtY8) st_stream<uint32_t>(row, X, c[0] | c[1] << 8 | c[2] << 16 | c[3] << 24);
+    else st_stream_pair_a4(row, X * 2u, c[0] | c[1] << 16, c[2] | c[3] << 16);
+}
+
 // =========================================================================
 // K1: luma rows -> half spectra of row pairs
 // =========================================================================
@@ -2333,6 +2384,49 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     }
 }
 
+// k_compose for the single-plane formats (FMT = kFmtY8 / kFmtY16): the same
+// tiles, the same Yh loads and the same vertical blur expression, and nothing
+// else: (I, Q) of a gray frame is zero, so no input pixel is staged (frames_in
+// and the resample tables are not read, no LDS, no barrier) and the pixel is
+// the code of sat(Y'), one sample per lane.  Same parameter list as k_compose
+// (launch_k4 launches either).
+template <int FMT>
+__global__ __launch_bounds__(kTileCols)
+void k_compose_mono(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__restrict__,
+                    uint8_t *__restrict__ frames_out, int frame0, int row_tiles,
+                    int col_tiles, Geo g, Blur5 bw, const float4 *__restrict__,
+                    const float4 *__restrict__)
+{
+    static_assert(kMono<FMT>, "the 4:2:0 and RGBA formats compose with k_compose");
+    constexpr int TR = kTileRows, TC = kTileCols;
+    int b = blockIdx.x;
+    const int ct = b % col_tiles;
+    b /= col_tiles;
+    const int rt = b % row_tiles;
+    const int frame = frame0 + b / row_tiles;
+    const int i0 = rt * TR, X = ct * TC + (int)threadIdx.x;
+    if (X >= g.W) return;
+    const float *Yf = Yh + (size_t)frame * yh_stride;
+    float yv[TR + 4];   // canvas rows y0+i0-2 .. y0+i0+TR+1 of this column (k_compose's)
+#pragma unroll
+    for (int v = 0; v < TR + 4; ++v) {
+        const int cy = wrap_near(g.y0 + i0 - 2 + v, g.N, g.edge);
+        const int k = (cy - g.rb + 2 * g.N) & (g.N - 1);
+        const float y = ld_off<float>(Yf, (unsigned)(min(k, g.Hn - 1) * g.Wy + X) * 4u);
+        yv[v] = k < g.Hn ? y : 0.0f;
+    }
+    uint8_t *outp = frames_out + (size_t)frame * g.lo.stride;
+#pragma unroll
+    for (int r = 0; r < TR; ++r) {
+        const int i = i0 + r;
+        if (i < g.H) {
+            const float yb = bw.w0 * yv[r + 2] + bw.w1 * (yv[r + 1] + yv[r + 3]) +
+                             bw.w2 * (yv[r] + yv[r + 4]);
+            mono_store<FMT>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, sat(yb), g);
+        }
+    }
+}
+
 // =========================================================================
 // K34: K3 + K4 fused (even W, H with W % 8 == 0, N - W >= 8, N - H >= 4)
 // =========================================================================
@@ -2392,48 +2486,50 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     // horizontally combined I/Q of one source row for the quad (k_compose's
     // staged 3-tap combine over columns X-1 .. X+4)
     auto chroma_row = [&](int i, c2 (&hc)[4]) {
-        const int row = wrap_near(min(i, g.H), g.H, g.edge);
-        c2 a[6];
-        if constexpr (k420<FMT>) {
-            // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
-            // outer two wrapped or clamped as pixels, then halved): the quad's
-            // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
-            // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
-            // (P010: pairs are dwords, the quad's own two as two dword loads)
-            const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
-            unsigned pm0, pm1;
-            c420_quad_pairs<FMT>(img, g, row, (unsigned)X, pm0, pm1);
-            const unsigned pr = ld_off<raw_t>(img, c420_off<FMT>(g, row, cr));
-            a[0] = c420_iq2<FMT>(pl, g);
-            a[1] = a[2] = c420_iq2<FMT>(pm0, g);
-            a[3] = a[4] = c420_iq2<FMT>(pm1, g);
-            a[5] = c420_iq2<FMT>(pr, g);
-        } else {
-            // (in pixels: an RGBA pitch is a multiple of the pixel size)
-            const unsigned base = (unsigned)row * (g.li.pitch / bpp);
-            raw_t p[6];
-            p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
-            if constexpr (bpp == 4) {   // one 16-byte load (dword aligned: ld_quad_a4)
-                const uint4 m = ld_quad_a4(img, (base + (unsigned)X) * bpp);
-                p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
+        if constexpr (!kMono<FMT>) {   // (a gray frame's (I, Q) is zero: nothing to read)
+            const int row = wrap_near(min(i, g.H), g.H, g.edge);
+            c2 a[6];
+            if constexpr (k420<FMT>) {
+                // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
+                // outer two wrapped or clamped as pixels, then halved): the quad's
+                // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
+                // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
+                // (P010: pairs are dwords, the quad's own two as two dword loads)
+                const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
+                unsigned pm0, pm1;
+                c420_quad_pairs<FMT>(img, g, row, (unsigned)X, pm0, pm1);
+                const unsigned pr = ld_off<raw_t>(img, c420_off<FMT>(g, row, cr));
+                a[0] = c420_iq2<FMT>(pl, g);
+                a[1] = a[2] = c420_iq2<FMT>(pm0, g);
+                a[3] = a[4] = c420_iq2<FMT>(pm1, g);
+                a[5] = c420_iq2<FMT>(pr, g);
             } else {
+                // (in pixels: an RGBA pitch is a multiple of the pixel size)
+                const unsigned base = (unsigned)row * (g.li.pitch / bpp);
+                raw_t p[6];
+                p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
+                if constexpr (bpp == 4) {   // one 16-byte load (dword aligned: ld_quad_a4)
+                    const uint4 m = ld_quad_a4(img, (base + (unsigned)X) * bpp);
+                    p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
+                } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) p[1 + k] = ld_off<raw_t>(img, (base + (unsigned)X + k) * bpp);
+                    for (int k = 0; k < 4; ++k) p[1 + k] = ld_off<raw_t>(img, (base + (unsigned)X + k) * bpp);
+                }
+                p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
             }
-            p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
 #pragma unroll
-            for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 wc = colW3[X + k];
-            hc[k] = wc.x * a[k] + wc.y * a[k + 1] + wc.z * a[k + 2];
+            for (int k = 0; k < 4; ++k) {
+                const float4 wc = colW3[X + k];
+                hc[k] = wc.x * a[k] + wc.y * a[k + 1] + wc.z * a[k + 2];
+            }
         }
     };
 
     float yw[8][4];            // list rows i0+4s-4 .. i0+4s+3 of the quad (blurred horizontally)
                                // (as column pairs for a packed vertical blur: +3 spills, not kept)
-    c2 hc[6][4];               // combined (I, Q) of source rows i0+4s-5 .. i0+4s
+    [[maybe_unused]] c2 hc[6][4];   // combined (I, Q) of source rows i0+4s-5 .. i0+4s (gray: none)
     chroma_row(i0 - 1, hc[4]);
     chroma_row(i0, hc[5]);
 #ifdef MM_K34_STAMPS
@@ -2523,7 +2619,19 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
             for (int r = 0; r < 4; ++r) {
                 K34_STAMP(4);
                 const int i = i0 + 4 * s - 4 + r;
-                if (vq && i < g.H) {
+                if constexpr (kMono<FMT>) {
+                    // a gray frame: the code of sat(Y'), the blur written as below
+                    if (vq && i < g.H) {
+                        float yl[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const float yb = bw.w0 * yw[r + 2][k] + bw.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
+                                             bw.w2 * (yw[r][k] + yw[r + 4][k]);
+                            yl[k] = sat(yb);
+                        }
+                        mono_store_quad<FMT>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, yl, g);
+                    }
+                } else if (vq && i < g.H) {
                     const float4 wr = rowW3[i];
                     float rr[4], gg[4], bb[4];
 #pragma unroll
@@ -2560,10 +2668,12 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
         for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int k = 0; k < 4; ++k) yw[r][k] = yw[4 + r][k];
+        if constexpr (!kMono<FMT>) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            hc[0][k] = hc[4][k];
-            hc[1][k] = hc[5][k];
+            for (int k = 0; k < 4; ++k) {
+                hc[0][k] = hc[4][k];
+                hc[1][k] = hc[5][k];
+            }
         }
     }
 #ifdef MM_K34_STAMPS
@@ -2650,47 +2760,51 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     const unsigned cl = (unsigned)wrap_near(X - 1, g.W, g.edge);
     const unsigned cr = (unsigned)wrap_near(X + 4, g.W, g.edge);
     auto chroma_row = [&](int i, c2 (&hc)[4]) {   // k_rows_inv_compose's
-        const int row = wrap_near(min(i, g.H), g.H, g.edge);
-        c2 a[6];
-        if constexpr (k420<FMT>) {
-            // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
-            // outer two wrapped or clamped as pixels, then halved): the quad's
-            // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
-            // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
-            // (P010: pairs are dwords, the quad's own two as two dword loads)
-            const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
-            unsigned pm0, pm1;
-            c420_quad_pairs<FMT>(img, g, row, (unsigned)X, pm0, pm1);
-            const unsigned pr = ld_off<raw_t>(img, c420_off<FMT>(g, row, cr));
-            a[0] = c420_iq2<FMT>(pl, g);
-            a[1] = a[2] = c420_iq2<FMT>(pm0, g);
-            a[3] = a[4] = c420_iq2<FMT>(pm1, g);
-            a[5] = c420_iq2<FMT>(pr, g);
-        } else {
-            // (in pixels: an RGBA pitch is a multiple of the pixel size)
-            const unsigned base = (unsigned)row * (g.li.pitch / bpp);
-            raw_t p[6];
-            p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
-            if constexpr (bpp == 4) {   // one 16-byte load (dword aligned: ld_quad_a4)
-                const uint4 m = ld_quad_a4(img, (base + (unsigned)X) * bpp);
-                p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
+        if constexpr (!kMono<FMT>) {   // (a gray frame's (I, Q) is zero: nothing to read)
+            const int row = wrap_near(min(i, g.H), g.H, g.edge);
+            c2 a[6];
+            if constexpr (k420<FMT>) {
+                // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
+                // outer two wrapped or clamped as pixels, then halved): the quad's
+                // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
+                // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
+                // (P010: pairs are dwords, the quad's own two as two dword loads)
+                const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
+                unsigned pm0, pm1;
+                c420_quad_pairs<FMT>(img, g, row, (unsigned)X, pm0, pm1);
+                const unsigned pr = ld_off<raw_t>(img, c420_off<FMT>(g, row, cr));
+                a[0] = c420_iq2<FMT>(pl, g);
+                a[1] = a[2] = c420_iq2<FMT>(pm0, g);
+                a[3] = a[4] = c420_iq2<FMT>(pm1, g);
+                a[5] = c420_iq2<FMT>(pr, g);
             } else {
+                // (in pixels: an RGBA pitch is a multiple of the pixel size)
+                const unsigned base = (unsigned)row * (g.li.pitch / bpp);
+                raw_t p[6];
+                p[0] = ld_off<raw_t>(img, (base + cl) * bpp);
+                if constexpr (bpp == 4) {   // one 16-byte load (dword aligned: ld_quad_a4)
+                    const uint4 m = ld_quad_a4(img, (base + (unsigned)X) * bpp);
+                    p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
+                } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) p[1 + k] = ld_off<raw_t>(img, (base + (unsigned)X + k) * bpp);
+                    for (int k = 0; k < 4; ++k) p[1 + k] = ld_off<raw_t>(img, (base + (unsigned)X + k) * bpp);
+                }
+                p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
             }
-            p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
 #pragma unroll
-            for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 wc = colW3[X + k];
-            hc[k] = wc.x * a[k] + wc.y * a[k + 1] + wc.z * a[k + 2];
+            for (int k = 0; k < 4; ++k) {
+                const float4 wc = colW3[X + k];
+                hc[k] = wc.x * a[k] + wc.y * a[k + 1] + wc.z * a[k + 2];
+            }
         }
     };
     const int r0 = i0 + 2 * hh;   // first output row of this half
-    c2 hc[4][4];                  // combined (I, Q) of source rows r0-1 .. r0+2
-    if constexpr (k420<FMT>) {   // rows r0, r0+1 (r0 even) share a chroma row
+    [[maybe_unused]] c2 hc[4][4];   // combined (I, Q) of source rows r0-1 .. r0+2 (gray: none)
+    if constexpr (kMono<FMT>) {
+        // (nothing to read)
+    } else if constexpr (k420<FMT>) {   // rows r0, r0+1 (r0 even) share a chroma row
         chroma_row(r0 - 1, hc[0]);
         chroma_row(r0, hc[1]);
 #pragma unroll
@@ -2716,7 +2830,18 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int i = r0 + r;
-        if (vq && i < g.H) {
+        if constexpr (kMono<FMT>) {   // the code of sat(Y') (k_rows_inv_compose's)
+            if (vq && i < g.H) {
+                float yl[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float yb = bw.w0 * yw[r + 2][k] + bw.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
+                                     bw.w2 * (yw[r][k] + yw[r + 4][k]);
+                    yl[k] = sat(yb);
+                }
+                mono_store_quad<FMT>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, yl, g);
+            }
+        } else if (vq && i < g.H) {
             const float4 wr = rowW3[i];
             float rr[4], gg[4], bb[4];
 #pragma unroll
@@ -2781,7 +2906,8 @@ void k_compose_odd(const float *__restrict__ Yh, size_t yh_stride, const uint8_t
             }
             const float yb = bw.w0 * yv[2] + bw.w1 * (yv[1] + yv[3]) + bw.w2 * (yv[0] + yv[4]);
             float ci = 0.0f, cq = 0.0f;
-            if (tx < g.W && ty < g.H) {
+            // (a gray frame's (I, Q) is zero: its instances read no input pixel)
+            if constexpr (!kMono<FMT>) if (tx < g.W && ty < g.H) {
                 const Tap4 tc = colT[tx], tr = rowT[ty];
                 for (int a = 0; a < 4; ++a) {
                     if (tr.w[a] == 0.0f) continue;
@@ -2802,8 +2928,10 @@ void k_compose_odd(const float *__restrict__ Yh, size_t yh_stride, const uint8_t
             acc[1] += wt * sat(1.0f * yb + -0.272f * ci + -0.647f * cq);
             acc[2] += wt * sat(1.0f * yb + -1.106f * ci + 1.703f * cq);
         }
-    Pix<FMT>::store(frames_out + (size_t)frame * g.lo.stride + (size_t)((unsigned)Y * g.lo.pitch), (unsigned)X,
-                    acc[0], acc[1], acc[2]);
+    uint8_t *row = frames_out + (size_t)frame * g.lo.stride + (size_t)((unsigned)Y * g.lo.pitch);
+    // gray: R = G = B = the mean of the texels' sat(Y'), whose luma is itself
+    if constexpr (kMono<FMT>) mono_store<FMT>(row, (unsigned)X, acc[0], g);
+    else Pix<FMT>::store(row, (unsigned)X, acc[0], acc[1], acc[2]);
 }
 
 // =========================================================================
@@ -2891,17 +3019,19 @@ void k_dbg_out(const float *__restrict__ tex, size_t tex_stride, uint8_t *__rest
     } else {
         v = (show_mag ? mag : pha)[(size_t)(g.y0 + Y) * g.N + g.x0 + X];
     }
-    if (kUnorm<FMT>) v = sat(v);   // UNORM destination
-    Pix<FMT>::store(frames_out + (size_t)(frame0 + k) * g.lo.stride + (size_t)((unsigned)Y * g.lo.pitch), (unsigned)X,
-                    v, 0.0f, 0.0f);
+    if (kUnorm<FMT> || kMono<FMT>) v = sat(v);   // UNORM destination
+    uint8_t *row = frames_out + (size_t)(frame0 + k) * g.lo.stride + (size_t)((unsigned)Y * g.lo.pitch);
+    // a gray frame holds the R channel the view is: the code of its value
+    if constexpr (kMono<FMT>) mono_store<FMT>(row, (unsigned)X, v, g);
+    else Pix<FMT>::store(row, (unsigned)X, v, 0.0f, 0.0f);
 }
 
 // =========================================================================
 // passthrough of pitched frames (the first frame, apply_magnification = 0)
 // =========================================================================
 // One workgroup per (plane row, frame): the row's samples and nothing else, in
-// words of U (NV12: 2 bytes, its unit; every other format: 4, which divides
-// its unit).  `rows_y` RGBA / luma rows, then the (Cb, Cr) rows of a 4:2:0
+// words of U (NV12 and the 16-bit single-plane formats: 2 bytes, their unit;
+// MM_Y8: 1; every other format: 4, which divides its unit).  `rows_y` RGBA / luma rows, then the (Cb, Cr) rows of a 4:2:0
 // frame.  Tight frames on both sides are one plain device copy instead.
 template <class U>
 __global__ __launch_bounds__(256)

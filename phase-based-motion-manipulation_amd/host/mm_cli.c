@@ -8,7 +8,7 @@
  *
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
- *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020]
+ *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
@@ -57,6 +57,15 @@
  * frame format as MM_MATRIX_BT709 / MM_MATRIX_BT2020.  A .y4m header has no
  * matrix tag, so files are the same whatever the value.  Only with --nv12 or
  * --p010: the host's own RGBA conversion of a .y4m is BT.601.
+ * --mono: a mono .y4m input (Cmono, Cmono10, Cmono12, Cmono16: a grayscale
+ * camera's or ffmpeg's gray / gray10le / gray12le / gray16le frames) goes to
+ * the device as it is stored, as MM_Y8 / MM_Y10 / MM_Y12 / MM_Y16 frames by the
+ * header's depth: one sample per pixel each way, no conversion, odd sizes, the
+ * standard and steerable modes and the debug views included.  The output is a
+ * .y4m of the same Cmono* type (any other extension: the raw frames).  Refused
+ * with a chroma-carrying input, with --nv12, --p010, --srgb, --matrix and
+ * --full-range (there is no matrix and no range) and with the ring modes.
+ * Without --mono a Cmono input is expanded to RGBA8 on the host, as before.
  * --surface-align P,R: the device frames, input and output, are held in
  * mm_surface_aligned(W, H, format, P, R) surfaces (256,16: a hardware
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
@@ -431,7 +440,7 @@ int main(int argc, char **argv)
     int W = 1920, H = 1080, F = 300, L = 5, B = 30, dev = 0;
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
-    int nv12 = 0, p010 = 0, srgb = 0;
+    int nv12 = 0, p010 = 0, srgb = 0, mono = 0;
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
@@ -442,6 +451,7 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--srgb")) { g_fmt = MM_RGBA8_SRGB; srgb = 1; continue; }
         if (!strcmp(a, "--nv12")) { nv12 = 1; continue; }
         if (!strcmp(a, "--p010")) { p010 = 1; continue; }
+        if (!strcmp(a, "--mono")) { mono = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
         if (!strcmp(a, "--show-magnitude")) { show_mag = 1; continue; }
         if (!strcmp(a, "--show-phase")) { show_phase = 1; continue; }
@@ -485,6 +495,21 @@ int main(int argc, char **argv)
         W = yi.width;
         H = yi.height;
     }
+    if (mono) {
+        if (nv12 || p010 || srgb || matrix_arg || full_range) {
+            fprintf(stderr, "--mono does not go with --nv12, --p010, --srgb, --matrix or --full-range\n");
+            return 2;
+        }
+        if (ring_local > 0 || ring_world > 0) {
+            fprintf(stderr, "--mono does not go with the ring modes (they take RGBA frames)\n");
+            return 2;
+        }
+        if (!y4m_in || yi.chroma != Y4M_MONO) {
+            fprintf(stderr, "--mono needs a mono .y4m input (-i, Cmono / Cmono10 / Cmono12 / Cmono16)\n");
+            return 2;
+        }
+        g_fmt = depth == 8 ? MM_Y8 : depth == 10 ? MM_Y10 : depth == 12 ? MM_Y12 : MM_Y16;
+    }
     if (p010) {
         if (nv12) {
             fprintf(stderr, "--p010 does not go with --nv12\n");
@@ -508,8 +533,11 @@ int main(int argc, char **argv)
             return 2;
         }
         g_fmt = full_range ? MM_P010_FULL : MM_P010;
-    } else if (depth != 8) {
-        fprintf(stderr, "%s is a 10-bit stream (C420p10): it needs --p010\n", in_path);
+    } else if (depth != 8 && !mono) {
+        if (yi.chroma == Y4M_MONO)
+            fprintf(stderr, "%s is a %d-bit mono stream (Cmono%d): it needs --mono\n", in_path, depth, depth);
+        else
+            fprintf(stderr, "%s is a 10-bit stream (C420p10): it needs --p010\n", in_path);
         return 2;
     }
     if (nv12) {
@@ -583,7 +611,7 @@ int main(int argc, char **argv)
     }
 
     size_t fb = (size_t)W * H * 4;
-    if (nv12 || p010) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
+    if (nv12 || p010 || mono) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
     /* --surface-align: the frames the operator sees live in `lay` surfaces
      * (d_in, d_out); d_tin / d_tout are tight device frames for the synthetic
      * source and for the checksums and files */
@@ -596,7 +624,7 @@ int main(int argc, char **argv)
         if (sscanf(surf_arg, "%llu,%d", &pa, &ra) != 2 ||
             (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK) {
             fprintf(stderr, "--surface-align %s: want P,R with P a multiple of the format's unit "
-                            "(pixel size; NV12 2, P010 4) and R >= 1 (4:2:0: even)\n", surf_arg);
+                            "(pixel size; NV12 2, P010 4, mono: the sample size) and R >= 1 (4:2:0: even)\n", surf_arg);
             return 2;
         }
         printf("surfaces: pitch %zu  chroma offset %zu  frame stride %zu\n", lay.pitch, lay.chroma_offset,
@@ -616,7 +644,8 @@ int main(int argc, char **argv)
                                          : 3 * (size_t)W * H)
         : NULL;
     /* (planes: 3 W H bytes hold a C420p10 frame, 2 bytes per sample, exactly) */
-    if (y4m_out && (p010   ? y4m_write_header_420p10(fo, W, H, yi.fps_num, yi.fps_den)
+    if (y4m_out && (mono   ? y4m_write_header_mono(fo, W, H, yi.fps_num, yi.fps_den, depth)
+                    : p010 ? y4m_write_header_420p10(fo, W, H, yi.fps_num, yi.fps_den)
                     : nv12 ? y4m_write_header_420(fo, W, H, yi.fps_num, yi.fps_den)
                            : y4m_write_header(fo, W, H, yi.fps_num, yi.fps_den))) {
         fprintf(stderr, "write failed\n");
@@ -633,9 +662,12 @@ int main(int argc, char **argv)
         if (fi && y4m_in) {
             int got = 0;
             for (; got < n; ++got) {
-                const int r = y4m_read_frame_depth(fi, &yi, depth, planes);
+                /* (mono: the samples are the frame, read straight into place) */
+                const int r = mono ? y4m_read_frame_mono(fi, W, H, depth, host + fb * got)
+                                   : y4m_read_frame_depth(fi, &yi, depth, planes);
                 if (r < 0) { fprintf(stderr, "%s: malformed frame\n", in_path); return 1; }
                 if (r == 0) break;
+                if (mono) continue;
                 if (p010) y4m_420p10_to_p010(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
                 else if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
                 else y4m_to_rgba(&yi, planes, host + fb * got, full_range);
@@ -672,6 +704,13 @@ int main(int argc, char **argv)
             hipMemcpy(host, d_res, fb * n, hipMemcpyDeviceToHost);
             if (y4m_out) {
                 for (int k = 0; k < n; ++k) {
+                    if (mono) {
+                        if (y4m_write_frame_mono(fo, W, H, depth, host + fb * k)) {
+                            fprintf(stderr, "write failed\n");
+                            return 1;
+                        }
+                        continue;
+                    }
                     if (p010) y4m_p010_to_420p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
                     else if (nv12) y4m_nv12_to_420(W, H, host + fb * k, planes);
                     else y4m_from_rgba(W, H, host + fb * k, planes, full_range);

@@ -52,6 +52,10 @@ static int read_header(FILE *f, y4m_info *info, int *depth)
                 *depth = 10;
             } else if (!strcmp(v, "444")) info->chroma = Y4M_444;
             else if (!strcmp(v, "mono")) info->chroma = Y4M_MONO;
+            else if (depth && (!strcmp(v, "mono10") || !strcmp(v, "mono12") || !strcmp(v, "mono16"))) {
+                info->chroma = Y4M_MONO;
+                *depth = atoi(v + 4);
+            }
             else return -1;   /* 422, 411, high bit depth, alpha: unsupported */
             break;
         default: break;       /* X (comments) and unknown tags */
@@ -227,4 +231,31 @@ int y4m_write_frame_420p10(FILE *f, int W, int H, const uint16_t *planes420)
     if (fputs("FRAME\n", f) < 0) return -1;
     const size_t nb = (size_t)W * H * 3;
     return fwrite(planes420, 1, nb, f) == nb ? 0 : -1;
+}
+
+static const char *mono_tag(int bit_depth)
+{
+    return bit_depth == 8 ? "mono" : bit_depth == 10 ? "mono10" : bit_depth == 12 ? "mono12"
+           : bit_depth == 16 ? "mono16" : NULL;
+}
+
+int y4m_write_header_mono(FILE *f, int W, int H, int fps_num, int fps_den, int bit_depth)
+{
+    const char *tag = mono_tag(bit_depth);
+    if (!tag || W <= 0 || H <= 0) return -1;
+    return fprintf(f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C%s\n", W, H, fps_num, fps_den, tag) > 0 ? 0 : -1;
+}
+
+int y4m_read_frame_mono(FILE *f, int W, int H, int bit_depth, void *samples)
+{
+    if (!mono_tag(bit_depth) || W <= 0 || H <= 0) return -1;
+    return read_frame(f, (size_t)W * H * (bit_depth > 8 ? 2 : 1), samples);
+}
+
+int y4m_write_frame_mono(FILE *f, int W, int H, int bit_depth, const void *samples)
+{
+    if (!mono_tag(bit_depth) || W <= 0 || H <= 0) return -1;
+    if (fputs("FRAME\n", f) < 0) return -1;
+    const size_t nb = (size_t)W * H * (bit_depth > 8 ? 2 : 1);
+    return fwrite(samples, 1, nb, f) == nb ? 0 : -1;
 }

@@ -8,7 +8,9 @@
  * limited range (Y 16..235, C 16..240) unless `full_range` (JPEG-style 0..255).
  * Host-side only: the frames then go through mm_process_stream as RGBA8, or,
  * 4:2:0 streams re-interleaved to NV12, as MM_NV12 without any conversion;
- * 10-bit 4:2:0 (C420p10) streams likewise as MM_P010 (the last section).
+ * 10-bit 4:2:0 (C420p10) streams likewise as MM_P010, and mono streams of 8, 10,
+ * 12 or 16 bits (Cmono, Cmono10, Cmono12, Cmono16) as MM_Y8 .. MM_Y16 (the
+ * last two sections).
  */
 #ifndef MM355_Y4M_H
 #define MM355_Y4M_H
@@ -68,8 +70,9 @@ int y4m_write_frame_420(FILE *f, int width, int height, const uint8_t *planes420
  * y4m_read_header keeps refusing the tag; these entry points stand beside it
  * and y4m_info keeps its layout (the depth travels separately). */
 
-/* y4m_read_header that also accepts C420p10: *bit_depth is 10 for it (chroma
- * Y4M_420), 8 for every tag y4m_read_header accepts. */
+/* y4m_read_header that also accepts C420p10 and Cmono10 / Cmono12 / Cmono16:
+ * *bit_depth is 10 for C420p10 (chroma Y4M_420), 10, 12 or 16 for the mono
+ * tags (chroma Y4M_MONO), 8 for every tag y4m_read_header accepts. */
 int y4m_read_header_depth(FILE *f, y4m_info *info, int *bit_depth);
 
 /* Bytes of one frame's planes at `bit_depth` (2 bytes per sample above 8), and
@@ -87,6 +90,18 @@ void y4m_p010_to_420p10(int width, int height, const uint16_t *p010, uint16_t *p
 /* Write a C420p10 header / one C420p10 frame (planes Y, Cb, Cr). */
 int y4m_write_header_420p10(FILE *f, int width, int height, int fps_num, int fps_den);
 int y4m_write_frame_420p10(FILE *f, int width, int height, const uint16_t *planes420);
+
+/* ---- mono (Cmono, Cmono10, Cmono12, Cmono16), for the MM_Y8 .. MM_Y16 path ---
+ * One plane of width * height samples: bytes at bit_depth 8, else 16-bit
+ * little-endian words with the code in the low bits, as ffmpeg writes gray,
+ * gray10le, gray12le and gray16le.  The samples are the frame as mm_process
+ * takes it: no conversion either way, every bit of a word is kept.
+ * y4m_read_header_depth reads the header (chroma Y4M_MONO and the depth).
+ * bit_depth other than 8, 10, 12, 16: -1 from each of these. */
+int y4m_write_header_mono(FILE *f, int width, int height, int fps_num, int fps_den, int bit_depth);
+/* as y4m_read_frame: 1 on a frame, 0 at end of stream, -1 on a malformed one */
+int y4m_read_frame_mono(FILE *f, int width, int height, int bit_depth, void *samples);
+int y4m_write_frame_mono(FILE *f, int width, int height, int bit_depth, const void *samples);
 
 #ifdef __cplusplus
 }

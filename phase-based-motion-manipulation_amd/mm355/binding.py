@@ -14,7 +14,16 @@ RGBA8 = 0
 RGBA32F = 1
 RGBA16F = 2         # linear half (the reference camera's HDR target), ABI 10
 RGBA8_SRGB = 3      # 8-bit sRGB target in Linear colour space, ABI 10
-FORMAT_BPP = {RGBA8: 4, RGBA32F: 16, RGBA16F: 8, RGBA8_SRGB: 4}
+# grayscale camera frames, one plane: H rows of W bytes (Y8) or of W
+# little-endian 16-bit words with the code in the LOW bits (GenICam Mono8 /
+# Mono10 / Mono12 / Mono16); every size, mode and debug view
+Y8 = 8              # v = byte / 255
+Y10 = 9             # v = word / 1023
+Y12 = 10            # v = word / 4095
+Y16 = 11            # v = word / 65535
+MONO_FORMATS = (Y8, Y10, Y12, Y16)
+MONO_BITS = {Y8: 8, Y10: 10, Y12: 12, Y16: 16}
+FORMAT_BPP = {RGBA8: 4, RGBA32F: 16, RGBA16F: 8, RGBA8_SRGB: 4, Y8: 1, Y10: 2, Y12: 2, Y16: 2}
 # video frames, planar 8-bit Y'CbCr 4:2:0 (H rows of W luma bytes, then H/2 rows
 # of W interleaved Cb, Cr bytes; W and H even): frame_bytes() gives W*H*3/2
 NV12 = 16           # BT.601 limited ("video") range

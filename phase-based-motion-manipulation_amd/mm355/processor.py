@@ -7,13 +7,14 @@ snake_case; methods keep the reference's Unity callback names.
 import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
-                      NV12, NV12_FULL, P010, P010_FULL, RGBA8, RGBA8_SRGB, RGBA16F, RGBA32F, Handle, MMError,
-                      Params, Surface, base_format)
+                      MONO_FORMATS, NV12, NV12_FULL, P010, P010_FULL, RGBA8, RGBA8_SRGB, RGBA16F, RGBA32F, Y8,
+                      Handle, MMError, Params, Surface, base_format)
 
 
 def _fmt_of(frame, srgb=False):
     """Frame format from the dtype: uint8 UNORM (or sRGB-encoded with srgb),
-    float16 (linear half, the HDR camera target), float32."""
+    float16 (linear half, the HDR camera target), float32.  (A bare uint8 frame
+    is RGBA8: the grayscale formats are always named, OnRenderImage's fmt=.)"""
     dt = str(getattr(frame, "dtype", ""))
     if dt.endswith("uint8"):
         return RGBA8_SRGB if srgb else RGBA8
@@ -33,14 +34,25 @@ def frame_layout(frame, width, height, fmt):
     array): channels and pixels packed, rows any valid pitch apart, so that a
     region of interest is ``parent[y:y+H, x:x+W]``.  None for a contiguous
     frame (the tight entry point); MMError for any other striding.  Needs no GPU."""
-    if tuple(frame.shape) != (height, width, 4):
-        raise MMError(-1, f"frame shape {tuple(frame.shape)} (want {(height, width, 4)})")
     if isinstance(frame, np.ndarray):
         item = frame.itemsize
         strides = tuple(frame.strides)                       # bytes
     else:
         item = frame.element_size()
         strides = tuple(s * item for s in frame.stride())    # elements -> bytes
+    if fmt in MONO_FORMATS:   # [H, W] samples: uint8 (Y8) or uint16
+        want = "uint8" if fmt == Y8 else "uint16"
+        if tuple(frame.shape) != (height, width) or not str(frame.dtype).endswith(want):
+            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height, width)} {want})")
+        if strides[1] != item or strides[0] <= 0:
+            raise MMError(-1, "frames must be contiguous or row-strided (samples packed)")
+        if strides[0] == item * width:
+            return None
+        lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
+        lay.bytes(width, height)
+        return lay
+    if tuple(frame.shape) != (height, width, 4):
+        raise MMError(-1, f"frame shape {tuple(frame.shape)} (want {(height, width, 4)})")
     if strides[2] != item or strides[1] != 4 * item or strides[0] <= 0:
         raise MMError(-1, "frames must be contiguous or row-strided (pixels and channels packed)")
     if strides[0] == 4 * item * width:
@@ -134,16 +146,21 @@ class MotionMagnificationProcessor:
         if self._handle is not None:
             self._handle.set_params(self._params())
 
-    def OnRenderImage(self, source, destination):
+    def OnRenderImage(self, source, destination, fmt=None):
         """OnRenderImage (.cs:101-143). source/destination: [H, W, 4] uint8,
         float16 or float32, both torch CUDA tensors (async on torch's current
-        stream) or both host numpy arrays (synchronous)."""
+        stream) or both host numpy arrays (synchronous).  fmt=Y8 / Y10 / Y12 /
+        Y16: grayscale camera frames, [H, W] uint8 (Y8) or uint16 on both sides
+        (contiguous or row-strided views)."""
         if self._handle is None:                       # !isInitialized -> Blit (.cs:103-107)
             destination[...] = source
             return
-        fmt = _fmt_of(source, self.srgb)
-        if _fmt_of(destination, self.srgb) != fmt:
-            raise MMError(-1, "source/destination formats differ")
+        if fmt is None:
+            fmt = _fmt_of(source, self.srgb)
+            if _fmt_of(destination, self.srgb) != fmt:
+                raise MMError(-1, "source/destination formats differ")
+        elif fmt not in MONO_FORMATS:
+            raise MMError(-1, f"fmt={fmt}: only the grayscale formats are named, the others follow the dtype")
         on_dev = _is_device(source)
         if on_dev != _is_device(destination):
             raise MMError(-1, "source and destination must both be device or host")
@@ -188,5 +205,7 @@ def host_frames(n, h, w, fmt):
         return np.zeros((n, h * 3 // 2, w), np.uint8)
     if fmt in (P010, P010_FULL):    # the same rows in 16-bit words (10-bit code << 6)
         return np.zeros((n, h * 3 // 2, w), np.uint16)
+    if fmt in MONO_FORMATS:         # one plane of samples
+        return np.zeros((n, h, w), np.uint8 if fmt == Y8 else np.uint16)
     dt = {RGBA8: np.uint8, RGBA8_SRGB: np.uint8, RGBA16F: np.float16}.get(fmt, np.float32)
     return np.zeros((n, h, w, 4), dt)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""RGBA8 against NV12 and P010 frames on one GPU, same process, alternating legs.
+"""RGBA8 against NV12, P010 and grayscale (Y8, Y16) frames on one GPU, same process, alternating legs.
 
 The flagship stream (1920x1080, 5 levels, phase scale 25, batches of 150
 frames as bench.py) in the three frame formats.  Frames are generated on the
@@ -22,6 +22,11 @@ MM_MATRIX_BT2020 (the timing does not depend on the sample values), whose K1
 reads the chroma plane too; in the same rounds, so that their K1 stands next to
 the luma-only K1 and to RGBA8's.  A library from before the matrix bits runs
 without them.
+
+Grayscale legs (y8, y16, and their _pitched forms): the luma of the same
+frames as MM_Y8 bytes and MM_Y16 words (code Yl max, rounded), one sample per
+pixel each way; their K34 reads no input.  A library from before the
+single-plane formats runs without them.
 
 usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--out FILE.json]
 """
@@ -57,6 +62,20 @@ def to_420(torch, rgba, ten_bit=False):
         out[k, :H] = code(yl * ys + y0)
         out[k, H:, 0::2] = code(cb * cs + c0)
         out[k, H:, 1::2] = code(cr * cs + c0)
+    return out
+
+
+def to_mono(torch, rgba, bits):
+    """[n][H][W][4] uint8 (device) -> [n][H][W] gray samples: the BT.601 luma of
+    the frame, code floor(Yl max + 0.5); uint8, or (16 bits) the bit pattern of
+    the uint16 word in an int16."""
+    n, H, W, _ = rgba.shape
+    top = (1 << bits) - 1
+    out = torch.empty((n, H, W), dtype=torch.uint8 if bits == 8 else torch.int16, device=rgba.device)
+    for k in range(n):
+        f = rgba[k, ..., :3].float() / 255.0
+        c = torch.clamp(torch.floor((0.299 * f[..., 0] + 0.587 * f[..., 1] + 0.114 * f[..., 2]) * top + 0.5), 0, top)
+        out[k] = c.to(torch.uint8) if bits == 8 else (c.to(torch.int32) & 0xFFFF).to(torch.int16)
     return out
 
 
@@ -97,6 +116,11 @@ def main():
         fmts += [("nv12_bt709", mm355.NV12 | mm355.MATRIX_BT709), ("p010_bt2020", mm355.P010 | mm355.MATRIX_BT2020)]
     except mm355.MMError:
         pass    # a build from before the matrix bits
+    try:
+        mm355.frame_bytes(W, H, mm355.Y8)
+        fmts += [("y8", mm355.Y8), ("y16", mm355.Y16)]
+    except mm355.MMError:
+        pass    # a build from before the single-plane formats
     for name, fmt in fmts:
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
@@ -106,6 +130,8 @@ def main():
             src = rgba
         elif name in ("nv12_bt709", "p010_bt2020"):
             src = legs[name.split("_")[0]]["src"]
+        elif name in ("y8", "y16"):
+            src = to_mono(torch, rgba, 8 if name == "y8" else 16)
         else:
             src = to_420(torch, rgba, ten_bit=name == "p010")
         legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[], lay=None,
@@ -114,7 +140,7 @@ def main():
             lay = mm355.Surface.aligned(W, H, fmt, 256, 16)
             h = mm355.Handle(W, H, p)
             h.set_batch(B)
-            buf = to_surface(torch, src, lay, W, H, name != "rgba8")
+            buf = to_surface(torch, src, lay, W, H, name not in ("rgba8", "y8", "y16"))
             legs[name + "_pitched"] = dict(h=h, fmt=fmt, src=buf, dst=torch.zeros_like(buf), fps=[], lay=lay,
                                            bytes_per_frame=lay.frame_stride)
     st = torch.cuda.Stream()
@@ -172,7 +198,12 @@ def main():
                                                 out["formats"][base]["fps_median"], 4)
             k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
             out[name + "_k1_us"] = {"matrixed": k1(name), base: k1(base), "rgba8": k1("rgba8")}
-    for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020"):
+    for name in ("y8", "y16"):
+        if name in out["formats"]:
+            out[name + "_over_nv12"] = round(out["formats"][name]["fps_median"] /
+                                             out["formats"]["nv12"]["fps_median"], 4)
+            out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
+    for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16"):
         if name + "_pitched" in out["formats"]:
             out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
                                                       out["formats"][name]["fps_median"], 4)
