@@ -172,7 +172,8 @@ extern "C" {
  * 2 x 2 matrix of (cb, cr) (mm_ycbcr_matrix); neutral chroma still gives
  * exactly zero I and Q and luma = y.
  * Out of scope: PQ / HLG transfer curves (the samples are taken as they are,
- * like every other format's), constant-luminance BT.2020, 4:2:2 and 4:4:4,
+ * like every other format's), constant-luminance BT.2020, 4:4:4 and planar or
+ * 10-bit 4:2:2 (packed 8-bit 4:2:2: MM_YUY2 / MM_UYVY below),
  * chroma siting other than the shared 2 x 2 sample, odd sizes. */
 #define MM_MATRIX_BT709   32   /* Kr 0.2126, Kb 0.0722 */
 #define MM_MATRIX_BT2020  64   /* Kr 0.2627, Kb 0.0593, non-constant luminance */
@@ -219,6 +220,54 @@ extern "C" {
 #define MM_Y10  9    /* 2 B/px, little-endian word, code in the LOW 10 bits: v = word / 1023 */
 #define MM_Y12  10   /* ... low 12 bits: v = word / 4095                            */
 #define MM_Y16  11   /* ... v = word / 65535                                        */
+
+/* Packed 4:2:2 capture frames (backward-compatible addition to ABI 10: a
+ * caller detects it by mm_frame_bytes(W, H, MM_YUY2, &n) == MM_OK).  8-bit
+ * Y'CbCr 4:2:2 as a live source hands it out: UVC webcams and most USB capture
+ * devices deliver YUY2 (V4L2 YUYV, ffmpeg yuyv422), SDI / HDMI capture cards
+ * and QuickTime 2vuy deliver UYVY (V4L2 UYVY, ffmpeg uyvy422).  One plane,
+ * tightly packed: H rows of W / 2 four-byte macropixels, bytes Y0 Cb Y1 Cr
+ * (MM_YUY2) or Cb Y0 Cr Y1 (MM_UYVY), 2 W bytes per row and 2 W H per frame;
+ * frame k of a stream at k * mm_frame_bytes.  W and H even (else
+ * MM_ERR_UNSUPPORTED from mm_frame_bytes, mm_surface_* and every frame entry
+ * point; 4:2:2 itself would allow odd H, which is left out);
+ * show_magnitude / show_phase are refused with MM_ERR_UNSUPPORTED, as for NV12.
+ * MM_MATRIX_BT709 / MM_MATRIX_BT2020 may be OR-ed on exactly as on the 4:2:0
+ * codes: the valid formats are 24..27 (BT.601), 56..59 and 88..91; codes
+ * 28..31 stay unknown (kept free for a 10-bit form).
+ * The codes and ranges are NV12's, the matrices the matrix bits', and a chroma
+ * sample is shared by its 1 x 2 pixels.  The frame IS the RGBA32F frame of
+ * this decode and the result the reference's result on it:
+ *   in:  y = (Y - 16) / 219, cb = (Cb - 128) / 224, cr = (Cr - 128) / 224
+ *        (_FULL: Y / 255, (C - 128) / 255); R, G, B by the format's decode:
+ *        BT.601 with the six-digit coefficients of the NV12 section, a matrix
+ *        bit with the (Kr, Kb) form of the matrix section; alpha 1, NOT
+ *        clamped;
+ *   out: of the saturated RGB, Y', Cb', Cr' by the format's weights; luma code
+ *        per pixel, chroma code 128 + scale x the mean of the macropixel's two
+ *        pixels' C'; codes floor(v + 0.5) clamped to 0..255.
+ * The first frame after mm_create / mm_reset and apply_magnification = 0 pass
+ * all 2 W H bytes through bitwise.  mm_ycbcr_matrix accepts these codes (the
+ * values of the 4:2:0 code of the same matrix); mm_nv12_chroma_matrix is
+ * unchanged.  For BT.601 frames the forward row kernel uses the luma bytes
+ * alone (every second byte; the chroma byte loaded beside each is dropped);
+ * matrixed frames cost it one dword per pixel and source row, which holds Y,
+ * Cb and Cr.  2 bytes per pixel travel each way and the
+ * host converts nothing; against NV12 the vertical chroma resolution is kept.
+ * Surfaces: the unit u is 4, one macropixel; chroma_offset = chroma_pitch = 0
+ * (else MM_ERR_INVALID); pitch >= 2 W; device frame pointers, pitch and frame
+ * stride are multiples of 4, so a region of interest starts on an even column;
+ * the extent and 4 GiB rules are unchanged.  Every row of every legal layout
+ * is dword aligned, so the fused kernels run under their geometry conditions
+ * alone.
+ * Out of scope: 10-bit 4:2:2 (Y210, v210, P210); planar 4:2:2 and 4:4:4 on the
+ * device; odd H; the debug views; chroma siting other than the shared 1 x 2
+ * sample; PQ / HLG; the ring entry points (include/mm_ring.h); the Unity shim;
+ * a host 4:2:2 to RGBA conversion. */
+#define MM_YUY2      24   /* 8-bit packed 4:2:2, bytes Y0 Cb Y1 Cr, BT.601 limited range */
+#define MM_YUY2_FULL 25   /* the same, full range */
+#define MM_UYVY      26   /* bytes Cb Y0 Cr Y1, BT.601 limited range */
+#define MM_UYVY_FULL 27   /* the same, full range */
 
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0  /* usePyramidDecomposition = true (.cs:18, :128-131) */
@@ -349,7 +398,7 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  * an unaligned frame takes the narrower access, never another kernel: a layout
  * aligned like a decoder's runs exactly the tight layout's kernels. */
 typedef struct {
-    int    format;         /* MM_RGBA8 ... MM_P010_FULL, MM_Y8 ... MM_Y16; 4:2:0: | MM_MATRIX_* */
+    int    format;         /* MM_RGBA8 ... MM_UYVY_FULL; 4:2:0 and 4:2:2: | MM_MATRIX_* */
     size_t pitch;          /* bytes from one row to the next: RGBA rows, or luma rows */
     size_t chroma_offset;  /* 4:2:0: bytes from the frame's base to the (Cb,Cr) plane; else 0 */
     size_t chroma_pitch;   /* 4:2:0: bytes from one (Cb,Cr) row to the next; else 0 */
@@ -505,7 +554,7 @@ int mm_resample_table(int width, int height, int axis, int edge_mode,
  * Q_cr}: RGBToYIQ's I and Q rows times the BT.601 conversion above, derived
  * in double (the kernels take it divided by the range's chroma scale). */
 int mm_nv12_chroma_matrix(double m[4]);
-/* The (cb, cr) -> (Y, I, Q) matrix of a 4:2:0 format, m = {Y_cb, I_cb, Q_cb,
+/* The (cb, cr) -> (Y, I, Q) matrix of a 4:2:0 or packed 4:2:2 format, m = {Y_cb, I_cb, Q_cb,
  * Y_cr, I_cr, Q_cr}: RGBToYIQ's rows times the format's decode (its matrix
  * bit's; the range does not enter), derived in double.  Y_cb, Y_cr are the a,
  * b of Yq above; for the BT.601 codes they are exactly 0 and the I, Q entries

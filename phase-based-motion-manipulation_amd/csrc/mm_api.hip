@@ -402,7 +402,7 @@ int mm_nv12_chroma_matrix(double m[4])
 
 int mm_ycbcr_matrix(int format, double m[6])
 {
-    if (!m || !fmt_valid(format) || !fmt_420(format)) return MM_ERR_INVALID;
+    if (!m || !fmt_valid(format) || !fmt_ycc(format)) return MM_ERR_INVALID;
     ycbcr_matrix(format, m);
     return MM_OK;
 }

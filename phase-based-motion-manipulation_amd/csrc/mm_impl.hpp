@@ -206,16 +206,24 @@ static inline size_t fmt_bpp(int fmt)
 {
     return fmt == MM_RGBA32F ? 16 : fmt == MM_RGBA16F ? 8 : fmt == MM_Y8 ? 1 : fmt >= MM_Y10 && fmt <= MM_Y16 ? 2 : 4;
 }
-// A 4:2:0 code may carry one matrix bit (MM_MATRIX_BT709 / MM_MATRIX_BT2020):
-// layout, sizes and units are its base code's, the bit changes coefficients
-// (geo_of) and K1's instance (MM_FMT_SWITCH_K1).
 static constexpr int kMatrixBits = MM_MATRIX_BT709 | MM_MATRIX_BT2020;
+// A 4:2:0 or packed 4:2:2 code may carry one matrix bit (MM_MATRIX_BT709 /
+// MM_MATRIX_BT2020): layout, sizes and units are its base code's, the bit
+// changes coefficients (geo_of) and K1's instance (MM_FMT_SWITCH_K1).
 static inline int fmt_base(int fmt) { return fmt & ~kMatrixBits; }
 static inline int fmt_matrix(int fmt) { return fmt & kMatrixBits; }
 static inline bool fmt_nv12(int fmt) { return fmt_base(fmt) == MM_NV12 || fmt_base(fmt) == MM_NV12_FULL; }
 static inline bool fmt_p010(int fmt) { return fmt_base(fmt) == MM_P010 || fmt_base(fmt) == MM_P010_FULL; }
 static inline bool fmt_420(int fmt) { return fmt_nv12(fmt) || fmt_p010(fmt); }   // planar, not Pix<FMT>
-static inline bool fmt_full(int fmt) { return fmt_base(fmt) == MM_NV12_FULL || fmt_base(fmt) == MM_P010_FULL; }
+// packed 8-bit 4:2:2: one plane of four-byte macropixels (YUY2 / UYVY byte order)
+static inline bool fmt_422(int fmt) { return fmt_base(fmt) >= MM_YUY2 && fmt_base(fmt) <= MM_UYVY_FULL; }
+static inline bool fmt_uyvy(int fmt) { return fmt_base(fmt) == MM_UYVY || fmt_base(fmt) == MM_UYVY_FULL; }
+static inline bool fmt_ycc(int fmt) { return fmt_420(fmt) || fmt_422(fmt); }   // Y'CbCr: takes a matrix bit
+static inline bool fmt_full(int fmt)
+{
+    const int b = fmt_base(fmt);
+    return b == MM_NV12_FULL || b == MM_P010_FULL || b == MM_YUY2_FULL || b == MM_UYVY_FULL;
+}
 // single-plane grayscale: one sample per pixel, a byte (MM_Y8) or a 16-bit word
 static inline bool fmt_mono(int fmt) { return fmt >= MM_Y8 && fmt <= MM_Y16; }
 static inline int mono_max(int fmt) { return fmt == MM_Y8 ? 255 : fmt == MM_Y10 ? 1023 : fmt == MM_Y12 ? 4095 : 65535; }
@@ -224,14 +232,14 @@ static inline bool fmt_valid(int fmt)
     if (fmt_mono(fmt)) return true;   // (a matrix bit on these codes: no 4:2:0 base, invalid below)
     if (fmt == MM_RGBA8 || fmt == MM_RGBA32F || fmt == MM_RGBA16F || fmt == MM_RGBA8_SRGB) return true;
     // (any other bit, a negative code included, leaves a base that is no 4:2:0 code)
-    return fmt_420(fmt) && fmt_matrix(fmt) != kMatrixBits;
+    return fmt_ycc(fmt) && fmt_matrix(fmt) != kMatrixBits;
 }
 // Bytes of one W x H frame (the planar 4:2:0 formats: W H luma samples and half
 // as many chroma samples, of 1 byte (NV12) or 2 (P010); W and H even, fmt_check).
 static inline size_t fmt_frame_bytes(int W, int H, int fmt)
 {
     const size_t px = (size_t)W * (size_t)H;
-    return fmt_p010(fmt) ? 3 * px : fmt_nv12(fmt) ? px + px / 2 : px * fmt_bpp(fmt);
+    return fmt_p010(fmt) ? 3 * px : fmt_nv12(fmt) ? px + px / 2 : fmt_422(fmt) ? 2 * px : px * fmt_bpp(fmt);
 }
 // What every frame entry point asks of (format, geometry, parameters) before
 // it queues anything.  NV12 and P010 are 4:2:0: even sizes only; the debug
@@ -240,18 +248,19 @@ static inline size_t fmt_frame_bytes(int W, int H, int fmt)
 static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
 {
     if (!fmt_valid(fmt)) return MM_ERR_INVALID;
-    if (fmt_420(fmt) && ((W | H) & 1)) return MM_ERR_UNSUPPORTED;
-    if (fmt_420(fmt) && p && (p->show_magnitude || p->show_phase)) return MM_ERR_UNSUPPORTED;
+    if (fmt_ycc(fmt) && ((W | H) & 1)) return MM_ERR_UNSUPPORTED;   // (4:2:2: even H too, include/mm.h)
+    if (fmt_ycc(fmt) && p && (p->show_magnitude || p->show_phase)) return MM_ERR_UNSUPPORTED;
     return MM_OK;
 }
 // ---- surfaces (mm_surface, include/mm.h) ----------------------------------
 // u: what pitches, offsets, strides and frame pointers are multiples of
 // (the single-plane formats: their sample, 1 or 2 bytes)
-static inline size_t fmt_unit(int fmt) { return fmt_nv12(fmt) ? 2 : fmt_p010(fmt) ? 4 : fmt_bpp(fmt); }
+// (packed 4:2:2: one macropixel)
+static inline size_t fmt_unit(int fmt) { return fmt_nv12(fmt) ? 2 : fmt_p010(fmt) || fmt_422(fmt) ? 4 : fmt_bpp(fmt); }
 // sample bytes of one row (4:2:0: of a luma row and of a (Cb, Cr) row alike)
 static inline size_t fmt_row_bytes(int W, int fmt)
 {
-    return (size_t)W * (fmt_p010(fmt) ? 2 : fmt_nv12(fmt) ? 1 : fmt_bpp(fmt));
+    return (size_t)W * (fmt_p010(fmt) || fmt_422(fmt) ? 2 : fmt_nv12(fmt) ? 1 : fmt_bpp(fmt));
 }
 static inline int surf_tight(int W, int H, int fmt, mm_surface *s)
 {
@@ -310,7 +319,7 @@ static inline Geo::Lay surf_lay(const mm_surface &s)
     l.pitch = (unsigned)s.pitch;            // (< 2^32 wherever a second row exists: extent <= 2^32)
     l.c_off = (unsigned)s.chroma_offset;
     l.c_pitch = (unsigned)s.chroma_pitch;
-    l.pad_ = 0;
+    l.yb = 0;
     l.stride = s.frame_stride;
     return l;
 }
@@ -343,10 +352,13 @@ static_assert(kFmtY8 == MM_Y8 && kFmtY16 == MM_Y16, "the kernels' single-plane t
 static_assert(kFmtP010 == MM_P010, "the kernels' P010 template argument is the format code");
 static_assert(kFmtNV12M == (MM_NV12 | MM_MATRIX_BT709) && kFmtP010M == (MM_P010 | MM_MATRIX_BT709),
               "K1's matrixed template arguments are the BT.709 limited-range codes");
+static_assert(kFmtYUY2 == MM_YUY2 && kFmtYUY2M == (MM_YUY2 | MM_MATRIX_BT709),
+              "the kernels' packed 4:2:2 template arguments are the YUY2 limited-range codes");
 // Runs the statement with the compile-time format FMT_ of the runtime `fmt`
 // (both NV12 ranges run the MM_NV12 instances, both P010 ranges the MM_P010
-// instances, whatever the matrix bit, and the three word depths of the
-// single-plane formats the MM_Y16 instances; geo_of sets their uniforms).
+// instances, whatever the matrix bit, the three word depths of the
+// single-plane formats the MM_Y16 instances, and both byte orders and ranges
+// of packed 4:2:2 the MM_YUY2 instances; geo_of sets their uniforms).
 #define MM_FMT_SWITCH(fmt, ...)                                                \
     switch (fmt_base(fmt)) {                                                   \
     case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
@@ -356,12 +368,16 @@ static_assert(kFmtNV12M == (MM_NV12 | MM_MATRIX_BT709) && kFmtP010M == (MM_P010 
     case MM_P010: case MM_P010_FULL: { constexpr int FMT_ = MM_P010; __VA_ARGS__; } break; \
     case MM_Y8: { constexpr int FMT_ = MM_Y8; __VA_ARGS__; } break;            \
     case MM_Y10: case MM_Y12: case MM_Y16: { constexpr int FMT_ = MM_Y16; __VA_ARGS__; } break; \
+    case MM_YUY2: case MM_YUY2_FULL: case MM_UYVY: case MM_UYVY_FULL:          \
+        { constexpr int FMT_ = MM_YUY2; __VA_ARGS__; } break;                  \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
 // ... K1's: a code with a matrix bit runs the matrixed NV12 / P010 instance,
-// which reads the chroma plane too (BT.709 and BT.2020, both ranges, share it)
+// which reads the chroma plane too (BT.709 and BT.2020, both ranges, share it);
+// a matrixed packed 4:2:2 code the instance that reads whole macropixels
 #define MM_FMT_SWITCH_K1(fmt, ...)                                             \
     if (fmt_matrix(fmt) && fmt_nv12(fmt)) { constexpr int FMT_ = kFmtNV12M; __VA_ARGS__; }      \
+    else if (fmt_matrix(fmt) && fmt_422(fmt)) { constexpr int FMT_ = kFmtYUY2M; __VA_ARGS__; }  \
     else if (fmt_matrix(fmt)) { constexpr int FMT_ = kFmtP010M; __VA_ARGS__; }                  \
     else MM_FMT_SWITCH(fmt, __VA_ARGS__)
 // K1's instance of a format: a single-plane frame IS a luma plane and runs the
@@ -370,7 +386,7 @@ static_assert(kFmtNV12M == (MM_NV12 | MM_MATRIX_BT709) && kFmtP010M == (MM_P010 
 // would compute (mm_kernels.hpp)
 template <int F> constexpr int kK1Fmt = F == MM_Y8 ? kFmtNV12 : F == MM_Y16 ? kFmtP010 : F;
 // ... and the kernels of the odd sizes and the debug views, which the 4:2:0
-// formats cannot have (refused by fmt_check before any launch): the RGBA and
+// and packed 4:2:2 formats cannot have (refused by fmt_check before any launch): the RGBA and
 // the single-plane instances
 #define MM_FMT_SWITCH_FULLRES(fmt, ...)                                        \
     switch (fmt) {                                                             \
@@ -447,7 +463,7 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
     const int fmt = fr.fmt;
     g.li = fr.in;
     g.lo = fr.out;
-    if (fmt_420(fmt)) {
+    if (fmt_ycc(fmt)) {
         const bool full = fmt_full(fmt), p10 = fmt_p010(fmt);
         const double ys = p10 ? (full ? 1023.0 : 876.0) : (full ? 255.0 : 219.0);
         const double cs = p10 ? (full ? 1023.0 : 896.0) : (full ? 255.0 : 224.0);
@@ -472,8 +488,12 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
         g.nv.yo_bias = (float)(y0 + 0.5);
         // C' = (B - Yl) 0.5 / (1 - Kb), (R - Yl) 0.5 / (1 - Kr) (BT.601: 0.886,
         // 0.701); the mean of four; the code scale
-        g.nv.cbo = (float)(0.25 * cs * 0.5 / (1.0 - kb));
-        g.nv.cro = (float)(0.25 * cs * 0.5 / (1.0 - kr));
+        // (packed 4:2:2: the mean of the macropixel's two)
+        const double mean = fmt_422(fmt) ? 0.5 : 0.25;
+        g.nv.cbo = (float)(mean * cs * 0.5 / (1.0 - kb));
+        g.nv.cro = (float)(mean * cs * 0.5 / (1.0 - kr));
+        // packed 4:2:2 byte order, the same on both sides: YUY2 is Y0 Cb Y1 Cr, UYVY Cb Y0 Cr Y1
+        g.li.yb = g.lo.yb = fmt_uyvy(fmt) ? 1u : 0u;
     } else if (fmt_mono(fmt)) {
         // v = sample / max in, code = floor(v max + 0.5) clamped to max out:
         // K1 runs the luma-plane instances (no offset), the compose instances
@@ -684,7 +704,7 @@ static int set_attrs(int W)
     (void)W;   // every other kernel stays within the default 64 KiB dynamic LDS
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 2 * lds_complex<4096>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         // k_sb_cols: exchange buffer (36.9 KB) + its own staging, past 64 KB for
@@ -713,7 +733,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 11) {   // k_rows_inv_compose4: four 2048-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 4 * lds_complex<2048>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
     }
@@ -861,7 +881,9 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
 // all its frames here, not from its first one).  NV12's unit is 2, so a valid
 // layout may fail this: it takes the unfused pair, same results.  (RGBA8's and
 // P010's quads are multi-dword accesses at dword-aligned addresses, which the
-// unit, 4, gives every layout: mm_kernels.hpp ld_quad_a4.)
+// unit, 4, gives every layout: mm_kernels.hpp ld_quad_a4; packed 4:2:2's quads
+// are 8-byte accesses of two macropixels at dword-aligned addresses, and its
+// unit is 4 too.)
 static bool nv12_quads_aligned(const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
     const uintptr_t a = reinterpret_cast<uintptr_t>(in) + fr.in.c_off, b = reinterpret_cast<uintptr_t>(out);

@@ -60,6 +60,7 @@ struct Geo {
         float kr, kg, kb;           // out: Yl = kr R + kg G + kb B, the matrix's luma weights
         float yo_scale, yo_bias;    // out: luma code = floor(Yl * yo_scale + yo_bias), bias = offset + 0.5
         float cbo, cro;             // out: chroma code = floor(sum of four (B - Yl) * cbo + 128.5), Cr: R - Yl
+                                    // (packed 4:2:2: the sum of the macropixel's two)
     } nv;
     // Where the caller's frames lie (mm_surface, include/mm.h), in bytes, the
     // input side (li) and the output side (lo) apart; filled per launch by
@@ -67,8 +68,10 @@ struct Geo {
     // c_off + j * c_pitch, frame k at k * stride.  Every offset inside a frame
     // fits 32 bits (extent <= 2^32, mm_surface_bytes): workgroup-uniform row
     // bases plus 32-bit lane offsets, as with the tight layout's W * bpp.
+    // yb (packed 4:2:2 only, else 0): the side's byte order, Y0's byte in the
+    // macropixel (YUY2 0, UYVY 1); Cb's is 1 - yb, Y1 and Cr lie two bytes on.
     struct Lay {
-        unsigned pitch, c_off, c_pitch, pad_;
+        unsigned pitch, c_off, c_pitch, yb;
         size_t stride;
     } li, lo;
 };
@@ -242,6 +245,11 @@ __device__ __forceinline__ void st_stream_pair_a4(void *base, unsigned byte_off,
     w.x = lo;
     w.y = hi;
     __builtin_nontemporal_store(w, reinterpret_cast<u32x2_a4 *>(reinterpret_cast<uint8_t *>(base) + byte_off));
+}
+__device__ __forceinline__ uint2 ld_pair_a4(const void *base, unsigned byte_off)
+{
+    const u32x2_a4 w = *reinterpret_cast<const u32x2_a4 *>(reinterpret_cast<const uint8_t *>(base) + byte_off);
+    return make_uint2(w.x, w.y);
 }
 
 // |z| rows of the row IFFTs (K3 four-wide path, K34, K34o) start kZShift
@@ -487,6 +495,20 @@ template <int FMT> constexpr bool kNV12 = FMT == kFmtNV12 || FMT == kFmtNV12M;
 template <int FMT> constexpr bool kP010 = FMT == kFmtP010 || FMT == kFmtP010M;
 template <int FMT> constexpr bool k420 = kNV12<FMT> || kP010<FMT>;
 template <int FMT> constexpr bool kMatrixed = FMT == kFmtNV12M || FMT == kFmtP010M;
+// packed 4:2:2 (section below): kFmtYUY2 runs every BT.601 YUY2 / UYVY frame and
+// every compose, kFmtYUY2M is K1's instance for a matrixed one
+constexpr int kFmtYUY2 = 24;   // MM_YUY2
+constexpr int kFmtYUY2M = 56;  // MM_YUY2 | MM_MATRIX_BT709 (K1 only: any matrixed packed 4:2:2)
+template <int FMT> constexpr bool k422 = FMT == kFmtYUY2 || FMT == kFmtYUY2M;
+// an input macropixel's chroma bytes (byte order: Geo::li.yb; the shifts are uniform)
+__device__ __forceinline__ float c422_cb(unsigned u, const Geo &g) { return (float)((u >> (8u - 8u * g.li.yb)) & 255u); }
+__device__ __forceinline__ float c422_cr(unsigned u, const Geo &g) { return (float)((u >> (24u - 8u * g.li.yb)) & 255u); }
+// (I, Q) of a macropixel's chroma: exact zero for neutral chroma (128, 128)
+__device__ __forceinline__ c2 c422_iq2(unsigned u, const Geo &g)
+{
+    const float cb = c422_cb(u, g) - 128.0f, cr = c422_cr(u, g) - 128.0f;
+    return mk(g.nv.icb, g.nv.qcb) * cb + mk(g.nv.icr, g.nv.qcr) * cr;
+}
 // the raw sample K1 loads per pixel
 template <int FMT> struct LumaSrc {
     using raw_t = typename Pix<FMT>::raw_t;
@@ -512,12 +534,12 @@ template <> struct ChromaSrc<kFmtP010M> : ChromaSrc<kFmtP010> {};
 template <int FMT>
 __device__ __forceinline__ float k1_luma(typename LumaSrc<FMT>::raw_t u, const Geo &g)
 {
-    if constexpr (k420<FMT>) return (float)u - g.nv.y_off;
+    if constexpr (k420<FMT> || k422<FMT>) return (float)u - g.nv.y_off;
     else return luma_units<FMT>(u);
 }
 template <int FMT> __device__ __forceinline__ float k1_unit(const Geo &g)
 {
-    if constexpr (k420<FMT>) return g.nv.y_unit;
+    if constexpr (k420<FMT> || k422<FMT>) return g.nv.y_unit;
     else return kLumaUnit<FMT>;
 }
 // K1, matrixed frames: what a (Cb, Cr) pair adds to the luma of its 2x2
@@ -528,6 +550,7 @@ __device__ __forceinline__ float k1_chroma(typename ChromaSrc<FMT>::raw_t u, con
 {
     float cb, cr;
     if constexpr (kP010<FMT>) cb = (float)(u & 0xFFFFu) - 32768.0f, cr = (float)(u >> 16) - 32768.0f;
+    else if constexpr (k422<FMT>) cb = c422_cb(u, g) - 128.0f, cr = c422_cr(u, g) - 128.0f;
     else cb = (float)(u & 255u) - 128.0f, cr = (float)((unsigned)u >> 8) - 128.0f;
     return fmaf(g.nv.lb, cr, g.nv.la * cb);
 }
@@ -576,6 +599,7 @@ template <int FMT>
 __device__ __forceinline__ c2 src_iq2(typename ChromaSrc<FMT>::raw_t u, const Geo &g)
 {
     if constexpr (k420<FMT>) return c420_iq2<FMT>(u, g);
+    else if constexpr (k422<FMT>) return c422_iq2(u, g);
     else return chroma_iq2<FMT>(u);
 }
 // Output of one pixel from yiq_rgb's saturated RGB: the luma code and the
@@ -723,6 +747,115 @@ __device__ __forceinline__ void mono_store_quad(uint8_t *row, unsigned X, const 
     else st_stream_pair_a4(row, X * 2u, c[0] | c[1] << 16, c[2] | c[3] << 16);
 }
 
+// ---- packed 4:2:2 (MM_YUY2 / MM_UYVY) access -------------------------------
+// A frame is one plane of H rows of W / 2 four-byte macropixels, Y0 Cb Y1 Cr
+// (YUY2) or Cb Y0 Cr Y1 (UYVY): two pixels that share one (Cb, Cr) pair; W and
+// H even.  It IS the RGBA32F frame its decode gives (include/mm.h), with NV12's
+// codes and ranges and the matrix bits' matrices, so every statement of the
+// NV12 section holds with "its 1 x 2 pixels" for "its 2 x 2 pixels".  Both byte
+// orders, both ranges and all three matrices share the instances: the byte
+// order travels in Geo::li.yb / lo.yb (Y0's byte; Cb's is the other one, Y1
+// and Cr lie 16 bits above), the ranges and matrices in Geo::nv where the
+// 4:2:0 formats keep them.
+//   K1, BT.601 (FMT = kFmtYUY2): the luma of the decoded pixel is its Y byte,
+//     at a byte stride of 2.  A lane loads the aligned 16-bit (Y, C) pair of
+//     its pixel, so that a wave's loads are contiguous like a P010 luma
+//     row's (the Y bytes alone, as byte loads at stride 2, ran K1 at 5.3-5.5
+//     us per 1080p frame against 4.3 for the matrixed instance's dwords), and
+//     keeps the Y byte by a uniform shift; the chroma byte is never used.
+//     k1_luma's expression and the packed V2 expressions are the kFmtNV12
+//     instance's: the state is bitwise an NV12 frame's with the same luma
+//     samples.
+//   K1, matrixed (FMT = kFmtYUY2M): one aligned dword per pixel and source row
+//     is the pixel's macropixel: Y by the column's parity, Cb and Cr through
+//     k1_chroma's one expression (neutral chroma adds exactly 0).  No second
+//     plane, no k1_crow.
+//   compose (FMT = kFmtYUY2, all three forms): source columns X-1 .. X+4 of
+//     the quad X .. X+3 are macropixels X/2-1 .. X/2+2, the outer two wrapped
+//     or clamped on PIXEL coordinates and then halved (dword loads), the
+//     quad's own two one 8-byte load.  Every output row has its own source
+//     rows: the RGBA formats' row schedule.  A chroma code is the scaled sum
+//     (left pixel's difference + right pixel's difference), formed that way in
+//     every kernel, so the fused and unfused outputs stay bitwise equal; a row
+//     of the quad leaves as two whole macropixels in one 8-byte store, the
+//     unfused k_compose's even lanes store one macropixel each (the lane pair
+//     exchanges one chroma difference and one 16-bit half).  No thread
+//     writes part of a macropixel.
+// Alignment: frame base, pitch and stride are multiples of 4 (mm_surface's
+// unit, one macropixel), so every dword access is aligned in every legal
+// layout and the 8-byte quads are multi-dword accesses at dword-aligned
+// addresses (ld_pair_a4 / st_stream_pair_a4): no layout rule of its own for
+// the fused kernels.  No GEN, k_compose_odd or k_dbg_out instance: odd sizes
+// and the debug views are refused on the host.
+template <> struct LumaSrc<kFmtYUY2> {     // the pixel's (Y, C) byte pair
+    using raw_t = uint16_t;
+    static constexpr int bpp = 2;
+};
+template <> struct LumaSrc<kFmtYUY2M> {    // the pixel's whole macropixel
+    using raw_t = uint32_t;
+    static constexpr int bpp = 2;
+};
+template <> struct ChromaSrc<kFmtYUY2> { using raw_t = uint32_t; };    // the macropixel
+template <> struct ChromaSrc<kFmtYUY2M> { using raw_t = uint32_t; };
+// K1: byte offset of pixel column col's sample in its source row
+template <int FMT> __device__ __forceinline__ unsigned k1_off(unsigned col)
+{
+    if constexpr (FMT == kFmtYUY2M) return (col & ~1u) * 2u;
+    else return col * (unsigned)LumaSrc<FMT>::bpp;
+}
+// K1: the luma of column col's loaded sample (in k1_luma's units).  One
+// expression for the three load forms.
+template <int FMT>
+__device__ __forceinline__ float k1_luma_at(typename LumaSrc<FMT>::raw_t u, [[maybe_unused]] unsigned col, const Geo &g)
+{
+    if constexpr (FMT == kFmtYUY2M) {
+        const unsigned yc = (u >> (8u * g.li.yb + ((col & 1u) << 4))) & 255u;
+        return k1_luma<FMT>(yc, g) + k1_chroma<FMT>(u, g);
+    } else if constexpr (FMT == kFmtYUY2) {
+        return k1_luma<FMT>((uint16_t)(((unsigned)u >> (8u * g.li.yb)) & 255u), g);
+    } else {
+        return k1_luma<FMT>(u, g);
+    }
+}
+// byte offset of the macropixel of source pixel (row, col), both already
+// wrapped or clamped on PIXEL coordinates (then halved)
+__device__ __forceinline__ unsigned c422_off(const Geo &g, int row, unsigned col)
+{
+    return (unsigned)row * g.li.pitch + (col >> 1) * 4u;
+}
+// One output macropixel: its two luma codes and the sum of its two pixels'
+// chroma differences (nv12_ycode's; cbo, cro hold the mean's 1/2)
+__device__ __forceinline__ unsigned c422_pack(unsigned y0, unsigned y1, c2 sum2, const Geo &g)
+{
+    const unsigned c = nv12_ccode(sum2.x, g.nv.cbo) | nv12_ccode(sum2.y, g.nv.cro) << 16;
+    return (y0 | y1 << 16) << (8u * g.lo.yb) | c << (8u - 8u * g.lo.yb);
+}
+// The fused kernels' store of output row i of the quad X .. X+3 (X % 4 == 0):
+// two macropixels as one 8-byte store at a dword-aligned address
+__device__ __forceinline__ void c422_store_quad(uint8_t *outp, const Geo &g, int i, int X, const float (&rr)[4],
+                                                const float (&gg)[4], const float (&bb)[4])
+{
+    c2 cd[4];
+    unsigned y[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = nv12_ycode(rr[k], gg[k], bb[k], g, cd[k]);
+    st_stream_pair_a4(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 2u,
+                      c422_pack(y[0], y[1], cd[0] + cd[1], g), c422_pack(y[2], y[3], cd[2] + cd[3], g));
+}
+// The fused kernels' (I, Q) of source columns X-1 .. X+4 (cl, cr: the outer two,
+// wrapped or clamped) of source row `row`
+__device__ __forceinline__ void c422_quad_iq(const uint8_t *img, const Geo &g, int row, unsigned X, unsigned cl,
+                                             unsigned cr, c2 (&a)[6])
+{
+    const unsigned pl = ld_off<uint32_t>(img, c422_off(g, row, cl));
+    const uint2 pm = ld_pair_a4(img, c422_off(g, row, X));
+    const unsigned pr = ld_off<uint32_t>(img, c422_off(g, row, cr));
+    a[0] = c422_iq2(pl, g);
+    a[1] = a[2] = c422_iq2(pm.x, g);
+    a[3] = a[4] = c422_iq2(pm.y, g);
+    a[5] = c422_iq2(pr, g);
+}
+
 // =========================================================================
 // K1: luma rows -> half spectra of row pairs
 // =========================================================================
@@ -841,7 +974,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
 #pragma unroll
                 for (int u = 0; u < CB; ++u) {
                     const unsigned col = (unsigned)min((int)threadIdx.x + (h * CB + u) * 2 * T, g.W - 1);
-                    const unsigned off = col * BPP;
+                    const unsigned off = k1_off<FMT>(col);
 #pragma unroll
                     for (int d = 0; d < 6; ++d) px[u][d] = ld_off<raw_t>(rowp[d], off);
                     if constexpr (kMatrixed<FMT>) {
@@ -855,7 +988,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
                     const int i = (int)threadIdx.x + (h * CB + u) * 2 * T;
                     float l[6];
 #pragma unroll
-                    for (int d = 0; d < 6; ++d) l[d] = k1_luma<FMT>(px[u][d], g);
+                    for (int d = 0; d < 6; ++d) l[d] = k1_luma_at<FMT>(px[u][d], (unsigned)min(i, g.W - 1), g);
                     if constexpr (kMatrixed<FMT>) {
 #pragma unroll
                         for (int d = 0; d < 6; ++d) l[d] += k1_chroma<FMT>(cx[u][(d + 1) >> 1], g);
@@ -897,7 +1030,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
                 const unsigned col = (unsigned)min(t + (h * UB + u) * T, g.W - 1);
-                const unsigned off = col * BPP;
+                const unsigned off = k1_off<FMT>(col);
 #pragma unroll
                 for (int d = 0; d < 4; ++d) px[u][d] = ld_off<raw_t>(rowp[d], off);
                 if constexpr (kMatrixed<FMT>) {
@@ -911,7 +1044,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
                 const int i = t + (h * UB + u) * T;
                 float l[4];
 #pragma unroll
-                for (int d = 0; d < 4; ++d) l[d] = k1_luma<FMT>(px[u][d], g);
+                for (int d = 0; d < 4; ++d) l[d] = k1_luma_at<FMT>(px[u][d], (unsigned)min(i, g.W - 1), g);
                 if constexpr (kMatrixed<FMT>) {
 #pragma unroll
                     for (int d = 0; d < 4; ++d) l[d] += k1_chroma<FMT>(cx[u][(d + 1) >> 1], g);
@@ -2289,6 +2422,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     // (NV12: the pixel's (Cb, Cr) pair, shared with its 2x2 neighbours)
     auto src_off = [&](int row, unsigned col) {
         if constexpr (k420<FMT>) return c420_off<FMT>(g, row, col);
+        else if constexpr (k422<FMT>) return c422_off(g, row, col);
         else return (unsigned)row * g.li.pitch + col * Pix<FMT>::bpp;
     };
     const unsigned colA = (unsigned)wrap_near(min(c0 - 1 + tid, g.W), g.W, g.edge);
@@ -2377,6 +2511,25 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                         st_off<uint8_t>(outp, g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch + (unsigned)X, (uint8_t)cc8);
                     }
                 }
+            } else if constexpr (k422<FMT>) {
+                // The lane pair (X ^ 1 is tid ^ 1: c0 and W are even, as above)
+                // is one macropixel.  As for NV12, each lane keeps the chroma
+                // component it encodes (even: Cb, odd: Cr) and sends the other
+                // one (a quad-perm DPP move): left + right either way.  Its
+                // luma and chroma codes are one 16-bit half of the macropixel;
+                // the odd lane's half goes to the even lane (a second move),
+                // which stores the whole dword.  The odd lane stores nothing.
+                static_assert(TC % 2 == 0, "packed 4:2:2: tiles of whole macropixels");
+                c2 cd;
+                const unsigned yc = nv12_ycode(rr, gg, bb, g, cd);
+                const float mine = X & 1 ? cd.y : cd.x, send = X & 1 ? cd.x : cd.y;
+                const float theirs = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
+                    __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
+                const unsigned cc = nv12_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
+                const unsigned half = yc << (8u * g.lo.yb) | cc << (8u - 8u * g.lo.yb);
+                const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)half, 0xB1, 0xF, 0xF, true);
+                if (!(X & 1))
+                    st_stream<uint32_t>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 2u, half | other << 16);
             } else {
                 Pix<FMT>::store(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
             }
@@ -2489,7 +2642,10 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
         if constexpr (!kMono<FMT>) {   // (a gray frame's (I, Q) is zero: nothing to read)
             const int row = wrap_near(min(i, g.H), g.H, g.edge);
             c2 a[6];
-            if constexpr (k420<FMT>) {
+            if constexpr (k422<FMT>) {
+                // macropixels X/2-1 .. X/2+2: the quad's own two as one 8-byte load
+                c422_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
+            } else if constexpr (k420<FMT>) {
                 // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
                 // outer two wrapped or clamped as pixels, then halved): the quad's
                 // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
@@ -2643,7 +2799,9 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                     }
                     // (in pixels: an RGBA pitch is a multiple of the pixel size)
                     [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
-                    if constexpr (k420<FMT>) {
+                    if constexpr (k422<FMT>) {
+                        c422_store_quad(outp, g, i, X, rr, gg, bb);
+                    } else if constexpr (k420<FMT>) {
                         c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
                     } else if constexpr (bpp == 4) {
                         uint4 px;
@@ -2763,7 +2921,10 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
         if constexpr (!kMono<FMT>) {   // (a gray frame's (I, Q) is zero: nothing to read)
             const int row = wrap_near(min(i, g.H), g.H, g.edge);
             c2 a[6];
-            if constexpr (k420<FMT>) {
+            if constexpr (k422<FMT>) {
+                // macropixels X/2-1 .. X/2+2: the quad's own two as one 8-byte load
+                c422_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
+            } else if constexpr (k420<FMT>) {
                 // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
                 // outer two wrapped or clamped as pixels, then halved): the quad's
                 // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
@@ -2852,7 +3013,9 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                 yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
             }
             [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
-            if constexpr (k420<FMT>) {
+            if constexpr (k422<FMT>) {
+                c422_store_quad(outp, g, i, X, rr, gg, bb);
+            } else if constexpr (k420<FMT>) {
                 c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
             } else if constexpr (bpp == 4) {
                 uint4 px;
@@ -3031,7 +3194,7 @@ void k_dbg_out(const float *__restrict__ tex, size_t tex_stride, uint8_t *__rest
 // =========================================================================
 // One workgroup per (plane row, frame): the row's samples and nothing else, in
 // words of U (NV12 and the 16-bit single-plane formats: 2 bytes, their unit;
-// MM_Y8: 1; every other format: 4, which divides its unit).  `rows_y` RGBA / luma rows, then the (Cb, Cr) rows of a 4:2:0
+// MM_Y8: 1; every other format: 4, which divides its unit; packed 4:2:2: 4, one macropixel).  `rows_y` RGBA / luma rows, then the (Cb, Cr) rows of a 4:2:0
 // frame.  Tight frames on both sides are one plain device copy instead.
 template <class U>
 __global__ __launch_bounds__(256)

@@ -9,6 +9,7 @@
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
  *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
+ *          [--yuy2] [--uyvy]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
@@ -52,11 +53,11 @@
  * what --nv12 is refused with, and with --nv12.  Bit depths are never
  * converted silently: an 8-bit input with --p010 and a 10-bit input without it
  * are refused.
- * --matrix 601|709|2020 (default 601): the Y'CbCr matrix of an --nv12 or
- * --p010 clip (HD content is BT.709, UHD BT.709 or BT.2020), OR-ed onto the
+ * --matrix 601|709|2020 (default 601): the Y'CbCr matrix of an --nv12,
+ * --p010, --yuy2 or --uyvy clip (HD content is BT.709, UHD BT.709 or BT.2020), OR-ed onto the
  * frame format as MM_MATRIX_BT709 / MM_MATRIX_BT2020.  A .y4m header has no
- * matrix tag, so files are the same whatever the value.  Only with --nv12 or
- * --p010: the host's own RGBA conversion of a .y4m is BT.601.
+ * matrix tag, so files are the same whatever the value.  Only with --nv12,
+ * --p010, --yuy2 or --uyvy: the host's own RGBA conversion of a .y4m is BT.601.
  * --mono: a mono .y4m input (Cmono, Cmono10, Cmono12, Cmono16: a grayscale
  * camera's or ffmpeg's gray / gray10le / gray12le / gray16le frames) goes to
  * the device as it is stored, as MM_Y8 / MM_Y10 / MM_Y12 / MM_Y16 frames by the
@@ -66,10 +67,19 @@
  * with a chroma-carrying input, with --nv12, --p010, --srgb, --matrix and
  * --full-range (there is no matrix and no range) and with the ring modes.
  * Without --mono a Cmono input is expanded to RGBA8 on the host, as before.
+ * --yuy2 / --uyvy: an 8-bit 4:2:2 .y4m input (C422: a capture device's frames,
+ * ffmpeg's yuv422p) goes to the device as packed macropixels, Y0 Cb Y1 Cr as
+ * MM_YUY2 or Cb Y0 Cr Y1 as MM_UYVY (_FULL with --full-range, a matrix bit
+ * with --matrix): the planes are interleaved on the way in and split on the
+ * way out (a C422 .y4m, the same file for both flags; any other extension: the
+ * raw packed frames), and no colour arithmetic runs on the host.  Refused
+ * with --srgb, the debug views, the ring modes, --nv12, --p010, --mono, each
+ * other, any other input and odd sizes.  A C422 input needs one of the two
+ * flags: the host has no 4:2:2 to RGBA conversion.
  * --surface-align P,R: the device frames, input and output, are held in
  * mm_surface_aligned(W, H, format, P, R) surfaces (256,16: a hardware
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
- * format, --nv12 and --p010 included.  Files and checksums are those of the
+ * format, --nv12, --p010, --yuy2 and --uyvy included.  Files and checksums are those of the
  * run without the flag, byte for byte.  Not with the ring modes.
  */
 #include <hip/hip_runtime_api.h>
@@ -440,7 +450,7 @@ int main(int argc, char **argv)
     int W = 1920, H = 1080, F = 300, L = 5, B = 30, dev = 0;
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
-    int nv12 = 0, p010 = 0, srgb = 0, mono = 0;
+    int nv12 = 0, p010 = 0, srgb = 0, mono = 0, yuy2 = 0, uyvy = 0;
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
@@ -452,6 +462,8 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--nv12")) { nv12 = 1; continue; }
         if (!strcmp(a, "--p010")) { p010 = 1; continue; }
         if (!strcmp(a, "--mono")) { mono = 1; continue; }
+        if (!strcmp(a, "--yuy2")) { yuy2 = 1; continue; }
+        if (!strcmp(a, "--uyvy")) { uyvy = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
         if (!strcmp(a, "--show-magnitude")) { show_mag = 1; continue; }
         if (!strcmp(a, "--show-phase")) { show_phase = 1; continue; }
@@ -494,6 +506,32 @@ int main(int argc, char **argv)
         if (y4m_read_header_depth(fi, &yi, &depth)) { fprintf(stderr, "%s: unsupported Y4M\n", in_path); return 1; }
         W = yi.width;
         H = yi.height;
+    }
+    const int p422 = yuy2 || uyvy;   /* packed 4:2:2 */
+    if (p422) {
+        const char *opt = yuy2 ? "--yuy2" : "--uyvy";
+        if (yuy2 && uyvy) {
+            fprintf(stderr, "--yuy2 does not go with --uyvy (one byte order)\n");
+            return 2;
+        }
+        if (srgb || show_mag || show_phase || ring_local > 0 || ring_world > 0 || nv12 || p010 || mono) {
+            fprintf(stderr, "%s does not go with --srgb, the debug views, the ring modes, --nv12, --p010 or --mono\n",
+                    opt);
+            return 2;
+        }
+        if (!y4m_in || yi.chroma != Y4M_422) {
+            fprintf(stderr, "%s needs an 8-bit 4:2:2 .y4m input (-i, C422)\n", opt);
+            return 2;
+        }
+        if ((W | H) & 1) {
+            fprintf(stderr, "%s needs even width and height (%dx%d)\n", opt, W, H);
+            return 2;
+        }
+        g_fmt = uyvy ? (full_range ? MM_UYVY_FULL : MM_UYVY) : (full_range ? MM_YUY2_FULL : MM_YUY2);
+    } else if (y4m_in && yi.chroma == Y4M_422) {
+        fprintf(stderr, "%s is a 4:2:2 stream (C422): it needs --yuy2 or --uyvy "
+                        "(there is no 4:2:2 to RGBA conversion on the host)\n", in_path);
+        return 2;
     }
     if (mono) {
         if (nv12 || p010 || srgb || matrix_arg || full_range) {
@@ -556,8 +594,8 @@ int main(int argc, char **argv)
         g_fmt = full_range ? MM_NV12_FULL : MM_NV12;
     }
     if (matrix_arg) {
-        if (!nv12 && !p010) {
-            fprintf(stderr, "--matrix needs --nv12 or --p010 (the RGBA conversion of a .y4m is BT.601)\n");
+        if (!nv12 && !p010 && !p422) {
+            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2 or --uyvy (the RGBA conversion of a .y4m is BT.601)\n");
             return 2;
         }
         if (!strcmp(matrix_arg, "709")) g_fmt |= MM_MATRIX_BT709;
@@ -611,7 +649,7 @@ int main(int argc, char **argv)
     }
 
     size_t fb = (size_t)W * H * 4;
-    if (nv12 || p010 || mono) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
+    if (nv12 || p010 || mono || p422) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
     /* --surface-align: the frames the operator sees live in `lay` surfaces
      * (d_in, d_out); d_tin / d_tout are tight device frames for the synthetic
      * source and for the checksums and files */
@@ -624,7 +662,7 @@ int main(int argc, char **argv)
         if (sscanf(surf_arg, "%llu,%d", &pa, &ra) != 2 ||
             (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK) {
             fprintf(stderr, "--surface-align %s: want P,R with P a multiple of the format's unit "
-                            "(pixel size; NV12 2, P010 4, mono: the sample size) and R >= 1 (4:2:0: even)\n", surf_arg);
+                            "(pixel size; NV12 2, P010 and 4:2:2 4, mono: the sample size) and R >= 1 (4:2:0: even)\n", surf_arg);
             return 2;
         }
         printf("surfaces: pitch %zu  chroma offset %zu  frame stride %zu\n", lay.pitch, lay.chroma_offset,
@@ -647,6 +685,7 @@ int main(int argc, char **argv)
     if (y4m_out && (mono   ? y4m_write_header_mono(fo, W, H, yi.fps_num, yi.fps_den, depth)
                     : p010 ? y4m_write_header_420p10(fo, W, H, yi.fps_num, yi.fps_den)
                     : nv12 ? y4m_write_header_420(fo, W, H, yi.fps_num, yi.fps_den)
+                    : p422 ? y4m_write_header_422(fo, W, H, yi.fps_num, yi.fps_den)
                            : y4m_write_header(fo, W, H, yi.fps_num, yi.fps_den))) {
         fprintf(stderr, "write failed\n");
         return 1;
@@ -670,6 +709,7 @@ int main(int argc, char **argv)
                 if (mono) continue;
                 if (p010) y4m_420p10_to_p010(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
                 else if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
+                else if (p422) y4m_422_to_packed(W, H, planes, host + fb * got, uyvy);
                 else y4m_to_rgba(&yi, planes, host + fb * got, full_range);
             }
             if (got == 0) break;
@@ -713,9 +753,11 @@ int main(int argc, char **argv)
                     }
                     if (p010) y4m_p010_to_420p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
                     else if (nv12) y4m_nv12_to_420(W, H, host + fb * k, planes);
+                    else if (p422) y4m_packed_to_422(W, H, host + fb * k, planes, uyvy);
                     else y4m_from_rgba(W, H, host + fb * k, planes, full_range);
                     if (p010   ? y4m_write_frame_420p10(fo, W, H, (const uint16_t *)planes)
                         : nv12 ? y4m_write_frame_420(fo, W, H, planes)
+                        : p422 ? y4m_write_frame_422(fo, W, H, planes)
                                : y4m_write_frame(fo, W, H, planes)) {
                         fprintf(stderr, "write failed\n");
                         return 1;

@@ -56,7 +56,8 @@ static int read_header(FILE *f, y4m_info *info, int *depth)
                 info->chroma = Y4M_MONO;
                 *depth = atoi(v + 4);
             }
-            else return -1;   /* 422, 411, high bit depth, alpha: unsupported */
+            else if (depth && !strcmp(v, "422")) info->chroma = Y4M_422;
+            else return -1;   /* 411, other high bit depths, alpha: unsupported */
             break;
         default: break;       /* X (comments) and unknown tags */
         }
@@ -80,6 +81,7 @@ size_t y4m_frame_bytes(const y4m_info *info)
     const size_t w = (size_t)info->width, h = (size_t)info->height;
     if (info->chroma == Y4M_MONO) return w * h;
     if (info->chroma == Y4M_444) return 3 * w * h;
+    if (info->chroma == Y4M_422) return w * h + 2 * ((w + 1) / 2) * h;
     const size_t cw = (w + 1) / 2, ch = (h + 1) / 2;
     return w * h + 2 * cw * ch;
 }
@@ -258,4 +260,44 @@ int y4m_write_frame_mono(FILE *f, int W, int H, int bit_depth, const void *sampl
     if (fputs("FRAME\n", f) < 0) return -1;
     const size_t nb = (size_t)W * H * (bit_depth > 8 ? 2 : 1);
     return fwrite(samples, 1, nb, f) == nb ? 0 : -1;
+}
+
+void y4m_422_to_packed(int W, int H, const uint8_t *planes422, uint8_t *out, int uyvy)
+{
+    const size_t ny = (size_t)W * H, nc = ny / 2;
+    const uint8_t *Y = planes422, *Cb = planes422 + ny, *Cr = Cb + nc;
+    const int yo = uyvy ? 1 : 0, co = uyvy ? 0 : 1;
+    for (size_t i = 0; i < nc; ++i) {   /* macropixel i: pixels 2 i, 2 i + 1 (W even: never across rows) */
+        uint8_t *m = out + 4 * i;
+        m[yo] = Y[2 * i];
+        m[yo + 2] = Y[2 * i + 1];
+        m[co] = Cb[i];
+        m[co + 2] = Cr[i];
+    }
+}
+
+void y4m_packed_to_422(int W, int H, const uint8_t *in, uint8_t *planes422, int uyvy)
+{
+    const size_t ny = (size_t)W * H, nc = ny / 2;
+    uint8_t *Y = planes422, *Cb = planes422 + ny, *Cr = Cb + nc;
+    const int yo = uyvy ? 1 : 0, co = uyvy ? 0 : 1;
+    for (size_t i = 0; i < nc; ++i) {
+        const uint8_t *m = in + 4 * i;
+        Y[2 * i] = m[yo];
+        Y[2 * i + 1] = m[yo + 2];
+        Cb[i] = m[co];
+        Cr[i] = m[co + 2];
+    }
+}
+
+int y4m_write_header_422(FILE *f, int W, int H, int fps_num, int fps_den)
+{
+    return fprintf(f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C422\n", W, H, fps_num, fps_den) > 0 ? 0 : -1;
+}
+
+int y4m_write_frame_422(FILE *f, int W, int H, const uint8_t *planes422)
+{
+    if (fputs("FRAME\n", f) < 0) return -1;
+    const size_t nb = (size_t)W * H * 2;
+    return fwrite(planes422, 1, nb, f) == nb ? 0 : -1;
 }

@@ -9,8 +9,9 @@
  * Host-side only: the frames then go through mm_process_stream as RGBA8, or,
  * 4:2:0 streams re-interleaved to NV12, as MM_NV12 without any conversion;
  * 10-bit 4:2:0 (C420p10) streams likewise as MM_P010, and mono streams of 8, 10,
- * 12 or 16 bits (Cmono, Cmono10, Cmono12, Cmono16) as MM_Y8 .. MM_Y16 (the
- * last two sections).
+ * 12 or 16 bits (Cmono, Cmono10, Cmono12, Cmono16) as MM_Y8 .. MM_Y16, and
+ * 8-bit 4:2:2 (C422) streams interleaved to YUY2 / UYVY as MM_YUY2 / MM_UYVY
+ * (the last three sections).  There is no 4:2:2 to RGBA conversion.
  */
 #ifndef MM355_Y4M_H
 #define MM355_Y4M_H
@@ -22,13 +23,13 @@
 extern "C" {
 #endif
 
-enum { Y4M_420 = 0, Y4M_444 = 1, Y4M_MONO = 2 };
+enum { Y4M_420 = 0, Y4M_444 = 1, Y4M_MONO = 2, Y4M_422 = 3 };   /* Y4M_422: y4m_read_header_depth only */
 
 typedef struct {
     int width, height;
     int fps_num, fps_den;   /* F tag (default 25:1) */
     int aspect_num, aspect_den;
-    int chroma;             /* Y4M_420 | Y4M_444 | Y4M_MONO */
+    int chroma;             /* Y4M_420 | Y4M_444 | Y4M_MONO | Y4M_422 */
     char interlace;         /* I tag, 'p' if absent */
 } y4m_info;
 
@@ -70,9 +71,10 @@ int y4m_write_frame_420(FILE *f, int width, int height, const uint8_t *planes420
  * y4m_read_header keeps refusing the tag; these entry points stand beside it
  * and y4m_info keeps its layout (the depth travels separately). */
 
-/* y4m_read_header that also accepts C420p10 and Cmono10 / Cmono12 / Cmono16:
- * *bit_depth is 10 for C420p10 (chroma Y4M_420), 10, 12 or 16 for the mono
- * tags (chroma Y4M_MONO), 8 for every tag y4m_read_header accepts. */
+/* y4m_read_header that also accepts C420p10, Cmono10 / Cmono12 / Cmono16 and
+ * C422: *bit_depth is 10 for C420p10 (chroma Y4M_420), 10, 12 or 16 for the
+ * mono tags (chroma Y4M_MONO), 8 for C422 (chroma Y4M_422) and for every tag
+ * y4m_read_header accepts. */
 int y4m_read_header_depth(FILE *f, y4m_info *info, int *bit_depth);
 
 /* Bytes of one frame's planes at `bit_depth` (2 bytes per sample above 8), and
@@ -102,6 +104,24 @@ int y4m_write_header_mono(FILE *f, int width, int height, int fps_num, int fps_d
 /* as y4m_read_frame: 1 on a frame, 0 at end of stream, -1 on a malformed one */
 int y4m_read_frame_mono(FILE *f, int width, int height, int bit_depth, void *samples);
 int y4m_write_frame_mono(FILE *f, int width, int height, int bit_depth, const void *samples);
+
+/* ---- 8-bit 4:2:2 (C422), for the MM_YUY2 / MM_UYVY path ---------------------
+ * Planes Y (width x height), Cb, Cr (width / 2 x height each); even width and
+ * height.  y4m_read_header_depth reads the header (chroma Y4M_422, depth 8),
+ * y4m_frame_bytes and y4m_read_frame take such an info; y4m_to_rgba does not
+ * (there is no 4:2:2 to RGBA conversion on the host). */
+
+/* 4:2:2 planes <-> one packed frame of width / 2 four-byte macropixels per
+ * row (2 * width * height bytes either way): bytes Y0 Cb Y1 Cr (YUY2), or
+ * Cb Y0 Cr Y1 with `uyvy` non-zero.  Interleave / de-interleave only, no
+ * arithmetic.  Frames in this layout go through mm_process_stream as MM_YUY2 /
+ * MM_UYVY (or their _FULL and matrixed forms). */
+void y4m_422_to_packed(int width, int height, const uint8_t *planes422, uint8_t *out, int uyvy);
+void y4m_packed_to_422(int width, int height, const uint8_t *in, uint8_t *planes422, int uyvy);
+
+/* Write a C422 header / one C422 frame (planes Y, Cb, Cr). */
+int y4m_write_header_422(FILE *f, int width, int height, int fps_num, int fps_den);
+int y4m_write_frame_422(FILE *f, int width, int height, const uint8_t *planes422);
 
 #ifdef __cplusplus
 }

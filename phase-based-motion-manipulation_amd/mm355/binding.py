@@ -23,7 +23,15 @@ Y12 = 10            # v = word / 4095
 Y16 = 11            # v = word / 65535
 MONO_FORMATS = (Y8, Y10, Y12, Y16)
 MONO_BITS = {Y8: 8, Y10: 10, Y12: 12, Y16: 16}
-FORMAT_BPP = {RGBA8: 4, RGBA32F: 16, RGBA16F: 8, RGBA8_SRGB: 4, Y8: 1, Y10: 2, Y12: 2, Y16: 2}
+# packed 8-bit Y'CbCr 4:2:2 capture frames, one plane: H rows of W/2 four-byte
+# macropixels (W and H even); a matrix bit may be OR-ed on as on the 4:2:0 codes
+YUY2 = 24           # bytes Y0 Cb Y1 Cr, BT.601 limited range
+YUY2_FULL = 25      # full range
+UYVY = 26           # bytes Cb Y0 Cr Y1, BT.601 limited range
+UYVY_FULL = 27      # full range
+PACKED422_FORMATS = (YUY2, YUY2_FULL, UYVY, UYVY_FULL)
+FORMAT_BPP = {RGBA8: 4, RGBA32F: 16, RGBA16F: 8, RGBA8_SRGB: 4, Y8: 1, Y10: 2, Y12: 2, Y16: 2,
+              YUY2: 2, YUY2_FULL: 2, UYVY: 2, UYVY_FULL: 2}
 # video frames, planar 8-bit Y'CbCr 4:2:0 (H rows of W luma bytes, then H/2 rows
 # of W interleaved Cb, Cr bytes; W and H even): frame_bytes() gives W*H*3/2
 NV12 = 16           # BT.601 limited ("video") range
@@ -32,7 +40,7 @@ NV12_FULL = 17      # full ("JPEG") range
 # << 6; a P016 surface's low bits are honoured): frame_bytes() gives W*H*3
 P010 = 18           # BT.601 matrix, limited range (Y 64..940, C 64..960)
 P010_FULL = 19      # full range (0..1023)
-# one matrix bit, OR-ed onto a 4:2:0 code above (HD / UHD content): the layout
+# one matrix bit, OR-ed onto a 4:2:0 or packed 4:2:2 code above (HD / UHD content): the layout
 # and sizes stay the base code's (base_format)
 MATRIX_BT709 = 32   # Kr 0.2126, Kb 0.0722
 MATRIX_BT2020 = 64  # Kr 0.2627, Kb 0.0593, non-constant luminance

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""RGBA8 against NV12, P010 and grayscale (Y8, Y16) frames on one GPU, same process, alternating legs.
+"""RGBA8 against NV12, P010, grayscale (Y8, Y16) and packed 4:2:2 (YUY2, UYVY) frames on one GPU, same
+process, alternating legs.
 
 The flagship stream (1920x1080, 5 levels, phase scale 25, batches of 150
 frames as bench.py) in the three frame formats.  Frames are generated on the
@@ -27,6 +28,12 @@ Grayscale legs (y8, y16, and their _pitched forms): the luma of the same
 frames as MM_Y8 bytes and MM_Y16 words (code Yl max, rounded), one sample per
 pixel each way; their K34 reads no input.  A library from before the
 single-plane formats runs without them.
+
+Packed 4:2:2 legs (yuy2, uyvy, yuy2_bt709, and their _pitched forms): the same
+frames as MM_YUY2 macropixels (BT.601 limited range, chroma the mean of each
+pixel pair), the same bytes pair-swapped as MM_UYVY, and the YUY2 bytes taken
+as MM_YUY2 | MM_MATRIX_BT709, whose K1 reads whole macropixels; 2 bytes per
+pixel each way.  A library from before these formats runs without them.
 
 usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--out FILE.json]
 """
@@ -62,6 +69,22 @@ def to_420(torch, rgba, ten_bit=False):
         out[k, :H] = code(yl * ys + y0)
         out[k, H:, 0::2] = code(cb * cs + c0)
         out[k, H:, 1::2] = code(cr * cs + c0)
+    return out
+
+
+def to_422(torch, rgba):
+    """[n][H][W][4] uint8 (device) -> [n][H][2 W] YUY2 (uint8): BT.601 limited
+    range, bytes Y0 Cb Y1 Cr, chroma the mean of each pixel pair."""
+    n, H, W, _ = rgba.shape
+    out = torch.empty((n, H, 2 * W), dtype=torch.uint8, device=rgba.device)
+    code = lambda v: torch.clamp(torch.floor(v + 0.5), 0, 255).to(torch.uint8)
+    for k in range(n):
+        f = rgba[k, ..., :3].float() / 255.0
+        r, g, b = f[..., 0], f[..., 1], f[..., 2]
+        yl = 0.299 * r + 0.587 * g + 0.114 * b
+        out[k, :, 0::2] = code(yl * 219.0 + 16.0)
+        out[k, :, 1::4] = code(((b - yl) * (0.5 / 0.886)).reshape(H, W // 2, 2).mean(dim=2) * 224.0 + 128.0)
+        out[k, :, 3::4] = code(((r - yl) * (0.5 / 0.701)).reshape(H, W // 2, 2).mean(dim=2) * 224.0 + 128.0)
     return out
 
 
@@ -121,6 +144,11 @@ def main():
         fmts += [("y8", mm355.Y8), ("y16", mm355.Y16)]
     except mm355.MMError:
         pass    # a build from before the single-plane formats
+    try:
+        mm355.frame_bytes(W, H, mm355.YUY2)
+        fmts += [("yuy2", mm355.YUY2), ("uyvy", mm355.UYVY), ("yuy2_bt709", mm355.YUY2 | mm355.MATRIX_BT709)]
+    except mm355.MMError:
+        pass    # a build from before the packed 4:2:2 formats
     for name, fmt in fmts:
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
@@ -128,8 +156,12 @@ def main():
             h.synth(rgba, 0, B, stream=torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
             src = rgba
-        elif name in ("nv12_bt709", "p010_bt2020"):
+        elif name in ("nv12_bt709", "p010_bt2020", "yuy2_bt709"):
             src = legs[name.split("_")[0]]["src"]
+        elif name == "yuy2":
+            src = to_422(torch, rgba)
+        elif name == "uyvy":       # the same picture: every byte pair swapped
+            src = legs["yuy2"]["src"].reshape(B, H, W, 2).flip(3).reshape(B, H, 2 * W).contiguous()
         elif name in ("y8", "y16"):
             src = to_mono(torch, rgba, 8 if name == "y8" else 16)
         else:
@@ -140,7 +172,7 @@ def main():
             lay = mm355.Surface.aligned(W, H, fmt, 256, 16)
             h = mm355.Handle(W, H, p)
             h.set_batch(B)
-            buf = to_surface(torch, src, lay, W, H, name not in ("rgba8", "y8", "y16"))
+            buf = to_surface(torch, src, lay, W, H, name.startswith(("nv12", "p010")))
             legs[name + "_pitched"] = dict(h=h, fmt=fmt, src=buf, dst=torch.zeros_like(buf), fps=[], lay=lay,
                                            bytes_per_frame=lay.frame_stride)
     st = torch.cuda.Stream()
@@ -203,7 +235,16 @@ def main():
             out[name + "_over_nv12"] = round(out["formats"][name]["fps_median"] /
                                              out["formats"]["nv12"]["fps_median"], 4)
             out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
-    for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16"):
+    for name in ("yuy2", "uyvy", "yuy2_bt709"):
+        if name in out["formats"]:
+            out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
+            out[name + "_over_nv12"] = round(out["formats"][name]["fps_median"] /
+                                             out["formats"]["nv12"]["fps_median"], 4)
+    if "yuy2_bt709" in out["formats"]:
+        k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
+        out["yuy2_bt709_k1_us"] = {"matrixed": k1("yuy2_bt709"), "yuy2": k1("yuy2"), "nv12_bt709": k1("nv12_bt709"),
+                                   "rgba8": k1("rgba8")}
+    for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16", "yuy2", "uyvy", "yuy2_bt709"):
         if name + "_pitched" in out["formats"]:
             out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
                                                       out["formats"][name]["fps_median"], 4)
