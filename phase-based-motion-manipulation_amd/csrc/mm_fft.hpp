@@ -233,14 +233,24 @@ __host__ __device__ constexpr int xpad(int i) { return i + xpad_a(LOG2N, NS) * (
 // spans several waves); true -> the group lies within one wave, whose LDS
 // operations execute in program order, so only the compiler's ordering of
 // the writes before the reads is needed (wave_barrier: no s_barrier).
-template <bool WSYNC>
+// kSyncLds -> a workgroup barrier that orders LDS accesses only: the wave's
+// own LDS operations retired (lgkmcnt), then a bare s_barrier.  For an
+// exchange that runs while an LDS-DMA of the caller's is in flight:
+// __syncthreads()'s fence would wait for that copy too (it is a pending LDS
+// write on the vector-memory counter).  The caller orders the copy itself.
+constexpr int kSyncLds = 2;
+template <int WSYNC>
 __device__ __forceinline__ void xsync()
 {
-    if constexpr (WSYNC) __builtin_amdgcn_wave_barrier();
+    if constexpr (WSYNC == kSyncLds) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    } else if constexpr (WSYNC) __builtin_amdgcn_wave_barrier();
     else __syncthreads();
 }
 
-template <int LOG2N, int P, int DIR, bool WSYNC = false>
+template <int LOG2N, int P, int DIR, int WSYNC = 0>
 __device__ __forceinline__ void fft_pass(c2 (&v)[8], int t, c2 *lds, const c2 (&wb)[kTwSlots])
 {
     constexpr int N = 1 << LOG2N, T = N / 8, R = pass_radix<LOG2N, P>(), B = 8 / R;
@@ -280,7 +290,7 @@ __device__ __forceinline__ void fft_pass(c2 (&v)[8], int t, c2 *lds, const c2 (&
     }
 }
 
-template <int LOG2N, int DIR, int P, bool WSYNC = false>
+template <int LOG2N, int DIR, int P, int WSYNC = 0>
 __device__ __forceinline__ void fft_pass_loop(c2 (&v)[8], int t, c2 *lds, const c2 (&wb)[kTwSlots])
 {
     if constexpr (P < fft_passes<LOG2N>()) {

@@ -698,12 +698,26 @@ template <int LOG2N> static size_t lds_fft_bytes()
 {
     return sizeof(c2) * (size_t)groups_per_wg<LOG2N>() * lds_complex<(1 << LOG2N)>();
 }
+// k_rows_inv_compose's dynamic LDS: two FFT regions, and in front of them the
+// four staged source rows of the SRCDMA instances (the launch and set_attrs)
+template <int LOG2N> static size_t k34_lds_bytes(bool srcdma)
+{
+    return sizeof(c2) * 2 * lds_complex<(1 << LOG2N)>() + (srcdma ? (size_t)k34_src_bytes<LOG2N>() : 0);
+}
 template <int LOG2N>
 static int set_attrs(int W)
 {
     (void)W;   // every other kernel stays within the default 64 KiB dynamic LDS
+    // k_rows_inv_compose with staged source rows: 68.9 KB at N = 2048, 137.7 KB at N = 4096
+    if constexpr (LOG2N <= 12) if (k34_lds_bytes<LOG2N>(true) > 65536) {
+        const int lds = (int)k34_lds_bytes<LOG2N>(true);
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<LOG2N, MM_RGBA8, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<LOG2N, MM_RGBA8_SRGB, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
-        const int lds = (int)(sizeof(c2) * 2 * lds_complex<4096>());
+        const int lds = (int)k34_lds_bytes<12>(false);
         for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
@@ -903,6 +917,18 @@ static bool mono_quads_aligned(const uint8_t *out, const Frames &fr, int nframes
     if (nframes > 1) m |= fr.out.stride;
     return (m & 3u) == 0;
 }
+// The RGBA8 formats' source rows staged in LDS (k_rows_inv_compose<.., true>):
+// a thread's quad travels as one 16-byte LDS-DMA, taken only where every quad
+// of every source row of the launch is 16-byte aligned (X % 4 == 0: the frame
+// pointer, the pitch and, past one frame, the stride).  Any other layout keeps
+// the register loads, which need dword alignment only.  Same results.
+static bool k34_src_dma(const uint8_t *in, const Frames &fr, int nframes)
+{
+    if (fr.fmt != MM_RGBA8 && fr.fmt != MM_RGBA8_SRGB) return false;
+    uintptr_t m = reinterpret_cast<uintptr_t>(in) | fr.in.pitch;
+    if (nframes > 1) m |= fr.in.stride;
+    return (m & 15u) == 0;
+}
 static bool k34_fits(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
     if (fmt_nv12(fr.fmt) && !nv12_quads_aligned(in, out, fr, nframes)) return false;
@@ -968,12 +994,20 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
     }
     if (R >= 4 && k34_fits(h, in, out, fr, nframes)) {   // K3 + K4 fused: Yh stays on chip
         const int strips = (h->H + R - 1) / R, steps = R / 4 + 1;
-        const size_t lds = sizeof(c2) * 2 * lds_complex<(1 << LOG2N)>();
+        const bool dma = LOG2N <= 12 && k34_src_dma(in, fr, nframes);
+        const size_t lds = k34_lds_bytes<LOG2N>(dma);
         const dim3 grid((unsigned)(strips * nout)), block(2 * fft_T<LOG2N>());
         ProfScope ps(h, s, MM_K_ROWS_INV_COMPOSE, nout);
-        MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_rows_inv_compose<LOG2N, FMT_>), grid, block, lds, s, h->d_Q,
-                                              h->q_stride, in, out, frame0, strips, steps, geo_of(h, fr),
-                                              h->blur, h->d_col3, h->d_row3, h->d_tw))
+#define MM_K34_LAUNCH(F, DMA)                                                                        \
+        hipLaunchKernelGGL((k_rows_inv_compose<LOG2N, F, DMA>), grid, block, lds, s, h->d_Q,          \
+                           h->q_stride, in, out, frame0, strips, steps, geo_of(h, fr), h->blur,      \
+                           h->d_col3, h->d_row3, h->d_tw)
+        if constexpr (LOG2N <= 12) if (dma) {
+            if (fmt == MM_RGBA8) MM_K34_LAUNCH(MM_RGBA8, true);
+            else MM_K34_LAUNCH(MM_RGBA8_SRGB, true);
+        }
+        if (!dma) MM_FMT_SWITCH(fmt, MM_K34_LAUNCH(FMT_, false))
+#undef MM_K34_LAUNCH
         HIPCHK(hipGetLastError());
         return MM_OK;
     }

@@ -2607,7 +2607,24 @@ __device__ unsigned long long mm_k34_stamps[65536 * 8];
 #else
 #define K34_STAMP(i) do { } while (0)
 #endif
-template <int LOG2N, int FMT>
+// SRCDMA (4-byte pixels, every source row of the launch on a multiple of 16
+// bytes: launch_k3): the compose's four new source rows per step do not go
+// through registers.  Each thread copies its quad of each row to LDS with one
+// global_load_lds_dwordx4 (no VGPR destination), issued between pass 0 and
+// pass 1 of the step's inverse FFT, so the round trip to memory runs under the
+// rest of the transform and the blur instead of in front of the compose; the
+// compose reads its six pixels per row from the staged rows.  Four rows of
+// 2T x 16 = 4 N bytes IN FRONT of the FFT regions (thread q's piece at 16 q:
+// wave base + lane x 16, the only destination form an LDS-DMA has).  A staged
+// row is the pixel row itself (pixel x at 4 x: the clamped quads of threads
+// past W land behind it), so the neighbour pixels cl / cr, whichever wave
+// copied them, are plain indexed reads.  Order: the DMA follows the two
+// barriers of pass 0, which every wave reaches only after its previous compose
+// (the last reader of the rows); each wave waits for its own copies before the
+// barrier that ends the blur, and the compose reads after that barrier.
+template <int FMT> constexpr bool k34_dma_fmt = FMT == MM_RGBA8 || FMT == MM_RGBA8_SRGB;
+template <int LOG2N> constexpr int k34_src_bytes() { return 4 * 4 * (1 << LOG2N); }
+template <int LOG2N, int FMT, bool SRCDMA = false>
 __global__ __launch_bounds__(2 * fft_T<LOG2N>()) __attribute__((amdgpu_waves_per_eu(4)))
 void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         const uint8_t *__restrict__ frames_in, uint8_t *__restrict__ frames_out,
@@ -2618,7 +2635,10 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     constexpr int N = 1 << LOG2N, T = fft_T<LOG2N>(), TK = q_tile<LOG2N>();
     using raw_t = typename ChromaSrc<FMT>::raw_t;
     constexpr unsigned bpp = LumaSrc<FMT>::bpp;   // (NV12: 1, the luma plane's)
-    extern __shared__ __attribute__((aligned(16))) c2 lds_all[];
+    static_assert(!SRCDMA || k34_dma_fmt<FMT>, "staged source rows: 4-byte pixels");
+    extern __shared__ __attribute__((aligned(16))) c2 lds_raw[];
+    [[maybe_unused]] const uint8_t *srcl = reinterpret_cast<const uint8_t *>(lds_raw);   // [4][4 N] staged rows
+    c2 *lds_all = lds_raw + (SRCDMA ? k34_src_bytes<LOG2N>() / (int)sizeof(c2) : 0);
     const int grp = T % 64 == 0 ? __builtin_amdgcn_readfirstlane(threadIdx.x / T) : threadIdx.x / T;
     const int t = threadIdx.x % T;
     c2 *lds = lds_all + grp * lds_complex<N>();
@@ -2682,6 +2702,39 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
             }
         }
     };
+    // SRCDMA: the step's source row r (i0+4s-3+r) to LDS, and chroma_row's
+    // RGBA branch on the staged row (the same six pixels, the same expressions)
+    [[maybe_unused]] auto stage_row = [&](int i, int r) {
+        if constexpr (SRCDMA) {
+            typedef __attribute__((address_space(1))) const void gptr_t;
+            typedef __attribute__((address_space(3))) void lptr_t;
+            // wrap_near(min(i, H), H, edge) for i >= 0 (a staged row is i0 + 1 or later)
+            const int row = i < g.H ? i : (g.edge ? g.H - 1 : 0);
+            const uint8_t *src = img + (size_t)((unsigned)row * g.li.pitch) + (unsigned)X * 4u;
+            // the wave's base (a scalar): the hardware adds lane x 16
+            const unsigned wbase = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)) * 16u;
+            const uint8_t *dst = srcl + r * (4 * N) + wbase;
+            __builtin_amdgcn_global_load_lds((gptr_t *)src, (lptr_t *)dst, 16, 0, 0);
+        }
+    };
+    [[maybe_unused]] auto chroma_row_staged = [&](int r, c2 (&hc)[4]) {
+        if constexpr (SRCDMA) {
+            const uint8_t *rowp = srcl + r * (4 * N);
+            unsigned p[6];
+            p[0] = *reinterpret_cast<const unsigned *>(rowp + cl * 4u);
+            const uint4 m = *reinterpret_cast<const uint4 *>(rowp + (unsigned)X * 4u);
+            p[1] = m.x; p[2] = m.y; p[3] = m.z; p[4] = m.w;
+            p[5] = *reinterpret_cast<const unsigned *>(rowp + cr * 4u);
+            c2 a[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float4 wc = colW3[X + k];
+                hc[k] = wc.x * a[k] + wc.y * a[k + 1] + wc.z * a[k + 2];
+            }
+        }
+    };
 
     float yw[8][4];            // list rows i0+4s-4 .. i0+4s+3 of the quad (blurred horizontally)
                                // (as column pairs for a packed vertical blur: +3 spills, not kept)
@@ -2725,7 +2778,22 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
             v[j] = valid ? mk(qq.x - qq.w, qq.y + qq.z) : mk(0.0f, 0.0f);
         }
         K34_STAMP(0);
-        fft_regs<LOG2N, +1>(v, t, lds, tw);
+        if constexpr (SRCDMA) {
+            // fft_regs, with the source rows' copies issued behind pass 0: after
+            // the Q loads in program order (their wait does not cover the
+            // copies) and after its barriers (the staged rows are free)
+            c2 wb[kTwSlots];
+            preload_twiddles<LOG2N>(wb, t, tw);
+            fft_pass<LOG2N, 0, +1>(v, t, lds, wb);
+            if (s > 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) stage_row(i0 + 4 * s - 3 + r, r);
+            }
+            // (barriers that order LDS only: the copies stay in flight)
+            fft_pass_loop<LOG2N, +1, 1, kSyncLds>(v, t, lds, wb);
+        } else {
+            fft_regs<LOG2N, +1>(v, t, lds, tw);
+        }
         K34_STAMP(1);
         float *raw = reinterpret_cast<float *>(lds) + kZShift;   // [2][N] |z| of rows ka, ka+1
 #pragma unroll
@@ -2733,7 +2801,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
             raw[t + j * T] = fabsf(v[j].x);
             raw[N + t + j * T] = fabsf(v[j].y);
         }
-        __syncthreads();
+        xsync<SRCDMA ? kSyncLds : 0>();
         K34_STAMP(2);
         // ---- horizontal blur of the 4 new list rows ----
         // |z| rows sit 2 floats into their LDS rows (zshift), so the taps
@@ -2746,12 +2814,26 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float4 *r4 = b4 + ((r >> 1) * GROUP_FLOATS + (r & 1) * N) / 4;
-            const float4 P = r4[0], Z = r4[1];   // z[c-2 .. c+1], z[c+2 .. c+5]
+            float4 P, Z;   // z[c-2 .. c+1], z[c+2 .. c+5]
+            if constexpr (SRCDMA) {
+                // (read as lds_ld reads: the compiler then orders these reads
+                // of the FFT regions behind no copy into the staged rows)
+                typedef float f32x4 __attribute__((ext_vector_type(4)));
+                typedef __attribute__((address_space(3))) const volatile f32x4 lds_vf4;
+                const f32x4 p = *(lds_vf4 *)(r4), z = *(lds_vf4 *)(r4 + 1);
+                P = make_float4(p.x, p.y, p.z, p.w);
+                Z = make_float4(z.x, z.y, z.z, z.w);
+            } else {
+                P = r4[0];
+                Z = r4[1];
+            }
             yw[4 + r][0] = bw.w0 * P.z + bw.w1 * (P.y + P.w) + bw.w2 * (P.x + Z.x);
             yw[4 + r][1] = bw.w0 * P.w + bw.w1 * (P.z + Z.x) + bw.w2 * (P.y + Z.y);
             yw[4 + r][2] = bw.w0 * Z.x + bw.w1 * (P.w + Z.y) + bw.w2 * (P.z + Z.z);
             yw[4 + r][3] = bw.w0 * Z.y + bw.w1 * (Z.x + Z.z) + bw.w2 * (P.w + Z.w);
         }
+        // (SRCDMA: the wave's own copies have landed before it arrives)
+        if constexpr (SRCDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();   // LDS free for the next step's FFT
         K34_STAMP(3);
         if (s > 0) {
@@ -2767,6 +2849,9 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
 #pragma unroll
                 for (int k = 0; k < 4; ++k) hc[4][k] = hc[3][k];
                 chroma_row(i0 + 4 * s, hc[5]);
+            } else if constexpr (SRCDMA) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) chroma_row_staged(r, hc[2 + r]);
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) chroma_row(i0 + 4 * s - 3 + r, hc[2 + r]);
