@@ -276,7 +276,7 @@ int mm_create(int width, int height, const mm_params *p, int hip_device, mm_hand
     g.Qs = N / 2 + 2;
     g.edge = p->edge_mode;
     build_spec(*p, N, h->spec);
-    h->k2_tab = bands_fit_table(h->spec) && !getenv("MM_K2_NOTAB");
+    h->k2_tab = bands_fit_table(h->spec) && tau_gates_zero_bins(h->spec) && !getenv("MM_K2_NOTAB");
     h->k2_tab2 = h->k2_tab && bands_overlap(h->spec) && h->N <= 4096;   // (N = 8192: LDS, set_attrs)
     h->ktab_mode = -1;
     h->blur = build_blur();
@@ -364,7 +364,7 @@ int mm_set_params(mm_handle *h, const mm_params *p)
     h->p = *p;
     h->geo.edge = p->edge_mode;
     build_spec(*p, h->N, h->spec);
-    h->k2_tab = bands_fit_table(h->spec) && !getenv("MM_K2_NOTAB");
+    h->k2_tab = bands_fit_table(h->spec) && tau_gates_zero_bins(h->spec) && !getenv("MM_K2_NOTAB");
     h->k2_tab2 = h->k2_tab && bands_overlap(h->spec) && h->N <= 4096;   // (N = 8192: LDS, set_attrs)
     h->ktab_mode = -1;
     if (edge_changed) return upload_tables(h);

@@ -627,6 +627,16 @@ static bool bands_fit_table(const Spec &sp)
     return true;
 }
 
+// The tabled ops take the phase of p conj c, which is 0 for an exactly zero p
+// or c; the reference takes arg p - arg c with atan2(0, 0) = 0, that is -arg c
+// for a zero p.  A positive threshold gates every such bin (0 < tau^2 / N^4);
+// where it cannot (magnitude_threshold = 0, or one whose scaled square
+// underflows), K2 runs the generic op, which handles the zero bins.
+static bool tau_gates_zero_bins(const Spec &sp)
+{
+    return sp.tau2_nn >= 1.17549435e-38f;
+}
+
 // Two middle bands overlap on an interval of positive width (relative 1e-5:
 // bands that only touch at a mask zero, L <= 5 at the default 0.05 / 0.45,
 // can share a bin by a rounding ulp, which the kernel's per-wave check still

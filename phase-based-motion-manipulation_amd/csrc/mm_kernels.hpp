@@ -1228,8 +1228,11 @@ __device__ __forceinline__ c2 pyramid_op(c2 c, c2 p, int fx, int fy, const Spec 
     }
     c2 a = scale(c, mpass * sp.inv_nn);
     if (mmag > 0.0f) {
-        // delta = wrap(arg p - arg c) = arg(p * conj c)
-        const float d = fast_atan2(p.y * c.x - p.x * c.y, p.x * c.x + p.y * c.y);
+        // delta = wrap(arg p - arg c) = arg(p * conj c); an exactly zero p
+        // (ungated only at tau = 0: a black previous frame) has arg p =
+        // atan2(0, 0) = 0 in the reference, so delta = -arg c = arg(conj c)
+        const bool pz = p.x == 0.0f && p.y == 0.0f;
+        const float d = fast_atan2(pz ? -c.y : p.y * c.x - p.x * c.y, pz ? c.x : p.x * c.x + p.y * c.y);
         const float ph = sp.S * d;
         const float k = mmag * sp.inv_nn;
         a = add(a, scale(mul_c(c, mk(__cosf(ph), __sinf(ph))), k));
@@ -1367,7 +1370,9 @@ __device__ __forceinline__ float bin_mask_sum(int fx, int fyy, const Spec &sp)
 __device__ __forceinline__ float atan2_nz(float y, float x)
 {
     const float ax = fabsf(x), ay = fabsf(y);
-    const float a = fminf(ax, ay) * __builtin_amdgcn_rcpf(fmaxf(ax, ay));
+    // (the max3 guard of fast_atan2: atan2(0, 0) = 0, not 0 * rcp(0) = NaN, should
+    // a zero bin get here ungated)
+    const float a = fminf(ax, ay) * __builtin_amdgcn_rcpf(fmaxf(fmaxf(ax, ay), 1.17549435e-38f));
     const float s = a * a;
     float r = -0.00405455008149147f;
     r = r * s + 0.021862903609871864f;
