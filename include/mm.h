@@ -20,7 +20,8 @@
  *     linear light on read, encoded on write).  MM_NV12 / MM_NV12_FULL are
  *     video frames, planar Y'CbCr 4:2:0, and MM_P010 / MM_P010_FULL their
  *     10-bit form, BT.601 or with a matrix bit BT.709 / BT.2020 (see the
- *     format list).  The handle
+ *     format list); MM_YUY2 / MM_UYVY are packed 4:2:2 capture frames and
+ *     MM_Y210 / MM_Y210_FULL their 10-bit form.  The handle
  *     owns all device scratch and the one-frame temporal state.
  *   - A handle is not thread-safe: one handle per video stream, calls in frame
  *     order (Unity calls OnRenderImage serially on its render thread).
@@ -63,7 +64,8 @@ extern "C" {
 
 /* frame formats (every entry point that takes frames takes each of them;
  * the NV12 and P010 pairs for even W and H and without the debug views; the
- * single-plane grayscale formats MM_Y8 .. MM_Y16 further down) */
+ * single-plane grayscale formats MM_Y8 .. MM_Y16, packed 4:2:2 MM_YUY2 /
+ * MM_UYVY and 10-bit packed 4:2:2 MM_Y210 further down) */
 #define MM_RGBA8   0       /* 4 B/px, UNORM: v = byte / 255; out round(saturate(v) * 255) */
 #define MM_RGBA32F 1       /* 16 B/px, linear float                                       */
 /* The frames the reference actually receives (since ABI 10): its camera
@@ -173,7 +175,7 @@ extern "C" {
  * exactly zero I and Q and luma = y.
  * Out of scope: PQ / HLG transfer curves (the samples are taken as they are,
  * like every other format's), constant-luminance BT.2020, 4:4:4 and planar or
- * 10-bit 4:2:2 (packed 8-bit 4:2:2: MM_YUY2 / MM_UYVY below),
+ * P210 4:2:2 (packed 4:2:2: MM_YUY2 / MM_UYVY and, 10-bit, MM_Y210 below),
  * chroma siting other than the shared 2 x 2 sample, odd sizes. */
 #define MM_MATRIX_BT709   32   /* Kr 0.2126, Kb 0.0722 */
 #define MM_MATRIX_BT2020  64   /* Kr 0.2627, Kb 0.0593, non-constant luminance */
@@ -234,7 +236,7 @@ extern "C" {
  * show_magnitude / show_phase are refused with MM_ERR_UNSUPPORTED, as for NV12.
  * MM_MATRIX_BT709 / MM_MATRIX_BT2020 may be OR-ed on exactly as on the 4:2:0
  * codes: the valid formats are 24..27 (BT.601), 56..59 and 88..91; codes
- * 28..31 stay unknown (kept free for a 10-bit form).
+ * 28..31 stay unknown (the 10-bit form lives at 22 / 23: MM_Y210 below).
  * The codes and ranges are NV12's, the matrices the matrix bits', and a chroma
  * sample is shared by its 1 x 2 pixels.  The frame IS the RGBA32F frame of
  * this decode and the result the reference's result on it:
@@ -260,7 +262,7 @@ extern "C" {
  * the extent and 4 GiB rules are unchanged.  Every row of every legal layout
  * is dword aligned, so the fused kernels run under their geometry conditions
  * alone.
- * Out of scope: 10-bit 4:2:2 (Y210, v210, P210); planar 4:2:2 and 4:4:4 on the
+ * Out of scope: v210 and P210 (10-bit packed 4:2:2 is MM_Y210 below); planar 4:2:2 and 4:4:4 on the
  * device; odd H; the debug views; chroma siting other than the shared 1 x 2
  * sample; PQ / HLG; the ring entry points (include/mm_ring.h); the Unity shim;
  * a host 4:2:2 to RGBA conversion. */
@@ -268,6 +270,63 @@ extern "C" {
 #define MM_YUY2_FULL 25   /* the same, full range */
 #define MM_UYVY      26   /* bytes Cb Y0 Cr Y1, BT.601 limited range */
 #define MM_UYVY_FULL 27   /* the same, full range */
+
+/* 10-bit packed 4:2:2 frames (backward-compatible addition to ABI 10: a caller
+ * detects it by mm_frame_bytes(W, H, MM_Y210, &n) == MM_OK).  The frame of the
+ * sources where bit depth matters most: SDI / HDMI capture SDKs offer it beside
+ * v210, HEVC 4:2:2 10-bit, ProRes and DNxHR decodes produce it; DirectX / Media
+ * Foundation, VA-API and ffmpeg (y210le) call it Y210: the YUY2 macropixel in
+ * 16-bit words, the code in the high bits exactly as P010 stores its samples.
+ * One plane, tightly packed: H rows of W / 2 eight-byte macropixels, four
+ * little-endian 16-bit words Y0 Cb Y1 Cr, 4 W bytes per row and 4 W H per
+ * frame (1920 x 1080: 8,294,400 bytes, pitch 7,680); frame k of a stream at
+ * k * mm_frame_bytes.  As in P010 the word is read as 16-bit fixed point,
+ * v = word / 64 in 10-bit code units: Y210 content has the low 6 bits zero, a
+ * Y216 surface is accepted as it is and its low bits are honoured.  W and H
+ * even (else MM_ERR_UNSUPPORTED from mm_frame_bytes, mm_surface_* and every
+ * frame entry point); show_magnitude / show_phase are refused with
+ * MM_ERR_UNSUPPORTED.  MM_MATRIX_BT709 / MM_MATRIX_BT2020 may be OR-ed on: the
+ * valid formats are 22, 23 (BT.601), 54, 55 and 86, 87; both bits together or
+ * any other stray bit give MM_ERR_INVALID before anything is queued.  Codes
+ * 20 and 21 stay unknown.
+ * The ranges are P010's, the matrices the matrix bits', and a chroma sample is
+ * shared by its 1 x 2 pixels.  The frame IS the RGBA32F frame of this decode
+ * and the result the reference's result on it:
+ *   in:  y = (v - 64) / 876, cb = (v - 512) / 896, cr = (v - 512) / 896
+ *        (_FULL: v / 1023, (v - 512) / 1023); R, G, B by the format's decode:
+ *        BT.601 with the six-digit coefficients of the NV12 section, a matrix
+ *        bit with the (Kr, Kb) form of the matrix section; alpha 1, NOT
+ *        clamped;
+ *   out: of the saturated RGB, Y', Cb', Cr' by the format's weights; luma code
+ *        per pixel, chroma code 512 + scale x the mean of the macropixel's two
+ *        pixels' C'; codes floor(v + 0.5) clamped to 0..1023, stored as
+ *        code << 6: the low 6 bits of every output word are zero.
+ * The first frame after mm_create / mm_reset and apply_magnification = 0 pass
+ * all 4 W H bytes through bitwise, low bits included.  mm_ycbcr_matrix accepts
+ * these codes (the values of the 4:2:0 code of the same matrix).  For BT.601
+ * frames the forward row kernel uses the luma words alone (the chroma word
+ * loaded beside each is dropped) and the state is bitwise that of a P010 frame
+ * with the same luma words; matrixed frames cost it one 8-byte macropixel per
+ * pixel and source row.  4 bytes per pixel travel each way and the host
+ * converts nothing; against P010 the vertical chroma resolution is kept,
+ * against MM_YUY2 the two bits that phase_scale would amplify as noise.
+ * in_layout->format == out_layout->format, as everywhere.
+ * Surfaces: the unit u is 8, one macropixel; chroma_offset = chroma_pitch = 0
+ * (else MM_ERR_INVALID); pitch >= 4 W; device frame pointers, pitch and frame
+ * stride are multiples of 8, so a region of interest starts on an even column;
+ * the extent and 4 GiB rules are unchanged.  mm_surface_aligned(1920, 1080,
+ * MM_Y210, 256, 16) has pitch 7,680 and frame_stride 8,355,840; with
+ * pitch_align 1024 the pitch is 8,192.  The fused kernels' 16-byte quads (two
+ * macropixels) are 16-byte aligned where base, pitch and stride are, and
+ * multi-dword accesses at 8-byte-aligned addresses in any other legal layout:
+ * the fused kernels run under their geometry conditions alone.
+ * Out of scope: v210 (three 10-bit samples per 32-bit word); v216 / a UYVY
+ * word order (codes 28..31 stay unknown); P210 and planar 4:2:2; Y410 / 4:4:4;
+ * low-bit-aligned words; odd H; the debug views; chroma siting other than the
+ * shared 1 x 2 sample; PQ / HLG; the ring entry points (include/mm_ring.h);
+ * the Unity shim; a host 4:2:2 to RGBA conversion. */
+#define MM_Y210      22   /* 10-bit packed 4:2:2, words Y0 Cb Y1 Cr, BT.601 limited range */
+#define MM_Y210_FULL 23   /* the same, full range */
 
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0  /* usePyramidDecomposition = true (.cs:18, :128-131) */
@@ -375,7 +434,8 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  *     modes, host-memory frames, stream ordering, aliasing) follows them.
  * Validation (mm_surface_bytes; every frame entry point applies it before it
  * queues anything; no GPU needed).  With the unit u = the pixel size of an RGBA
- * format (4, 16, 8, 4), 2 for NV12 (a (Cb, Cr) pair), 4 for P010 and the sample
+ * format (4, 16, 8, 4), 2 for NV12 (a (Cb, Cr) pair), 4 for P010 and packed
+ * 4:2:2, 8 for MM_Y210 (a macropixel each) and the sample
  * size of a single-plane format (1 for MM_Y8, 2 for MM_Y10 / Y12 / Y16):
  *   - unknown format: MM_ERR_INVALID; 4:2:0 with odd W or H: MM_ERR_UNSUPPORTED;
  *   - pitch (4:2:0: and chroma_pitch) at least the row's sample bytes (W pixels;
@@ -394,11 +454,12 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  *     multiples of 4 get the dword accesses.)  With count > 1, frame_stride is
  *     at least extent and a multiple of u.
  * Wide accesses (RGBA8's 16-byte quads, NV12's dword quads, P010's 8-byte
- * quads) are decided per frame from base, pitch and chroma offset and pitch;
+ * quads; MM_Y210's 16-byte quads are one access at any 8-byte-aligned address)
+ * are decided per frame from base, pitch and chroma offset and pitch;
  * an unaligned frame takes the narrower access, never another kernel: a layout
  * aligned like a decoder's runs exactly the tight layout's kernels. */
 typedef struct {
-    int    format;         /* MM_RGBA8 ... MM_UYVY_FULL; 4:2:0 and 4:2:2: | MM_MATRIX_* */
+    int    format;         /* MM_RGBA8 ... MM_UYVY_FULL, MM_Y210(_FULL); 4:2:0 and 4:2:2: | MM_MATRIX_* */
     size_t pitch;          /* bytes from one row to the next: RGBA rows, or luma rows */
     size_t chroma_offset;  /* 4:2:0: bytes from the frame's base to the (Cb,Cr) plane; else 0 */
     size_t chroma_pitch;   /* 4:2:0: bytes from one (Cb,Cr) row to the next; else 0 */
@@ -554,7 +615,7 @@ int mm_resample_table(int width, int height, int axis, int edge_mode,
  * Q_cr}: RGBToYIQ's I and Q rows times the BT.601 conversion above, derived
  * in double (the kernels take it divided by the range's chroma scale). */
 int mm_nv12_chroma_matrix(double m[4]);
-/* The (cb, cr) -> (Y, I, Q) matrix of a 4:2:0 or packed 4:2:2 format, m = {Y_cb, I_cb, Q_cb,
+/* The (cb, cr) -> (Y, I, Q) matrix of a 4:2:0 or packed 4:2:2 (8- or 10-bit) format, m = {Y_cb, I_cb, Q_cb,
  * Y_cr, I_cr, Q_cr}: RGBToYIQ's rows times the format's decode (its matrix
  * bit's; the range does not enter), derived in double.  Y_cb, Y_cr are the a,
  * b of Yq above; for the BT.601 codes they are exactly 0 and the I, Q entries

@@ -218,11 +218,13 @@ static inline bool fmt_420(int fmt) { return fmt_nv12(fmt) || fmt_p010(fmt); }  
 // packed 8-bit 4:2:2: one plane of four-byte macropixels (YUY2 / UYVY byte order)
 static inline bool fmt_422(int fmt) { return fmt_base(fmt) >= MM_YUY2 && fmt_base(fmt) <= MM_UYVY_FULL; }
 static inline bool fmt_uyvy(int fmt) { return fmt_base(fmt) == MM_UYVY || fmt_base(fmt) == MM_UYVY_FULL; }
-static inline bool fmt_ycc(int fmt) { return fmt_420(fmt) || fmt_422(fmt); }   // Y'CbCr: takes a matrix bit
+// packed 10-bit 4:2:2: one plane of eight-byte macropixels, words Y0 Cb Y1 Cr (P010's words)
+static inline bool fmt_y210(int fmt) { return fmt_base(fmt) == MM_Y210 || fmt_base(fmt) == MM_Y210_FULL; }
+static inline bool fmt_ycc(int fmt) { return fmt_420(fmt) || fmt_422(fmt) || fmt_y210(fmt); }   // Y'CbCr: takes a matrix bit
 static inline bool fmt_full(int fmt)
 {
     const int b = fmt_base(fmt);
-    return b == MM_NV12_FULL || b == MM_P010_FULL || b == MM_YUY2_FULL || b == MM_UYVY_FULL;
+    return b == MM_NV12_FULL || b == MM_P010_FULL || b == MM_YUY2_FULL || b == MM_UYVY_FULL || b == MM_Y210_FULL;
 }
 // single-plane grayscale: one sample per pixel, a byte (MM_Y8) or a 16-bit word
 static inline bool fmt_mono(int fmt) { return fmt >= MM_Y8 && fmt <= MM_Y16; }
@@ -239,6 +241,7 @@ static inline bool fmt_valid(int fmt)
 static inline size_t fmt_frame_bytes(int W, int H, int fmt)
 {
     const size_t px = (size_t)W * (size_t)H;
+    // (MM_Y210: 4 bytes per pixel, fmt_bpp's default)
     return fmt_p010(fmt) ? 3 * px : fmt_nv12(fmt) ? px + px / 2 : fmt_422(fmt) ? 2 * px : px * fmt_bpp(fmt);
 }
 // What every frame entry point asks of (format, geometry, parameters) before
@@ -255,9 +258,13 @@ static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
 // ---- surfaces (mm_surface, include/mm.h) ----------------------------------
 // u: what pitches, offsets, strides and frame pointers are multiples of
 // (the single-plane formats: their sample, 1 or 2 bytes)
-// (packed 4:2:2: one macropixel)
-static inline size_t fmt_unit(int fmt) { return fmt_nv12(fmt) ? 2 : fmt_p010(fmt) || fmt_422(fmt) ? 4 : fmt_bpp(fmt); }
-// sample bytes of one row (4:2:0: of a luma row and of a (Cb, Cr) row alike)
+// (packed 4:2:2: one macropixel, 4 bytes or, MM_Y210, 8)
+static inline size_t fmt_unit(int fmt)
+{
+    return fmt_nv12(fmt) ? 2 : fmt_p010(fmt) || fmt_422(fmt) ? 4 : fmt_y210(fmt) ? 8 : fmt_bpp(fmt);
+}
+// sample bytes of one row (4:2:0: of a luma row and of a (Cb, Cr) row alike;
+// MM_Y210: 4 W, fmt_bpp's default)
 static inline size_t fmt_row_bytes(int W, int fmt)
 {
     return (size_t)W * (fmt_p010(fmt) || fmt_422(fmt) ? 2 : fmt_nv12(fmt) ? 1 : fmt_bpp(fmt));
@@ -354,11 +361,14 @@ static_assert(kFmtNV12M == (MM_NV12 | MM_MATRIX_BT709) && kFmtP010M == (MM_P010 
               "K1's matrixed template arguments are the BT.709 limited-range codes");
 static_assert(kFmtYUY2 == MM_YUY2 && kFmtYUY2M == (MM_YUY2 | MM_MATRIX_BT709),
               "the kernels' packed 4:2:2 template arguments are the YUY2 limited-range codes");
+static_assert(kFmtY210 == MM_Y210 && kFmtY210M == (MM_Y210 | MM_MATRIX_BT709),
+              "the kernels' 10-bit packed 4:2:2 template arguments are the Y210 limited-range codes");
 // Runs the statement with the compile-time format FMT_ of the runtime `fmt`
 // (both NV12 ranges run the MM_NV12 instances, both P010 ranges the MM_P010
 // instances, whatever the matrix bit, the three word depths of the
-// single-plane formats the MM_Y16 instances, and both byte orders and ranges
-// of packed 4:2:2 the MM_YUY2 instances; geo_of sets their uniforms).
+// single-plane formats the MM_Y16 instances, both byte orders and ranges
+// of packed 4:2:2 the MM_YUY2 instances, and both ranges of its 10-bit form the
+// MM_Y210 instances; geo_of sets their uniforms).
 #define MM_FMT_SWITCH(fmt, ...)                                                \
     switch (fmt_base(fmt)) {                                                   \
     case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
@@ -370,14 +380,17 @@ static_assert(kFmtYUY2 == MM_YUY2 && kFmtYUY2M == (MM_YUY2 | MM_MATRIX_BT709),
     case MM_Y10: case MM_Y12: case MM_Y16: { constexpr int FMT_ = MM_Y16; __VA_ARGS__; } break; \
     case MM_YUY2: case MM_YUY2_FULL: case MM_UYVY: case MM_UYVY_FULL:          \
         { constexpr int FMT_ = MM_YUY2; __VA_ARGS__; } break;                  \
+    case MM_Y210: case MM_Y210_FULL: { constexpr int FMT_ = MM_Y210; __VA_ARGS__; } break; \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
 // ... K1's: a code with a matrix bit runs the matrixed NV12 / P010 instance,
 // which reads the chroma plane too (BT.709 and BT.2020, both ranges, share it);
-// a matrixed packed 4:2:2 code the instance that reads whole macropixels
+// a matrixed packed 4:2:2 code the instance that reads whole macropixels (four
+// bytes, or the 10-bit form's eight)
 #define MM_FMT_SWITCH_K1(fmt, ...)                                             \
     if (fmt_matrix(fmt) && fmt_nv12(fmt)) { constexpr int FMT_ = kFmtNV12M; __VA_ARGS__; }      \
     else if (fmt_matrix(fmt) && fmt_422(fmt)) { constexpr int FMT_ = kFmtYUY2M; __VA_ARGS__; }  \
+    else if (fmt_matrix(fmt) && fmt_y210(fmt)) { constexpr int FMT_ = kFmtY210M; __VA_ARGS__; } \
     else if (fmt_matrix(fmt)) { constexpr int FMT_ = kFmtP010M; __VA_ARGS__; }                  \
     else MM_FMT_SWITCH(fmt, __VA_ARGS__)
 // K1's instance of a format: a single-plane frame IS a luma plane and runs the
@@ -464,7 +477,7 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
     g.li = fr.in;
     g.lo = fr.out;
     if (fmt_ycc(fmt)) {
-        const bool full = fmt_full(fmt), p10 = fmt_p010(fmt);
+        const bool full = fmt_full(fmt), p10 = fmt_p010(fmt) || fmt_y210(fmt);   // (MM_Y210: P010's words)
         const double ys = p10 ? (full ? 1023.0 : 876.0) : (full ? 255.0 : 219.0);
         const double cs = p10 ? (full ? 1023.0 : 896.0) : (full ? 255.0 : 224.0);
         const double y0 = full ? 0.0 : p10 ? 64.0 : 16.0, u = p10 ? 64.0 : 1.0;
@@ -489,10 +502,11 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
         // C' = (B - Yl) 0.5 / (1 - Kb), (R - Yl) 0.5 / (1 - Kr) (BT.601: 0.886,
         // 0.701); the mean of four; the code scale
         // (packed 4:2:2: the mean of the macropixel's two)
-        const double mean = fmt_422(fmt) ? 0.5 : 0.25;
+        const double mean = fmt_422(fmt) || fmt_y210(fmt) ? 0.5 : 0.25;
         g.nv.cbo = (float)(mean * cs * 0.5 / (1.0 - kb));
         g.nv.cro = (float)(mean * cs * 0.5 / (1.0 - kr));
         // packed 4:2:2 byte order, the same on both sides: YUY2 is Y0 Cb Y1 Cr, UYVY Cb Y0 Cr Y1
+        // (MM_Y210 has the one word order: 0)
         g.li.yb = g.lo.yb = fmt_uyvy(fmt) ? 1u : 0u;
     } else if (fmt_mono(fmt)) {
         // v = sample / max in, code = floor(v max + 0.5) clamped to max out:
@@ -728,7 +742,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)k34_lds_bytes<12>(false);
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         // k_sb_cols: exchange buffer (36.9 KB) + its own staging, past 64 KB for
@@ -757,7 +771,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 11) {   // k_rows_inv_compose4: four 2048-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 4 * lds_complex<2048>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
     }
@@ -907,7 +921,8 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
 // P010's quads are multi-dword accesses at dword-aligned addresses, which the
 // unit, 4, gives every layout: mm_kernels.hpp ld_quad_a4; packed 4:2:2's quads
 // are 8-byte accesses of two macropixels at dword-aligned addresses, and its
-// unit is 4 too.)
+// unit is 4 too; MM_Y210's are 16-byte accesses at 8-byte-aligned addresses,
+// its unit: ld_quad_a8.)
 static bool nv12_quads_aligned(const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
     const uintptr_t a = reinterpret_cast<uintptr_t>(in) + fr.in.c_off, b = reinterpret_cast<uintptr_t>(out);

@@ -238,6 +238,20 @@ __device__ __forceinline__ void st_stream_quad_a4(void *base, unsigned byte_off,
     __builtin_nontemporal_store(w, reinterpret_cast<u32x4_a4 *>(reinterpret_cast<uint8_t *>(base) + byte_off));
 }
 
+// ... and MM_Y210 quads (two 8-byte macropixels) at an 8-byte-aligned address
+typedef unsigned u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+__device__ __forceinline__ uint4 ld_quad_a8(const void *base, unsigned byte_off)
+{
+    const u32x4_a8 w = *reinterpret_cast<const u32x4_a8 *>(reinterpret_cast<const uint8_t *>(base) + byte_off);
+    return make_uint4(w.x, w.y, w.z, w.w);
+}
+__device__ __forceinline__ void st_stream_quad_a8(void *base, unsigned byte_off, uint4 v)
+{
+    u32x4_a8 w;
+    __builtin_memcpy(&w, &v, 16);
+    __builtin_nontemporal_store(w, reinterpret_cast<u32x4_a8 *>(reinterpret_cast<uint8_t *>(base) + byte_off));
+}
+
 typedef unsigned u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 __device__ __forceinline__ void st_stream_pair_a4(void *base, unsigned byte_off, unsigned lo, unsigned hi)
 {
@@ -500,6 +514,11 @@ template <int FMT> constexpr bool kMatrixed = FMT == kFmtNV12M || FMT == kFmtP01
 constexpr int kFmtYUY2 = 24;   // MM_YUY2
 constexpr int kFmtYUY2M = 56;  // MM_YUY2 | MM_MATRIX_BT709 (K1 only: any matrixed packed 4:2:2)
 template <int FMT> constexpr bool k422 = FMT == kFmtYUY2 || FMT == kFmtYUY2M;
+// 10-bit packed 4:2:2 (section below): kFmtY210 runs every BT.601 Y210 frame and
+// every compose, kFmtY210M is K1's instance for a matrixed one
+constexpr int kFmtY210 = 22;   // MM_Y210
+constexpr int kFmtY210M = 54;  // MM_Y210 | MM_MATRIX_BT709 (K1 only: any matrixed Y210)
+template <int FMT> constexpr bool kY210 = FMT == kFmtY210 || FMT == kFmtY210M;
 // an input macropixel's chroma bytes (byte order: Geo::li.yb; the shifts are uniform)
 __device__ __forceinline__ float c422_cb(unsigned u, const Geo &g) { return (float)((u >> (8u - 8u * g.li.yb)) & 255u); }
 __device__ __forceinline__ float c422_cr(unsigned u, const Geo &g) { return (float)((u >> (24u - 8u * g.li.yb)) & 255u); }
@@ -534,12 +553,12 @@ template <> struct ChromaSrc<kFmtP010M> : ChromaSrc<kFmtP010> {};
 template <int FMT>
 __device__ __forceinline__ float k1_luma(typename LumaSrc<FMT>::raw_t u, const Geo &g)
 {
-    if constexpr (k420<FMT> || k422<FMT>) return (float)u - g.nv.y_off;
+    if constexpr (k420<FMT> || k422<FMT> || kY210<FMT>) return (float)u - g.nv.y_off;
     else return luma_units<FMT>(u);
 }
 template <int FMT> __device__ __forceinline__ float k1_unit(const Geo &g)
 {
-    if constexpr (k420<FMT> || k422<FMT>) return g.nv.y_unit;
+    if constexpr (k420<FMT> || k422<FMT> || kY210<FMT>) return g.nv.y_unit;
     else return kLumaUnit<FMT>;
 }
 // K1, matrixed frames: what a (Cb, Cr) pair adds to the luma of its 2x2
@@ -583,6 +602,10 @@ __device__ __forceinline__ c2 p010_iq2(unsigned u, const Geo &g)
     const float cb = (float)(u & 0xFFFFu) - 32768.0f, cr = (float)(u >> 16) - 32768.0f;
     return mk(g.nv.icb, g.nv.qcb) * cb + mk(g.nv.icr, g.nv.qcr) * cr;
 }
+// an MM_Y210 macropixel (dwords Y0 | Cb << 16, Y1 | Cr << 16): its chroma as
+// P010's word pair Cb | Cr << 16, and its (I, Q)
+__device__ __forceinline__ unsigned y210_cword(uint2 m) { return (m.x >> 16) | (m.y & 0xFFFF0000u); }
+__device__ __forceinline__ c2 y210_iq2(uint2 m, const Geo &g) { return p010_iq2(y210_cword(m), g); }
 // both for a 4:2:0 format's sample size
 template <int FMT> __device__ __forceinline__ unsigned c420_off(const Geo &g, int row, unsigned col)
 {
@@ -600,6 +623,7 @@ __device__ __forceinline__ c2 src_iq2(typename ChromaSrc<FMT>::raw_t u, const Ge
 {
     if constexpr (k420<FMT>) return c420_iq2<FMT>(u, g);
     else if constexpr (k422<FMT>) return c422_iq2(u, g);
+    else if constexpr (kY210<FMT>) return y210_iq2(u, g);
     else return chroma_iq2<FMT>(u);
 }
 // Output of one pixel from yiq_rgb's saturated RGB: the luma code and the
@@ -801,6 +825,7 @@ template <> struct ChromaSrc<kFmtYUY2M> { using raw_t = uint32_t; };
 template <int FMT> __device__ __forceinline__ unsigned k1_off(unsigned col)
 {
     if constexpr (FMT == kFmtYUY2M) return (col & ~1u) * 2u;
+    else if constexpr (FMT == kFmtY210M) return (col & ~1u) * 4u;
     else return col * (unsigned)LumaSrc<FMT>::bpp;
 }
 // K1: the luma of column col's loaded sample (in k1_luma's units).  One
@@ -813,6 +838,11 @@ __device__ __forceinline__ float k1_luma_at(typename LumaSrc<FMT>::raw_t u, [[ma
         return k1_luma<FMT>(yc, g) + k1_chroma<FMT>(u, g);
     } else if constexpr (FMT == kFmtYUY2) {
         return k1_luma<FMT>((uint16_t)(((unsigned)u >> (8u * g.li.yb)) & 255u), g);
+    } else if constexpr (FMT == kFmtY210M) {
+        const unsigned yc = (col & 1u ? u.y : u.x) & 0xFFFFu;
+        return k1_luma<kFmtP010M>((uint16_t)yc, g) + k1_chroma<kFmtP010M>(y210_cword(u), g);
+    } else if constexpr (FMT == kFmtY210) {
+        return k1_luma<kFmtP010>((uint16_t)(u & 0xFFFFu), g);
     } else {
         return k1_luma<FMT>(u, g);
     }
@@ -854,6 +884,94 @@ __device__ __forceinline__ void c422_quad_iq(const uint8_t *img, const Geo &g, i
     a[1] = a[2] = c422_iq2(pm.x, g);
     a[3] = a[4] = c422_iq2(pm.y, g);
     a[5] = c422_iq2(pr, g);
+}
+
+// ---- 10-bit packed 4:2:2 (MM_Y210) access ----------------------------------
+// A frame is one plane of H rows of W / 2 eight-byte macropixels: four
+// little-endian 16-bit words Y0 Cb Y1 Cr, the 10-bit code in the word's high
+// bits as in P010 (v = word / 64; the low 6 bits of a Y216 surface are
+// honoured).  It IS the RGBA32F frame its decode gives (include/mm.h), with
+// P010's codes and ranges and the matrix bits' matrices; every statement of the
+// packed 4:2:2 section holds with the word as the sample and Geo::nv as P010
+// has it (word units in, 10-bit code units out, the mean of two).  There is
+// one word order (Geo::li.yb / lo.yb stay 0).
+//   K1, BT.601 (FMT = kFmtY210): a lane loads the aligned dword (Y, C) of its
+//     pixel, so that a wave's loads are contiguous, and keeps the low word;
+//     k1_luma's expression and the packed V2 expressions are the kFmtP010
+//     instance's: the state is bitwise a P010 frame's with the same luma words.
+//   K1, matrixed (FMT = kFmtY210M): one aligned 8-byte load per pixel and source
+//     row is the pixel's macropixel, dwords Y0 | Cb << 16 and Y1 | Cr << 16: Y
+//     by the column's parity, and (d0 >> 16) | (d1 & 0xffff0000) is P010's
+//     chroma word Cb | Cr << 16, which goes through k1_chroma's P010 expression
+//     (neutral chroma, 0x8000, adds exactly 0).
+//   compose (FMT = kFmtY210, all three forms): the schedule of the 8-bit form
+//     with 8-byte macropixels.  The outer source columns X-1 and X+4 are 8-byte
+//     loads, the quad's own two macropixels one 16-byte load; a row of the quad
+//     leaves as two whole macropixels in one 16-byte store, the unfused
+//     k_compose's even lanes store one macropixel (8 bytes) each.  Codes are
+//     P010's (nv12_ycode by the range's scale, p010_ccode), stored << 6.
+// Alignment: frame base, pitch and stride are multiples of 8 (mm_surface's
+// unit, one macropixel), so every 8-byte access is aligned in every legal
+// layout.  The 16-byte quads lie at multiples of 16 from the row's start (X % 4
+// == 0): 16-byte aligned wherever base, pitch and stride are (every tight frame
+// with W % 4 == 0, every decoder layout), and multi-dword accesses at
+// 8-byte-aligned addresses otherwise (ld_quad_a8 / st_stream_quad_a8, as
+// RGBA8's quads at dword-aligned ones): one access in every layout, no layout
+// rule of its own for the fused kernels.  No GEN, k_compose_odd or k_dbg_out
+// instance: odd sizes and the debug views are refused on the host.
+template <> struct LumaSrc<kFmtY210> {     // the pixel's (Y, C) word pair
+    using raw_t = uint32_t;
+    static constexpr int bpp = 4;
+};
+template <> struct LumaSrc<kFmtY210M> {    // the pixel's whole macropixel
+    using raw_t = uint2;
+    static constexpr int bpp = 4;
+};
+template <> struct ChromaSrc<kFmtY210> { using raw_t = uint2; };    // the macropixel
+template <> struct ChromaSrc<kFmtY210M> { using raw_t = uint2; };
+// byte offset of the macropixel of source pixel (row, col), both already
+// wrapped or clamped on PIXEL coordinates (then halved)
+__device__ __forceinline__ unsigned y210_off(const Geo &g, int row, unsigned col)
+{
+    return (unsigned)row * g.li.pitch + (col >> 1) * 8u;
+}
+// One word pair of an output macropixel: a luma code and a chroma code (of the
+// sum of the macropixel's two chroma differences; cbo, cro hold the mean's 1/2)
+__device__ __forceinline__ unsigned y210_half(unsigned y, float sum2, float k)
+{
+    return y << 6 | p010_ccode(sum2, k) << 22;
+}
+// The fused kernels' store of output row i of the quad X .. X+3 (X % 4 == 0):
+// two macropixels as one 16-byte store
+__device__ __forceinline__ void y210_store_quad(uint8_t *outp, const Geo &g, int i, int X, const float (&rr)[4],
+                                                const float (&gg)[4], const float (&bb)[4])
+{
+    c2 cd[4];
+    unsigned y[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = nv12_ycode(rr[k], gg[k], bb[k], g, cd[k]);
+    const c2 s0 = cd[0] + cd[1], s1 = cd[2] + cd[3];
+    // (the column offset formed here, per row: hoisted out of the walking
+    // kernel's row loop as a 64-bit address it cost that kernel 2 to 3 spilled
+    // VGPRs under its 128)
+    unsigned off = (unsigned)X * 4u;
+    asm volatile("" : "+v"(off));
+    st_stream_quad_a8(outp + (size_t)((unsigned)i * g.lo.pitch), off,
+                      make_uint4(y210_half(y[0], s0.x, g.nv.cbo), y210_half(y[1], s0.y, g.nv.cro),
+                                 y210_half(y[2], s1.x, g.nv.cbo), y210_half(y[3], s1.y, g.nv.cro)));
+}
+// The fused kernels' (I, Q) of source columns X-1 .. X+4 (cl, cr: the outer two,
+// wrapped or clamped) of source row `row`
+__device__ __forceinline__ void y210_quad_iq(const uint8_t *img, const Geo &g, int row, unsigned X, unsigned cl,
+                                             unsigned cr, c2 (&a)[6])
+{
+    const uint2 pl = ld_off<uint2>(img, y210_off(g, row, cl));
+    const uint4 pm = ld_quad_a8(img, y210_off(g, row, X));
+    const uint2 pr = ld_off<uint2>(img, y210_off(g, row, cr));
+    a[0] = y210_iq2(pl, g);
+    a[1] = a[2] = y210_iq2(make_uint2(pm.x, pm.y), g);
+    a[3] = a[4] = y210_iq2(make_uint2(pm.z, pm.w), g);
+    a[5] = y210_iq2(pr, g);
 }
 
 // =========================================================================
@@ -904,7 +1022,9 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
     }
     // RGBA8 / RGBA16F: all 32 pixel loads of the thread in one batch; RGBA32F
     // (4x the registers of RGBA8): two batches of 16
-    constexpr int UB = BPP == 16 ? 4 : 8;
+    // (MM_Y210's matrixed instance, 8-byte loads, at N = 8192, where 1024
+    // threads leave 128 VGPRs: two batches too; one batch spilled 21)
+    constexpr int UB = BPP == 16 || (FMT == kFmtY210M && LOG2N == 13) ? 4 : 8;
     if constexpr (GEN) {
         if (valid) {
             Tap4 ta = rowT[ra];
@@ -2428,6 +2548,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     auto src_off = [&](int row, unsigned col) {
         if constexpr (k420<FMT>) return c420_off<FMT>(g, row, col);
         else if constexpr (k422<FMT>) return c422_off(g, row, col);
+        else if constexpr (kY210<FMT>) return y210_off(g, row, col);
         else return (unsigned)row * g.li.pitch + col * Pix<FMT>::bpp;
     };
     const unsigned colA = (unsigned)wrap_near(min(c0 - 1 + tid, g.W), g.W, g.edge);
@@ -2535,6 +2656,20 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)half, 0xB1, 0xF, 0xF, true);
                 if (!(X & 1))
                     st_stream<uint32_t>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 2u, half | other << 16);
+            } else if constexpr (kY210<FMT>) {
+                // The same exchange with 10-bit codes: a lane's luma and chroma
+                // words are one dword of the macropixel, and the even lane
+                // stores the macropixel's two dwords (8 bytes, always aligned).
+                static_assert(TC % 2 == 0, "packed 4:2:2: tiles of whole macropixels");
+                c2 cd;
+                const unsigned yc = nv12_ycode(rr, gg, bb, g, cd);
+                const float mine = X & 1 ? cd.y : cd.x, send = X & 1 ? cd.x : cd.y;
+                const float theirs = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
+                    __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
+                const unsigned half = y210_half(yc, mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
+                const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)half, 0xB1, 0xF, 0xF, true);
+                if (!(X & 1))
+                    st_stream<uint2>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 4u, make_uint2(half, other));
             } else {
                 Pix<FMT>::store(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
             }
@@ -2670,6 +2805,9 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
             if constexpr (k422<FMT>) {
                 // macropixels X/2-1 .. X/2+2: the quad's own two as one 8-byte load
                 c422_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
+            } else if constexpr (kY210<FMT>) {
+                // ... of 8 bytes each: the quad's own two as one 16-byte load
+                y210_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
             } else if constexpr (k420<FMT>) {
                 // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
                 // outer two wrapped or clamped as pixels, then halved): the quad's
@@ -2891,6 +3029,8 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                     [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
                     if constexpr (k422<FMT>) {
                         c422_store_quad(outp, g, i, X, rr, gg, bb);
+                    } else if constexpr (kY210<FMT>) {
+                        y210_store_quad(outp, g, i, X, rr, gg, bb);
                     } else if constexpr (k420<FMT>) {
                         c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
                     } else if constexpr (bpp == 4) {
@@ -3014,6 +3154,9 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
             if constexpr (k422<FMT>) {
                 // macropixels X/2-1 .. X/2+2: the quad's own two as one 8-byte load
                 c422_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
+            } else if constexpr (kY210<FMT>) {
+                // ... of 8 bytes each: the quad's own two as one 16-byte load
+                y210_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
             } else if constexpr (k420<FMT>) {
                 // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
                 // outer two wrapped or clamped as pixels, then halved): the quad's
@@ -3105,6 +3248,8 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
             [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
             if constexpr (k422<FMT>) {
                 c422_store_quad(outp, g, i, X, rr, gg, bb);
+            } else if constexpr (kY210<FMT>) {
+                y210_store_quad(outp, g, i, X, rr, gg, bb);
             } else if constexpr (k420<FMT>) {
                 c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
             } else if constexpr (bpp == 4) {
@@ -3284,7 +3429,7 @@ void k_dbg_out(const float *__restrict__ tex, size_t tex_stride, uint8_t *__rest
 // =========================================================================
 // One workgroup per (plane row, frame): the row's samples and nothing else, in
 // words of U (NV12 and the 16-bit single-plane formats: 2 bytes, their unit;
-// MM_Y8: 1; every other format: 4, which divides its unit; packed 4:2:2: 4, one macropixel).  `rows_y` RGBA / luma rows, then the (Cb, Cr) rows of a 4:2:0
+// MM_Y8: 1; every other format: 4, which divides its unit; packed 4:2:2: 4, one macropixel or, MM_Y210, half of one).  `rows_y` RGBA / luma rows, then the (Cb, Cr) rows of a 4:2:0
 // frame.  Tight frames on both sides are one plain device copy instead.
 template <class U>
 __global__ __launch_bounds__(256)

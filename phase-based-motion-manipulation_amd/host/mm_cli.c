@@ -9,7 +9,7 @@
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
  *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
- *          [--yuy2] [--uyvy]
+ *          [--yuy2] [--uyvy] [--y210]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
@@ -54,10 +54,10 @@
  * converted silently: an 8-bit input with --p010 and a 10-bit input without it
  * are refused.
  * --matrix 601|709|2020 (default 601): the Y'CbCr matrix of an --nv12,
- * --p010, --yuy2 or --uyvy clip (HD content is BT.709, UHD BT.709 or BT.2020), OR-ed onto the
+ * --p010, --yuy2, --uyvy or --y210 clip (HD content is BT.709, UHD BT.709 or BT.2020), OR-ed onto the
  * frame format as MM_MATRIX_BT709 / MM_MATRIX_BT2020.  A .y4m header has no
  * matrix tag, so files are the same whatever the value.  Only with --nv12,
- * --p010, --yuy2 or --uyvy: the host's own RGBA conversion of a .y4m is BT.601.
+ * --p010, --yuy2, --uyvy or --y210: the host's own RGBA conversion of a .y4m is BT.601.
  * --mono: a mono .y4m input (Cmono, Cmono10, Cmono12, Cmono16: a grayscale
  * camera's or ffmpeg's gray / gray10le / gray12le / gray16le frames) goes to
  * the device as it is stored, as MM_Y8 / MM_Y10 / MM_Y12 / MM_Y16 frames by the
@@ -76,10 +76,19 @@
  * with --srgb, the debug views, the ring modes, --nv12, --p010, --mono, each
  * other, any other input and odd sizes.  A C422 input needs one of the two
  * flags: the host has no 4:2:2 to RGBA conversion.
+ * --y210: a 10-bit 4:2:2 .y4m input (C422p10: planar, the code in the low 10
+ * bits of each word; ffmpeg's yuv422p10le) goes to the device as MM_Y210
+ * frames, words Y0 Cb Y1 Cr with the code << 6 (_FULL with --full-range, a
+ * matrix bit with --matrix): the planes are interleaved and shifted on the way
+ * in and split on the way out (a C422p10 .y4m; any other extension: the raw
+ * Y210 frames), and no colour arithmetic runs on the host.  Refused with
+ * --yuy2, --uyvy, --nv12, --p010, --mono, --srgb, the debug views, the ring
+ * modes, any other input and odd sizes.  A C422p10 input needs --y210: it is
+ * never converted on the host.
  * --surface-align P,R: the device frames, input and output, are held in
  * mm_surface_aligned(W, H, format, P, R) surfaces (256,16: a hardware
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
- * format, --nv12, --p010, --yuy2 and --uyvy included.  Files and checksums are those of the
+ * format, --nv12, --p010, --yuy2, --uyvy and --y210 included.  Files and checksums are those of the
  * run without the flag, byte for byte.  Not with the ring modes.
  */
 #include <hip/hip_runtime_api.h>
@@ -450,7 +459,7 @@ int main(int argc, char **argv)
     int W = 1920, H = 1080, F = 300, L = 5, B = 30, dev = 0;
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
-    int nv12 = 0, p010 = 0, srgb = 0, mono = 0, yuy2 = 0, uyvy = 0;
+    int nv12 = 0, p010 = 0, srgb = 0, mono = 0, yuy2 = 0, uyvy = 0, y210 = 0;
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
@@ -464,6 +473,7 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--mono")) { mono = 1; continue; }
         if (!strcmp(a, "--yuy2")) { yuy2 = 1; continue; }
         if (!strcmp(a, "--uyvy")) { uyvy = 1; continue; }
+        if (!strcmp(a, "--y210")) { y210 = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
         if (!strcmp(a, "--show-magnitude")) { show_mag = 1; continue; }
         if (!strcmp(a, "--show-phase")) { show_phase = 1; continue; }
@@ -503,12 +513,31 @@ int main(int argc, char **argv)
     yi.fps_den = 1;
     int depth = 8;
     if (y4m_in) {
-        if (y4m_read_header_depth(fi, &yi, &depth)) { fprintf(stderr, "%s: unsupported Y4M\n", in_path); return 1; }
+        if (y4m_read_header_ext(fi, &yi, &depth)) { fprintf(stderr, "%s: unsupported Y4M\n", in_path); return 1; }
         W = yi.width;
         H = yi.height;
     }
     const int p422 = yuy2 || uyvy;   /* packed 4:2:2 */
-    if (p422) {
+    if (y210) {   /* its 10-bit form */
+        if (p422 || nv12 || p010 || mono || srgb || show_mag || show_phase || ring_local > 0 || ring_world > 0) {
+            fprintf(stderr, "--y210 does not go with --yuy2, --uyvy, --nv12, --p010, --mono, --srgb, the debug views "
+                            "or the ring modes\n");
+            return 2;
+        }
+        if (!y4m_in || yi.chroma != Y4M_422 || depth != 10) {
+            fprintf(stderr, "--y210 needs a 10-bit 4:2:2 .y4m input (-i, C422p10)\n");
+            return 2;
+        }
+        if ((W | H) & 1) {
+            fprintf(stderr, "--y210 needs even width and height (%dx%d)\n", W, H);
+            return 2;
+        }
+        g_fmt = full_range ? MM_Y210_FULL : MM_Y210;
+    } else if (y4m_in && yi.chroma == Y4M_422 && depth == 10) {
+        fprintf(stderr, "%s is a 10-bit 4:2:2 stream (C422p10): it needs --y210 "
+                        "(there is no 4:2:2 to RGBA conversion on the host)\n", in_path);
+        return 2;
+    } else if (p422) {
         const char *opt = yuy2 ? "--yuy2" : "--uyvy";
         if (yuy2 && uyvy) {
             fprintf(stderr, "--yuy2 does not go with --uyvy (one byte order)\n");
@@ -571,7 +600,7 @@ int main(int argc, char **argv)
             return 2;
         }
         g_fmt = full_range ? MM_P010_FULL : MM_P010;
-    } else if (depth != 8 && !mono) {
+    } else if (depth != 8 && !mono && !y210) {
         if (yi.chroma == Y4M_MONO)
             fprintf(stderr, "%s is a %d-bit mono stream (Cmono%d): it needs --mono\n", in_path, depth, depth);
         else
@@ -594,8 +623,8 @@ int main(int argc, char **argv)
         g_fmt = full_range ? MM_NV12_FULL : MM_NV12;
     }
     if (matrix_arg) {
-        if (!nv12 && !p010 && !p422) {
-            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2 or --uyvy (the RGBA conversion of a .y4m is BT.601)\n");
+        if (!nv12 && !p010 && !p422 && !y210) {
+            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2, --uyvy or --y210 (the RGBA conversion of a .y4m is BT.601)\n");
             return 2;
         }
         if (!strcmp(matrix_arg, "709")) g_fmt |= MM_MATRIX_BT709;
@@ -649,7 +678,7 @@ int main(int argc, char **argv)
     }
 
     size_t fb = (size_t)W * H * 4;
-    if (nv12 || p010 || mono || p422) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
+    if (nv12 || p010 || mono || p422 || y210) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
     /* --surface-align: the frames the operator sees live in `lay` surfaces
      * (d_in, d_out); d_tin / d_tout are tight device frames for the synthetic
      * source and for the checksums and files */
@@ -662,7 +691,7 @@ int main(int argc, char **argv)
         if (sscanf(surf_arg, "%llu,%d", &pa, &ra) != 2 ||
             (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK) {
             fprintf(stderr, "--surface-align %s: want P,R with P a multiple of the format's unit "
-                            "(pixel size; NV12 2, P010 and 4:2:2 4, mono: the sample size) and R >= 1 (4:2:0: even)\n", surf_arg);
+                            "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, mono: the sample size) and R >= 1 (4:2:0: even)\n", surf_arg);
             return 2;
         }
         printf("surfaces: pitch %zu  chroma offset %zu  frame stride %zu\n", lay.pitch, lay.chroma_offset,
@@ -677,15 +706,17 @@ int main(int argc, char **argv)
     hipStream_t s = (hipStream_t)mm_stream(h);
     unsigned char *host = (fi || fo) ? (unsigned char *)malloc(fb * B) : NULL;
     unsigned char *planes = (y4m_in || y4m_out)
-        ? (unsigned char *)malloc(y4m_in ? (y4m_frame_bytes(&yi) > 3 * (size_t)W * H
-                                               ? y4m_frame_bytes(&yi) : 3 * (size_t)W * H)
+        ? (unsigned char *)malloc(y4m_in ? (y4m_frame_bytes_depth(&yi, depth) > 3 * (size_t)W * H
+                                               ? y4m_frame_bytes_depth(&yi, depth) : 3 * (size_t)W * H)
                                          : 3 * (size_t)W * H)
         : NULL;
-    /* (planes: 3 W H bytes hold a C420p10 frame, 2 bytes per sample, exactly) */
+    /* (planes: 3 W H bytes hold a C420p10 frame, 2 bytes per sample, exactly; a
+     * C422p10 frame takes 4 W H) */
     if (y4m_out && (mono   ? y4m_write_header_mono(fo, W, H, yi.fps_num, yi.fps_den, depth)
                     : p010 ? y4m_write_header_420p10(fo, W, H, yi.fps_num, yi.fps_den)
                     : nv12 ? y4m_write_header_420(fo, W, H, yi.fps_num, yi.fps_den)
                     : p422 ? y4m_write_header_422(fo, W, H, yi.fps_num, yi.fps_den)
+                    : y210 ? y4m_write_header_422p10(fo, W, H, yi.fps_num, yi.fps_den)
                            : y4m_write_header(fo, W, H, yi.fps_num, yi.fps_den))) {
         fprintf(stderr, "write failed\n");
         return 1;
@@ -710,6 +741,7 @@ int main(int argc, char **argv)
                 if (p010) y4m_420p10_to_p010(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
                 else if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
                 else if (p422) y4m_422_to_packed(W, H, planes, host + fb * got, uyvy);
+                else if (y210) y4m_422p10_to_y210(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
                 else y4m_to_rgba(&yi, planes, host + fb * got, full_range);
             }
             if (got == 0) break;
@@ -754,10 +786,12 @@ int main(int argc, char **argv)
                     if (p010) y4m_p010_to_420p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
                     else if (nv12) y4m_nv12_to_420(W, H, host + fb * k, planes);
                     else if (p422) y4m_packed_to_422(W, H, host + fb * k, planes, uyvy);
+                    else if (y210) y4m_y210_to_422p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
                     else y4m_from_rgba(W, H, host + fb * k, planes, full_range);
                     if (p010   ? y4m_write_frame_420p10(fo, W, H, (const uint16_t *)planes)
                         : nv12 ? y4m_write_frame_420(fo, W, H, planes)
                         : p422 ? y4m_write_frame_422(fo, W, H, planes)
+                        : y210 ? y4m_write_frame_422p10(fo, W, H, (const uint16_t *)planes)
                                : y4m_write_frame(fo, W, H, planes)) {
                         fprintf(stderr, "write failed\n");
                         return 1;

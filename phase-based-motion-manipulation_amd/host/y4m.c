@@ -16,8 +16,9 @@ static int parse_ratio(const char *s, int *a, int *b)
     return sscanf(s, "%d:%d", a, b) == 2 ? 0 : -1;
 }
 
-/* depth: NULL refuses the high-bit-depth tags (y4m_read_header) */
-static int read_header(FILE *f, y4m_info *info, int *depth)
+/* depth: NULL refuses the high-bit-depth tags (y4m_read_header); p422p10:
+ * C422p10 is accepted too (y4m_read_header_ext) */
+static int read_header(FILE *f, y4m_info *info, int *depth, int p422p10)
 {
     char line[512];
     size_t n = 0;
@@ -57,6 +58,10 @@ static int read_header(FILE *f, y4m_info *info, int *depth)
                 *depth = atoi(v + 4);
             }
             else if (depth && !strcmp(v, "422")) info->chroma = Y4M_422;
+            else if (depth && p422p10 && !strcmp(v, "422p10")) {
+                info->chroma = Y4M_422;
+                *depth = 10;
+            }
             else return -1;   /* 411, other high bit depths, alpha: unsupported */
             break;
         default: break;       /* X (comments) and unknown tags */
@@ -68,12 +73,17 @@ static int read_header(FILE *f, y4m_info *info, int *depth)
 
 int y4m_read_header(FILE *f, y4m_info *info)
 {
-    return read_header(f, info, NULL);
+    return read_header(f, info, NULL, 0);
 }
 
 int y4m_read_header_depth(FILE *f, y4m_info *info, int *bit_depth)
 {
-    return bit_depth ? read_header(f, info, bit_depth) : -1;
+    return bit_depth ? read_header(f, info, bit_depth, 0) : -1;
+}
+
+int y4m_read_header_ext(FILE *f, y4m_info *info, int *bit_depth)
+{
+    return bit_depth ? read_header(f, info, bit_depth, 1) : -1;
 }
 
 size_t y4m_frame_bytes(const y4m_info *info)
@@ -299,5 +309,43 @@ int y4m_write_frame_422(FILE *f, int W, int H, const uint8_t *planes422)
 {
     if (fputs("FRAME\n", f) < 0) return -1;
     const size_t nb = (size_t)W * H * 2;
+    return fwrite(planes422, 1, nb, f) == nb ? 0 : -1;
+}
+
+void y4m_422p10_to_y210(int W, int H, const uint16_t *planes422, uint16_t *y210)
+{
+    const size_t ny = (size_t)W * H, nc = ny / 2;
+    const uint16_t *Y = planes422, *Cb = planes422 + ny, *Cr = Cb + nc;
+    for (size_t i = 0; i < nc; ++i) {   /* macropixel i: pixels 2 i, 2 i + 1 (W even: never across rows) */
+        uint16_t *m = y210 + 4 * i;
+        m[0] = (uint16_t)(Y[2 * i] << 6);
+        m[1] = (uint16_t)(Cb[i] << 6);
+        m[2] = (uint16_t)(Y[2 * i + 1] << 6);
+        m[3] = (uint16_t)(Cr[i] << 6);
+    }
+}
+
+void y4m_y210_to_422p10(int W, int H, const uint16_t *y210, uint16_t *planes422)
+{
+    const size_t ny = (size_t)W * H, nc = ny / 2;
+    uint16_t *Y = planes422, *Cb = planes422 + ny, *Cr = Cb + nc;
+    for (size_t i = 0; i < nc; ++i) {
+        const uint16_t *m = y210 + 4 * i;
+        Y[2 * i] = (uint16_t)(m[0] >> 6);
+        Cb[i] = (uint16_t)(m[1] >> 6);
+        Y[2 * i + 1] = (uint16_t)(m[2] >> 6);
+        Cr[i] = (uint16_t)(m[3] >> 6);
+    }
+}
+
+int y4m_write_header_422p10(FILE *f, int W, int H, int fps_num, int fps_den)
+{
+    return fprintf(f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C422p10\n", W, H, fps_num, fps_den) > 0 ? 0 : -1;
+}
+
+int y4m_write_frame_422p10(FILE *f, int W, int H, const uint16_t *planes422)
+{
+    if (fputs("FRAME\n", f) < 0) return -1;
+    const size_t nb = (size_t)W * H * 4;
     return fwrite(planes422, 1, nb, f) == nb ? 0 : -1;
 }

@@ -11,7 +11,8 @@
  * 10-bit 4:2:0 (C420p10) streams likewise as MM_P010, and mono streams of 8, 10,
  * 12 or 16 bits (Cmono, Cmono10, Cmono12, Cmono16) as MM_Y8 .. MM_Y16, and
  * 8-bit 4:2:2 (C422) streams interleaved to YUY2 / UYVY as MM_YUY2 / MM_UYVY
- * (the last three sections).  There is no 4:2:2 to RGBA conversion.
+ * and 10-bit 4:2:2 (C422p10) streams interleaved to Y210 as MM_Y210 (the last
+ * four sections).  There is no 4:2:2 to RGBA conversion.
  */
 #ifndef MM355_Y4M_H
 #define MM355_Y4M_H
@@ -23,7 +24,7 @@
 extern "C" {
 #endif
 
-enum { Y4M_420 = 0, Y4M_444 = 1, Y4M_MONO = 2, Y4M_422 = 3 };   /* Y4M_422: y4m_read_header_depth only */
+enum { Y4M_420 = 0, Y4M_444 = 1, Y4M_MONO = 2, Y4M_422 = 3 };   /* Y4M_422: y4m_read_header_depth / _ext only */
 
 typedef struct {
     int width, height;
@@ -122,6 +123,29 @@ void y4m_packed_to_422(int width, int height, const uint8_t *in, uint8_t *planes
 /* Write a C422 header / one C422 frame (planes Y, Cb, Cr). */
 int y4m_write_header_422(FILE *f, int width, int height, int fps_num, int fps_den);
 int y4m_write_frame_422(FILE *f, int width, int height, const uint8_t *planes422);
+
+/* ---- 10-bit 4:2:2 (C422p10), for the MM_Y210 path -----------------------------
+ * Planes Y (width x height), Cb, Cr (width / 2 x height each) of little-endian
+ * 16-bit words, the code in the LOW 10 bits (ffmpeg's yuv422p10le); even width
+ * and height.  y4m_read_header and y4m_read_header_depth keep refusing the
+ * tag; the entry point below stands beside them. */
+
+/* y4m_read_header_depth that also accepts C422p10: chroma Y4M_422 and
+ * *bit_depth 10 (C422: Y4M_422 and 8).  y4m_frame_bytes_depth and
+ * y4m_read_frame_depth take such an info and depth. */
+int y4m_read_header_ext(FILE *f, y4m_info *info, int *bit_depth);
+
+/* 4:2:2 10-bit planes <-> one Y210 frame of width / 2 eight-byte macropixels
+ * per row (4 * width * height bytes either way): words Y0 Cb Y1 Cr, each the
+ * code << 6 (out: word >> 6).  Interleave and shift only, no arithmetic.
+ * Frames in this layout go through mm_process_stream as MM_Y210 (or its _FULL
+ * and matrixed forms). */
+void y4m_422p10_to_y210(int width, int height, const uint16_t *planes422, uint16_t *y210);
+void y4m_y210_to_422p10(int width, int height, const uint16_t *y210, uint16_t *planes422);
+
+/* Write a C422p10 header / one C422p10 frame (planes Y, Cb, Cr). */
+int y4m_write_header_422p10(FILE *f, int width, int height, int fps_num, int fps_den);
+int y4m_write_frame_422p10(FILE *f, int width, int height, const uint16_t *planes422);
 
 #ifdef __cplusplus
 }

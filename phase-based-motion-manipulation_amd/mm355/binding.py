@@ -30,8 +30,14 @@ YUY2_FULL = 25      # full range
 UYVY = 26           # bytes Cb Y0 Cr Y1, BT.601 limited range
 UYVY_FULL = 27      # full range
 PACKED422_FORMATS = (YUY2, YUY2_FULL, UYVY, UYVY_FULL)
+# 10-bit packed 4:2:2, one plane: H rows of W/2 eight-byte macropixels, four
+# little-endian 16-bit words Y0 Cb Y1 Cr, each the 10-bit code << 6 as in P010 (a
+# Y216 surface's low bits are honoured); W and H even; a matrix bit may be OR-ed on
+Y210 = 22           # BT.601 limited range
+Y210_FULL = 23      # full range
+Y210_FORMATS = (Y210, Y210_FULL)
 FORMAT_BPP = {RGBA8: 4, RGBA32F: 16, RGBA16F: 8, RGBA8_SRGB: 4, Y8: 1, Y10: 2, Y12: 2, Y16: 2,
-              YUY2: 2, YUY2_FULL: 2, UYVY: 2, UYVY_FULL: 2}
+              YUY2: 2, YUY2_FULL: 2, UYVY: 2, UYVY_FULL: 2, Y210: 4, Y210_FULL: 4}
 # video frames, planar 8-bit Y'CbCr 4:2:0 (H rows of W luma bytes, then H/2 rows
 # of W interleaved Cb, Cr bytes; W and H even): frame_bytes() gives W*H*3/2
 NV12 = 16           # BT.601 limited ("video") range

@@ -8,7 +8,7 @@ import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       MONO_FORMATS, NV12, NV12_FULL, P010, P010_FULL, PACKED422_FORMATS, RGBA8, RGBA8_SRGB, RGBA16F,
-                      RGBA32F, Y8,
+                      RGBA32F, Y8, Y210_FORMATS,
                       Handle, MMError, Params, Surface, base_format)
 
 
@@ -50,6 +50,16 @@ def frame_layout(frame, width, height, fmt):
             return None
         lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
         lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation (a multiple of 4)
+        return lay
+    if base_format(fmt) in Y210_FORMATS:   # [H, 2 W] words: rows of W / 2 macropixels Y0 Cb Y1 Cr
+        if tuple(frame.shape) != (height, 2 * width) or not str(frame.dtype).endswith("uint16"):
+            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height, 2 * width)} uint16)")
+        if strides[1] != 2 or strides[0] <= 0:
+            raise MMError(-1, "frames must be contiguous or row-strided (words packed)")
+        if strides[0] == 4 * width:
+            return None
+        lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
+        lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation (a multiple of 8)
         return lay
     if fmt in MONO_FORMATS:   # [H, W] samples: uint8 (Y8) or uint16
         want = "uint8" if fmt == Y8 else "uint16"
@@ -164,7 +174,10 @@ class MotionMagnificationProcessor:
         Y16: grayscale camera frames, [H, W] uint8 (Y8) or uint16 on both sides
         (contiguous or row-strided views).  fmt=YUY2 / YUY2_FULL / UYVY /
         UYVY_FULL, with or without a matrix bit: packed 4:2:2 capture frames,
-        [H, 2 W] uint8 on both sides (contiguous or row-strided views)."""
+        [H, 2 W] uint8 on both sides (contiguous or row-strided views).
+        fmt=Y210 / Y210_FULL, with or without a matrix bit: 10-bit packed 4:2:2,
+        [H, 2 W] uint16 on both sides (P010's convention: the words as they lie;
+        contiguous or row-strided views)."""
         if self._handle is None:                       # !isInitialized -> Blit (.cs:103-107)
             destination[...] = source
             return
@@ -172,7 +185,8 @@ class MotionMagnificationProcessor:
             fmt = _fmt_of(source, self.srgb)
             if _fmt_of(destination, self.srgb) != fmt:
                 raise MMError(-1, "source/destination formats differ")
-        elif fmt not in MONO_FORMATS and base_format(fmt) not in PACKED422_FORMATS:
+        elif (fmt not in MONO_FORMATS and base_format(fmt) not in PACKED422_FORMATS and
+              base_format(fmt) not in Y210_FORMATS):
             raise MMError(-1, f"fmt={fmt}: only the grayscale and packed 4:2:2 formats are named, "
                               "the others follow the dtype")
         on_dev = _is_device(source)
@@ -221,6 +235,8 @@ def host_frames(n, h, w, fmt):
         return np.zeros((n, h * 3 // 2, w), np.uint16)
     if fmt in PACKED422_FORMATS:    # one plane, h rows of w / 2 four-byte macropixels
         return np.zeros((n, h, 2 * w), np.uint8)
+    if fmt in Y210_FORMATS:         # ... of w / 2 macropixels of four 16-bit words
+        return np.zeros((n, h, 2 * w), np.uint16)
     if fmt in MONO_FORMATS:         # one plane of samples
         return np.zeros((n, h, w), np.uint8 if fmt == Y8 else np.uint16)
     dt = {RGBA8: np.uint8, RGBA8_SRGB: np.uint8, RGBA16F: np.float16}.get(fmt, np.float32)

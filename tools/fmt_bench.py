@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""RGBA8 against NV12, P010, grayscale (Y8, Y16) and packed 4:2:2 (YUY2, UYVY) frames on one GPU, same
-process, alternating legs.
+"""RGBA8 against NV12, P010, grayscale (Y8, Y16) and packed 4:2:2 (YUY2, UYVY, 10-bit Y210) frames on
+one GPU, same process, alternating legs.
 
 The flagship stream (1920x1080, 5 levels, phase scale 25, batches of 150
 frames as bench.py) in the three frame formats.  Frames are generated on the
@@ -34,6 +34,12 @@ frames as MM_YUY2 macropixels (BT.601 limited range, chroma the mean of each
 pixel pair), the same bytes pair-swapped as MM_UYVY, and the YUY2 bytes taken
 as MM_YUY2 | MM_MATRIX_BT709, whose K1 reads whole macropixels; 2 bytes per
 pixel each way.  A library from before these formats runs without them.
+
+10-bit packed 4:2:2 legs (y210, y210_bt709, and their _pitched forms): the
+YUY2 legs' pictures at 10 bits as MM_Y210 macropixels (words Y0 Cb Y1 Cr, code
+<< 6), and the same words taken as MM_Y210 | MM_MATRIX_BT709, whose K1 reads
+whole 8-byte macropixels; 4 bytes per pixel each way.  A library from before
+this format runs without them.
 
 usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--out FILE.json]
 """
@@ -85,6 +91,23 @@ def to_422(torch, rgba):
         out[k, :, 0::2] = code(yl * 219.0 + 16.0)
         out[k, :, 1::4] = code(((b - yl) * (0.5 / 0.886)).reshape(H, W // 2, 2).mean(dim=2) * 224.0 + 128.0)
         out[k, :, 3::4] = code(((r - yl) * (0.5 / 0.701)).reshape(H, W // 2, 2).mean(dim=2) * 224.0 + 128.0)
+    return out
+
+
+def to_y210(torch, rgba):
+    """[n][H][W][4] uint8 (device) -> [n][H][2 W] Y210 words (the bit pattern of
+    the uint16 in an int16): to_422's picture with 10-bit codes (Y 64 .. 940,
+    C 64 .. 960), each stored as code << 6, words Y0 Cb Y1 Cr."""
+    n, H, W, _ = rgba.shape
+    out = torch.empty((n, H, 2 * W), dtype=torch.int16, device=rgba.device)
+    code = lambda v: ((torch.clamp(torch.floor(v + 0.5), 0, 1023).to(torch.int32) << 6) & 0xFFFF).to(torch.int16)
+    for k in range(n):
+        f = rgba[k, ..., :3].float() / 255.0
+        r, g, b = f[..., 0], f[..., 1], f[..., 2]
+        yl = 0.299 * r + 0.587 * g + 0.114 * b
+        out[k, :, 0::2] = code(yl * 876.0 + 64.0)
+        out[k, :, 1::4] = code(((b - yl) * (0.5 / 0.886)).reshape(H, W // 2, 2).mean(dim=2) * 896.0 + 512.0)
+        out[k, :, 3::4] = code(((r - yl) * (0.5 / 0.701)).reshape(H, W // 2, 2).mean(dim=2) * 896.0 + 512.0)
     return out
 
 
@@ -149,6 +172,11 @@ def main():
         fmts += [("yuy2", mm355.YUY2), ("uyvy", mm355.UYVY), ("yuy2_bt709", mm355.YUY2 | mm355.MATRIX_BT709)]
     except mm355.MMError:
         pass    # a build from before the packed 4:2:2 formats
+    try:
+        mm355.frame_bytes(W, H, mm355.Y210)
+        fmts += [("y210", mm355.Y210), ("y210_bt709", mm355.Y210 | mm355.MATRIX_BT709)]
+    except (mm355.MMError, AttributeError):
+        pass    # a build from before the 10-bit packed 4:2:2 format
     for name, fmt in fmts:
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
@@ -156,10 +184,12 @@ def main():
             h.synth(rgba, 0, B, stream=torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
             src = rgba
-        elif name in ("nv12_bt709", "p010_bt2020", "yuy2_bt709"):
+        elif name in ("nv12_bt709", "p010_bt2020", "yuy2_bt709", "y210_bt709"):
             src = legs[name.split("_")[0]]["src"]
         elif name == "yuy2":
             src = to_422(torch, rgba)
+        elif name == "y210":
+            src = to_y210(torch, rgba)
         elif name == "uyvy":       # the same picture: every byte pair swapped
             src = legs["yuy2"]["src"].reshape(B, H, W, 2).flip(3).reshape(B, H, 2 * W).contiguous()
         elif name in ("y8", "y16"):
@@ -244,7 +274,17 @@ def main():
         k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
         out["yuy2_bt709_k1_us"] = {"matrixed": k1("yuy2_bt709"), "yuy2": k1("yuy2"), "nv12_bt709": k1("nv12_bt709"),
                                    "rgba8": k1("rgba8")}
-    for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16", "yuy2", "uyvy", "yuy2_bt709"):
+    for name in ("y210", "y210_bt709"):
+        if name in out["formats"]:
+            for base in ("rgba8", "p010", "yuy2"):
+                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                    out["formats"][base]["fps_median"], 4)
+    if "y210_bt709" in out["formats"]:
+        k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
+        out["y210_bt709_k1_us"] = {"matrixed": k1("y210_bt709"), "y210": k1("y210"), "yuy2_bt709": k1("yuy2_bt709"),
+                                   "p010": k1("p010"), "rgba8": k1("rgba8")}
+    for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16", "yuy2", "uyvy", "yuy2_bt709",
+                 "y210", "y210_bt709"):
         if name + "_pitched" in out["formats"]:
             out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
                                                       out["formats"][name]["fps_median"], 4)
