@@ -65,7 +65,8 @@ extern "C" {
 /* frame formats (every entry point that takes frames takes each of them;
  * the NV12 and P010 pairs for even W and H and without the debug views; the
  * single-plane grayscale formats MM_Y8 .. MM_Y16, packed 4:2:2 MM_YUY2 /
- * MM_UYVY and 10-bit packed 4:2:2 MM_Y210 further down) */
+ * MM_UYVY, 10-bit packed 4:2:2 MM_Y210 and packed RGB MM_RGB24 / MM_BGR24
+ * further down) */
 #define MM_RGBA8   0       /* 4 B/px, UNORM: v = byte / 255; out round(saturate(v) * 255) */
 #define MM_RGBA32F 1       /* 16 B/px, linear float                                       */
 /* The frames the reference actually receives (since ABI 10): its camera
@@ -328,6 +329,60 @@ extern "C" {
 #define MM_Y210      22   /* 10-bit packed 4:2:2, words Y0 Cb Y1 Cr, BT.601 limited range */
 #define MM_Y210_FULL 23   /* the same, full range */
 
+/* Packed RGB frames (a backward-compatible addition to ABI 10: a caller
+ * detects it by mm_frame_bytes(W, H, MM_RGB24, &n) == MM_OK).  What Python and
+ * desktop imaging hand out: cv2.VideoCapture / cv2.imread (in B, G, R order),
+ * PIL, imageio, torchvision, ffmpeg's rgb24 / bgr24, binary PPM: [H, W, 3]
+ * bytes.  One plane, tightly packed: H rows of W three-byte pixels, bytes
+ * R G B (MM_RGB24) or B G R (MM_BGR24 = MM_RGB24 | MM_ORDER_BGR), 3 W bytes per
+ * row and 3 W H per frame (1920 x 1080: 6,220,800 bytes, pitch 5,760); frame k
+ * of a stream at k * mm_frame_bytes.  There is no alpha byte and no
+ * subsampling: every size the RGBA formats take, odd W and H included, every
+ * mode (pyramid, standard, steerable) and the debug views.
+ * The frame IS the RGBA32F frame R, G, B = byte / 255, alpha 1, equivalently
+ * the MM_RGBA8 frame with the same colour bytes and alpha 255, and the result
+ * the reference's result on it:
+ *   in:  v = byte / 255 per channel, as MM_RGBA8;
+ *   out: round(saturate(v) * 255) per channel, MM_RGBA8's rule, three bytes.
+ * Two identities hold bitwise, in every mode, view, call form and layout:
+ *   1. the output bytes are the MM_RGBA8 path's R, G, B bytes on that frame,
+ *      and the temporal state (mm_get_state / mm_compute_state) is bitwise
+ *      that MM_RGBA8 frame's (the operator gives alpha weight 0 everywhere);
+ *   2. MM_BGR24 on the byte-swapped frame gives the byte-swapped output of
+ *      MM_RGB24, and the same state.
+ * A debug view's output is the MM_RGBA8 view's R, G, B bytes (R the view's
+ * value, G = B = 0, in the frame's byte order).  The first frame after
+ * mm_create / mm_reset and apply_magnification = 0 pass all 3 W H bytes through
+ * bitwise.  in_layout->format == out_layout->format, as everywhere: MM_RGB24
+ * in with MM_BGR24 out is MM_ERR_INVALID.
+ * The byte-order bit is valid on MM_RGB24 alone: MM_RGBA8 | 128,
+ * MM_RGBA8_SRGB | 128, the bit on any Y'CbCr or single-plane code, code 14, a
+ * matrix bit on 13 or 141 (45, 77, 173), any other stray bit (13 | 256) and
+ * negative codes are MM_ERR_INVALID from mm_frame_bytes, mm_surface_* and every
+ * frame entry point, before anything is queued.
+ * Surfaces: the unit u is 1: a real [H, W, 3] array and any region of interest
+ * of one start at any byte; chroma_offset = chroma_pitch = 0 (else
+ * MM_ERR_INVALID); pitch >= 3 W, any value; device frame pointers and
+ * frame_stride need no alignment (frame_stride >= extent when count > 1); the
+ * extent and 4 GiB rules are unchanged.  mm_surface_aligned(1920, 1080,
+ * MM_RGB24, 256, 16) has pitch 5,888 and frame_stride 6,406,144;
+ * mm_surface_aligned(97, 63, MM_RGB24, 256, 16) has pitch 512, frame_stride
+ * 32,768 and extent 32,035.  Padding is never read and never written, the byte
+ * after a row's last pixel included.  The fused kernels' quads (four pixels,
+ * 12 bytes, one 12-byte load and one 12-byte store at a 4-byte-aligned
+ * address) run where base, pitch and, past one frame, frame_stride are
+ * multiples of 4 on both sides (every tight frame with W % 8 == 0); any other
+ * legal layout takes the unfused kernels: the same bytes.  3 bytes per pixel
+ * travel each way and nobody widens a frame to RGBA8 or strips an alpha.
+ * Out of scope: BGRA8 / BGRA8 sRGB (MM_ORDER_BGR on MM_RGBA8 / MM_RGBA8_SRGB
+ * is where they can live later; today MM_ERR_INVALID); RGB48; planar RGB; an
+ * sRGB-decoded RGB24; MM_RGB24 in with MM_BGR24 out; the LDS-DMA staging of the
+ * fused kernels' source rows (MM_RGBA8's alone: 4-byte pixels); the ring
+ * entry points (include/mm_ring.h); the Unity shim; mm_extmem_check. */
+#define MM_RGB24     13    /* 3 B/px, bytes R G B, UNORM as MM_RGBA8, no alpha */
+#define MM_ORDER_BGR 128   /* byte-order bit: B G R */
+#define MM_BGR24     (MM_RGB24 | MM_ORDER_BGR)   /* 141 */
+
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0  /* usePyramidDecomposition = true (.cs:18, :128-131) */
 #define MM_MODE_STANDARD  1   /* usePyramidDecomposition = false (.cs:132-135, :208-232) */
@@ -436,7 +491,8 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  * queues anything; no GPU needed).  With the unit u = the pixel size of an RGBA
  * format (4, 16, 8, 4), 2 for NV12 (a (Cb, Cr) pair), 4 for P010 and packed
  * 4:2:2, 8 for MM_Y210 (a macropixel each) and the sample
- * size of a single-plane format (1 for MM_Y8, 2 for MM_Y10 / Y12 / Y16):
+ * size of a single-plane format (1 for MM_Y8, 2 for MM_Y10 / Y12 / Y16), 1 for
+ * packed RGB (MM_RGB24 / MM_BGR24: any byte):
  *   - unknown format: MM_ERR_INVALID; 4:2:0 with odd W or H: MM_ERR_UNSUPPORTED;
  *   - pitch (4:2:0: and chroma_pitch) at least the row's sample bytes (W pixels;
  *     4:2:0: W samples) and a multiple of u; chroma_offset a multiple of u and
@@ -459,7 +515,7 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  * an unaligned frame takes the narrower access, never another kernel: a layout
  * aligned like a decoder's runs exactly the tight layout's kernels. */
 typedef struct {
-    int    format;         /* MM_RGBA8 ... MM_UYVY_FULL, MM_Y210(_FULL); 4:2:0 and 4:2:2: | MM_MATRIX_* */
+    int    format;         /* MM_RGBA8 ... MM_UYVY_FULL, MM_Y210(_FULL), MM_RGB24 / MM_BGR24; 4:2:0 and 4:2:2: | MM_MATRIX_* */
     size_t pitch;          /* bytes from one row to the next: RGBA rows, or luma rows */
     size_t chroma_offset;  /* 4:2:0: bytes from the frame's base to the (Cb,Cr) plane; else 0 */
     size_t chroma_pitch;   /* 4:2:0: bytes from one (Cb,Cr) row to the next; else 0 */

@@ -204,13 +204,19 @@ struct ProfScope {
 // argument is the format code itself (Pix<FMT>, mm_kernels.hpp).
 static inline size_t fmt_bpp(int fmt)
 {
-    return fmt == MM_RGBA32F ? 16 : fmt == MM_RGBA16F ? 8 : fmt == MM_Y8 ? 1 : fmt >= MM_Y10 && fmt <= MM_Y16 ? 2 : 4;
+    return fmt == MM_RGBA32F ? 16 : fmt == MM_RGBA16F ? 8 : fmt == MM_Y8 ? 1 : fmt >= MM_Y10 && fmt <= MM_Y16 ? 2 :
+           fmt == MM_RGB24 || fmt == MM_BGR24 ? 3 : 4;
 }
 static constexpr int kMatrixBits = MM_MATRIX_BT709 | MM_MATRIX_BT2020;
 // A 4:2:0 or packed 4:2:2 code may carry one matrix bit (MM_MATRIX_BT709 /
 // MM_MATRIX_BT2020): layout, sizes and units are its base code's, the bit
 // changes coefficients (geo_of) and K1's instance (MM_FMT_SWITCH_K1).
-static inline int fmt_base(int fmt) { return fmt & ~kMatrixBits; }
+// The byte-order bit MM_ORDER_BGR is valid on MM_RGB24 alone (MM_BGR24): the
+// base code of both is MM_RGB24, the bit sets the order uniforms (geo_of).  On
+// any other code the bit stays in the base, which is then no format.
+static inline int fmt_base(int fmt) { return fmt == MM_BGR24 ? MM_RGB24 : fmt & ~kMatrixBits; }
+// packed RGB: three bytes per pixel, R G B or B G R
+static inline bool fmt_rgb24(int fmt) { return fmt == MM_RGB24 || fmt == MM_BGR24; }
 static inline int fmt_matrix(int fmt) { return fmt & kMatrixBits; }
 static inline bool fmt_nv12(int fmt) { return fmt_base(fmt) == MM_NV12 || fmt_base(fmt) == MM_NV12_FULL; }
 static inline bool fmt_p010(int fmt) { return fmt_base(fmt) == MM_P010 || fmt_base(fmt) == MM_P010_FULL; }
@@ -232,6 +238,7 @@ static inline int mono_max(int fmt) { return fmt == MM_Y8 ? 255 : fmt == MM_Y10 
 static inline bool fmt_valid(int fmt)
 {
     if (fmt_mono(fmt)) return true;   // (a matrix bit on these codes: no 4:2:0 base, invalid below)
+    if (fmt_rgb24(fmt)) return true;  // (the two exact codes: 14, a matrix bit, the order bit elsewhere stay invalid)
     if (fmt == MM_RGBA8 || fmt == MM_RGBA32F || fmt == MM_RGBA16F || fmt == MM_RGBA8_SRGB) return true;
     // (any other bit, a negative code included, leaves a base that is no 4:2:0 code)
     return fmt_ycc(fmt) && fmt_matrix(fmt) != kMatrixBits;
@@ -261,7 +268,8 @@ static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
 // (packed 4:2:2: one macropixel, 4 bytes or, MM_Y210, 8)
 static inline size_t fmt_unit(int fmt)
 {
-    return fmt_nv12(fmt) ? 2 : fmt_p010(fmt) || fmt_422(fmt) ? 4 : fmt_y210(fmt) ? 8 : fmt_bpp(fmt);
+    // (packed RGB: 1, a real [H, W, 3] array or a region of one starts at any byte)
+    return fmt_nv12(fmt) ? 2 : fmt_p010(fmt) || fmt_422(fmt) ? 4 : fmt_y210(fmt) ? 8 : fmt_rgb24(fmt) ? 1 : fmt_bpp(fmt);
 }
 // sample bytes of one row (4:2:0: of a luma row and of a (Cb, Cr) row alike;
 // MM_Y210: 4 W, fmt_bpp's default)
@@ -363,6 +371,8 @@ static_assert(kFmtYUY2 == MM_YUY2 && kFmtYUY2M == (MM_YUY2 | MM_MATRIX_BT709),
               "the kernels' packed 4:2:2 template arguments are the YUY2 limited-range codes");
 static_assert(kFmtY210 == MM_Y210 && kFmtY210M == (MM_Y210 | MM_MATRIX_BT709),
               "the kernels' 10-bit packed 4:2:2 template arguments are the Y210 limited-range codes");
+static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && !(MM_ORDER_BGR & kMatrixBits),
+              "the kernels' packed RGB template argument is the MM_RGB24 code; the order bit is no matrix bit");
 // Runs the statement with the compile-time format FMT_ of the runtime `fmt`
 // (both NV12 ranges run the MM_NV12 instances, both P010 ranges the MM_P010
 // instances, whatever the matrix bit, the three word depths of the
@@ -381,6 +391,7 @@ static_assert(kFmtY210 == MM_Y210 && kFmtY210M == (MM_Y210 | MM_MATRIX_BT709),
     case MM_YUY2: case MM_YUY2_FULL: case MM_UYVY: case MM_UYVY_FULL:          \
         { constexpr int FMT_ = MM_YUY2; __VA_ARGS__; } break;                  \
     case MM_Y210: case MM_Y210_FULL: { constexpr int FMT_ = MM_Y210; __VA_ARGS__; } break; \
+    case MM_RGB24: { constexpr int FMT_ = MM_RGB24; __VA_ARGS__; } break;      \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
 // ... K1's: a code with a matrix bit runs the matrixed NV12 / P010 instance,
@@ -409,6 +420,7 @@ template <int F> constexpr int kK1Fmt = F == MM_Y8 ? kFmtNV12 : F == MM_Y16 ? kF
     case MM_RGBA32F: { constexpr int FMT_ = MM_RGBA32F; __VA_ARGS__; } break;  \
     case MM_RGBA16F: { constexpr int FMT_ = MM_RGBA16F; __VA_ARGS__; } break;  \
     case MM_RGBA8_SRGB: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break; \
+    case MM_RGB24: case MM_BGR24: { constexpr int FMT_ = MM_RGB24; __VA_ARGS__; } break; \
     default: return MM_ERR_UNSUPPORTED;                                        \
     }
 
@@ -517,6 +529,10 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
         g.nv.y_unit = (float)(1.0 / mx);
         g.nv.yo_scale = (float)mx;
         g.nv.yo_bias = 0.5f;
+    } else if (fmt_rgb24(fmt)) {
+        // the byte order, the same on both sides (0: R G B, 1: B G R): K1's dot
+        // weights and the compose kernels' byte selectors derive from it
+        g.li.yb = g.lo.yb = fmt == MM_BGR24 ? 1u : 0u;
     }
     return g;
 }
@@ -742,7 +758,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)k34_lds_bytes<12>(false);
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         // k_sb_cols: exchange buffer (36.9 KB) + its own staging, past 64 KB for
@@ -771,7 +787,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 11) {   // k_rows_inv_compose4: four 2048-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 4 * lds_complex<2048>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
     }
@@ -954,10 +970,24 @@ static bool k34_src_dma(const uint8_t *in, const Frames &fr, int nframes)
     if (nframes > 1) m |= fr.in.stride;
     return (m & 15u) == 0;
 }
+// Packed RGB's quads are 12 bytes at 3 X (X % 4 == 0) from the row's start,
+// one dwordx3 load and one dwordx3 store typed 4-byte aligned: every row of
+// every frame of the launch starts on a multiple of 4, on both sides (every
+// tight frame with W % 8 == 0: 3 W and 3 W H are multiples of 4).  The unit is
+// 1, so a valid layout may fail this (a region of interest at byte offset 21,
+// a pitch of 3 W + 3): it takes the unfused pair, whose accesses are
+// byte-aligned dword loads and byte stores.  Same arithmetic, same results.
+static bool rgb24_quads_aligned(const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
+{
+    uintptr_t m = reinterpret_cast<uintptr_t>(in) | fr.in.pitch | reinterpret_cast<uintptr_t>(out) | fr.out.pitch;
+    if (nframes > 1) m |= fr.in.stride | fr.out.stride;
+    return (m & 3u) == 0;
+}
 static bool k34_fits(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
     if (fmt_nv12(fr.fmt) && !nv12_quads_aligned(in, out, fr, nframes)) return false;
     if (fmt_mono(fr.fmt) && !mono_quads_aligned(out, fr, nframes)) return false;
+    if (fmt_rgb24(fr.fmt) && !rgb24_quads_aligned(in, out, fr, nframes)) return false;
     const Geo &g = h->geo;
     return g.N <= 4096 &&   // two transforms per workgroup: 2 N / 8 <= 1024 threads
            !g.ox && !g.oy && g.W % 8 == 0 && g.x0 >= 4 && g.x0 % 4 == 0 &&

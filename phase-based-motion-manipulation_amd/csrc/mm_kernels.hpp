@@ -519,6 +519,9 @@ template <int FMT> constexpr bool k422 = FMT == kFmtYUY2 || FMT == kFmtYUY2M;
 constexpr int kFmtY210 = 22;   // MM_Y210
 constexpr int kFmtY210M = 54;  // MM_Y210 | MM_MATRIX_BT709 (K1 only: any matrixed Y210)
 template <int FMT> constexpr bool kY210 = FMT == kFmtY210 || FMT == kFmtY210M;
+// packed RGB (section below): kFmtRGB24 runs every MM_RGB24 and MM_BGR24 frame
+constexpr int kFmtRGB24 = 13;  // MM_RGB24
+template <int FMT> constexpr bool kRGB24 = FMT == kFmtRGB24;
 // an input macropixel's chroma bytes (byte order: Geo::li.yb; the shifts are uniform)
 __device__ __forceinline__ float c422_cb(unsigned u, const Geo &g) { return (float)((u >> (8u - 8u * g.li.yb)) & 255u); }
 __device__ __forceinline__ float c422_cr(unsigned u, const Geo &g) { return (float)((u >> (24u - 8u * g.li.yb)) & 255u); }
@@ -559,6 +562,7 @@ __device__ __forceinline__ float k1_luma(typename LumaSrc<FMT>::raw_t u, const G
 template <int FMT> __device__ __forceinline__ float k1_unit(const Geo &g)
 {
     if constexpr (k420<FMT> || k422<FMT> || kY210<FMT>) return g.nv.y_unit;
+    else if constexpr (kRGB24<FMT>) return kLumaUnit<0>;   // RGBA8's integer luma
     else return kLumaUnit<FMT>;
 }
 // K1, matrixed frames: what a (Cb, Cr) pair adds to the luma of its 2x2
@@ -617,6 +621,7 @@ template <int FMT> __device__ __forceinline__ c2 c420_iq2(unsigned u, const Geo 
     if constexpr (kP010<FMT>) return p010_iq2(u, g);
     else return nv12_iq2(u, g);
 }
+__device__ __forceinline__ c2 rgb24_iq2(uint32_t u, const Geo &g);   // (packed RGB section below)
 // the compose kernels' (I, Q) of a staged raw sample
 template <int FMT>
 __device__ __forceinline__ c2 src_iq2(typename ChromaSrc<FMT>::raw_t u, const Geo &g)
@@ -624,6 +629,7 @@ __device__ __forceinline__ c2 src_iq2(typename ChromaSrc<FMT>::raw_t u, const Ge
     if constexpr (k420<FMT>) return c420_iq2<FMT>(u, g);
     else if constexpr (k422<FMT>) return c422_iq2(u, g);
     else if constexpr (kY210<FMT>) return y210_iq2(u, g);
+    else if constexpr (kRGB24<FMT>) return rgb24_iq2(u, g);
     else return chroma_iq2<FMT>(u);
 }
 // Output of one pixel from yiq_rgb's saturated RGB: the luma code and the
@@ -771,6 +777,130 @@ __device__ __forceinline__ void mono_store_quad(uint8_t *row, unsigned X, const 
     else st_stream_pair_a4(row, X * 2u, c[0] | c[1] << 16, c[2] | c[3] << 16);
 }
 
+// ---- packed RGB (MM_RGB24 / MM_BGR24) access -------------------------------
+// A frame is H rows of W three-byte pixels, bytes R G B (MM_RGB24) or B G R
+// (MM_BGR24), UNORM as MM_RGBA8's and no alpha byte.  It IS the MM_RGBA8 frame
+// with the same colour bytes and alpha 255 (include/mm.h), and the operator
+// gives the alpha byte weight 0 everywhere, so every value is computed by
+// MM_RGBA8's own expressions (luma_units<0>'s integer, chroma_iq2<0>,
+// Pix<0>::pack) and the output bytes and the state are bitwise that frame's:
+// a 3-byte pixel is an addressing problem.  Both byte orders share the one
+// instance of every kernel (FMT = kFmtRGB24); the order travels in Geo::li.yb /
+// lo.yb (0: R first, 1: B first), where packed 4:2:2 keeps its own, and turns
+// into uniform operands: K1's two dot weights, the compose's byte selectors.
+//   Loads of one pixel (K1, the unfused, odd-size kernels, the fused kernels'
+//     two outer columns): ONE byte-aligned dword at 3 col, whose fourth byte is
+//     the next pixel's first and is never used (weight 0 in K1's dots, dropped
+//     by the selector elsewhere).  The row's last pixel is loaded one byte
+//     earlier and shifted down 8, so no byte outside the row's 3 W is touched
+//     (W >= 2).  Three lanes in four are misaligned; global memory takes that.
+//     (The other form, two aligned dwords and v_alignbyte_b32, was built and
+//     measured in K1: the same time per 1080p frame, 5.3-5.4 us, with twice
+//     the loads, 90 VGPRs for 57 at N = 2048 and 19 spilled at N = 8192.  Not
+//     kept.  DESIGN.md, "Packed RGB frames".)
+//   K1: the luma is RGBA8's exact integer 299 R + 587 G + 114 B by the same two
+//     v_dot4_u32_u8, the weights in the frame's byte order (R G B: 0x00000201
+//     and 0x00724B2B; B G R: 0x00010200 and 0x002B4B72), so every form (regular,
+//     shared rows, LAT, GEN) has the RGBA8 instance's lumas bit for bit.
+//   compose: a pixel's R, G, B come out of the loaded dword(s) by one v_perm_b32
+//     with a uniform selector as the RGBA8 word R | G << 8 | B << 16 and go
+//     through chroma_iq2<0>; results are packed by Pix<0>::pack and leave
+//     through the same permute.  The fused kernels' quad X .. X+3 (X % 4 == 0)
+//     is 12 bytes at 3 X: one dwordx3 load and one non-temporal dwordx3 store,
+//     typed 4-byte aligned like RGBA8's quads (ld_quad_a4), which the host
+//     launches only where every row of the launch starts on a multiple of 4
+//     on both sides (rgb24_quads_aligned, mm_impl.hpp; any other layout takes
+//     the unfused pair).  The unfused kernels store a pixel as three bytes.
+// The unit is 1: base, pitch and stride are any bytes.  No subsampling: odd
+// sizes and the debug views (R = the view's value, G = B = 0, as RGBA8's) are
+// supported.  The LDS-DMA source staging stays RGBA8's (4-byte pixels).
+template <> struct LumaSrc<kFmtRGB24> {    // the dword that starts at the pixel
+    using raw_t = uint32_t;
+    static constexpr int bpp = 3;
+};
+template <> struct ChromaSrc<kFmtRGB24> { using raw_t = uint32_t; };
+typedef uint32_t u32_a1 __attribute__((aligned(1)));
+typedef unsigned u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
+// byte offset in its row of the dword loaded for pixel column col, and the
+// pixel (its three bytes in the low 24 bits) of that dword
+__device__ __forceinline__ unsigned rgb24_off(unsigned col, const Geo &g)
+{
+    return 3u * col - (col == (unsigned)(g.W - 1) ? 1u : 0u);
+}
+__device__ __forceinline__ uint32_t rgb24_fix(uint32_t u, unsigned col, const Geo &g)
+{
+    return col == (unsigned)(g.W - 1) ? u >> 8 : u;
+}
+__device__ __forceinline__ uint32_t rgb24_px(const void *row, unsigned row_off, unsigned col, const Geo &g)
+{
+    const uint32_t u = *reinterpret_cast<const u32_a1 *>(reinterpret_cast<const uint8_t *>(row) + (row_off + rgb24_off(col, g)));
+    return rgb24_fix(u, col, g);
+}
+// K1: luma_units<0>'s integer of a pixel in the frame's byte order
+__device__ __forceinline__ float rgb24_luma_units(uint32_t u, const Geo &g)
+{
+    const unsigned w0 = g.li.yb ? 0x00010200u : 0x00000201u, w1 = g.li.yb ? 0x002B4B72u : 0x00724B2Bu;
+    const unsigned hi = __builtin_amdgcn_udot4(u, w0, 0u, false);     // R + 2 G
+    return (float)__builtin_amdgcn_udot4(u, w1, hi << 8, false);      // + 43 R + 75 G + 114 B
+}
+// v_perm_b32 selector of three bytes that start at byte `pos` of the pair
+// (hi : lo), as R | G << 8 | B << 16 (top byte 0) for byte order yb, and the
+// reverse for pos = 0: the frame's three bytes of an RGBA8 word
+__device__ __forceinline__ unsigned rgb24_sel(unsigned pos, unsigned yb)
+{
+    return 0x0C000000u | (pos + 1u) << 8 | (yb ? pos << 16 | (pos + 2u) : (pos + 2u) << 16 | pos);
+}
+// the RGBA8 word (alpha byte 0, never used) of a loaded pixel, and its (I, Q)
+__device__ __forceinline__ uint32_t rgb24_canon(uint32_t u, const Geo &g)
+{
+    return __builtin_amdgcn_perm(u, u, rgb24_sel(0u, g.li.yb));
+}
+__device__ __forceinline__ c2 rgb24_iq2(uint32_t u, const Geo &g) { return chroma_iq2<0>(rgb24_canon(u, g)); }
+// one output pixel of row `row` (the unfused, odd-size and debug kernels):
+// Pix<0>::pack's bytes in the frame's order, three byte stores
+__device__ __forceinline__ void rgb24_store(uint8_t *row, unsigned X, float r, float gg, float b, const Geo &g)
+{
+    const uint32_t q = __builtin_amdgcn_perm(0u, Pix<0>::pack(r, gg, b), rgb24_sel(0u, g.lo.yb));
+    st_off<uint8_t>(row, 3u * X, (uint8_t)q);
+    st_off<uint8_t>(row, 3u * X + 1u, (uint8_t)(q >> 8));
+    st_off<uint8_t>(row, 3u * X + 2u, (uint8_t)(q >> 16));
+}
+// The fused kernels' (I, Q) of source columns X-1 .. X+4 (cl, cr: the outer
+// two, wrapped or clamped) of source row `row`: the quad's 12 bytes as one load
+__device__ __forceinline__ void rgb24_quad_iq(const uint8_t *img, const Geo &g, int row, unsigned X, unsigned cl,
+                                              unsigned cr, c2 (&a)[6])
+{
+    const unsigned ro = (unsigned)row * g.li.pitch;
+    const uint32_t pl = rgb24_px(img, ro, cl, g);
+    const u32x3_a4 m = *reinterpret_cast<const u32x3_a4 *>(img + (ro + 3u * X));
+    const uint32_t pr = rgb24_px(img, ro, cr, g);
+    const unsigned yb = g.li.yb;
+    a[0] = rgb24_iq2(pl, g);
+    a[1] = chroma_iq2<0>(__builtin_amdgcn_perm(m.x, m.x, rgb24_sel(0u, yb)));   // bytes 0 .. 2
+    a[2] = chroma_iq2<0>(__builtin_amdgcn_perm(m.y, m.x, rgb24_sel(3u, yb)));   // 3 .. 5
+    a[3] = chroma_iq2<0>(__builtin_amdgcn_perm(m.z, m.y, rgb24_sel(2u, yb)));   // 6 .. 8
+    a[4] = chroma_iq2<0>(__builtin_amdgcn_perm(m.z, m.z, rgb24_sel(1u, yb)));   // 9 .. 11
+    a[5] = rgb24_iq2(pr, g);
+}
+// The fused kernels' store of output row i of the quad X .. X+3 (X % 4 == 0):
+// four packed pixels as 12 bytes, one non-temporal store at a dword-aligned
+// address.  Byte j of output pixel k is byte c(j) of its RGBA8 word, c(j) = j
+// (R G B) or 2 - j (B G R).
+__device__ __forceinline__ void rgb24_store_quad(uint8_t *outp, const Geo &g, int i, int X, const float (&rr)[4],
+                                                 const float (&gg)[4], const float (&bb)[4])
+{
+    uint32_t p[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = Pix<0>::pack(rr[k], gg[k], bb[k]);
+    const bool sw = g.lo.yb != 0;
+    u32x3_a4 w;
+    w.x = __builtin_amdgcn_perm(p[1], p[0], sw ? 0x06000102u : 0x04020100u);   // c0 c1 c2 | c0
+    w.y = __builtin_amdgcn_perm(p[2], p[1], sw ? 0x05060001u : 0x05040201u);   // c1 c2 | c0 c1
+    w.z = __builtin_amdgcn_perm(p[3], p[2], sw ? 0x04050600u : 0x06050402u);   // c2 | c0 c1 c2
+    unsigned off = (unsigned)X * 3u;
+    __builtin_nontemporal_store(w, reinterpret_cast<u32x3_a4 *>(outp + (size_t)((unsigned)i * g.lo.pitch) + off));
+}
+
 // ---- packed 4:2:2 (MM_YUY2 / MM_UYVY) access -------------------------------
 // A frame is one plane of H rows of W / 2 four-byte macropixels, Y0 Cb Y1 Cr
 // (YUY2) or Cb Y0 Cr Y1 (UYVY): two pixels that share one (Cb, Cr) pair; W and
@@ -828,6 +958,20 @@ template <int FMT> __device__ __forceinline__ unsigned k1_off(unsigned col)
     else if constexpr (FMT == kFmtY210M) return (col & ~1u) * 4u;
     else return col * (unsigned)LumaSrc<FMT>::bpp;
 }
+// ... of the load for pixel column col (packed RGB: the row's last pixel is
+// loaded one byte earlier, rgb24_off)
+template <int FMT> __device__ __forceinline__ unsigned k1_off(unsigned col, [[maybe_unused]] const Geo &g)
+{
+    if constexpr (kRGB24<FMT>) return rgb24_off(col, g);
+    else return k1_off<FMT>(col);
+}
+// K1's load of a sample (packed RGB: a dword at any byte)
+template <int FMT> __device__ __forceinline__ typename LumaSrc<FMT>::raw_t k1_ld(const void *row, unsigned off)
+{
+    // (the typedef itself: a template argument would drop its alignment)
+    if constexpr (kRGB24<FMT>) return *reinterpret_cast<const u32_a1 *>(reinterpret_cast<const uint8_t *>(row) + off);
+    else return ld_off<typename LumaSrc<FMT>::raw_t>(row, off);
+}
 // K1: the luma of column col's loaded sample (in k1_luma's units).  One
 // expression for the three load forms.
 template <int FMT>
@@ -843,6 +987,8 @@ __device__ __forceinline__ float k1_luma_at(typename LumaSrc<FMT>::raw_t u, [[ma
         return k1_luma<kFmtP010M>((uint16_t)yc, g) + k1_chroma<kFmtP010M>(y210_cword(u), g);
     } else if constexpr (FMT == kFmtY210) {
         return k1_luma<kFmtP010>((uint16_t)(u & 0xFFFFu), g);
+    } else if constexpr (kRGB24<FMT>) {
+        return rgb24_luma_units(rgb24_fix(u, col, g), g);
     } else {
         return k1_luma<FMT>(u, g);
     }
@@ -1044,8 +1190,13 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
                 float va = 0.0f, vb = 0.0f;
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    va += ta.w[m] * k1_luma<FMT>(ld_off<raw_t>(img, pa[m] + (unsigned)i * BPP), g);
-                    vb += tb.w[m] * k1_luma<FMT>(ld_off<raw_t>(img, pb[m] + (unsigned)i * BPP), g);
+                    if constexpr (kRGB24<FMT>) {   // (the byte-aligned dword of pixel i)
+                        va += ta.w[m] * rgb24_luma_units(rgb24_px(img, pa[m], (unsigned)i, g), g);
+                        vb += tb.w[m] * rgb24_luma_units(rgb24_px(img, pb[m], (unsigned)i, g), g);
+                    } else {
+                        va += ta.w[m] * k1_luma<FMT>(ld_off<raw_t>(img, pa[m] + (unsigned)i * BPP), g);
+                        vb += tb.w[m] * k1_luma<FMT>(ld_off<raw_t>(img, pb[m] + (unsigned)i * BPP), g);
+                    }
                 }
                 V[i] = va;
                 V[g.W + i] = vb;
@@ -1094,9 +1245,9 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
 #pragma unroll
                 for (int u = 0; u < CB; ++u) {
                     const unsigned col = (unsigned)min((int)threadIdx.x + (h * CB + u) * 2 * T, g.W - 1);
-                    const unsigned off = k1_off<FMT>(col);
+                    const unsigned off = k1_off<FMT>(col, g);
 #pragma unroll
-                    for (int d = 0; d < 6; ++d) px[u][d] = ld_off<raw_t>(rowp[d], off);
+                    for (int d = 0; d < 6; ++d) px[u][d] = k1_ld<FMT>(rowp[d], off);
                     if constexpr (kMatrixed<FMT>) {
 #pragma unroll
                         for (int d = 0; d < 4; ++d)
@@ -1150,9 +1301,9 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
                 const unsigned col = (unsigned)min(t + (h * UB + u) * T, g.W - 1);
-                const unsigned off = k1_off<FMT>(col);
+                const unsigned off = k1_off<FMT>(col, g);
 #pragma unroll
-                for (int d = 0; d < 4; ++d) px[u][d] = ld_off<raw_t>(rowp[d], off);
+                for (int d = 0; d < 4; ++d) px[u][d] = k1_ld<FMT>(rowp[d], off);
                 if constexpr (kMatrixed<FMT>) {
 #pragma unroll
                     for (int d = 0; d < 3; ++d)
@@ -2549,14 +2700,20 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
         if constexpr (k420<FMT>) return c420_off<FMT>(g, row, col);
         else if constexpr (k422<FMT>) return c422_off(g, row, col);
         else if constexpr (kY210<FMT>) return y210_off(g, row, col);
+        else if constexpr (kRGB24<FMT>) return (unsigned)row * g.li.pitch;   // (the row: rgb24_px adds the column)
         else return (unsigned)row * g.li.pitch + col * Pix<FMT>::bpp;
+    };
+    // (packed RGB: the byte-aligned dword of the pixel)
+    auto ld_src = [&](int row, unsigned col) {
+        if constexpr (kRGB24<FMT>) return rgb24_px(img, src_off(row, col), col, g);
+        else return ld_off<raw_t>(img, src_off(row, col));
     };
     const unsigned colA = (unsigned)wrap_near(min(c0 - 1 + tid, g.W), g.W, g.edge);
     raw_t pa[TR + 2];
 #pragma unroll
     for (int sr = 0; sr < TR + 2; ++sr) {   // all staging loads in flight, then convert
         const int row = wrap_near(min(i0 - 1 + sr, g.H), g.H, g.edge);
-        pa[sr] = ld_off<raw_t>(img, src_off(row, colA));
+        pa[sr] = ld_src(row, colA);
     }
     const int X = c0 + tid;
     const bool vx = X < g.W;
@@ -2580,7 +2737,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     const int hs = min(tid, NH - 1);
     const int hrow = wrap_near(min(i0 - 1 + (hs >> 1), g.H), g.H, g.edge);
     const int hcol = wrap_near(min(c0 - 1 + TC + (hs & 1), g.W), g.W, g.edge);
-    const raw_t ph = ld_off<raw_t>(img, src_off(hrow, (unsigned)hcol));
+    const raw_t ph = ld_src(hrow, (unsigned)hcol);
     if (tid < NH) iq[(hs >> 1) * WC + TC + (hs & 1)] = src_iq2<FMT>(ph, g);
 #pragma unroll
     for (int sr = 0; sr < TR + 2; ++sr) iq[sr * WC + tid] = src_iq2<FMT>(pa[sr], g);
@@ -2670,6 +2827,8 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)half, 0xB1, 0xF, 0xF, true);
                 if (!(X & 1))
                     st_stream<uint2>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 4u, make_uint2(half, other));
+            } else if constexpr (kRGB24<FMT>) {   // three bytes per lane
+                rgb24_store(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, rr, gg, bb, g);
             } else {
                 Pix<FMT>::store(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
             }
@@ -2808,6 +2967,9 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
             } else if constexpr (kY210<FMT>) {
                 // ... of 8 bytes each: the quad's own two as one 16-byte load
                 y210_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
+            } else if constexpr (kRGB24<FMT>) {
+                // three-byte pixels: the quad's own four as one 12-byte load
+                rgb24_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
             } else if constexpr (k420<FMT>) {
                 // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
                 // outer two wrapped or clamped as pixels, then halved): the quad's
@@ -3031,6 +3193,8 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         c422_store_quad(outp, g, i, X, rr, gg, bb);
                     } else if constexpr (kY210<FMT>) {
                         y210_store_quad(outp, g, i, X, rr, gg, bb);
+                    } else if constexpr (kRGB24<FMT>) {
+                        rgb24_store_quad(outp, g, i, X, rr, gg, bb);
                     } else if constexpr (k420<FMT>) {
                         c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
                     } else if constexpr (bpp == 4) {
@@ -3157,6 +3321,9 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
             } else if constexpr (kY210<FMT>) {
                 // ... of 8 bytes each: the quad's own two as one 16-byte load
                 y210_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
+            } else if constexpr (kRGB24<FMT>) {
+                // three-byte pixels: the quad's own four as one 12-byte load
+                rgb24_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
             } else if constexpr (k420<FMT>) {
                 // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
                 // outer two wrapped or clamped as pixels, then halved): the quad's
@@ -3250,6 +3417,8 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                 c422_store_quad(outp, g, i, X, rr, gg, bb);
             } else if constexpr (kY210<FMT>) {
                 y210_store_quad(outp, g, i, X, rr, gg, bb);
+            } else if constexpr (kRGB24<FMT>) {
+                rgb24_store_quad(outp, g, i, X, rr, gg, bb);
             } else if constexpr (k420<FMT>) {
                 c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
             } else if constexpr (bpp == 4) {
@@ -3313,10 +3482,17 @@ void k_compose_odd(const float *__restrict__ Yh, size_t yh_stride, const uint8_t
                     float hi = 0.0f, hq = 0.0f;
                     for (int b = 0; b < 4; ++b) {
                         const int sc = wrap_near(tc.idx[b], g.W, g.edge);
-                        const float2 iq = chroma_iq<FMT>(ld_off<typename Pix<FMT>::raw_t>(
-                            img, (unsigned)sr * g.li.pitch + (unsigned)sc * Pix<FMT>::bpp));
-                        hi += tc.w[b] * iq.x;
-                        hq += tc.w[b] * iq.y;
+                        if constexpr (kRGB24<FMT>) {   // RGBA8's expression on the pixel's RGBA8 word
+                            const float2 iq = chroma_iq<0>(
+                                rgb24_canon(rgb24_px(img, (unsigned)sr * g.li.pitch, (unsigned)sc, g), g));
+                            hi += tc.w[b] * iq.x;
+                            hq += tc.w[b] * iq.y;
+                        } else {
+                            const float2 iq = chroma_iq<FMT>(ld_off<typename Pix<FMT>::raw_t>(
+                                img, (unsigned)sr * g.li.pitch + (unsigned)sc * Pix<FMT>::bpp));
+                            hi += tc.w[b] * iq.x;
+                            hq += tc.w[b] * iq.y;
+                        }
                     }
                     ci += tr.w[a] * hi;
                     cq += tr.w[a] * hq;
@@ -3329,6 +3505,7 @@ void k_compose_odd(const float *__restrict__ Yh, size_t yh_stride, const uint8_t
     uint8_t *row = frames_out + (size_t)frame * g.lo.stride + (size_t)((unsigned)Y * g.lo.pitch);
     // gray: R = G = B = the mean of the texels' sat(Y'), whose luma is itself
     if constexpr (kMono<FMT>) mono_store<FMT>(row, (unsigned)X, acc[0], g);
+    else if constexpr (kRGB24<FMT>) rgb24_store(row, (unsigned)X, acc[0], acc[1], acc[2], g);
     else Pix<FMT>::store(row, (unsigned)X, acc[0], acc[1], acc[2]);
 }
 
@@ -3417,10 +3594,11 @@ void k_dbg_out(const float *__restrict__ tex, size_t tex_stride, uint8_t *__rest
     } else {
         v = (show_mag ? mag : pha)[(size_t)(g.y0 + Y) * g.N + g.x0 + X];
     }
-    if (kUnorm<FMT> || kMono<FMT>) v = sat(v);   // UNORM destination
+    if (kUnorm<FMT> || kMono<FMT> || kRGB24<FMT>) v = sat(v);   // UNORM destination
     uint8_t *row = frames_out + (size_t)(frame0 + k) * g.lo.stride + (size_t)((unsigned)Y * g.lo.pitch);
     // a gray frame holds the R channel the view is: the code of its value
     if constexpr (kMono<FMT>) mono_store<FMT>(row, (unsigned)X, v, g);
+    else if constexpr (kRGB24<FMT>) rgb24_store(row, (unsigned)X, v, 0.0f, 0.0f, g);   // (the RGBA8 view's R, G, B)
     else Pix<FMT>::store(row, (unsigned)X, v, 0.0f, 0.0f);
 }
 
@@ -3429,7 +3607,7 @@ void k_dbg_out(const float *__restrict__ tex, size_t tex_stride, uint8_t *__rest
 // =========================================================================
 // One workgroup per (plane row, frame): the row's samples and nothing else, in
 // words of U (NV12 and the 16-bit single-plane formats: 2 bytes, their unit;
-// MM_Y8: 1; every other format: 4, which divides its unit; packed 4:2:2: 4, one macropixel or, MM_Y210, half of one).  `rows_y` RGBA / luma rows, then the (Cb, Cr) rows of a 4:2:0
+// MM_Y8 and packed RGB: 1; every other format: 4, which divides its unit; packed 4:2:2: 4, one macropixel or, MM_Y210, half of one).  `rows_y` RGBA / luma rows, then the (Cb, Cr) rows of a 4:2:0
 // frame.  Tight frames on both sides are one plain device copy instead.
 template <class U>
 __global__ __launch_bounds__(256)

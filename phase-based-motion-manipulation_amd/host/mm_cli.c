@@ -9,7 +9,7 @@
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
  *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
- *          [--yuy2] [--uyvy] [--y210]
+ *          [--yuy2] [--uyvy] [--y210] [--ppm [--bgr]]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
@@ -85,6 +85,14 @@
  * --yuy2, --uyvy, --nv12, --p010, --mono, --srgb, the debug views, the ring
  * modes, any other input and odd sizes.  A C422p10 input needs --y210: it is
  * never converted on the host.
+ * --ppm: the input (-i) is a stream of concatenated binary PPM images (P6,
+ * maxval 255, one size: what ffmpeg -f image2pipe -vcodec ppm writes; host/ppm.h).
+ * Its frames go to the device as MM_RGB24 as they lie, 3 bytes per pixel each
+ * way, and -o gets the same container back.  --bgr swaps R and B on read and
+ * on write and sends MM_BGR24 (the files are the run without it, byte for
+ * byte).  Every size, -l, -s, -b, --standard and --surface-align as usual.
+ * Refused with the other format options, --srgb, --matrix, --full-range, the
+ * debug views, the ring modes and a .y4m on either side.
  * --surface-align P,R: the device frames, input and output, are held in
  * mm_surface_aligned(W, H, format, P, R) surfaces (256,16: a hardware
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
@@ -99,6 +107,7 @@
 #include "mm.h"
 #include "mm_ring.h"
 #include "mm_ring_local.h"
+#include "ppm.h"
 #include "y4m.h"
 
 #include <pthread.h>
@@ -459,7 +468,7 @@ int main(int argc, char **argv)
     int W = 1920, H = 1080, F = 300, L = 5, B = 30, dev = 0;
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
-    int nv12 = 0, p010 = 0, srgb = 0, mono = 0, yuy2 = 0, uyvy = 0, y210 = 0;
+    int nv12 = 0, p010 = 0, srgb = 0, mono = 0, yuy2 = 0, uyvy = 0, y210 = 0, ppm = 0, bgr = 0;
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
@@ -474,6 +483,8 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--yuy2")) { yuy2 = 1; continue; }
         if (!strcmp(a, "--uyvy")) { uyvy = 1; continue; }
         if (!strcmp(a, "--y210")) { y210 = 1; continue; }
+        if (!strcmp(a, "--ppm")) { ppm = 1; continue; }
+        if (!strcmp(a, "--bgr")) { bgr = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
         if (!strcmp(a, "--show-magnitude")) { show_mag = 1; continue; }
         if (!strcmp(a, "--show-phase")) { show_phase = 1; continue; }
@@ -516,6 +527,36 @@ int main(int argc, char **argv)
         if (y4m_read_header_ext(fi, &yi, &depth)) { fprintf(stderr, "%s: unsupported Y4M\n", in_path); return 1; }
         W = yi.width;
         H = yi.height;
+    }
+    /* --ppm: a stream of binary PPM images is a stream of MM_RGB24 frames */
+    ppm_info pi = {0, 0};
+    int ppm_pending = 0;   /* the first image's header is read, its pixels are not */
+    if (bgr && !ppm) {
+        fprintf(stderr, "--bgr needs --ppm\n");
+        return 2;
+    }
+    if (ppm) {
+        if (nv12 || p010 || mono || yuy2 || uyvy || y210 || srgb || matrix_arg || full_range || show_mag || show_phase ||
+            ring_local > 0 || ring_world > 0) {
+            fprintf(stderr, "--ppm does not go with --nv12, --p010, --mono, --yuy2, --uyvy, --y210, --srgb, --matrix, "
+                            "--full-range, the debug views or the ring modes\n");
+            return 2;
+        }
+        if (!fi || y4m_in || y4m_out) {
+            fprintf(stderr, "--ppm needs a binary PPM stream as input (-i, P6, maxval 255) and writes one (-o)\n");
+            return 2;
+        }
+        const int rc = ppm_read_header(fi, &pi);
+        if (rc) {
+            fprintf(stderr, "%s: %s\n", in_path,
+                    rc == PPM_EOF ? "empty file" : rc == PPM_ERR_MAGIC ? "not a binary PPM (P6)"
+                    : rc == PPM_ERR_MAXVAL ? "maxval is not 255" : "malformed PPM header");
+            return 1;
+        }
+        W = pi.width;
+        H = pi.height;
+        ppm_pending = 1;
+        g_fmt = bgr ? MM_BGR24 : MM_RGB24;
     }
     const int p422 = yuy2 || uyvy;   /* packed 4:2:2 */
     if (y210) {   /* its 10-bit form */
@@ -678,7 +719,7 @@ int main(int argc, char **argv)
     }
 
     size_t fb = (size_t)W * H * 4;
-    if (nv12 || p010 || mono || p422 || y210) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
+    if (nv12 || p010 || mono || p422 || y210 || ppm) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
     /* --surface-align: the frames the operator sees live in `lay` surfaces
      * (d_in, d_out); d_tin / d_tout are tight device frames for the synthetic
      * source and for the checksums and files */
@@ -691,7 +732,7 @@ int main(int argc, char **argv)
         if (sscanf(surf_arg, "%llu,%d", &pa, &ra) != 2 ||
             (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK) {
             fprintf(stderr, "--surface-align %s: want P,R with P a multiple of the format's unit "
-                            "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, mono: the sample size) and R >= 1 (4:2:0: even)\n", surf_arg);
+                            "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, mono: the sample size, --ppm: 1) and R >= 1 (4:2:0: even)\n", surf_arg);
             return 2;
         }
         printf("surfaces: pitch %zu  chroma offset %zu  frame stride %zu\n", lay.pitch, lay.chroma_offset,
@@ -747,6 +788,27 @@ int main(int argc, char **argv)
             if (got == 0) break;
             n = got;
             if (surf_copy(d_in, &lay, host, &tight, W, H, n, hipMemcpyHostToDevice, s)) return 1;
+        } else if (fi && ppm) {
+            /* images of the first one's size, as they lie (--bgr: R and B swapped) */
+            int got = 0;
+            for (; got < n; ++got) {
+                const int r = ppm_pending ? ppm_read_pixels(fi, &pi, host + fb * got)
+                                          : ppm_read_next(fi, &pi, host + fb * got);
+                ppm_pending = 0;
+                if (r == PPM_EOF) break;
+                if (r) {
+                    fprintf(stderr, "%s: %s\n", in_path,
+                            r == PPM_ERR_TRUNCATED ? "truncated frame"
+                            : r == PPM_ERR_SIZE    ? "a frame's size differs from the first's"
+                            : r == PPM_ERR_MAXVAL  ? "maxval is not 255"
+                            : r == PPM_ERR_MAGIC   ? "not a binary PPM (P6)" : "malformed PPM header");
+                    return 1;
+                }
+                if (bgr) ppm_swap_rb(host + fb * got, (size_t)W * H);
+            }
+            if (got == 0) break;
+            n = got;
+            if (surf_copy(d_in, &lay, host, &tight, W, H, n, hipMemcpyHostToDevice, s)) return 1;
         } else if (fi) {
             size_t got = fread(host, fb, (size_t)n, fi);
             if (got == 0) break;
@@ -793,6 +855,14 @@ int main(int argc, char **argv)
                         : p422 ? y4m_write_frame_422(fo, W, H, planes)
                         : y210 ? y4m_write_frame_422p10(fo, W, H, (const uint16_t *)planes)
                                : y4m_write_frame(fo, W, H, planes)) {
+                        fprintf(stderr, "write failed\n");
+                        return 1;
+                    }
+                }
+            } else if (ppm) {   /* the same container back */
+                for (int k = 0; k < n; ++k) {
+                    if (bgr) ppm_swap_rb(host + fb * k, (size_t)W * H);
+                    if (ppm_write_frame(fo, W, H, host + fb * k)) {
                         fprintf(stderr, "write failed\n");
                         return 1;
                     }

@@ -36,8 +36,15 @@ PACKED422_FORMATS = (YUY2, YUY2_FULL, UYVY, UYVY_FULL)
 Y210 = 22           # BT.601 limited range
 Y210_FULL = 23      # full range
 Y210_FORMATS = (Y210, Y210_FULL)
+# packed RGB, what cv2 / PIL / imageio / torchvision / ffmpeg rgb24, bgr24 / PPM
+# hand out: [H, W, 3] bytes, no alpha; every size, mode and debug view.  The
+# byte-order bit is valid on RGB24 alone (BGRA orders are not taken).
+RGB24 = 13          # bytes R G B, v = byte / 255 as RGBA8
+ORDER_BGR = 128     # byte-order bit: B G R (OpenCV's order)
+BGR24 = RGB24 | ORDER_BGR
+RGB24_FORMATS = (RGB24, BGR24)
 FORMAT_BPP = {RGBA8: 4, RGBA32F: 16, RGBA16F: 8, RGBA8_SRGB: 4, Y8: 1, Y10: 2, Y12: 2, Y16: 2,
-              YUY2: 2, YUY2_FULL: 2, UYVY: 2, UYVY_FULL: 2, Y210: 4, Y210_FULL: 4}
+              YUY2: 2, YUY2_FULL: 2, UYVY: 2, UYVY_FULL: 2, Y210: 4, Y210_FULL: 4, RGB24: 3, BGR24: 3}
 # video frames, planar 8-bit Y'CbCr 4:2:0 (H rows of W luma bytes, then H/2 rows
 # of W interleaved Cb, Cr bytes; W and H even): frame_bytes() gives W*H*3/2
 NV12 = 16           # BT.601 limited ("video") range
@@ -287,7 +294,10 @@ def nv12_chroma_matrix():
 
 
 def base_format(fmt):
-    """The format without its matrix bit: what decides a frame's size and shape."""
+    """The format without its matrix bit, and BGR24 without its byte-order bit:
+    what decides a frame's size and shape."""
+    if fmt == BGR24:
+        return RGB24
     return fmt & ~(MATRIX_BT709 | MATRIX_BT2020)
 
 

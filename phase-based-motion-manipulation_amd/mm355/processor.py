@@ -8,15 +8,20 @@ import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       MONO_FORMATS, NV12, NV12_FULL, P010, P010_FULL, PACKED422_FORMATS, RGBA8, RGBA8_SRGB, RGBA16F,
-                      RGBA32F, Y8, Y210_FORMATS,
+                      RGB24_FORMATS, RGBA32F, Y8, Y210_FORMATS,
                       Handle, MMError, Params, Surface, base_format)
 
 
 def _fmt_of(frame, srgb=False):
     """Frame format from the dtype: uint8 UNORM (or sRGB-encoded with srgb),
     float16 (linear half, the HDR camera target), float32.  (A bare uint8 frame
-    is RGBA8: the grayscale formats are always named, OnRenderImage's fmt=.)"""
+    is RGBA8: the grayscale formats are always named, OnRenderImage's fmt=.
+    An [H, W, 3] frame must be named too: its byte order cannot be guessed.)"""
     dt = str(getattr(frame, "dtype", ""))
+    shape = tuple(getattr(frame, "shape", ()))
+    if len(shape) == 3 and shape[2] == 3:
+        raise MMError(-1, f"frame shape {shape}: a three-channel frame needs fmt=mm355.RGB24 "
+                          "(bytes R G B) or fmt=mm355.BGR24 (B G R, OpenCV's order)")
     if dt.endswith("uint8"):
         return RGBA8_SRGB if srgb else RGBA8
     if dt.endswith("float16"):
@@ -60,6 +65,16 @@ def frame_layout(frame, width, height, fmt):
             return None
         lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
         lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation (a multiple of 8)
+        return lay
+    if fmt in RGB24_FORMATS:   # [H, W, 3] bytes: rows any pitch >= 3 W apart, at any byte
+        if tuple(frame.shape) != (height, width, 3) or not str(frame.dtype).endswith("uint8"):
+            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height, width, 3)} uint8)")
+        if strides[2] != 1 or strides[1] != 3 or strides[0] <= 0:
+            raise MMError(-1, "frames must be contiguous or row-strided (pixels and channels packed)")
+        if strides[0] == 3 * width:
+            return None
+        lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
+        lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation (at least 3 W)
         return lay
     if fmt in MONO_FORMATS:   # [H, W] samples: uint8 (Y8) or uint16
         want = "uint8" if fmt == Y8 else "uint16"
@@ -177,7 +192,10 @@ class MotionMagnificationProcessor:
         [H, 2 W] uint8 on both sides (contiguous or row-strided views).
         fmt=Y210 / Y210_FULL, with or without a matrix bit: 10-bit packed 4:2:2,
         [H, 2 W] uint16 on both sides (P010's convention: the words as they lie;
-        contiguous or row-strided views)."""
+        contiguous or row-strided views).  fmt=RGB24 / BGR24: [H, W, 3] uint8
+        on both sides, as cv2 (BGR24), PIL and imageio (RGB24) hand them out:
+        device tensors, contiguous or row-strided views that start at any
+        byte, or host numpy arrays; such a frame without fmt= raises."""
         if self._handle is None:                       # !isInitialized -> Blit (.cs:103-107)
             destination[...] = source
             return
@@ -186,8 +204,8 @@ class MotionMagnificationProcessor:
             if _fmt_of(destination, self.srgb) != fmt:
                 raise MMError(-1, "source/destination formats differ")
         elif (fmt not in MONO_FORMATS and base_format(fmt) not in PACKED422_FORMATS and
-              base_format(fmt) not in Y210_FORMATS):
-            raise MMError(-1, f"fmt={fmt}: only the grayscale and packed 4:2:2 formats are named, "
+              base_format(fmt) not in Y210_FORMATS and fmt not in RGB24_FORMATS):
+            raise MMError(-1, f"fmt={fmt}: only the grayscale, packed 4:2:2 and packed RGB formats are named, "
                               "the others follow the dtype")
         on_dev = _is_device(source)
         if on_dev != _is_device(destination):
@@ -228,6 +246,8 @@ class MotionMagnificationProcessor:
 
 
 def host_frames(n, h, w, fmt):
+    if fmt in RGB24_FORMATS:        # three bytes per pixel, either order
+        return np.zeros((n, h, w, 3), np.uint8)
     fmt = base_format(fmt)          # a matrix bit changes no size or shape
     if fmt in (NV12, NV12_FULL):    # h luma rows, then h/2 rows of interleaved Cb, Cr
         return np.zeros((n, h * 3 // 2, w), np.uint8)

@@ -41,6 +41,13 @@ YUY2 legs' pictures at 10 bits as MM_Y210 macropixels (words Y0 Cb Y1 Cr, code
 whole 8-byte macropixels; 4 bytes per pixel each way.  A library from before
 this format runs without them.
 
+Packed RGB legs (rgb24, bgr24, rgb24_pitched): the RGBA8 leg's pictures with
+the alpha byte dropped as MM_RGB24, the same pixels byte-swapped as MM_BGR24, 3
+bytes per pixel each way; computed by the RGBA8 path's own expressions, so the
+legs compare addressing alone (K1's byte-aligned dword loads, K34's 12-byte
+quads without RGBA8's LDS-DMA source staging).  A library from before these
+formats runs without them.
+
 usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--out FILE.json]
 """
 import argparse
@@ -177,6 +184,11 @@ def main():
         fmts += [("y210", mm355.Y210), ("y210_bt709", mm355.Y210 | mm355.MATRIX_BT709)]
     except (mm355.MMError, AttributeError):
         pass    # a build from before the 10-bit packed 4:2:2 format
+    try:
+        mm355.frame_bytes(W, H, mm355.RGB24)
+        fmts += [("rgb24", mm355.RGB24), ("bgr24", mm355.BGR24)]
+    except (mm355.MMError, AttributeError):
+        pass    # a build from before the packed RGB formats
     for name, fmt in fmts:
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
@@ -186,6 +198,10 @@ def main():
             src = rgba
         elif name in ("nv12_bt709", "p010_bt2020", "yuy2_bt709", "y210_bt709"):
             src = legs[name.split("_")[0]]["src"]
+        elif name == "rgb24":      # the RGBA8 leg's pictures without their alpha
+            src = rgba[..., :3].contiguous()
+        elif name == "bgr24":
+            src = legs["rgb24"]["src"].flip(3).contiguous()
         elif name == "yuy2":
             src = to_422(torch, rgba)
         elif name == "y210":
@@ -198,7 +214,7 @@ def main():
             src = to_420(torch, rgba, ten_bit=name == "p010")
         legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[], lay=None,
                           bytes_per_frame=mm355.frame_bytes(W, H, fmt))
-        if not a.no_pitched and mm355.has_surfaces():
+        if not a.no_pitched and mm355.has_surfaces() and name != "bgr24":   # (one pitched packed RGB leg)
             lay = mm355.Surface.aligned(W, H, fmt, 256, 16)
             h = mm355.Handle(W, H, p)
             h.set_batch(B)
@@ -283,8 +299,17 @@ def main():
         k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
         out["y210_bt709_k1_us"] = {"matrixed": k1("y210_bt709"), "y210": k1("y210"), "yuy2_bt709": k1("yuy2_bt709"),
                                    "p010": k1("p010"), "rgba8": k1("rgba8")}
+    for name in ("rgb24", "bgr24"):
+        if name in out["formats"]:
+            for base in ("rgba8", "nv12"):
+                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                    out["formats"][base]["fps_median"], 4)
+    if "rgb24" in out["formats"]:
+        ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
+        out["rgb24_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
+                                  for n in ("rgb24", "bgr24", "rgba8", "nv12")}
     for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16", "yuy2", "uyvy", "yuy2_bt709",
-                 "y210", "y210_bt709"):
+                 "y210", "y210_bt709", "rgb24"):
         if name + "_pitched" in out["formats"]:
             out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
                                                       out["formats"][name]["fps_median"], 4)
