@@ -560,6 +560,65 @@ int mm_process_surface(mm_handle *h, const void *in, const mm_surface *in_layout
 int mm_process_stream_surfaces(mm_handle *h, const void *in, const mm_surface *in_layout,
                                void *out, const mm_surface *out_layout, int count, void *hip_stream);
 
+/* ---- Different formats in and out ----------------------------------------
+ * (a backward-compatible addition to ABI 10; detect it by the presence of
+ * mm_convert_supported)
+ * mm_process_surface / mm_process_stream_surfaces keep refusing differing
+ * formats with MM_ERR_INVALID.  mm_process_convert / mm_process_stream_convert
+ * are those two calls with in_layout->format != out_layout->format allowed for
+ * these pairs, every range and matrix variant (the matrix bit belongs to the
+ * Y'CbCr side):
+ *   decode: any MM_NV12 code (16, 17, 48, 49, 80, 81) or MM_P010 code (18, 19,
+ *           50, 51, 82, 83) in, MM_RGBA8 out;
+ *   encode: MM_RGBA8 in, any MM_NV12 code out.
+ * With equal formats they ARE the existing calls: same bytes, same state, same
+ * kernels.  mm_convert_supported(in, out) needs no GPU: MM_OK for the pairs
+ * above and any valid equal pair, MM_ERR_UNSUPPORTED for every other pair of
+ * two valid codes, MM_ERR_INVALID if either code is unknown.
+ * Semantics: the frame IS the RGBA32F frame given by the in format's "in"
+ * rule, the result is the reference's result on that frame, and it is stored
+ * by the out format's "out" rule: MM_RGBA8 round(saturate(v) * 255), alpha
+ * 255; NV12 Y', Cb', Cr' of the saturated RGB by the OUT code's weights and
+ * range, chroma the mean of the 2 x 2 block, floor(v + 0.5) clamped.  MM_RGBA8
+ * to NV12 ignores the input alpha.  P010 to MM_RGBA8 keeps all 16 bits of the
+ * words on the input side and rounds once, at the store.  The frame never
+ * takes a second trip through memory: the compose stage reads the one format
+ * and stores the other.
+ * The first frame after mm_create / mm_reset and apply_magnification = 0:
+ * there is NO bitwise passthrough between different formats.  The output is
+ * the plain conversion: the out rule applied to the in frame's RGBA32F frame,
+ * saturated first (one kernel for the n frames, the decode by the format's
+ * matrix in fp32).  The destination's padding is untouched.
+ * Temporal state: after a convert call it is bitwise the state the same-format
+ * call on the in format leaves behind (K1's output, which has no out side).
+ * So convert calls, same-format calls and different layouts may alternate on
+ * one handle, and mm_get_state / mm_set_state / mm_compute_state* are unchanged.
+ * Restrictions are the union of both formats': W and H even, show_magnitude /
+ * show_phase refused, both MM_ERR_UNSUPPORTED.  Each layout is validated by its
+ * own format's rules (unit, pitch, chroma offset, extent, alignment of device
+ * pointers); unknown codes, null pointers and count < 0 are MM_ERR_INVALID; all
+ * of it before anything is queued: the handle stays usable and its state is
+ * unchanged.  Host-memory frames (flags without MM_FRAMES_ON_DEVICE) are
+ * staged per side with each side's own frame size; the stream form takes
+ * device pointers only and is equivalent, frame for frame, to `count` single
+ * calls.  Every mode, both edge modes and every batch size work.
+ * The fused kernels run where each side's quads are aligned: NV12 in, the
+ * input's chroma rows on multiples of 4 bytes; MM_RGBA8 in with NV12 out, the
+ * output's luma and chroma rows; the MM_RGBA8 and P010 sides in every layout.
+ * Any other legal layout takes the unfused kernels: the same bytes.
+ * Out of scope: any pair not listed (packed 4:2:2 or MM_Y210 to MM_RGBA8,
+ * MM_RGBA8 to P010, P010 to MM_RGBA16F, MM_RGB24 / MM_BGR24 on either side of a
+ * mixed pair, MM_RGB24 to MM_BGR24 included, MM_RGBA8_SRGB, grayscale, Y'CbCr
+ * to Y'CbCr transcodes such as NV12 to P010 or a matrix change); scaling or
+ * cropping between the sides; chroma siting other than the shared 2 x 2
+ * sample; PQ / HLG; odd sizes; the debug views; the ring entry points
+ * (include/mm_ring.h); the Unity shim; mm_extmem_check. */
+int mm_convert_supported(int in_format, int out_format);
+int mm_process_convert(mm_handle *h, const void *in, const mm_surface *in_layout,
+                       void *out, const mm_surface *out_layout, int flags, void *hip_stream);
+int mm_process_stream_convert(mm_handle *h, const void *in, const mm_surface *in_layout,
+                              void *out, const mm_surface *out_layout, int count, void *hip_stream);
+
 /* isFirstFrame = true (.cs:75): the next frame is passed through.  The same
  * happens after a MM_MODE_STEERABLE mm_set_state followed by a switch to
  * another mode (that state holds local phases, not G_{t-1}). */

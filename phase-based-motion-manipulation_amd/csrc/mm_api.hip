@@ -463,12 +463,26 @@ int mm_surface_bytes(int width, int height, const mm_surface *s, size_t *extent)
     return surf_check(width, height, s, extent);
 }
 
-int mm_process_stream_surfaces(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
-                               const mm_surface *out_layout, int count, void *hip_stream)
+// What a frame entry point asks of the two formats: one format on both sides
+// (mm_process_surface / mm_process_stream_surfaces: anything else is invalid),
+// or, `convert`, a pair convert_supported takes, each side within its own
+// format's restrictions (the union: even sizes, no debug view).
+static int formats_check(const mm_handle *h, const mm_surface *in_layout, const mm_surface *out_layout, bool convert)
+{
+    if (!convert || in_layout->format == out_layout->format) {
+        if (int rc = fmt_check(h->W, h->H, in_layout->format, &h->p)) return rc;
+        return in_layout->format != out_layout->format ? MM_ERR_INVALID : MM_OK;
+    }
+    if (int rc = convert_supported(in_layout->format, out_layout->format)) return rc;
+    if (int rc = fmt_check(h->W, h->H, in_layout->format, &h->p)) return rc;
+    return fmt_check(h->W, h->H, out_layout->format, &h->p);
+}
+
+static int stream_surfaces(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                           const mm_surface *out_layout, int count, void *hip_stream, bool convert)
 {
     if (!h || !in || !out || !in_layout || !out_layout || count < 0) return MM_ERR_INVALID;
-    if (int rc = fmt_check(h->W, h->H, in_layout->format, &h->p)) return rc;
-    if (in_layout->format != out_layout->format) return MM_ERR_INVALID;
+    if (int rc = formats_check(h, in_layout, out_layout, convert)) return rc;
     int rc;
     if ((rc = surf_check_frames(h->W, h->H, in, in_layout, count)) ||
         (rc = surf_check_frames(h->W, h->H, out, out_layout, count)))
@@ -485,6 +499,20 @@ int mm_process_stream_surfaces(mm_handle *h, const void *in, const mm_surface *i
     const int rn = note_work(h, s);
     return rc ? rc : rn;
 }
+
+int mm_process_stream_surfaces(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                               const mm_surface *out_layout, int count, void *hip_stream)
+{
+    return stream_surfaces(h, in, in_layout, out, out_layout, count, hip_stream, false);
+}
+
+int mm_process_stream_convert(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                              const mm_surface *out_layout, int count, void *hip_stream)
+{
+    return stream_surfaces(h, in, in_layout, out, out_layout, count, hip_stream, true);
+}
+
+int mm_convert_supported(int in_format, int out_format) { return convert_supported(in_format, out_format); }
 
 int mm_process_stream(mm_handle *h, const void *in, void *out, int count, int format,
                       void *hip_stream)
@@ -503,14 +531,13 @@ static hipError_t stage_plane(void *dst, size_t dpitch, const void *src, size_t 
     return hipMemcpy2DAsync(dst, dpitch, src, spitch, row_bytes, rows, kind, s);
 }
 
-int mm_process_surface(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
-                       const mm_surface *out_layout, int flags, void *hip_stream)
+static int process_surface(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                           const mm_surface *out_layout, int flags, void *hip_stream, bool convert)
 {
     if (!h || !in || !out || !in_layout || !out_layout) return MM_ERR_INVALID;
     if (flags & MM_FRAMES_ON_DEVICE)
-        return mm_process_stream_surfaces(h, in, in_layout, out, out_layout, 1, hip_stream);
-    if (int rc = fmt_check(h->W, h->H, in_layout->format, &h->p)) return rc;
-    if (in_layout->format != out_layout->format) return MM_ERR_INVALID;
+        return stream_surfaces(h, in, in_layout, out, out_layout, 1, hip_stream, convert);
+    if (int rc = formats_check(h, in_layout, out_layout, convert)) return rc;
     int rc;
     if ((rc = surf_check_frames(h->W, h->H, in, in_layout, 1, false)) ||
         (rc = surf_check_frames(h->W, h->H, out, out_layout, 1, false)))
@@ -518,11 +545,14 @@ int mm_process_surface(mm_handle *h, const void *in, const mm_surface *in_layout
     // host frames: stage through tight device buffers and synchronise; the 2D
     // copies move the W x H samples only (the host frames' padding is neither
     // read nor written)
-    const int format = in_layout->format;
-    mm_surface t;
+    // (a convert call: each side staged tight in its own format, with its own frame size)
+    const int format = in_layout->format, oformat = out_layout->format;
+    mm_surface t, to;
     (void)surf_tight(h->W, h->H, format, &t);
-    const Frames fr = frames_of(h->W, h->H, t, t);
-    const size_t fb = fr.fb, rb = t.pitch, luma = rb * (size_t)h->H;
+    (void)surf_tight(h->W, h->H, oformat, &to);
+    const Frames fr = frames_of(h->W, h->H, t, to);
+    const size_t fbo = fmt_frame_bytes(h->W, h->H, oformat), rbo = to.pitch, lumao = rbo * (size_t)h->H;
+    const size_t fb = std::max(fr.fb, fbo), rb = t.pitch, luma = rb * (size_t)h->H;
     DEVICE_SCOPE(h);
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     int ro = order_after_last(h, s);
@@ -538,10 +568,10 @@ int mm_process_surface(mm_handle *h, const void *in, const mm_surface *in_layout
     }
     const bool in_tight = in_layout->pitch == rb && (!fmt_420(format) || (in_layout->chroma_offset == luma &&
                                                                           in_layout->chroma_pitch == rb));
-    const bool out_tight = out_layout->pitch == rb && (!fmt_420(format) || (out_layout->chroma_offset == luma &&
-                                                                            out_layout->chroma_pitch == rb));
+    const bool out_tight = out_layout->pitch == rbo && (!fmt_420(oformat) || (out_layout->chroma_offset == lumao &&
+                                                                              out_layout->chroma_pitch == rbo));
     if (in_tight) {
-        HIPCHK(hipMemcpyAsync(h->d_stage_in, in, fb, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->d_stage_in, in, fr.fb, hipMemcpyHostToDevice, s));
     } else {
         HIPCHK(stage_plane(h->d_stage_in, rb, in, in_layout->pitch, rb, h->H, hipMemcpyHostToDevice, s));
         if (fmt_420(format))
@@ -552,15 +582,27 @@ int mm_process_surface(mm_handle *h, const void *in, const mm_surface *in_layout
     const int rn = note_work(h, s);
     if (rc || (rc = rn)) return rc;
     if (out_tight) {
-        HIPCHK(hipMemcpyAsync(out, h->d_stage_out, fb, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out, h->d_stage_out, fbo, hipMemcpyDeviceToHost, s));
     } else {
-        HIPCHK(stage_plane(out, out_layout->pitch, h->d_stage_out, rb, rb, h->H, hipMemcpyDeviceToHost, s));
-        if (fmt_420(format))
+        HIPCHK(stage_plane(out, out_layout->pitch, h->d_stage_out, rbo, rbo, h->H, hipMemcpyDeviceToHost, s));
+        if (fmt_420(oformat))
             HIPCHK(stage_plane((uint8_t *)out + out_layout->chroma_offset, out_layout->chroma_pitch,
-                               h->d_stage_out + luma, rb, rb, h->H / 2, hipMemcpyDeviceToHost, s));
+                               h->d_stage_out + lumao, rbo, rbo, h->H / 2, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
     return MM_OK;
+}
+
+int mm_process_surface(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                       const mm_surface *out_layout, int flags, void *hip_stream)
+{
+    return process_surface(h, in, in_layout, out, out_layout, flags, hip_stream, false);
+}
+
+int mm_process_convert(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                       const mm_surface *out_layout, int flags, void *hip_stream)
+{
+    return process_surface(h, in, in_layout, out, out_layout, flags, hip_stream, true);
 }
 
 int mm_process(mm_handle *h, const void *in, void *out, int format, int flags, void *hip_stream)

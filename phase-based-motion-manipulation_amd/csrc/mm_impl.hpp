@@ -338,17 +338,31 @@ static inline Geo::Lay surf_lay(const mm_surface &s)
     l.stride = s.frame_stride;
     return l;
 }
-// The frames of one call: their format and where the two sides lie.
+// The pairs of different formats mm_process_convert takes (include/mm.h):
+// decode, any NV12 or P010 code to MM_RGBA8; encode, MM_RGBA8 to any NV12 code.
+static inline int convert_supported(int in_fmt, int out_fmt)
+{
+    if (!fmt_valid(in_fmt) || !fmt_valid(out_fmt)) return MM_ERR_INVALID;
+    if (in_fmt == out_fmt) return MM_OK;
+    if (fmt_420(in_fmt) && out_fmt == MM_RGBA8) return MM_OK;
+    if (in_fmt == MM_RGBA8 && fmt_nv12(out_fmt)) return MM_OK;
+    return MM_ERR_UNSUPPORTED;
+}
+// The frames of one call: their formats and where the two sides lie.  fmt is
+// the input side's (K1, the state and every same-format path read it alone),
+// ofmt the output side's: the same but in a convert call.
 struct Frames {
-    int fmt;
+    int fmt, ofmt;
     Geo::Lay in, out;
-    size_t fb;       // mm_frame_bytes
-    bool packed;     // both sides tight, frames back to back: a passthrough is one plain copy
+    size_t fb;       // mm_frame_bytes (of fmt)
+    bool packed;     // one format, both sides tight, frames back to back: a passthrough is one plain copy
+    bool mixed() const { return fmt != ofmt; }
 };
 static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surface &lo)
 {
     Frames f;
     f.fmt = li.format;
+    f.ofmt = lo.format;
     f.in = surf_lay(li);
     f.out = surf_lay(lo);
     f.fb = fmt_frame_bytes(W, H, f.fmt);
@@ -358,7 +372,7 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
         return s.pitch == t.pitch && s.chroma_offset == t.chroma_offset && s.chroma_pitch == t.chroma_pitch &&
                s.frame_stride == t.frame_stride;
     };
-    f.packed = tight(li) && tight(lo);
+    f.packed = !f.mixed() && tight(li) && tight(lo);
     return f;
 }
 
@@ -394,6 +408,16 @@ static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && 
     case MM_RGB24: { constexpr int FMT_ = MM_RGB24; __VA_ARGS__; } break;      \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
+// ... the compose kernels' (k_compose, k_rows_inv_compose, k_rows_inv_compose4):
+// FMT_ is the pair's code for the frames of a convert call (mm_kernels.hpp
+// fmt_pair; convert_supported leaves these three), else the format's
+#define MM_PAIR_SWITCH(fr, ...)                                                \
+    do {                                                                       \
+        if (!(fr).mixed()) { MM_FMT_SWITCH((fr).fmt, __VA_ARGS__) }            \
+        else if (fmt_nv12((fr).fmt)) { constexpr int FMT_ = kFmtNV12toRGBA8; __VA_ARGS__; } \
+        else if (fmt_p010((fr).fmt)) { constexpr int FMT_ = kFmtP010toRGBA8; __VA_ARGS__; } \
+        else { constexpr int FMT_ = kFmtRGBA8toNV12; __VA_ARGS__; }            \
+    } while (0);
 // ... K1's: a code with a matrix bit runs the matrixed NV12 / P010 instance,
 // which reads the chroma plane too (BT.709 and BT.2020, both ranges, share it);
 // a matrixed packed 4:2:2 code the instance that reads whole macropixels (four
@@ -484,6 +508,21 @@ static inline void nv12_chroma_matrix(double m[4])
 // input side in units of the 16-bit word, 64 per code: u = 64).
 static inline Geo geo_of(const mm_handle *h, const Frames &fr)
 {
+    if (fr.mixed()) {
+        // each side's uniforms from its own format: the input-side fields
+        // (y_off .. qcr, li.yb) of the in format's geometry, the output-side
+        // fields (kr .. cro, lo.yb) of the out format's
+        Frames a = fr, b = fr;
+        a.ofmt = fr.fmt;
+        b.fmt = fr.ofmt;
+        Geo g = geo_of(h, a);
+        const Geo go = geo_of(h, b);
+        g.nv.kr = go.nv.kr, g.nv.kg = go.nv.kg, g.nv.kb = go.nv.kb;
+        g.nv.yo_scale = go.nv.yo_scale, g.nv.yo_bias = go.nv.yo_bias;
+        g.nv.cbo = go.nv.cbo, g.nv.cro = go.nv.cro;
+        g.lo.yb = go.lo.yb;
+        return g;
+    }
     Geo g = h->geo;
     const int fmt = fr.fmt;
     g.li = fr.in;
@@ -755,12 +794,20 @@ static int set_attrs(int W)
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<LOG2N, MM_RGBA8_SRGB, true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<LOG2N, kFmtRGBA8toNV12, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)k34_lds_bytes<12>(false);
         for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtNV12toRGBA8>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtP010toRGBA8>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtRGBA8toNV12>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         // k_sb_cols: exchange buffer (36.9 KB) + its own staging, past 64 KB for
         // frames taller than ~3,570 rows (run_steer's bound)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sb_cols<12>),
@@ -790,6 +837,12 @@ static int set_attrs(int W)
         for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtNV12toRGBA8>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtP010toRGBA8>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtRGBA8toNV12>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
     return MM_OK;
 }
@@ -939,12 +992,26 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
 // are 8-byte accesses of two macropixels at dword-aligned addresses, and its
 // unit is 4 too; MM_Y210's are 16-byte accesses at 8-byte-aligned addresses,
 // its unit: ld_quad_a8.)
+// The two halves, a side each (a convert call has NV12 on one side only: NV12
+// in asks this of the input's chroma rows, RGBA8 in with NV12 out of the
+// output's luma and chroma rows; the RGBA8 side's quads are dword aligned in
+// every layout).
+static bool nv12_in_aligned(const uint8_t *in, const Frames &fr, int nframes)
+{
+    uintptr_t m = (reinterpret_cast<uintptr_t>(in) + fr.in.c_off) | fr.in.c_pitch;
+    if (nframes > 1) m |= fr.in.stride;
+    return (m & 3u) == 0;
+}
+static bool nv12_out_aligned(const uint8_t *out, const Frames &fr, int nframes)
+{
+    const uintptr_t b = reinterpret_cast<uintptr_t>(out);
+    uintptr_t m = b | fr.out.pitch | (b + fr.out.c_off) | fr.out.c_pitch;
+    if (nframes > 1) m |= fr.out.stride;
+    return (m & 3u) == 0;
+}
 static bool nv12_quads_aligned(const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(in) + fr.in.c_off, b = reinterpret_cast<uintptr_t>(out);
-    uintptr_t m = a | fr.in.c_pitch | b | fr.out.pitch | (b + fr.out.c_off) | fr.out.c_pitch;
-    if (nframes > 1) m |= fr.in.stride | fr.out.stride;
-    return (m & 3u) == 0;
+    return nv12_in_aligned(in, fr, nframes) && nv12_out_aligned(out, fr, nframes);
 }
 // The single-plane formats' quads are stores only (their compose reads no
 // input): four bytes as one dword, four words as one 8-byte store at a
@@ -966,6 +1033,7 @@ static bool mono_quads_aligned(const uint8_t *out, const Frames &fr, int nframes
 static bool k34_src_dma(const uint8_t *in, const Frames &fr, int nframes)
 {
     if (fr.fmt != MM_RGBA8 && fr.fmt != MM_RGBA8_SRGB) return false;
+    // (a convert call with MM_RGBA8 in is the encode pair: the same source rows)
     uintptr_t m = reinterpret_cast<uintptr_t>(in) | fr.in.pitch;
     if (nframes > 1) m |= fr.in.stride;
     return (m & 15u) == 0;
@@ -985,7 +1053,10 @@ static bool rgb24_quads_aligned(const uint8_t *in, const uint8_t *out, const Fra
 }
 static bool k34_fits(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
-    if (fmt_nv12(fr.fmt) && !nv12_quads_aligned(in, out, fr, nframes)) return false;
+    if (fr.mixed()) {   // each side by its own format (P010 in, RGBA8 either side: every layout)
+        if (fmt_nv12(fr.fmt) && !nv12_in_aligned(in, fr, nframes)) return false;
+        if (fmt_nv12(fr.ofmt) && !nv12_out_aligned(out, fr, nframes)) return false;
+    } else if (fmt_nv12(fr.fmt) && !nv12_quads_aligned(in, out, fr, nframes)) return false;
     if (fmt_mono(fr.fmt) && !mono_quads_aligned(out, fr, nframes)) return false;
     if (fmt_rgb24(fr.fmt) && !rgb24_quads_aligned(in, out, fr, nframes)) return false;
     const Geo &g = h->geo;
@@ -1041,7 +1112,7 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
         const size_t lds = sizeof(c2) * 4 * lds_complex<(1 << LOG2N)>();
         const dim3 grid((unsigned)(strips * nout)), block(4 * fft_T<LOG2N>());
         ProfScope ps(h, s, MM_K_ROWS_INV_COMPOSE, nout);
-        MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k_rows_inv_compose4<LOG2N, FMT_>), grid, block, lds, s, h->d_Q,
+        MM_PAIR_SWITCH(fr, hipLaunchKernelGGL((k_rows_inv_compose4<LOG2N, FMT_>), grid, block, lds, s, h->d_Q,
                                               h->q_stride, in, out, frame0, strips, geo_of(h, fr), h->blur,
                                               h->d_col3, h->d_row3, h->d_tw))
         HIPCHK(hipGetLastError());
@@ -1058,10 +1129,11 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
                            h->q_stride, in, out, frame0, strips, steps, geo_of(h, fr), h->blur,      \
                            h->d_col3, h->d_row3, h->d_tw)
         if constexpr (LOG2N <= 12) if (dma) {
-            if (fmt == MM_RGBA8) MM_K34_LAUNCH(MM_RGBA8, true);
+            if (fr.mixed()) MM_K34_LAUNCH(kFmtRGBA8toNV12, true);
+            else if (fmt == MM_RGBA8) MM_K34_LAUNCH(MM_RGBA8, true);
             else MM_K34_LAUNCH(MM_RGBA8_SRGB, true);
         }
-        if (!dma) MM_FMT_SWITCH(fmt, MM_K34_LAUNCH(FMT_, false))
+        if (!dma) MM_PAIR_SWITCH(fr, MM_K34_LAUNCH(FMT_, false))
 #undef MM_K34_LAUNCH
         HIPCHK(hipGetLastError());
         return MM_OK;
@@ -1109,7 +1181,7 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
     const int rt = (h->H + kTileRows - 1) / kTileRows, ct = (h->W + kTileCols - 1) / kTileCols;
     const dim3 grid(rt * ct * nout);
     ProfScope ps(h, s, MM_K_COMPOSE, nout);
-    MM_FMT_SWITCH(fmt, hipLaunchKernelGGL((k4_kernel<FMT_>()), grid, dim3(kTileCols), 0, s, h->d_Yh,
+    MM_PAIR_SWITCH(fr, hipLaunchKernelGGL((k4_kernel<FMT_>()), grid, dim3(kTileCols), 0, s, h->d_Yh,
                                           h->yh_stride, in, out, frame0, rt, ct, geo_of(h, fr), h->blur,
                                           h->d_col3, h->d_row3))
     HIPCHK(hipGetLastError());
@@ -1120,9 +1192,11 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
 // W x H samples bitwise, the destination's padding untouched.  Tight frames
 // back to back on both sides are one device copy; any other layout goes
 // through k_copy_rows, one launch for the n frames.
+static int convert_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const Frames &fr, hipStream_t s);
 static int copy_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const Frames &fr, hipStream_t s)
 {
     if (n <= 0) return MM_OK;
+    if (fr.mixed()) return convert_frames(h, in, out, n, fr, s);   // no bitwise passthrough between two formats
     if (fr.packed) {
         HIPCHK(hipMemcpyAsync(out, in, fr.fb * n, hipMemcpyDeviceToDevice, s));
         return MM_OK;
@@ -1137,6 +1211,64 @@ static int copy_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, con
         if (fmt_unit(fr.fmt) == 1) hipLaunchKernelGGL((k_copy_rows<uint8_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
         else if (fmt_unit(fr.fmt) == 2) hipLaunchKernelGGL((k_copy_rows<uint16_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
         else hipLaunchKernelGGL((k_copy_rows<uint32_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
+        HIPCHK(hipGetLastError());
+    }
+    return MM_OK;
+}
+
+// k_convert's quads: W % 4 == 0 and, on the NV12 side, rows on multiples of 4
+// (the RGBA8 side's 16-byte quads and P010's 8-byte ones are multi-dword
+// accesses at dword-aligned addresses in every layout)
+static bool convert_quads_aligned(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int n)
+{
+    if (h->W % 4) return false;
+    if (fmt_nv12(fr.fmt)) {   // luma rows too: a luma dword per row
+        uintptr_t m = reinterpret_cast<uintptr_t>(in) | fr.in.pitch;
+        if (n > 1) m |= fr.in.stride;
+        return (m & 3u) == 0 && nv12_in_aligned(in, fr, n);
+    }
+    return !fmt_nv12(fr.ofmt) || nv12_out_aligned(out, fr, n);
+}
+// The passthrough frames of a convert call: the plain conversion (k_convert),
+// one launch for the n frames.  The decode's coefficients over the chroma code
+// scale (of the 16-bit word for P010) travel in Cvt; BT.601's are its standing
+// six-digit ones (include/mm.h).
+static int convert_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const Frames &fr, hipStream_t s)
+{
+    if (n <= 0) return MM_OK;
+    const Geo g = geo_of(h, fr);
+    Cvt cv = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (fmt_420(fr.fmt)) {
+        const int fmt = fr.fmt;
+        const bool full = fmt_full(fmt), p10 = fmt_p010(fmt);
+        const double cs = (p10 ? (full ? 1023.0 : 896.0) : (full ? 255.0 : 224.0)) * (p10 ? 64.0 : 1.0);
+        double rcr = 1.402, gcb = -0.344136, gcr = -0.714136, bcb = 1.772;
+        if (fmt_matrix(fmt)) {
+            double kr, kb;
+            matrix_krkb(fmt, &kr, &kb);
+            const double kg = 1.0 - kr - kb;
+            rcr = 2.0 * (1.0 - kr), gcb = -2.0 * kb * (1.0 - kb) / kg, gcr = -2.0 * kr * (1.0 - kr) / kg,
+            bcb = 2.0 * (1.0 - kb);
+        }
+        cv.rcr = (float)(rcr / cs), cv.gcb = (float)(gcb / cs), cv.gcr = (float)(gcr / cs), cv.bcb = (float)(bcb / cs);
+    }
+    const bool quad = convert_quads_aligned(h, in, out, fr, n);
+    const size_t nb = (size_t)((h->W + 3) / 4) * (size_t)(h->H / 2);
+    const int per = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, ((size_t)1 << 38) / nb));   // (grid x < 2^31)
+    for (int f0 = 0; f0 < n; f0 += per) {
+        const int m = std::min(per, n - f0);
+        const dim3 grid((unsigned)((nb * m + 255) / 256));
+        const uint8_t *src = in + fr.in.stride * f0;
+        uint8_t *dst = out + fr.out.stride * f0;
+#define MM_CONVERT_LAUNCH(F)                                                                              \
+        do {                                                                                              \
+            if (quad) hipLaunchKernelGGL((k_convert<F, true>), grid, dim3(256), 0, s, src, dst, g, cv, m); \
+            else hipLaunchKernelGGL((k_convert<F, false>), grid, dim3(256), 0, s, src, dst, g, cv, m);    \
+        } while (0)
+        if (fmt_nv12(fr.fmt)) MM_CONVERT_LAUNCH(kFmtNV12toRGBA8);
+        else if (fmt_p010(fr.fmt)) MM_CONVERT_LAUNCH(kFmtP010toRGBA8);
+        else MM_CONVERT_LAUNCH(kFmtRGBA8toNV12);
+#undef MM_CONVERT_LAUNCH
         HIPCHK(hipGetLastError());
     }
     return MM_OK;

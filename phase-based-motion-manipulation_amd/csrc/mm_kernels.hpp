@@ -522,6 +522,22 @@ template <int FMT> constexpr bool kY210 = FMT == kFmtY210 || FMT == kFmtY210M;
 // packed RGB (section below): kFmtRGB24 runs every MM_RGB24 and MM_BGR24 frame
 constexpr int kFmtRGB24 = 13;  // MM_RGB24
 template <int FMT> constexpr bool kRGB24 = FMT == kFmtRGB24;
+// Different formats in and out (mm_process_convert): the compose kernels'
+// FMT names a PAIR.  A plain format code (< 256) is that format on both sides,
+// so the same-format instances keep their names and their code; a mixed pair
+// is in | (out + 1) << 8.  Every load-side choice of a compose kernel reads
+// kFmtIn<FMT> (the staged raw type, chroma_row / src_iq2, the 4:2:0 sharing of
+// chroma rows), every store-side choice kFmtOut<FMT> (the quad store, cd0).
+// The ranges and matrices stay uniforms: Geo::nv's (cb, cr) -> (I, Q) fields
+// are the input format's, its kr .. cro fields the output format's (geo_of).
+constexpr int fmt_pair(int in, int out) { return in | (out + 1) << 8; }
+template <int FMT> constexpr int kFmtIn = FMT & 255;
+template <int FMT> constexpr int kFmtOut = FMT < 256 ? FMT : (FMT >> 8) - 1;
+constexpr int kFmtNV12toRGBA8 = fmt_pair(kFmtNV12, 0);   // decode: MM_NV12* in, MM_RGBA8 out
+constexpr int kFmtP010toRGBA8 = fmt_pair(kFmtP010, 0);   // decode: MM_P010* in, MM_RGBA8 out
+constexpr int kFmtRGBA8toNV12 = fmt_pair(0, kFmtNV12);   // encode: MM_RGBA8 in, MM_NV12* out
+template <int FMT> constexpr bool kFmtPairOk = FMT < 256 || FMT == kFmtNV12toRGBA8 || FMT == kFmtP010toRGBA8 ||
+                                               FMT == kFmtRGBA8toNV12;
 // an input macropixel's chroma bytes (byte order: Geo::li.yb; the shifts are uniform)
 __device__ __forceinline__ float c422_cb(unsigned u, const Geo &g) { return (float)((u >> (8u - 8u * g.li.yb)) & 255u); }
 __device__ __forceinline__ float c422_cr(unsigned u, const Geo &g) { return (float)((u >> (24u - 8u * g.li.yb)) & 255u); }
@@ -2678,6 +2694,8 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                const float4 *__restrict__ rowW3)
 {
     constexpr int TR = kTileRows, TC = kTileCols, WC = TC + 2;
+    constexpr int FI = kFmtIn<FMT>, FO = kFmtOut<FMT>;   // (a plain format: both are FMT)
+    static_assert(kFmtPairOk<FMT>, "a format, or one of the three mixed pairs");
     __shared__ c2 iq[(TR + 2) * WC];         // I/Q of the staged source pixels
     const int tid = threadIdx.x;
     int b = blockIdx.x;
@@ -2692,20 +2710,20 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     // or clamped like the resample's sampler.  Rows are workgroup-uniform (scalar
     // base pointers); thread tid stages column j = tid of every row, and threads
     // 0, 1 also the halo columns j = TC, TC+1.
-    using raw_t = typename ChromaSrc<FMT>::raw_t;
+    using raw_t = typename ChromaSrc<FI>::raw_t;
     // 32-bit offsets from workgroup-uniform row pointers: scalar base + vector
     // offset addressing, no 64-bit address math per access
     // (NV12: the pixel's (Cb, Cr) pair, shared with its 2x2 neighbours)
     auto src_off = [&](int row, unsigned col) {
-        if constexpr (k420<FMT>) return c420_off<FMT>(g, row, col);
-        else if constexpr (k422<FMT>) return c422_off(g, row, col);
-        else if constexpr (kY210<FMT>) return y210_off(g, row, col);
-        else if constexpr (kRGB24<FMT>) return (unsigned)row * g.li.pitch;   // (the row: rgb24_px adds the column)
-        else return (unsigned)row * g.li.pitch + col * Pix<FMT>::bpp;
+        if constexpr (k420<FI>) return c420_off<FI>(g, row, col);
+        else if constexpr (k422<FI>) return c422_off(g, row, col);
+        else if constexpr (kY210<FI>) return y210_off(g, row, col);
+        else if constexpr (kRGB24<FI>) return (unsigned)row * g.li.pitch;   // (the row: rgb24_px adds the column)
+        else return (unsigned)row * g.li.pitch + col * Pix<FI>::bpp;
     };
     // (packed RGB: the byte-aligned dword of the pixel)
     auto ld_src = [&](int row, unsigned col) {
-        if constexpr (kRGB24<FMT>) return rgb24_px(img, src_off(row, col), col, g);
+        if constexpr (kRGB24<FI>) return rgb24_px(img, src_off(row, col), col, g);
         else return ld_off<raw_t>(img, src_off(row, col));
     };
     const unsigned colA = (unsigned)wrap_near(min(c0 - 1 + tid, g.W), g.W, g.edge);
@@ -2738,9 +2756,9 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     const int hrow = wrap_near(min(i0 - 1 + (hs >> 1), g.H), g.H, g.edge);
     const int hcol = wrap_near(min(c0 - 1 + TC + (hs & 1), g.W), g.W, g.edge);
     const raw_t ph = ld_src(hrow, (unsigned)hcol);
-    if (tid < NH) iq[(hs >> 1) * WC + TC + (hs & 1)] = src_iq2<FMT>(ph, g);
+    if (tid < NH) iq[(hs >> 1) * WC + TC + (hs & 1)] = src_iq2<FI>(ph, g);
 #pragma unroll
-    for (int sr = 0; sr < TR + 2; ++sr) iq[sr * WC + tid] = src_iq2<FMT>(pa[sr], g);
+    for (int sr = 0; sr < TR + 2; ++sr) iq[sr * WC + tid] = src_iq2<FI>(pa[sr], g);
     __syncthreads();
     if (!vx) return;
     c2 hc[TR + 2];   // horizontally combined (I, Q) of each staged row
@@ -2761,7 +2779,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                              bw.w2 * (yv[r] + yv[r + 4]);
             float rr, gg, bb;
             yiq_rgb(yb, cc, rr, gg, bb);
-            if constexpr (k420<FMT>) {
+            if constexpr (k420<FO>) {
                 // One luma byte per pixel.  The 2x2 chroma mean: this column's
                 // two rows (i0 and TR even: r even starts a block; H even: both
                 // rows are inside), plus the neighbour column's from the lane
@@ -2772,7 +2790,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 static_assert(TR % 2 == 0 && TC % 2 == 0, "NV12: tiles of whole 2x2 blocks");
                 c2 cd;
                 const unsigned yc = nv12_ycode(rr, gg, bb, g, cd);
-                if constexpr (kP010<FMT>) {   // one 16-bit word per lane (always aligned)
+                if constexpr (kP010<FO>) {   // one 16-bit word per lane (always aligned)
                     st_off<uint16_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X * 2u, (uint16_t)(yc << 6));
                 } else {
                     st_off<uint8_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X, (uint8_t)yc);
@@ -2785,7 +2803,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                     const float mine = X & 1 ? v.y : v.x, send = X & 1 ? v.x : v.y;
                     const float theirs = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
                         __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
-                    if constexpr (kP010<FMT>) {
+                    if constexpr (kP010<FO>) {
                         const unsigned cc10 = p010_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
                         st_off<uint16_t>(outp, g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch + (unsigned)X * 2u,
                                          (uint16_t)(cc10 << 6));
@@ -2794,7 +2812,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                         st_off<uint8_t>(outp, g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch + (unsigned)X, (uint8_t)cc8);
                     }
                 }
-            } else if constexpr (k422<FMT>) {
+            } else if constexpr (k422<FO>) {
                 // The lane pair (X ^ 1 is tid ^ 1: c0 and W are even, as above)
                 // is one macropixel.  As for NV12, each lane keeps the chroma
                 // component it encodes (even: Cb, odd: Cr) and sends the other
@@ -2813,7 +2831,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)half, 0xB1, 0xF, 0xF, true);
                 if (!(X & 1))
                     st_stream<uint32_t>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 2u, half | other << 16);
-            } else if constexpr (kY210<FMT>) {
+            } else if constexpr (kY210<FO>) {
                 // The same exchange with 10-bit codes: a lane's luma and chroma
                 // words are one dword of the macropixel, and the even lane
                 // stores the macropixel's two dwords (8 bytes, always aligned).
@@ -2827,10 +2845,10 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)half, 0xB1, 0xF, 0xF, true);
                 if (!(X & 1))
                     st_stream<uint2>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 4u, make_uint2(half, other));
-            } else if constexpr (kRGB24<FMT>) {   // three bytes per lane
+            } else if constexpr (kRGB24<FO>) {   // three bytes per lane
                 rgb24_store(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, rr, gg, bb, g);
             } else {
-                Pix<FMT>::store(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
+                Pix<FO>::store(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
             }
         }
     }
@@ -2921,7 +2939,8 @@ __device__ unsigned long long mm_k34_stamps[65536 * 8];
 // barriers of pass 0, which every wave reaches only after its previous compose
 // (the last reader of the rows); each wave waits for its own copies before the
 // barrier that ends the blur, and the compose reads after that barrier.
-template <int FMT> constexpr bool k34_dma_fmt = FMT == MM_RGBA8 || FMT == MM_RGBA8_SRGB;
+// (... and the encode pair's, MM_RGBA8 in with NV12 out: the same 4-byte source pixels)
+template <int FMT> constexpr bool k34_dma_fmt = FMT == MM_RGBA8 || FMT == MM_RGBA8_SRGB || FMT == kFmtRGBA8toNV12;
 template <int LOG2N> constexpr int k34_src_bytes() { return 4 * 4 * (1 << LOG2N); }
 template <int LOG2N, int FMT, bool SRCDMA = false>
 __global__ __launch_bounds__(2 * fft_T<LOG2N>()) __attribute__((amdgpu_waves_per_eu(4)))
@@ -2932,8 +2951,11 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         const c2 *__restrict__ tw)
 {
     constexpr int N = 1 << LOG2N, T = fft_T<LOG2N>(), TK = q_tile<LOG2N>();
-    using raw_t = typename ChromaSrc<FMT>::raw_t;
-    constexpr unsigned bpp = LumaSrc<FMT>::bpp;   // (NV12: 1, the luma plane's)
+    constexpr int FI = kFmtIn<FMT>, FO = kFmtOut<FMT>;   // (a plain format: both are FMT)
+    static_assert(kFmtPairOk<FMT>, "a format, or one of the three mixed pairs");
+    using raw_t = typename ChromaSrc<FI>::raw_t;
+    constexpr unsigned bpp = LumaSrc<FI>::bpp;   // (NV12: 1, the luma plane's)
+    [[maybe_unused]] constexpr unsigned bppo = LumaSrc<FO>::bpp;   // ... and the output side's
     static_assert(!SRCDMA || k34_dma_fmt<FMT>, "staged source rows: 4-byte pixels");
     extern __shared__ __attribute__((aligned(16))) c2 lds_raw[];
     [[maybe_unused]] const uint8_t *srcl = reinterpret_cast<const uint8_t *>(lds_raw);   // [4][4 N] staged rows
@@ -2958,32 +2980,32 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     // horizontally combined I/Q of one source row for the quad (k_compose's
     // staged 3-tap combine over columns X-1 .. X+4)
     auto chroma_row = [&](int i, c2 (&hc)[4]) {
-        if constexpr (!kMono<FMT>) {   // (a gray frame's (I, Q) is zero: nothing to read)
+        if constexpr (!kMono<FI>) {   // (a gray frame's (I, Q) is zero: nothing to read)
             const int row = wrap_near(min(i, g.H), g.H, g.edge);
             c2 a[6];
-            if constexpr (k422<FMT>) {
+            if constexpr (k422<FI>) {
                 // macropixels X/2-1 .. X/2+2: the quad's own two as one 8-byte load
                 c422_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
-            } else if constexpr (kY210<FMT>) {
+            } else if constexpr (kY210<FI>) {
                 // ... of 8 bytes each: the quad's own two as one 16-byte load
                 y210_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
-            } else if constexpr (kRGB24<FMT>) {
+            } else if constexpr (kRGB24<FI>) {
                 // three-byte pixels: the quad's own four as one 12-byte load
                 rgb24_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
-            } else if constexpr (k420<FMT>) {
+            } else if constexpr (k420<FI>) {
                 // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
                 // outer two wrapped or clamped as pixels, then halved): the quad's
                 // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
                 // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
                 // (P010: pairs are dwords, the quad's own two as two dword loads)
-                const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
+                const unsigned pl = ld_off<raw_t>(img, c420_off<FI>(g, row, cl));
                 unsigned pm0, pm1;
-                c420_quad_pairs<FMT>(img, g, row, (unsigned)X, pm0, pm1);
-                const unsigned pr = ld_off<raw_t>(img, c420_off<FMT>(g, row, cr));
-                a[0] = c420_iq2<FMT>(pl, g);
-                a[1] = a[2] = c420_iq2<FMT>(pm0, g);
-                a[3] = a[4] = c420_iq2<FMT>(pm1, g);
-                a[5] = c420_iq2<FMT>(pr, g);
+                c420_quad_pairs<FI>(img, g, row, (unsigned)X, pm0, pm1);
+                const unsigned pr = ld_off<raw_t>(img, c420_off<FI>(g, row, cr));
+                a[0] = c420_iq2<FI>(pl, g);
+                a[1] = a[2] = c420_iq2<FI>(pm0, g);
+                a[3] = a[4] = c420_iq2<FI>(pm1, g);
+                a[5] = c420_iq2<FI>(pr, g);
             } else {
                 // (in pixels: an RGBA pitch is a multiple of the pixel size)
                 const unsigned base = (unsigned)row * (g.li.pitch / bpp);
@@ -2998,7 +3020,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                 }
                 p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
 #pragma unroll
-                for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
+                for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FI>(p[k]);
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -3032,7 +3054,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
             p[5] = *reinterpret_cast<const unsigned *>(rowp + cr * 4u);
             c2 a[6];
 #pragma unroll
-            for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
+            for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FI>(p[k]);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float4 wc = colW3[X + k];
@@ -3144,7 +3166,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
         if (s > 0) {
             // ---- K4 on output rows i0+4s-4 .. i0+4s-1, two at a time ----
             // the 4 chroma rows' loads first (one memory round trip)
-            if constexpr (k420<FMT>) {
+            if constexpr (k420<FI>) {
                 // source rows 2j and 2j+1 share a chroma row (i0 % 4 == 0, H
                 // even): row i0+4s-3 has the kept row i0+4s-4's samples, row
                 // i0+4s-1 those of i0+4s-2; two loads per step, not four
@@ -3188,27 +3210,27 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
                     }
                     // (in pixels: an RGBA pitch is a multiple of the pixel size)
-                    [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
-                    if constexpr (k422<FMT>) {
+                    [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bppo) + (unsigned)X;
+                    if constexpr (k422<FO>) {
                         c422_store_quad(outp, g, i, X, rr, gg, bb);
-                    } else if constexpr (kY210<FMT>) {
+                    } else if constexpr (kY210<FO>) {
                         y210_store_quad(outp, g, i, X, rr, gg, bb);
-                    } else if constexpr (kRGB24<FMT>) {
+                    } else if constexpr (kRGB24<FO>) {
                         rgb24_store_quad(outp, g, i, X, rr, gg, bb);
-                    } else if constexpr (k420<FMT>) {
-                        c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
-                    } else if constexpr (bpp == 4) {
+                    } else if constexpr (k420<FO>) {
+                        c420_store_quad<FO>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
+                    } else if constexpr (bppo == 4) {
                         uint4 px;
-                        px.x = Pix<FMT>::pack(rr[0], gg[0], bb[0]);
-                        px.y = Pix<FMT>::pack(rr[1], gg[1], bb[1]);
-                        px.z = Pix<FMT>::pack(rr[2], gg[2], bb[2]);
-                        px.w = Pix<FMT>::pack(rr[3], gg[3], bb[3]);
+                        px.x = Pix<FO>::pack(rr[0], gg[0], bb[0]);
+                        px.y = Pix<FO>::pack(rr[1], gg[1], bb[1]);
+                        px.z = Pix<FO>::pack(rr[2], gg[2], bb[2]);
+                        px.w = Pix<FO>::pack(rr[3], gg[3], bb[3]);
                         // scalar row base + the thread's column offset: one
                         // live VGPR, not a hoisted offset per row
                         st_stream_quad_a4(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 4u, px);
                     } else {
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) Pix<FMT>::store(outp, o + k, rr[k], gg[k], bb[k]);
+                        for (int k = 0; k < 4; ++k) Pix<FO>::store(outp, o + k, rr[k], gg[k], bb[k]);
                     }
                 }
             }
@@ -3256,8 +3278,11 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                          const c2 *__restrict__ tw)
 {
     constexpr int N = 1 << LOG2N, T = fft_T<LOG2N>(), TK = q_tile<LOG2N>();
-    using raw_t = typename ChromaSrc<FMT>::raw_t;
-    constexpr unsigned bpp = LumaSrc<FMT>::bpp;   // (NV12: 1, the luma plane's)
+    constexpr int FI = kFmtIn<FMT>, FO = kFmtOut<FMT>;   // (a plain format: both are FMT)
+    static_assert(kFmtPairOk<FMT>, "a format, or one of the three mixed pairs");
+    using raw_t = typename ChromaSrc<FI>::raw_t;
+    constexpr unsigned bpp = LumaSrc<FI>::bpp;   // (NV12: 1, the luma plane's)
+    [[maybe_unused]] constexpr unsigned bppo = LumaSrc<FO>::bpp;   // ... and the output side's
     extern __shared__ __attribute__((aligned(16))) c2 lds_all[];
     const int grp = T % 64 == 0 ? __builtin_amdgcn_readfirstlane(threadIdx.x / T) : threadIdx.x / T;
     const int t = threadIdx.x % T;
@@ -3312,32 +3337,32 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     const unsigned cl = (unsigned)wrap_near(X - 1, g.W, g.edge);
     const unsigned cr = (unsigned)wrap_near(X + 4, g.W, g.edge);
     auto chroma_row = [&](int i, c2 (&hc)[4]) {   // k_rows_inv_compose's
-        if constexpr (!kMono<FMT>) {   // (a gray frame's (I, Q) is zero: nothing to read)
+        if constexpr (!kMono<FI>) {   // (a gray frame's (I, Q) is zero: nothing to read)
             const int row = wrap_near(min(i, g.H), g.H, g.edge);
             c2 a[6];
-            if constexpr (k422<FMT>) {
+            if constexpr (k422<FI>) {
                 // macropixels X/2-1 .. X/2+2: the quad's own two as one 8-byte load
                 c422_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
-            } else if constexpr (kY210<FMT>) {
+            } else if constexpr (kY210<FI>) {
                 // ... of 8 bytes each: the quad's own two as one 16-byte load
                 y210_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
-            } else if constexpr (kRGB24<FMT>) {
+            } else if constexpr (kRGB24<FI>) {
                 // three-byte pixels: the quad's own four as one 12-byte load
                 rgb24_quad_iq(img, g, row, (unsigned)X, cl, cr, a);
-            } else if constexpr (k420<FMT>) {
+            } else if constexpr (k420<FI>) {
                 // source columns X-1 .. X+4 are chroma samples X/2-1 .. X/2+2 (the
                 // outer two wrapped or clamped as pixels, then halved): the quad's
                 // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
                 // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
                 // (P010: pairs are dwords, the quad's own two as two dword loads)
-                const unsigned pl = ld_off<raw_t>(img, c420_off<FMT>(g, row, cl));
+                const unsigned pl = ld_off<raw_t>(img, c420_off<FI>(g, row, cl));
                 unsigned pm0, pm1;
-                c420_quad_pairs<FMT>(img, g, row, (unsigned)X, pm0, pm1);
-                const unsigned pr = ld_off<raw_t>(img, c420_off<FMT>(g, row, cr));
-                a[0] = c420_iq2<FMT>(pl, g);
-                a[1] = a[2] = c420_iq2<FMT>(pm0, g);
-                a[3] = a[4] = c420_iq2<FMT>(pm1, g);
-                a[5] = c420_iq2<FMT>(pr, g);
+                c420_quad_pairs<FI>(img, g, row, (unsigned)X, pm0, pm1);
+                const unsigned pr = ld_off<raw_t>(img, c420_off<FI>(g, row, cr));
+                a[0] = c420_iq2<FI>(pl, g);
+                a[1] = a[2] = c420_iq2<FI>(pm0, g);
+                a[3] = a[4] = c420_iq2<FI>(pm1, g);
+                a[5] = c420_iq2<FI>(pr, g);
             } else {
                 // (in pixels: an RGBA pitch is a multiple of the pixel size)
                 const unsigned base = (unsigned)row * (g.li.pitch / bpp);
@@ -3352,7 +3377,7 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                 }
                 p[5] = ld_off<raw_t>(img, (base + cr) * bpp);
 #pragma unroll
-                for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FMT>(p[k]);
+                for (int k = 0; k < 6; ++k) a[k] = chroma_iq2<FI>(p[k]);
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -3365,7 +3390,7 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
     [[maybe_unused]] c2 hc[4][4];   // combined (I, Q) of source rows r0-1 .. r0+2 (gray: none)
     if constexpr (kMono<FMT>) {
         // (nothing to read)
-    } else if constexpr (k420<FMT>) {   // rows r0, r0+1 (r0 even) share a chroma row
+    } else if constexpr (k420<FI>) {   // rows r0, r0+1 (r0 even) share a chroma row
         chroma_row(r0 - 1, hc[0]);
         chroma_row(r0, hc[1]);
 #pragma unroll
@@ -3412,25 +3437,25 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                                  bw.w2 * (yw[r][k] + yw[r + 4][k]);
                 yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
             }
-            [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bpp) + (unsigned)X;
-            if constexpr (k422<FMT>) {
+            [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bppo) + (unsigned)X;
+            if constexpr (k422<FO>) {
                 c422_store_quad(outp, g, i, X, rr, gg, bb);
-            } else if constexpr (kY210<FMT>) {
+            } else if constexpr (kY210<FO>) {
                 y210_store_quad(outp, g, i, X, rr, gg, bb);
-            } else if constexpr (kRGB24<FMT>) {
+            } else if constexpr (kRGB24<FO>) {
                 rgb24_store_quad(outp, g, i, X, rr, gg, bb);
-            } else if constexpr (k420<FMT>) {
-                c420_store_quad<FMT>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
-            } else if constexpr (bpp == 4) {
+            } else if constexpr (k420<FO>) {
+                c420_store_quad<FO>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
+            } else if constexpr (bppo == 4) {
                 uint4 px;
-                px.x = Pix<FMT>::pack(rr[0], gg[0], bb[0]);
-                px.y = Pix<FMT>::pack(rr[1], gg[1], bb[1]);
-                px.z = Pix<FMT>::pack(rr[2], gg[2], bb[2]);
-                px.w = Pix<FMT>::pack(rr[3], gg[3], bb[3]);
+                px.x = Pix<FO>::pack(rr[0], gg[0], bb[0]);
+                px.y = Pix<FO>::pack(rr[1], gg[1], bb[1]);
+                px.z = Pix<FO>::pack(rr[2], gg[2], bb[2]);
+                px.w = Pix<FO>::pack(rr[3], gg[3], bb[3]);
                 st_stream_quad_a4(outp, o * 4u, px);
             } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) Pix<FMT>::store(outp, o + k, rr[k], gg[k], bb[k]);
+                for (int k = 0; k < 4; ++k) Pix<FO>::store(outp, o + k, rr[k], gg[k], bb[k]);
             }
         }
     }
@@ -3621,6 +3646,162 @@ void k_copy_rows(const uint8_t *__restrict__ frames_in, uint8_t *__restrict__ fr
                    (c < 0 ? (size_t)((unsigned)r * g.lo.pitch) : (size_t)(g.lo.c_off + (unsigned)c * g.lo.c_pitch));
     for (unsigned o = threadIdx.x * (unsigned)sizeof(U); o < row_bytes; o += 256u * (unsigned)sizeof(U))
         st_off<U>(dst, o, ld_off<U>(src, o));
+}
+
+// =========================================================================
+// plain conversion between two formats (mm_process_convert's passthrough frames)
+// =========================================================================
+// Where the formats of the two sides differ, the frames that pass through (the
+// first frame, apply_magnification = 0, the seed frame of a stream) cannot be
+// copied: they are converted, the out rule applied to the saturated RGBA32F
+// frame the in frame IS (include/mm.h).  One launch for n frames, one lane per
+// block of 4 x 2 pixels, so that the two (Cb, Cr) pairs of a 4:2:0 side stay
+// in the lane: FMT is one of the three mixed pairs.
+//   NV12 in:  two luma dwords and one chroma dword, two 16-byte stores
+//   P010 in:  two 8-byte luma loads and two 4-byte chroma loads (c420_quad_pairs)
+//   RGBA8 in: two 16-byte loads, two luma dwords and one chroma dword out
+// QUAD: W % 4 == 0 and every row of every frame of the launch on a multiple of
+// 4 bytes on the 8-bit 4:2:0 side (convert_quads_aligned, mm_impl.hpp); the
+// multi-dword accesses are typed with the alignment they have (ld_quad_a4).
+// !QUAD: the same lane, the same arithmetic, single samples, pairs and pixels,
+// and the columns of the block that lie inside W (W is even: two or four).
+// The decode is the format's matrix in fp32, not the YIQ detour: the decode's
+// coefficients over the chroma code scale come in Cvt (Geo has no field for
+// them), the luma scale and every output weight in Geo::nv.  Nothing outside
+// the W x H samples is read or written.
+struct Cvt {
+    float rcr, gcb, gcr, bcb;   // R = y + rcr (Cr - mid), G = y + gcb (Cb - mid) + gcr (Cr - mid), B = y + bcb (Cb - mid)
+};
+template <int FMT, bool QUAD>
+__global__ __launch_bounds__(256)
+void k_convert(const uint8_t *__restrict__ frames_in, uint8_t *__restrict__ frames_out, Geo g, Cvt cv, int nframes)
+{
+    constexpr int FI = kFmtIn<FMT>, FO = kFmtOut<FMT>;
+    static_assert(FMT >= 256 && kFmtPairOk<FMT>, "one of the three mixed pairs");
+    const unsigned bw = (unsigned)(g.W + 3) / 4u;            // blocks per row pair
+    const size_t nb = (size_t)bw * (unsigned)(g.H / 2);     // ... per frame
+    const size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (e >= nb * (size_t)nframes) return;
+    const unsigned frame = (unsigned)(e / nb), p = (unsigned)(e - (size_t)frame * nb);
+    const unsigned by = p / bw, X = (p - by * bw) * 4u, Y = by * 2u;
+    const int nc = QUAD ? 4 : min(4, g.W - (int)X);          // columns of the block inside W: 4 or 2
+    const uint8_t *img = frames_in + (size_t)frame * g.li.stride;
+    uint8_t *outp = frames_out + (size_t)frame * g.lo.stride;
+
+    float rr[2][4], gg[2][4], bb[2][4];   // the block's saturated RGB
+    if constexpr (k420<FI>) {
+        constexpr unsigned sb = kP010<FI> ? 2u : 1u;           // bytes per sample
+        constexpr float mid = kP010<FI> ? 32768.0f : 128.0f;   // neutral chroma, in the sample's units
+        float yv[2][4];
+        unsigned pr[2];   // the block's two (Cb, Cr) pairs
+        [[maybe_unused]] const unsigned coff = g.li.c_off + by * g.li.c_pitch + X * sb;
+        if constexpr (QUAD) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const unsigned off = (Y + r) * g.li.pitch + X * sb;
+                if constexpr (kP010<FI>) {
+                    const uint2 w = ld_pair_a4(img, off);
+                    yv[r][0] = (float)(w.x & 0xFFFFu); yv[r][1] = (float)(w.x >> 16);
+                    yv[r][2] = (float)(w.y & 0xFFFFu); yv[r][3] = (float)(w.y >> 16);
+                } else {
+                    const unsigned w = ld_off<uint32_t>(img, off);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) yv[r][k] = (float)((w >> (8 * k)) & 255u);
+                }
+            }
+            c420_quad_pairs<FI>(img, g, (int)Y, X, pr[0], pr[1]);
+        } else {
+            using luma_t = typename LumaSrc<FI>::raw_t;
+            using pair_t = typename ChromaSrc<FI>::raw_t;
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    yv[r][k] = k < nc ? (float)ld_off<luma_t>(img, (Y + r) * g.li.pitch + (X + k) * sb) : 0.0f;
+            pr[0] = ld_off<pair_t>(img, coff);
+            pr[1] = nc > 2 ? (unsigned)ld_off<pair_t>(img, coff + 2u * sb) : pr[0];
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float cb, cr;
+            if constexpr (kP010<FI>) cb = (float)(pr[j] & 0xFFFFu) - mid, cr = (float)(pr[j] >> 16) - mid;
+            else cb = (float)(pr[j] & 255u) - mid, cr = (float)((pr[j] >> 8) & 255u) - mid;
+            const float dr = cv.rcr * cr, dg = cv.gcb * cb + cv.gcr * cr, db = cv.bcb * cb;
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int k = 2 * j; k < 2 * j + 2; ++k) {
+                    const float y = (yv[r][k] - g.nv.y_off) * g.nv.y_unit;
+                    rr[r][k] = sat(y + dr); gg[r][k] = sat(y + dg); bb[r][k] = sat(y + db);
+                }
+        }
+    } else {   // RGBA8 in: byte / 255 (in [0, 1] already), alpha ignored
+        constexpr float s = 1.0f / 255.0f;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const unsigned off = (Y + r) * g.li.pitch + X * 4u;
+            unsigned px[4];
+            if constexpr (QUAD) {
+                const uint4 m = ld_quad_a4(img, off);
+                px[0] = m.x; px[1] = m.y; px[2] = m.z; px[3] = m.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) px[k] = k < nc ? ld_off<uint32_t>(img, off + 4u * k) : 0u;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                rr[r][k] = (float)(px[k] & 255u) * s;
+                gg[r][k] = (float)((px[k] >> 8) & 255u) * s;
+                bb[r][k] = (float)((px[k] >> 16) & 255u) * s;
+            }
+        }
+    }
+
+    if constexpr (FO == 0) {   // RGBA8 out: Pix<0>::pack, alpha 255
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            uint8_t *row = outp + (size_t)((Y + r) * g.lo.pitch);
+            if constexpr (QUAD) {
+                uint4 px;
+                px.x = Pix<0>::pack(rr[r][0], gg[r][0], bb[r][0]);
+                px.y = Pix<0>::pack(rr[r][1], gg[r][1], bb[r][1]);
+                px.z = Pix<0>::pack(rr[r][2], gg[r][2], bb[r][2]);
+                px.w = Pix<0>::pack(rr[r][3], gg[r][3], bb[r][3]);
+                st_stream_quad_a4(row, X * 4u, px);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < nc) st_off<uint32_t>(row, (X + k) * 4u, Pix<0>::pack(rr[r][k], gg[r][k], bb[r][k]));
+            }
+        }
+    } else {   // NV12 out: the compose kernels' codes (nv12_ycode, nv12_ccode) and their order of sums
+        static_assert(kNV12<FO>, "the 4:2:0 destination of a mixed pair is NV12");
+        c2 cd[2][4];
+        unsigned yc[2][4];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) yc[r][k] = nv12_ycode(rr[r][k], gg[r][k], bb[r][k], g, cd[r][k]);
+        const c2 b0 = (cd[0][0] + cd[1][0]) + (cd[0][1] + cd[1][1]), b1 = (cd[0][2] + cd[1][2]) + (cd[0][3] + cd[1][3]);
+        const unsigned c0 = nv12_ccode(b0.x, g.nv.cbo) | nv12_ccode(b0.y, g.nv.cro) << 8;
+        const unsigned c1 = nv12_ccode(b1.x, g.nv.cbo) | nv12_ccode(b1.y, g.nv.cro) << 8;
+        uint8_t *crow = outp + (size_t)(g.lo.c_off + by * g.lo.c_pitch);
+        if constexpr (QUAD) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+                st_stream<uint32_t>(outp + (size_t)((Y + r) * g.lo.pitch), X,
+                                    yc[r][0] | yc[r][1] << 8 | yc[r][2] << 16 | yc[r][3] << 24);
+            st_stream<uint32_t>(crow, X, c0 | c1 << 16);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < nc) st_off<uint8_t>(outp + (size_t)((Y + r) * g.lo.pitch), X + k, (uint8_t)yc[r][k]);
+            st_off<uint16_t>(crow, X, (uint16_t)c0);
+            if (nc > 2) st_off<uint16_t>(crow, X + 2u, (uint16_t)c1);
+        }
+    }
 }
 
 // =========================================================================

@@ -9,7 +9,7 @@
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
  *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
- *          [--yuy2] [--uyvy] [--y210] [--ppm [--bgr]]
+ *          [--yuy2] [--uyvy] [--y210] [--ppm [--bgr]] [--out-rgba8] [--out-nv12]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
@@ -98,6 +98,20 @@
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
  * format, --nv12, --p010, --yuy2, --uyvy and --y210 included.  Files and checksums are those of the
  * run without the flag, byte for byte.  Not with the ring modes.
+ * --out-rgba8 (with --nv12 or --p010): decode on the way out.  The frames go
+ * in as stored and raw MM_RGBA8 frames come out, through
+ * mm_process_stream_convert: -o gets the raw RGBA8 frames, or, a .y4m, the 4:4:4
+ * file the default RGBA8 path writes from them.  Refused without --nv12 /
+ * --p010, with --out-nv12, and with whatever --nv12 / --p010 are refused with.
+ * --out-nv12 (with the RGBA8 input path: a synthetic stream, raw RGBA8 frames,
+ * or a .y4m the host expands as above): encode on the way out.  MM_RGBA8 frames
+ * go in and NV12 frames come out: -o gets a C420 .y4m, or the raw NV12 frames.
+ * --full-range and --matrix then name the OUTPUT code (MM_NV12_FULL, a matrix
+ * bit) and nothing else: a .y4m input is expanded as BT.601 limited range.  Refused with --out-rgba8, every other format option (--nv12, --p010,
+ * --mono, --yuy2, --uyvy, --y210, --ppm), --srgb, the debug views, the ring
+ * modes and odd sizes.
+ * With either, --surface-align lays out each side in its own format's
+ * surface, and --checksum hashes the output frames, as usual.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -469,6 +483,7 @@ int main(int argc, char **argv)
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
     int nv12 = 0, p010 = 0, srgb = 0, mono = 0, yuy2 = 0, uyvy = 0, y210 = 0, ppm = 0, bgr = 0;
+    int out_rgba8 = 0, out_nv12 = 0;
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
@@ -485,6 +500,8 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--y210")) { y210 = 1; continue; }
         if (!strcmp(a, "--ppm")) { ppm = 1; continue; }
         if (!strcmp(a, "--bgr")) { bgr = 1; continue; }
+        if (!strcmp(a, "--out-rgba8")) { out_rgba8 = 1; continue; }
+        if (!strcmp(a, "--out-nv12")) { out_nv12 = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
         if (!strcmp(a, "--show-magnitude")) { show_mag = 1; continue; }
         if (!strcmp(a, "--show-phase")) { show_phase = 1; continue; }
@@ -527,6 +544,27 @@ int main(int argc, char **argv)
         if (y4m_read_header_ext(fi, &yi, &depth)) { fprintf(stderr, "%s: unsupported Y4M\n", in_path); return 1; }
         W = yi.width;
         H = yi.height;
+    }
+    /* different formats in and out (mm_process_stream_convert) */
+    if (out_rgba8 && out_nv12) {
+        fprintf(stderr, "--out-rgba8 does not go with --out-nv12\n");
+        return 2;
+    }
+    if (out_rgba8 && !nv12 && !p010) {
+        fprintf(stderr, "--out-rgba8 needs --nv12 or --p010 (the default path's output is RGBA8 already)\n");
+        return 2;
+    }
+    if (out_nv12) {
+        if (nv12 || p010 || mono || yuy2 || uyvy || y210 || ppm || srgb || show_mag || show_phase || ring_local > 0 ||
+            ring_world > 0) {
+            fprintf(stderr, "--out-nv12 takes the RGBA8 input path: not with --nv12, --p010, --mono, --yuy2, --uyvy, "
+                            "--y210, --ppm, --srgb, the debug views or the ring modes\n");
+            return 2;
+        }
+        if ((W | H) & 1) {
+            fprintf(stderr, "--out-nv12 needs even width and height (%dx%d)\n", W, H);
+            return 2;
+        }
     }
     /* --ppm: a stream of binary PPM images is a stream of MM_RGB24 frames */
     ppm_info pi = {0, 0};
@@ -663,18 +701,27 @@ int main(int argc, char **argv)
         }
         g_fmt = full_range ? MM_NV12_FULL : MM_NV12;
     }
+    /* the output side's format: the input's, but with --out-rgba8 / --out-nv12 */
+    int o_fmt = out_nv12 ? (full_range ? MM_NV12_FULL : MM_NV12) : 0;
     if (matrix_arg) {
-        if (!nv12 && !p010 && !p422 && !y210) {
-            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2, --uyvy or --y210 (the RGBA conversion of a .y4m is BT.601)\n");
+        if (!nv12 && !p010 && !p422 && !y210 && !out_nv12) {
+            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2, --uyvy, --y210 or --out-nv12 (the RGBA conversion of a .y4m is BT.601)\n");
             return 2;
         }
-        if (!strcmp(matrix_arg, "709")) g_fmt |= MM_MATRIX_BT709;
-        else if (!strcmp(matrix_arg, "2020")) g_fmt |= MM_MATRIX_BT2020;
+        /* (--out-nv12: the bit names the output code; the input is RGBA8) */
+        int *mf = out_nv12 ? &o_fmt : &g_fmt;
+        if (!strcmp(matrix_arg, "709")) *mf |= MM_MATRIX_BT709;
+        else if (!strcmp(matrix_arg, "2020")) *mf |= MM_MATRIX_BT2020;
         else if (strcmp(matrix_arg, "601")) {
             fprintf(stderr, "--matrix takes 601, 709 or 2020, not %s\n", matrix_arg);
             return 2;
         }
     }
+    if (out_rgba8) o_fmt = MM_RGBA8;
+    else if (!out_nv12) o_fmt = g_fmt;
+    const int convert = o_fmt != g_fmt;
+    /* what the output files hold */
+    const int w_nv12 = out_nv12 || (nv12 && !out_rgba8), w_p010 = p010 && !out_rgba8;
     mm_params p;
     mm_params_default(&p);
     p.levels = L;
@@ -723,14 +770,19 @@ int main(int argc, char **argv)
     /* --surface-align: the frames the operator sees live in `lay` surfaces
      * (d_in, d_out); d_tin / d_tout are tight device frames for the synthetic
      * source and for the checksums and files */
-    mm_surface tight, lay;
+    size_t fbo = fb;   /* ... and of the output side */
+    if (convert) CHECK(mm_frame_bytes(W, H, o_fmt, &fbo));
+    mm_surface tight, lay, otight, olay;
     CHECK(mm_surface_tight(W, H, g_fmt, &tight));
+    CHECK(mm_surface_tight(W, H, o_fmt, &otight));
     lay = tight;
+    olay = otight;
     if (surf_arg) {
         unsigned long long pa = 0;
         int ra = 0, rc;
         if (sscanf(surf_arg, "%llu,%d", &pa, &ra) != 2 ||
-            (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK) {
+            (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK ||
+            (rc = mm_surface_aligned(W, H, o_fmt, (size_t)pa, ra, &olay)) != MM_OK) {
             fprintf(stderr, "--surface-align %s: want P,R with P a multiple of the format's unit "
                             "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, mono: the sample size, --ppm: 1) and R >= 1 (4:2:0: even)\n", surf_arg);
             return 2;
@@ -739,13 +791,13 @@ int main(int argc, char **argv)
                lay.frame_stride);
     }
     void *d_in = NULL, *d_out = NULL, *d_tin = NULL, *d_tout = NULL;
-    if (hipMalloc(&d_in, lay.frame_stride * B) != hipSuccess || hipMalloc(&d_out, lay.frame_stride * B) != hipSuccess ||
-        (surf_arg && (hipMalloc(&d_tin, fb * B) != hipSuccess || hipMalloc(&d_tout, fb * B) != hipSuccess))) {
+    if (hipMalloc(&d_in, lay.frame_stride * B) != hipSuccess || hipMalloc(&d_out, olay.frame_stride * B) != hipSuccess ||
+        (surf_arg && (hipMalloc(&d_tin, fb * B) != hipSuccess || hipMalloc(&d_tout, fbo * B) != hipSuccess))) {
         fprintf(stderr, "hipMalloc failed\n");
         return 1;
     }
     hipStream_t s = (hipStream_t)mm_stream(h);
-    unsigned char *host = (fi || fo) ? (unsigned char *)malloc(fb * B) : NULL;
+    unsigned char *host = (fi || fo) ? (unsigned char *)malloc((fb > fbo ? fb : fbo) * B) : NULL;
     unsigned char *planes = (y4m_in || y4m_out)
         ? (unsigned char *)malloc(y4m_in ? (y4m_frame_bytes_depth(&yi, depth) > 3 * (size_t)W * H
                                                ? y4m_frame_bytes_depth(&yi, depth) : 3 * (size_t)W * H)
@@ -754,8 +806,8 @@ int main(int argc, char **argv)
     /* (planes: 3 W H bytes hold a C420p10 frame, 2 bytes per sample, exactly; a
      * C422p10 frame takes 4 W H) */
     if (y4m_out && (mono   ? y4m_write_header_mono(fo, W, H, yi.fps_num, yi.fps_den, depth)
-                    : p010 ? y4m_write_header_420p10(fo, W, H, yi.fps_num, yi.fps_den)
-                    : nv12 ? y4m_write_header_420(fo, W, H, yi.fps_num, yi.fps_den)
+                    : w_p010 ? y4m_write_header_420p10(fo, W, H, yi.fps_num, yi.fps_den)
+                    : w_nv12 ? y4m_write_header_420(fo, W, H, yi.fps_num, yi.fps_den)
                     : p422 ? y4m_write_header_422(fo, W, H, yi.fps_num, yi.fps_den)
                     : y210 ? y4m_write_header_422p10(fo, W, H, yi.fps_num, yi.fps_den)
                            : y4m_write_header(fo, W, H, yi.fps_num, yi.fps_den))) {
@@ -783,7 +835,8 @@ int main(int argc, char **argv)
                 else if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
                 else if (p422) y4m_422_to_packed(W, H, planes, host + fb * got, uyvy);
                 else if (y210) y4m_422p10_to_y210(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
-                else y4m_to_rgba(&yi, planes, host + fb * got, full_range);
+                /* (--out-nv12: --full-range names the output code, the input is limited range) */
+                else y4m_to_rgba(&yi, planes, host + fb * got, out_nv12 ? 0 : full_range);
             }
             if (got == 0) break;
             n = got;
@@ -819,7 +872,8 @@ int main(int argc, char **argv)
             if (surf_arg && surf_copy(d_in, &lay, d_tin, &tight, W, H, n, hipMemcpyDeviceToDevice, s)) return 1;
         }
         hipEventRecord(e0, s);
-        if (surf_arg) CHECK(mm_process_stream_surfaces(h, d_in, &lay, d_out, &lay, n, s));
+        if (convert) CHECK(mm_process_stream_convert(h, d_in, &lay, d_out, &olay, n, s));
+        else if (surf_arg) CHECK(mm_process_stream_surfaces(h, d_in, &lay, d_out, &lay, n, s));
         else CHECK(mm_process_stream(h, d_in, d_out, n, g_fmt, s));
         hipEventRecord(e1, s);
         hipEventSynchronize(e1);
@@ -828,14 +882,14 @@ int main(int argc, char **argv)
         if (done > 0) t_proc += ms * 1e-3;      /* first call holds the passthrough frame */
         const void *d_res = d_out;   /* the output frames, tight */
         if (surf_arg && (checksum || fo)) {
-            if (surf_copy(d_tout, &tight, d_out, &lay, W, H, n, hipMemcpyDeviceToDevice, s) ||
+            if (surf_copy(d_tout, &otight, d_out, &olay, W, H, n, hipMemcpyDeviceToDevice, s) ||
                 hipStreamSynchronize(s) != hipSuccess)
                 return 1;
             d_res = d_tout;
         }
-        if (checksum) print_checksums((const unsigned char *)d_res, fb, n, done);
+        if (checksum) print_checksums((const unsigned char *)d_res, fbo, n, done);
         if (fo) {
-            hipMemcpy(host, d_res, fb * n, hipMemcpyDeviceToHost);
+            hipMemcpy(host, d_res, fbo * n, hipMemcpyDeviceToHost);
             if (y4m_out) {
                 for (int k = 0; k < n; ++k) {
                     if (mono) {
@@ -845,13 +899,13 @@ int main(int argc, char **argv)
                         }
                         continue;
                     }
-                    if (p010) y4m_p010_to_420p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
-                    else if (nv12) y4m_nv12_to_420(W, H, host + fb * k, planes);
+                    if (w_p010) y4m_p010_to_420p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
+                    else if (w_nv12) y4m_nv12_to_420(W, H, host + fbo * k, planes);
                     else if (p422) y4m_packed_to_422(W, H, host + fb * k, planes, uyvy);
                     else if (y210) y4m_y210_to_422p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
-                    else y4m_from_rgba(W, H, host + fb * k, planes, full_range);
-                    if (p010   ? y4m_write_frame_420p10(fo, W, H, (const uint16_t *)planes)
-                        : nv12 ? y4m_write_frame_420(fo, W, H, planes)
+                    else y4m_from_rgba(W, H, host + fbo * k, planes, full_range);
+                    if (w_p010   ? y4m_write_frame_420p10(fo, W, H, (const uint16_t *)planes)
+                        : w_nv12 ? y4m_write_frame_420(fo, W, H, planes)
                         : p422 ? y4m_write_frame_422(fo, W, H, planes)
                         : y210 ? y4m_write_frame_422p10(fo, W, H, (const uint16_t *)planes)
                                : y4m_write_frame(fo, W, H, planes)) {
@@ -868,7 +922,7 @@ int main(int argc, char **argv)
                     }
                 }
             } else {
-                fwrite(host, fb, (size_t)n, fo);
+                fwrite(host, fbo, (size_t)n, fo);
             }
         }
         done += n;

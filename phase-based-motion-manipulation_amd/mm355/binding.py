@@ -172,6 +172,30 @@ def _surface_fn(name):
     return getattr(lib(), name)
 
 
+# different formats in and out (include/mm.h "Different formats in and out"):
+# NV12 / P010 codes in with RGBA8 out, RGBA8 in with an NV12 code out
+CONVERT_SYMBOLS = ("mm_convert_supported", "mm_process_convert", "mm_process_stream_convert")
+
+
+def has_convert():
+    """The loaded library converts between formats (detected, as include/mm.h
+    says, by the presence of mm_convert_supported)."""
+    return hasattr(lib(), "mm_convert_supported")
+
+
+def _convert_fn(name):
+    if not has_convert():
+        raise MMError(-2, f"{library_path()} has no {name} (a build from before the format conversion)")
+    return getattr(lib(), name)
+
+
+def convert_supported(in_fmt, out_fmt):
+    """mm_convert_supported: 0 (MM_OK) where frames of in_fmt can come out as
+    out_fmt, -2 (MM_ERR_UNSUPPORTED) for any other pair of valid codes, -1
+    (MM_ERR_INVALID) if either code is unknown.  Needs no GPU."""
+    return _convert_fn("mm_convert_supported")(int(in_fmt), int(out_fmt))
+
+
 _lib = None
 _lib_path = None
 ABI_VERSION = 10  # include/mm.h MM_ABI_VERSION
@@ -197,6 +221,9 @@ def load_library(path=None):
         "mm_process_surface": (ci, [vp, vp, ps, vp, ps, ci, vp]),
         "mm_process_stream_surfaces": (ci, [vp, vp, ps, vp, ps, ci, vp]),
         "mm_compute_state_surface": (ci, [vp, vp, ps, vp, sz, vp]),
+        "mm_convert_supported": (ci, [ci, ci]),
+        "mm_process_convert": (ci, [vp, vp, ps, vp, ps, ci, vp]),
+        "mm_process_stream_convert": (ci, [vp, vp, ps, vp, ps, ci, vp]),
         "mm_abi_version": (ci, []),
         "mm_strerror": (ctypes.c_char_p, [ci]),
         "mm_params_default": (ci, [pp]),
@@ -240,6 +267,8 @@ def load_library(path=None):
             continue    # an A/B build from before the NV12 formats or the matrix bits (same ABI version)
         if name in SURFACE_SYMBOLS and not hasattr(L, name):
             continue    # ... or from before the pitched surfaces
+        if name in CONVERT_SYMBOLS and not hasattr(L, name):
+            continue    # ... or from before the format conversion
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -407,6 +436,20 @@ class Handle:
         check(_surface_fn("mm_process_stream_surfaces")(self.h, _ptr(src), ctypes.byref(src_layout),
                                                         _ptr(dst), ctypes.byref(dst_layout), count,
                                                         _ptr(stream)), "mm_process_stream_surfaces")
+
+    def process_convert(self, src, src_layout, dst, dst_layout, on_device=True, stream=None):
+        """mm_process_convert: one frame in src_layout.format, out in
+        dst_layout.format (convert_supported)."""
+        check(_convert_fn("mm_process_convert")(self.h, _ptr(src), ctypes.byref(src_layout), _ptr(dst),
+                                                ctypes.byref(dst_layout),
+                                                FRAMES_ON_DEVICE if on_device else 0, _ptr(stream)),
+              "mm_process_convert")
+
+    def process_stream_convert(self, src, src_layout, dst, dst_layout, count, stream=None):
+        """mm_process_stream_convert: frame k at k * frame_stride of its side."""
+        check(_convert_fn("mm_process_stream_convert")(self.h, _ptr(src), ctypes.byref(src_layout),
+                                                       _ptr(dst), ctypes.byref(dst_layout), count,
+                                                       _ptr(stream)), "mm_process_stream_convert")
 
     def reset(self):
         check(lib().mm_reset(self.h), "mm_reset")

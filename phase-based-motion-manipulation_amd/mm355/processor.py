@@ -9,7 +9,7 @@ import numpy as np
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       MONO_FORMATS, NV12, NV12_FULL, P010, P010_FULL, PACKED422_FORMATS, RGBA8, RGBA8_SRGB, RGBA16F,
                       RGB24_FORMATS, RGBA32F, Y8, Y210_FORMATS,
-                      Handle, MMError, Params, Surface, base_format)
+                      Handle, MMError, Params, Surface, base_format, convert_supported)
 
 
 def _fmt_of(frame, srgb=False):
@@ -98,6 +98,27 @@ def frame_layout(frame, width, height, fmt):
     return lay
 
 
+def _convert_side(frame, width, height, fmt, side):
+    """One side of a convert call, checked by that side's format: a 4:2:0 frame
+    is one contiguous [H * 3 / 2, W] array, uint8 (NV12 codes) or uint16 (P010
+    codes: the words as they lie); an RGBA8 frame is [H, W, 4] uint8, contiguous
+    or row-strided.  -> its Surface.  MMError on any mismatch, before any frame
+    call into the library."""
+    base = base_format(fmt)
+    if base in (NV12, NV12_FULL, P010, P010_FULL):
+        want = "uint8" if base in (NV12, NV12_FULL) else "uint16"
+        if tuple(frame.shape) != (height * 3 // 2, width) or not str(frame.dtype).endswith(want):
+            raise MMError(-1, f"{side} {tuple(frame.shape)} {frame.dtype} "
+                              f"(want {(height * 3 // 2, width)} {want} for format {fmt})")
+        contiguous = frame.flags["C_CONTIGUOUS"] if isinstance(frame, np.ndarray) else frame.is_contiguous()
+        if not contiguous:
+            raise MMError(-1, f"{side}: a 4:2:0 frame must be contiguous (name a Surface through Handle.process_convert)")
+        return Surface.tight(width, height, fmt)
+    if tuple(frame.shape) != (height, width, 4) or not str(frame.dtype).endswith("uint8"):
+        raise MMError(-1, f"{side} {tuple(frame.shape)} {frame.dtype} (want {(height, width, 4)} uint8 for format {fmt})")
+    return frame_layout(frame, width, height, fmt) or Surface.tight(width, height, fmt)
+
+
 class MotionMagnificationProcessor:
     """[RequireComponent(typeof(Camera))] class MotionMagnificationProcessor (.cs:4-5).
 
@@ -182,7 +203,7 @@ class MotionMagnificationProcessor:
         if self._handle is not None:
             self._handle.set_params(self._params())
 
-    def OnRenderImage(self, source, destination, fmt=None):
+    def OnRenderImage(self, source, destination, fmt=None, dst_fmt=None):
         """OnRenderImage (.cs:101-143). source/destination: [H, W, 4] uint8,
         float16 or float32, both torch CUDA tensors (async on torch's current
         stream) or both host numpy arrays (synchronous).  fmt=Y8 / Y10 / Y12 /
@@ -195,7 +216,33 @@ class MotionMagnificationProcessor:
         contiguous or row-strided views).  fmt=RGB24 / BGR24: [H, W, 3] uint8
         on both sides, as cv2 (BGR24), PIL and imageio (RGB24) hand them out:
         device tensors, contiguous or row-strided views that start at any
-        byte, or host numpy arrays; such a frame without fmt= raises."""
+        byte, or host numpy arrays; such a frame without fmt= raises.
+        dst_fmt (None, or equal to fmt: the above): the destination's format
+        where it differs from the source's (mm355.convert_supported): fmt=NV12 /
+        P010 codes with dst_fmt=RGBA8, the source one contiguous [H * 3 / 2, W]
+        uint8 / uint16 array and the destination [H, W, 4] uint8; or an [H, W, 4]
+        uint8 source (fmt None or RGBA8) with dst_fmt an NV12 code.  Each side's
+        shape and dtype are checked by that side's format, before any frame
+        call into the library."""
+        if dst_fmt is not None and dst_fmt != (fmt if fmt is not None else _fmt_of(source, self.srgb)):
+            if fmt is None:
+                fmt = _fmt_of(source, self.srgb)
+            if self._handle is None:
+                raise MMError(-1, "dst_fmt: no Blit between two formats before Start()")
+            rc = convert_supported(fmt, dst_fmt)
+            if rc:
+                raise MMError(rc, f"fmt={fmt}, dst_fmt={dst_fmt}")
+            on_dev = _is_device(source)
+            if on_dev != _is_device(destination):
+                raise MMError(-1, "source and destination must both be device or host")
+            src_lay = _convert_side(source, self.width, self.height, fmt, "source")
+            dst_lay = _convert_side(destination, self.width, self.height, dst_fmt, "destination")
+            stream = None
+            if on_dev:
+                import torch
+                stream = torch.cuda.current_stream(source.device).cuda_stream
+            self._handle.process_convert(source, src_lay, destination, dst_lay, on_device=on_dev, stream=stream)
+            return
         if self._handle is None:                       # !isInitialized -> Blit (.cs:103-107)
             destination[...] = source
             return

@@ -48,7 +48,20 @@ legs compare addressing alone (K1's byte-aligned dword loads, K34's 12-byte
 quads without RGBA8's LDS-DMA source staging).  A library from before these
 formats runs without them.
 
-usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--out FILE.json]
+Convert legs (nv12>rgba8, nv12_bt709>rgba8, p010>rgba8, rgba8>nv12,
+rgba8>nv12_bt709, and their _pitched forms): the NV12 / P010 / RGBA8 legs' own
+frames in as the one format and out as the other through
+mm_process_stream_convert, tight, and with the Y'CbCr side in the decoder
+layout (the RGBA8 side tight).  Plain legs (<pair>_plain): the same call on a
+handle with apply_magnification = 0, which runs the conversion kernel alone on
+every frame (plus K1 of the batch's last frame, which keeps the state): its
+time per frame and its bandwidth against the bytes it must move.  The summary
+sets the same-format stream's time per frame plus that conversion pass against
+the mixed leg: two passes against one.  A library from before the conversion
+runs without them; --no-convert gives this library that leg set (an A/B of the
+existing legs alone, with the same number of legs in every round).
+
+usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--no-convert] [--out FILE.json]
 """
 import argparse
 import json
@@ -154,6 +167,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--leg-seconds", type=float, default=0.6)
     ap.add_argument("--no-pitched", action="store_true")
+    ap.add_argument("--no-convert", action="store_true",
+                    help="leave the convert legs out (the leg set of a library from before the conversion)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -221,10 +236,45 @@ def main():
             buf = to_surface(torch, src, lay, W, H, name.startswith(("nv12", "p010")))
             legs[name + "_pitched"] = dict(h=h, fmt=fmt, src=buf, dst=torch.zeros_like(buf), fps=[], lay=lay,
                                            bytes_per_frame=lay.frame_stride)
+    convs = []
+    if not a.no_convert and getattr(mm355, "has_convert", lambda: False)():
+        convs = [("nv12>rgba8", "nv12", mm355.NV12, mm355.RGBA8),
+                 ("nv12_bt709>rgba8", "nv12", mm355.NV12 | mm355.MATRIX_BT709, mm355.RGBA8),
+                 ("p010>rgba8", "p010", mm355.P010, mm355.RGBA8),
+                 ("rgba8>nv12", "rgba8", mm355.RGBA8, mm355.NV12),
+                 ("rgba8>nv12_bt709", "rgba8", mm355.RGBA8, mm355.NV12 | mm355.MATRIX_BT709)]
+    p_off = mm355.Params.make(levels=5, phase_scale=25.0, apply_magnification=False)
+
+    def out_of(fo):
+        return torch.empty((B, H, W, 4) if fo == mm355.RGBA8 else (B, H * 3 // 2, W), dtype=torch.uint8, device="cuda")
+
+    for name, base, fi, fo in convs:
+        src = legs[base]["src"]
+        forms = [(name, p, False)]
+        if not name.startswith("nv12_bt709") and not name.endswith("bt709"):
+            forms.append((name + "_plain", p_off, False))
+        if not a.no_pitched:
+            forms.append((name + "_pitched", p, True))
+        for leg_name, prm, pitched in forms:
+            h = mm355.Handle(W, H, prm)
+            h.set_batch(B)
+            li, lo = mm355.Surface.tight(W, H, fi), mm355.Surface.tight(W, H, fo)
+            s_in, s_out = src, out_of(fo)
+            if pitched:   # the Y'CbCr side as a decoder lays it out, the RGBA8 side tight
+                if fi != mm355.RGBA8:
+                    li = mm355.Surface.aligned(W, H, fi, 256, 16)
+                    s_in = to_surface(torch, src, li, W, H, True)
+                else:
+                    lo = mm355.Surface.aligned(W, H, fo, 256, 16)
+                    s_out = torch.zeros(B * lo.frame_stride, dtype=torch.uint8, device="cuda")
+            legs[leg_name] = dict(h=h, fmt=fi, ofmt=fo, src=s_in, dst=s_out, fps=[], lay=li, olay=lo, convert=True,
+                                  bytes_per_frame=mm355.frame_bytes(W, H, fi) + mm355.frame_bytes(W, H, fo))
     st = torch.cuda.Stream()
 
     def call(L):
-        if L["lay"] is None:
+        if L.get("convert"):
+            L["h"].process_stream_convert(L["src"], L["lay"], L["dst"], L["olay"], B, stream=st.cuda_stream)
+        elif L["lay"] is None:
             L["h"].process_stream(L["src"], L["dst"], B, L["fmt"], stream=st.cuda_stream)
         else:
             L["h"].process_stream_surfaces(L["src"], L["lay"], L["dst"], L["lay"], B, stream=st.cuda_stream)
@@ -260,6 +310,7 @@ def main():
         out["formats"][name] = {
             "bytes_per_frame": L["bytes_per_frame"], "calls_per_leg": L["calls"],
             **({"pitch": L["lay"].pitch, "chroma_offset": L["lay"].chroma_offset} if L["lay"] is not None else {}),
+            **({"out_format": L["ofmt"], "out_pitch": L["olay"].pitch} if L.get("convert") else {}),
             "leg_seconds": round(L["calls"] * B / statistics.median(f), 3),
             "fps_legs": [round(x, 1) for x in f], "fps_median": round(statistics.median(f), 1),
             "fps_min": round(min(f), 1), "fps_max": round(max(f), 1),
@@ -313,6 +364,18 @@ def main():
         if name + "_pitched" in out["formats"]:
             out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
                                                       out["formats"][name]["fps_median"], 4)
+    # two passes against one: the same-format stream plus a conversion pass of its own, against the mixed leg
+    us = lambda n: 1e6 / out["formats"][n]["fps_median"]
+    for name, same in (("nv12>rgba8", "nv12"), ("p010>rgba8", "p010"), ("rgba8>nv12", "rgba8")):
+        if name in out["formats"] and name + "_plain" in out["formats"]:
+            conv_us = us(name + "_plain")
+            out[name + "_two_pass"] = {
+                "same_format_us_per_frame": round(us(same), 3), "convert_pass_us_per_frame": round(conv_us, 3),
+                "two_pass_us_per_frame": round(us(same) + conv_us, 3), "mixed_us_per_frame": round(us(name), 3),
+                "mixed_over_two_pass": round(us(name) / (us(same) + conv_us), 4),
+                "convert_pass_GBps": round(out["formats"][name]["bytes_per_frame"] / conv_us * 1e-3, 1),
+            }
+            out[name + "_kernel_us"] = {n: out["formats"][n]["kernel_us_per_frame"] for n in (name, "rgba8", "nv12")}
     txt = json.dumps(out, indent=1)
     print(txt)
     if a.out:

@@ -7,7 +7,9 @@ Every translation unit's code object is taken out of the library's fat binary
 (the clang offload bundles inside it), disassembled with llvm-objdump, and the
 functions the two builds share are compared instruction by instruction.  Three
 classes: identical; identical but for the literals of s_add_u32 / s_addc_u32
-(the PC-relative offsets of constant data that moved); different.  Functions
+(the PC-relative offsets of constant data that moved); different.  A function
+is the st_size bytes from its symbol, so blocks laid out after its last s_endpgm
+are compared and the fill up to the next symbol is not.  Functions
 only one build has are listed by name.  Per-kernel instruction counts (valu,
 salu, vmem, lds) of the new functions are printed at the end.
 """
@@ -48,19 +50,34 @@ def functions(elf, objdump):
     try:
         txt = subprocess.run([objdump, "-d", "--no-show-raw-insn", "--no-leading-addr", tmp],
                              check=True, capture_output=True, text=True).stdout
+        syms = subprocess.run([objdump, "-t", tmp], check=True, capture_output=True, text=True).stdout
     finally:
         os.unlink(tmp)
-    funcs, cur = {}, None
+    # a function is the st_size bytes from its symbol: basic blocks after its
+    # last s_endpgm belong to it, the fill up to the next symbol's alignment
+    # (which moves with the neighbours and may decode as instructions) does not
+    end = {}
+    for line in syms.splitlines():
+        m = re.match(r"^([0-9a-f]+) .{7} (\S+)\s+([0-9a-f]+)\s+(?:\.\w+\s+)?(\S+)$", line)
+        if m and "F" in line[17:24]:
+            end[m.group(4)] = int(m.group(1), 16) + int(m.group(3), 16)
+    funcs, cur, stop = {}, None, None
     for line in txt.splitlines():
         m = re.match(r"^(?:[0-9a-f]+ )?<([^>]+)>:$", line)
         if m:
-            cur = funcs.setdefault(m.group(1), [])
+            cur, stop = funcs.setdefault(m.group(1), []), end.get(m.group(1))
             continue
         if cur is None or not line.startswith(("\t", " ")):
             continue
-        ins = line.split("//")[0].strip()
-        if ins:
-            cur.append(re.sub(r"\s+", " ", ins))
+        ins, _, where = line.partition("//")
+        ins = ins.strip()
+        if not ins or ins == "...":     # (a run of zero bytes)
+            continue
+        # (the comment holds the instruction's address and its encoding)
+        a = re.match(r"\s*([0-9A-Fa-f]+):", where)
+        if stop is not None and a and int(a.group(1), 16) >= stop:
+            continue
+        cur.append(re.sub(r"\s+", " ", ins))
     return funcs
 
 
