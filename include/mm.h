@@ -383,6 +383,73 @@ extern "C" {
 #define MM_ORDER_BGR 128   /* byte-order bit: B G R */
 #define MM_BGR24     (MM_RGB24 | MM_ORDER_BGR)   /* 141 */
 
+/* Three-plane 4:2:0 frames (backward-compatible addition to ABI 10: a caller
+ * detects it by mm_frame_bytes(W, H, MM_I420, &n) == MM_OK).  What every
+ * software decoder (libavcodec, libvpx, dav1d), WebRTC's frame buffers, the
+ * x264 / x265 / SVT encoder inputs and every C420 .y4m file hold: I420, ffmpeg's
+ * yuv420p.  Tightly packed: H rows of W luma bytes, then H/2 rows of W/2 Cb
+ * bytes, then H/2 rows of W/2 Cr bytes, W H 3/2 bytes in all (the frame payload
+ * of a C420 .y4m as it lies in the file); frame k of a stream at
+ * k * mm_frame_bytes.  MM_PLANAR is a plane-layout bit beside the matrix and
+ * order bits: MM_I420 = MM_NV12 | MM_PLANAR, and a matrix bit may be OR-ed on
+ * as on NV12.  The valid codes are 528, 529, 560, 561, 592 and 593.
+ * The bit is valid on the two NV12 codes alone: MM_PLANAR by itself, the bit on
+ * an RGBA, single-plane, P010, packed 4:2:2, MM_Y210 or packed RGB code, the
+ * bit together with MM_ORDER_BGR, both matrix bits together and any other stray
+ * bit (528 | 256, 528 | 1024) are MM_ERR_INVALID from mm_frame_bytes,
+ * mm_surface_* and every frame entry point, before anything is queued.
+ * Restrictions, all NV12's: W and H even (else MM_ERR_UNSUPPORTED);
+ * show_magnitude / show_phase are refused with MM_ERR_UNSUPPORTED;
+ * in_layout->format == out_layout->format.
+ * The semantics are NV12's word for word (ranges, matrices, the chroma sample
+ * shared by its 2 x 2 pixels, the out rule, rounding and clamps): an I420 frame
+ * IS the NV12 frame with the same samples, and where a pixel's two chroma
+ * samples lie is a matter of loads and stores.  Two identities hold bitwise, in
+ * every mode (pyramid, standard, steerable), call form (single, stream,
+ * host-memory frames), batch size, edge mode and layout:
+ *   1. the output is the NV12 path's output on the interleaved frame,
+ *      de-interleaved;
+ *   2. the temporal state (mm_get_state / mm_compute_state) is bitwise that
+ *      NV12 frame's.
+ * The first frame after mm_create / mm_reset and apply_magnification = 0 pass
+ * all W H 3/2 bytes through bitwise.
+ * Surfaces: mm_surface has one chroma offset, so the third plane's place is
+ * derived.  pitch is the luma pitch, chroma_offset the Cb plane's offset,
+ * chroma_pitch the pitch of a Cb row and of a Cr row alike, and THE Cr PLANE
+ * STARTS chroma_pitch x H/2 BYTES AFTER THE Cb PLANE.  The unit u is 1: frame
+ * pointers, pitches and strides need no alignment (W = 98 has chroma rows of 49
+ * bytes).  pitch >= W; chroma_pitch >= W/2; chroma_offset at or past the end of
+ * the last luma row's samples; the extent is the byte after the last Cr sample,
+ * at most 2^32; frame_stride >= extent when count > 1; size_t overflows are
+ * MM_ERR_INVALID; padding is never read and never written.
+ * mm_surface_tight(1920, 1080, MM_I420): pitch 1,920, chroma_offset 2,073,600,
+ * chroma_pitch 960, frame_stride 3,110,400.  mm_surface_tight(98, 62, MM_I420):
+ * pitch 98, chroma_offset 6,076, chroma_pitch 49 (the Cr plane at 7,595),
+ * frame_stride 9,114.  mm_surface_aligned: the luma pitch is W rounded up to
+ * pitch_align, chroma_pitch = pitch / 2 (MM_ERR_INVALID where that pitch is
+ * odd), rows_align even, chroma_offset = pitch x padded rows, frame_stride =
+ * pitch x padded rows x 3/2: mm_surface_aligned(1920, 1080, MM_I420, 256, 16)
+ * has pitch 2,048, chroma_offset 2,228,224, chroma_pitch 1,024 (the Cr plane at
+ * 2,781,184), frame_stride 3,342,336 and extent 3,334,080.
+ * The fused kernels move a quad's two Cb and two Cr samples as one 2-byte
+ * access per plane and its four luma codes as one dword: they run where the
+ * output's luma rows lie on multiples of 4 and every Cb and Cr row of every
+ * frame of the launch on a multiple of 2, on both sides (every tight frame
+ * with W % 8 == 0); any other legal layout takes the unfused kernels, whose
+ * chroma accesses are single bytes: the same bytes.
+ * mm_ycbcr_matrix takes the six codes and returns the NV12 code's values;
+ * mm_convert_supported(x, x) is MM_OK for them and any mixed pair with a planar
+ * code MM_ERR_UNSUPPORTED; mm_compute_state* takes them.
+ * Out of scope: YV12 (the Cr plane first); planes at independent addresses or
+ * with padded chroma rows between them (a region of interest narrower in
+ * height than its parent needs that); 10-bit planar (yuv420p10le: low-bit
+ * words); planar 4:2:2 / 4:4:4; any mixed convert pair; the ring entry points
+ * (include/mm_ring.h), the Unity shim and mm_extmem_check; odd sizes and the
+ * debug views. */
+#define MM_PLANAR    512                          /* plane-layout bit: Cb and Cr in planes of their own */
+#define MM_I420      (MM_NV12 | MM_PLANAR)        /* 528 */
+#define MM_I420_FULL (MM_NV12_FULL | MM_PLANAR)   /* 529 */
+
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0  /* usePyramidDecomposition = true (.cs:18, :128-131) */
 #define MM_MODE_STANDARD  1   /* usePyramidDecomposition = false (.cs:132-135, :208-232) */

@@ -449,7 +449,9 @@ int mm_surface_aligned(int width, int height, int format, size_t pitch_align, in
     t.frame_stride = planes;
     if (fmt_420(format)) {
         t.chroma_offset = planes;
-        t.chroma_pitch = pitch;
+        // (three-plane: Cb and Cr rows of half the luma pitch, which is then even)
+        if (fmt_i420(format) && (pitch & 1)) return MM_ERR_INVALID;
+        t.chroma_pitch = fmt_i420(format) ? pitch / 2 : pitch;
         if (__builtin_add_overflow(planes, planes / 2, &t.frame_stride)) return MM_ERR_INVALID;
     }
     if (int rc = surf_check(width, height, &t, nullptr)) return rc;
@@ -566,17 +568,23 @@ static int process_surface(mm_handle *h, const void *in, const mm_surface *in_la
             return MM_ERR_OOM;
         h->stage_bytes = fb;
     }
+    // (a chroma row: W / 2 bytes in each of the two planes of a three-plane frame)
+    const size_t rc_in = t.chroma_pitch, rc_out = to.chroma_pitch, hc = (size_t)(h->H / 2);
     const bool in_tight = in_layout->pitch == rb && (!fmt_420(format) || (in_layout->chroma_offset == luma &&
-                                                                          in_layout->chroma_pitch == rb));
+                                                                          in_layout->chroma_pitch == rc_in));
     const bool out_tight = out_layout->pitch == rbo && (!fmt_420(oformat) || (out_layout->chroma_offset == lumao &&
-                                                                              out_layout->chroma_pitch == rbo));
+                                                                              out_layout->chroma_pitch == rc_out));
     if (in_tight) {
         HIPCHK(hipMemcpyAsync(h->d_stage_in, in, fr.fb, hipMemcpyHostToDevice, s));
     } else {
         HIPCHK(stage_plane(h->d_stage_in, rb, in, in_layout->pitch, rb, h->H, hipMemcpyHostToDevice, s));
         if (fmt_420(format))
-            HIPCHK(stage_plane(h->d_stage_in + luma, rb, (const uint8_t *)in + in_layout->chroma_offset,
-                               in_layout->chroma_pitch, rb, h->H / 2, hipMemcpyHostToDevice, s));
+            HIPCHK(stage_plane(h->d_stage_in + luma, rc_in, (const uint8_t *)in + in_layout->chroma_offset,
+                               in_layout->chroma_pitch, rc_in, hc, hipMemcpyHostToDevice, s));
+        if (fmt_i420(format))   // the Cr plane, chroma_pitch x H/2 after the Cb plane
+            HIPCHK(stage_plane(h->d_stage_in + luma + rc_in * hc, rc_in,
+                               (const uint8_t *)in + in_layout->chroma_offset + i420_cr_delta(h->H, in_layout->chroma_pitch),
+                               in_layout->chroma_pitch, rc_in, hc, hipMemcpyHostToDevice, s));
     }
     rc = do_stream(h, h->d_stage_in, h->d_stage_out, 1, fr, s);
     const int rn = note_work(h, s);
@@ -587,7 +595,11 @@ static int process_surface(mm_handle *h, const void *in, const mm_surface *in_la
         HIPCHK(stage_plane(out, out_layout->pitch, h->d_stage_out, rbo, rbo, h->H, hipMemcpyDeviceToHost, s));
         if (fmt_420(oformat))
             HIPCHK(stage_plane((uint8_t *)out + out_layout->chroma_offset, out_layout->chroma_pitch,
-                               h->d_stage_out + lumao, rbo, rbo, h->H / 2, hipMemcpyDeviceToHost, s));
+                               h->d_stage_out + lumao, rc_out, rc_out, hc, hipMemcpyDeviceToHost, s));
+        if (fmt_i420(oformat))
+            HIPCHK(stage_plane((uint8_t *)out + out_layout->chroma_offset + i420_cr_delta(h->H, out_layout->chroma_pitch),
+                               out_layout->chroma_pitch, h->d_stage_out + lumao + rc_out * hc, rc_out, rc_out, hc,
+                               hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
     return MM_OK;

@@ -507,8 +507,16 @@ constexpr int kFmtNV12M = 48;  // MM_NV12 | MM_MATRIX_BT709 (K1 only: any matrix
 constexpr int kFmtP010M = 50;  // MM_P010 | MM_MATRIX_BT709 (K1 only: any matrixed P010)
 template <int FMT> constexpr bool kNV12 = FMT == kFmtNV12 || FMT == kFmtNV12M;
 template <int FMT> constexpr bool kP010 = FMT == kFmtP010 || FMT == kFmtP010M;
-template <int FMT> constexpr bool k420 = kNV12<FMT> || kP010<FMT>;
-template <int FMT> constexpr bool kMatrixed = FMT == kFmtNV12M || FMT == kFmtP010M;
+// three-plane 4:2:0 (MM_I420 = MM_NV12 | MM_PLANAR; section below).  A format
+// code past 255 names a pair (fmt_pair), so the template arguments are internal
+// codes, NV12's with bit 7: kFmtI420 runs every compose of a three-plane frame,
+// kFmtI420M is K1's instance for a matrixed one (a BT.601 frame's K1 is
+// kFmtNV12's own: the luma plane is the same plane)
+constexpr int kFmtI420 = 144;   // MM_I420* (every range and matrix)
+constexpr int kFmtI420M = 176;  // K1 only: any matrixed MM_I420*
+template <int FMT> constexpr bool kI420 = FMT == kFmtI420 || FMT == kFmtI420M;
+template <int FMT> constexpr bool k420 = kNV12<FMT> || kP010<FMT> || kI420<FMT>;
+template <int FMT> constexpr bool kMatrixed = FMT == kFmtNV12M || FMT == kFmtP010M || FMT == kFmtI420M;
 // packed 4:2:2 (section below): kFmtYUY2 runs every BT.601 YUY2 / UYVY frame and
 // every compose, kFmtYUY2M is K1's instance for a matrixed one
 constexpr int kFmtYUY2 = 24;   // MM_YUY2
@@ -568,6 +576,11 @@ template <> struct LumaSrc<kFmtNV12M> : LumaSrc<kFmtNV12> {};
 template <> struct LumaSrc<kFmtP010M> : LumaSrc<kFmtP010> {};
 template <> struct ChromaSrc<kFmtNV12M> : ChromaSrc<kFmtNV12> {};
 template <> struct ChromaSrc<kFmtP010M> : ChromaSrc<kFmtP010> {};
+// (three-plane: NV12's luma bytes; the pixel's Cb and Cr bytes put together as NV12's pair)
+template <> struct LumaSrc<kFmtI420> : LumaSrc<kFmtNV12> {};
+template <> struct LumaSrc<kFmtI420M> : LumaSrc<kFmtNV12> {};
+template <> struct ChromaSrc<kFmtI420> : ChromaSrc<kFmtNV12> {};
+template <> struct ChromaSrc<kFmtI420M> : ChromaSrc<kFmtNV12> {};
 // K1's luma of a raw sample and its unit (folded into the resample weights)
 template <int FMT>
 __device__ __forceinline__ float k1_luma(typename LumaSrc<FMT>::raw_t u, const Geo &g)
@@ -603,6 +616,21 @@ template <int FMT> __device__ __forceinline__ unsigned k1_ccol(unsigned col)
 {
     return (col & ~1u) * (unsigned)LumaSrc<FMT>::bpp;
 }
+// Three-plane 4:2:0: the Cr plane lies c_pitch x H/2 bytes after the Cb plane
+// (include/mm.h: derived, no Geo field; uniform), and a pixel's (Cb, Cr) is one
+// byte of each plane at the same offset, put together as NV12's pair Cb | Cr << 8
+__device__ __forceinline__ unsigned i420_cr_delta(const Geo::Lay &l, const Geo &g) { return l.c_pitch * (unsigned)(g.H >> 1); }
+__device__ __forceinline__ unsigned i420_ld_pair(const uint8_t *cb, unsigned off, unsigned cr_delta)
+{
+    return (unsigned)ld_off<uint8_t>(cb, off) | (unsigned)ld_off<uint8_t>(cb, off + cr_delta) << 8;
+}
+// K1's load of pixel column col's (Cb, Cr) from chroma row crow (k1_crow's)
+template <int FMT>
+__device__ __forceinline__ typename ChromaSrc<FMT>::raw_t k1_cld(const uint8_t *crow, unsigned col, [[maybe_unused]] const Geo &g)
+{
+    if constexpr (kI420<FMT>) return (uint16_t)i420_ld_pair(crow, col >> 1, i420_cr_delta(g.li, g));
+    else return ld_off<typename ChromaSrc<FMT>::raw_t>(crow, k1_ccol<FMT>(col));
+}
 // byte offset of the (Cb, Cr) pair of source pixel (row, col), both already
 // wrapped or clamped on PIXEL coordinates (then halved: the decoded frame's
 // REPEAT / CLAMP behaviour exactly)
@@ -630,7 +658,14 @@ __device__ __forceinline__ c2 y210_iq2(uint2 m, const Geo &g) { return p010_iq2(
 template <int FMT> __device__ __forceinline__ unsigned c420_off(const Geo &g, int row, unsigned col)
 {
     if constexpr (kP010<FMT>) return g.li.c_off + (unsigned)(row >> 1) * g.li.c_pitch + (col & ~1u) * 2u;
+    else if constexpr (kI420<FMT>) return g.li.c_off + (unsigned)(row >> 1) * g.li.c_pitch + (col >> 1);   // (the Cb byte)
     else return nv12_c_off(g, row, col);
+}
+// the (Cb, Cr) pair of source pixel (row, col) as the format's raw pair
+template <int FMT> __device__ __forceinline__ unsigned c420_pair(const uint8_t *img, const Geo &g, int row, unsigned col)
+{
+    if constexpr (kI420<FMT>) return i420_ld_pair(img, c420_off<FMT>(g, row, col), i420_cr_delta(g.li, g));
+    else return ld_off<typename ChromaSrc<FMT>::raw_t>(img, c420_off<FMT>(g, row, col));
 }
 template <int FMT> __device__ __forceinline__ c2 c420_iq2(unsigned u, const Geo &g)
 {
@@ -718,6 +753,31 @@ __device__ __forceinline__ void p010_store_quad(uint8_t *outp, const Geo &g, int
         p010_st4(outp + (size_t)(g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch), (unsigned)X, c0, c1);
     }
 }
+// Three-plane 4:2:0: nv12_store_quad with the two blocks' Cb codes as one
+// 2-byte store to the Cb plane and their Cr codes as one to the Cr plane (X / 2
+// is even, chroma rows on multiples of 2: i420_quads_aligned, mm_impl.hpp).
+// Same codes, same order of sums.
+__device__ __forceinline__ void i420_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
+                                                const float (&rr)[4], const float (&gg)[4],
+                                                const float (&bb)[4], c2 (&cd0)[4])
+{
+    c2 cd[4];
+    unsigned y4 = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y4 |= nv12_ycode(rr[k], gg[k], bb[k], g, cd[k]) << (8 * k);
+    st_stream<uint32_t>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, y4);
+    if (!odd) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) cd0[k] = cd[k];
+    } else {
+        const c2 b0 = (cd0[0] + cd[0]) + (cd0[1] + cd[1]), b1 = (cd0[2] + cd[2]) + (cd0[3] + cd[3]);
+        const unsigned cb2 = nv12_ccode(b0.x, g.nv.cbo) | nv12_ccode(b1.x, g.nv.cbo) << 8;
+        const unsigned cr2 = nv12_ccode(b0.y, g.nv.cro) | nv12_ccode(b1.y, g.nv.cro) << 8;
+        uint8_t *cb = outp + (size_t)(g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch) + ((unsigned)X >> 1);
+        __builtin_nontemporal_store((uint16_t)cb2, reinterpret_cast<uint16_t *>(cb));
+        __builtin_nontemporal_store((uint16_t)cr2, reinterpret_cast<uint16_t *>(cb + i420_cr_delta(g.lo, g)));
+    }
+}
 // the fused kernels' quad store for a 4:2:0 format
 template <int FMT>
 __device__ __forceinline__ void c420_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
@@ -725,6 +785,7 @@ __device__ __forceinline__ void c420_store_quad(uint8_t *outp, const Geo &g, int
                                                 const float (&gg)[4], const float (&bb)[4], c2 (&cd0)[4])
 {
     if constexpr (kP010<FMT>) p010_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
+    else if constexpr (kI420<FMT>) i420_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
     else nv12_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
 }
 // the fused kernels' load of the two (Cb, Cr) pairs of the quad X .. X+3 in
@@ -736,6 +797,11 @@ __device__ __forceinline__ void c420_quad_pairs(const uint8_t *img, const Geo &g
     if constexpr (kP010<FMT>) {   // two 4-byte loads: rows are 4-byte aligned only
         p0 = ld_off<uint32_t>(img, c420_off<FMT>(g, row, X));
         p1 = ld_off<uint32_t>(img, c420_off<FMT>(g, row, X) + 4u);
+    } else if constexpr (kI420<FMT>) {   // one 2-byte load per plane (chroma rows on multiples of 2, X / 2 even)
+        const unsigned off = c420_off<FMT>(g, row, X);
+        const unsigned cb2 = ld_off<uint16_t>(img, off), cr2 = ld_off<uint16_t>(img, off + i420_cr_delta(g.li, g));
+        p0 = (cb2 & 255u) | (cr2 & 255u) << 8;
+        p1 = (cb2 >> 8) | (cr2 >> 8) << 8;
     } else {                      // one dword (rows dword aligned: nv12_quads_aligned)
         p0 = ld_off<uint32_t>(img, nv12_c_off(g, row, X));
         p1 = p0 >> 16;
@@ -1185,8 +1251,10 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
     // RGBA8 / RGBA16F: all 32 pixel loads of the thread in one batch; RGBA32F
     // (4x the registers of RGBA8): two batches of 16
     // (MM_Y210's matrixed instance, 8-byte loads, at N = 8192, where 1024
-    // threads leave 128 VGPRs: two batches too; one batch spilled 21)
-    constexpr int UB = BPP == 16 || (FMT == kFmtY210M && LOG2N == 13) ? 4 : 8;
+    // threads leave 128 VGPRs: two batches too; one batch spilled 21; the
+    // matrixed three-plane instance, two chroma byte loads per pair, the same:
+    // one batch spilled 29)
+    constexpr int UB = BPP == 16 || ((FMT == kFmtY210M || FMT == kFmtI420M) && LOG2N == 13) ? 4 : 8;
     if constexpr (GEN) {
         if (valid) {
             Tap4 ta = rowT[ra];
@@ -1267,7 +1335,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
                     if constexpr (kMatrixed<FMT>) {
 #pragma unroll
                         for (int d = 0; d < 4; ++d)
-                            cx[u][d] = ld_off<typename ChromaSrc<FMT>::raw_t>(crowp[d], k1_ccol<FMT>(col));
+                            cx[u][d] = k1_cld<FMT>(crowp[d], col, g);
                     }
                 }
 #pragma unroll
@@ -1323,7 +1391,7 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
                 if constexpr (kMatrixed<FMT>) {
 #pragma unroll
                     for (int d = 0; d < 3; ++d)
-                        cx[u][d] = ld_off<typename ChromaSrc<FMT>::raw_t>(crowp[d], k1_ccol<FMT>(col));
+                        cx[u][d] = k1_cld<FMT>(crowp[d], col, g);
                 }
             }
 #pragma unroll
@@ -2724,6 +2792,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     // (packed RGB: the byte-aligned dword of the pixel)
     auto ld_src = [&](int row, unsigned col) {
         if constexpr (kRGB24<FI>) return rgb24_px(img, src_off(row, col), col, g);
+        else if constexpr (kI420<FI>) return (raw_t)c420_pair<FI>(img, g, row, col);   // (a byte of each chroma plane)
         else return ld_off<raw_t>(img, src_off(row, col));
     };
     const unsigned colA = (unsigned)wrap_near(min(c0 - 1 + tid, g.W), g.W, g.edge);
@@ -2809,7 +2878,10 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                                          (uint16_t)(cc10 << 6));
                     } else {
                         const unsigned cc8 = nv12_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
-                        st_off<uint8_t>(outp, g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch + (unsigned)X, (uint8_t)cc8);
+                        // (three planes: the even lane's Cb is byte X / 2 of the
+                        // Cb row, the odd lane's Cr the same byte of the Cr row)
+                        const unsigned co = kI420<FO> ? ((unsigned)X >> 1) + (X & 1 ? i420_cr_delta(g.lo, g) : 0u) : (unsigned)X;
+                        st_off<uint8_t>(outp, g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch + co, (uint8_t)cc8);
                     }
                 }
             } else if constexpr (k422<FO>) {
@@ -2998,10 +3070,10 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                 // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
                 // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
                 // (P010: pairs are dwords, the quad's own two as two dword loads)
-                const unsigned pl = ld_off<raw_t>(img, c420_off<FI>(g, row, cl));
+                const unsigned pl = c420_pair<FI>(img, g, row, cl);
                 unsigned pm0, pm1;
                 c420_quad_pairs<FI>(img, g, row, (unsigned)X, pm0, pm1);
-                const unsigned pr = ld_off<raw_t>(img, c420_off<FI>(g, row, cr));
+                const unsigned pr = c420_pair<FI>(img, g, row, cr);
                 a[0] = c420_iq2<FI>(pl, g);
                 a[1] = a[2] = c420_iq2<FI>(pm0, g);
                 a[3] = a[4] = c420_iq2<FI>(pm1, g);
@@ -3355,10 +3427,10 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                 // own two pairs as one dword (X % 4 == 0, chroma rows dword aligned
                 // in every frame of the launch: nv12_quads_aligned), the outer two as 2-byte loads
                 // (P010: pairs are dwords, the quad's own two as two dword loads)
-                const unsigned pl = ld_off<raw_t>(img, c420_off<FI>(g, row, cl));
+                const unsigned pl = c420_pair<FI>(img, g, row, cl);
                 unsigned pm0, pm1;
                 c420_quad_pairs<FI>(img, g, row, (unsigned)X, pm0, pm1);
-                const unsigned pr = ld_off<raw_t>(img, c420_off<FI>(g, row, cr));
+                const unsigned pr = c420_pair<FI>(img, g, row, cr);
                 a[0] = c420_iq2<FI>(pl, g);
                 a[1] = a[2] = c420_iq2<FI>(pm0, g);
                 a[3] = a[4] = c420_iq2<FI>(pm1, g);

@@ -9,7 +9,7 @@
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
  *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
- *          [--yuy2] [--uyvy] [--y210] [--ppm [--bgr]] [--out-rgba8] [--out-nv12]
+ *          [--yuy2] [--uyvy] [--y210] [--ppm [--bgr]] [--i420] [--out-rgba8] [--out-nv12]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
@@ -93,6 +93,15 @@
  * byte).  Every size, -l, -s, -b, --standard and --surface-align as usual.
  * Refused with the other format options, --srgb, --matrix, --full-range, the
  * debug views, the ring modes and a .y4m on either side.
+ * --i420: an 8-bit 4:2:0 .y4m input (C420) goes to the device as its frames lie
+ * in the file, as MM_I420 frames (MM_I420_FULL with --full-range, a matrix bit
+ * with --matrix): three planes, no interleave on the way in and no split on the
+ * way out (a C420 .y4m; any other extension on either side: the raw I420
+ * frames, -w/-h).  The output file is --nv12's, byte for byte.  -l, -s, -b,
+ * --standard, --surface-align and --checksum as usual.  Refused with every
+ * other format option (--nv12, --p010, --mono, --yuy2, --uyvy, --y210, --ppm),
+ * --out-rgba8, --out-nv12, --srgb, the debug views, the ring modes, a .y4m
+ * that is not 4:2:0 or is 10-bit, no input at all, and odd sizes.
  * --surface-align P,R: the device frames, input and output, are held in
  * mm_surface_aligned(W, H, format, P, R) surfaces (256,16: a hardware
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
@@ -203,8 +212,15 @@ static int surf_copy(void *dst, const mm_surface *dl, const void *src, const mm_
         unsigned char *d = (unsigned char *)dst + dl->frame_stride * (size_t)k;
         const unsigned char *a = (const unsigned char *)src + sl->frame_stride * (size_t)k;
         if (hipMemcpy2DAsync(d, dl->pitch, a, sl->pitch, rb, (size_t)H, kind, s) != hipSuccess) return 1;
+        /* (a chroma row: the luma row's bytes, or, three planes, half of them) */
         if (t.chroma_pitch && hipMemcpy2DAsync(d + dl->chroma_offset, dl->chroma_pitch, a + sl->chroma_offset,
-                                               sl->chroma_pitch, rb, (size_t)H / 2, kind, s) != hipSuccess)
+                                               sl->chroma_pitch, t.chroma_pitch, (size_t)H / 2, kind, s) != hipSuccess)
+            return 1;
+        /* three planes: the Cr plane lies chroma_pitch x H/2 after the Cb plane */
+        if ((dl->format & MM_PLANAR) &&
+            hipMemcpy2DAsync(d + dl->chroma_offset + dl->chroma_pitch * ((size_t)H / 2), dl->chroma_pitch,
+                             a + sl->chroma_offset + sl->chroma_pitch * ((size_t)H / 2), sl->chroma_pitch,
+                             t.chroma_pitch, (size_t)H / 2, kind, s) != hipSuccess)
             return 1;
     }
     return 0;
@@ -483,7 +499,7 @@ int main(int argc, char **argv)
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
     int nv12 = 0, p010 = 0, srgb = 0, mono = 0, yuy2 = 0, uyvy = 0, y210 = 0, ppm = 0, bgr = 0;
-    int out_rgba8 = 0, out_nv12 = 0;
+    int out_rgba8 = 0, out_nv12 = 0, i420 = 0;
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
@@ -500,6 +516,7 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--y210")) { y210 = 1; continue; }
         if (!strcmp(a, "--ppm")) { ppm = 1; continue; }
         if (!strcmp(a, "--bgr")) { bgr = 1; continue; }
+        if (!strcmp(a, "--i420")) { i420 = 1; continue; }
         if (!strcmp(a, "--out-rgba8")) { out_rgba8 = 1; continue; }
         if (!strcmp(a, "--out-nv12")) { out_nv12 = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
@@ -531,9 +548,20 @@ int main(int argc, char **argv)
         ++i;
     }
     if (B < 1) B = 1;
+    /* --i420 with another format option: refused before any file is opened */
+    if (i420 && (nv12 || p010 || mono || yuy2 || uyvy || y210 || ppm || out_rgba8 || out_nv12 || srgb || show_mag ||
+                 show_phase || ring_local > 0 || ring_world > 0)) {
+        fprintf(stderr, "--i420 does not go with --nv12, --p010, --mono, --yuy2, --uyvy, --y210, --ppm, --out-rgba8, "
+                        "--out-nv12, --srgb, the debug views or the ring modes\n");
+        return 2;
+    }
+    if (i420 && !in_path) {
+        fprintf(stderr, "--i420 needs an input (-i): an 8-bit 4:2:0 .y4m (C420) or raw I420 frames\n");
+        return 2;
+    }
     FILE *fi = in_path ? fopen(in_path, "rb") : NULL;
-    FILE *fo = out_path ? fopen(out_path, "wb") : NULL;
-    if ((in_path && !fi) || (out_path && !fo)) { fprintf(stderr, "cannot open file\n"); return 1; }
+    FILE *fo = out_path && !i420 ? fopen(out_path, "wb") : NULL;
+    if ((in_path && !fi) || (out_path && !fo && !i420)) { fprintf(stderr, "cannot open file\n"); return 1; }
     const int y4m_in = in_path && ends_with(in_path, ".y4m");
     const int y4m_out = out_path && ends_with(out_path, ".y4m");
     y4m_info yi = {0};
@@ -544,6 +572,25 @@ int main(int argc, char **argv)
         if (y4m_read_header_ext(fi, &yi, &depth)) { fprintf(stderr, "%s: unsupported Y4M\n", in_path); return 1; }
         W = yi.width;
         H = yi.height;
+    }
+    /* --i420: the frames of a C420 .y4m are MM_I420 frames as they lie (the
+     * output file is opened after the refusals: they write nothing) */
+    if (i420) {
+        if (y4m_in && (yi.chroma != Y4M_420 || depth != 8)) {
+            fprintf(stderr, "--i420 needs an 8-bit 4:2:0 .y4m input (C420; a C420p10 stream takes --p010), "
+                            "or raw I420 frames under any other extension\n");
+            return 2;
+        }
+        if ((W | H) & 1) {
+            fprintf(stderr, "--i420 needs even width and height (%dx%d)\n", W, H);
+            return 2;
+        }
+        if (matrix_arg && strcmp(matrix_arg, "601") && strcmp(matrix_arg, "709") && strcmp(matrix_arg, "2020")) {
+            fprintf(stderr, "--matrix takes 601, 709 or 2020, not %s (--i420)\n", matrix_arg);
+            return 2;
+        }
+        g_fmt = full_range ? MM_I420_FULL : MM_I420;
+        if (out_path && !(fo = fopen(out_path, "wb"))) { fprintf(stderr, "cannot open file\n"); return 1; }
     }
     /* different formats in and out (mm_process_stream_convert) */
     if (out_rgba8 && out_nv12) {
@@ -704,8 +751,8 @@ int main(int argc, char **argv)
     /* the output side's format: the input's, but with --out-rgba8 / --out-nv12 */
     int o_fmt = out_nv12 ? (full_range ? MM_NV12_FULL : MM_NV12) : 0;
     if (matrix_arg) {
-        if (!nv12 && !p010 && !p422 && !y210 && !out_nv12) {
-            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2, --uyvy, --y210 or --out-nv12 (the RGBA conversion of a .y4m is BT.601)\n");
+        if (!nv12 && !p010 && !p422 && !y210 && !out_nv12 && !i420) {
+            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2, --uyvy, --y210, --i420 or --out-nv12 (the RGBA conversion of a .y4m is BT.601)\n");
             return 2;
         }
         /* (--out-nv12: the bit names the output code; the input is RGBA8) */
@@ -721,7 +768,8 @@ int main(int argc, char **argv)
     else if (!out_nv12) o_fmt = g_fmt;
     const int convert = o_fmt != g_fmt;
     /* what the output files hold */
-    const int w_nv12 = out_nv12 || (nv12 && !out_rgba8), w_p010 = p010 && !out_rgba8;
+    /* (--i420: a C420 file too, its frames written as they lie) */
+    const int w_nv12 = out_nv12 || (nv12 && !out_rgba8) || i420, w_p010 = p010 && !out_rgba8;
     mm_params p;
     mm_params_default(&p);
     p.levels = L;
@@ -766,7 +814,7 @@ int main(int argc, char **argv)
     }
 
     size_t fb = (size_t)W * H * 4;
-    if (nv12 || p010 || mono || p422 || y210 || ppm) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
+    if (nv12 || p010 || mono || p422 || y210 || ppm || i420) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
     /* --surface-align: the frames the operator sees live in `lay` surfaces
      * (d_in, d_out); d_tin / d_tout are tight device frames for the synthetic
      * source and for the checksums and files */
@@ -784,7 +832,7 @@ int main(int argc, char **argv)
             (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK ||
             (rc = mm_surface_aligned(W, H, o_fmt, (size_t)pa, ra, &olay)) != MM_OK) {
             fprintf(stderr, "--surface-align %s: want P,R with P a multiple of the format's unit "
-                            "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, mono: the sample size, --ppm: 1) and R >= 1 (4:2:0: even)\n", surf_arg);
+                            "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, mono: the sample size, --ppm and --i420: 1; --i420: an even pitch) and R >= 1 (4:2:0: even)\n", surf_arg);
             return 2;
         }
         printf("surfaces: pitch %zu  chroma offset %zu  frame stride %zu\n", lay.pitch, lay.chroma_offset,
@@ -825,12 +873,14 @@ int main(int argc, char **argv)
         if (fi && y4m_in) {
             int got = 0;
             for (; got < n; ++got) {
-                /* (mono: the samples are the frame, read straight into place) */
+                /* (mono: the samples are the frame, read straight into place;
+                 * --i420: the three planes are the frame, the same way) */
                 const int r = mono ? y4m_read_frame_mono(fi, W, H, depth, host + fb * got)
-                                   : y4m_read_frame_depth(fi, &yi, depth, planes);
+                              : i420 ? y4m_read_frame_depth(fi, &yi, depth, host + fb * got)
+                                     : y4m_read_frame_depth(fi, &yi, depth, planes);
                 if (r < 0) { fprintf(stderr, "%s: malformed frame\n", in_path); return 1; }
                 if (r == 0) break;
-                if (mono) continue;
+                if (mono || i420) continue;
                 if (p010) y4m_420p10_to_p010(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
                 else if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
                 else if (p422) y4m_422_to_packed(W, H, planes, host + fb * got, uyvy);
@@ -894,6 +944,13 @@ int main(int argc, char **argv)
                 for (int k = 0; k < n; ++k) {
                     if (mono) {
                         if (y4m_write_frame_mono(fo, W, H, depth, host + fb * k)) {
+                            fprintf(stderr, "write failed\n");
+                            return 1;
+                        }
+                        continue;
+                    }
+                    if (i420) {   /* the frame is the file's three planes */
+                        if (y4m_write_frame_420(fo, W, H, host + fb * k)) {
                             fprintf(stderr, "write failed\n");
                             return 1;
                         }

@@ -20,6 +20,7 @@ from .binding import (MMError, lib, load_library, LIB_PATH, RGBA8, RGBA32F, RGBA
                       NV12, NV12_FULL, P010, P010_FULL, MATRIX_BT709, MATRIX_BT2020, FORMAT_BPP, frame_bytes,
                       Y8, Y10, Y12, Y16, MONO_FORMATS, MONO_BITS,
                       RGB24, BGR24, ORDER_BGR, RGB24_FORMATS,
+                      I420, I420_FULL, PLANAR, I420_FORMATS,
                       YUY2, YUY2_FULL, UYVY, UYVY_FULL, PACKED422_FORMATS,
                       Y210, Y210_FULL, Y210_FORMATS,
                       nv12_chroma_matrix, ycbcr_matrix, base_format,
@@ -34,6 +35,7 @@ __all__ = ["MMError", "lib", "load_library", "LIB_PATH", "RGBA8", "RGBA32F", "RG
            "RGBA8_SRGB", "NV12", "NV12_FULL", "P010", "P010_FULL", "FORMAT_BPP", "frame_bytes",
            "Y8", "Y10", "Y12", "Y16", "MONO_FORMATS", "MONO_BITS",
            "RGB24", "BGR24", "ORDER_BGR", "RGB24_FORMATS",
+           "I420", "I420_FULL", "PLANAR", "I420_FORMATS",
            "YUY2", "YUY2_FULL", "UYVY", "UYVY_FULL", "PACKED422_FORMATS",
            "Y210", "Y210_FULL", "Y210_FORMATS",
            "MATRIX_BT709", "MATRIX_BT2020", "nv12_chroma_matrix", "ycbcr_matrix", "base_format",

@@ -53,6 +53,13 @@ NV12_FULL = 17      # full ("JPEG") range
 # << 6; a P016 surface's low bits are honoured): frame_bytes() gives W*H*3
 P010 = 18           # BT.601 matrix, limited range (Y 64..940, C 64..960)
 P010_FULL = 19      # full range (0..1023)
+# three-plane 8-bit 4:2:0 (I420, ffmpeg's yuv420p, a C420 .y4m's frames): H rows of
+# W luma bytes, then H/2 rows of W/2 Cb bytes, then H/2 rows of W/2 Cr bytes, NV12's
+# samples and semantics; the plane-layout bit is valid on the two NV12 codes alone
+PLANAR = 512        # plane-layout bit: Cb and Cr in planes of their own
+I420 = NV12 | PLANAR            # 528, BT.601 limited range
+I420_FULL = NV12_FULL | PLANAR  # 529, full range
+I420_FORMATS = (I420, I420_FULL)
 # one matrix bit, OR-ed onto a 4:2:0 or packed 4:2:2 code above (HD / UHD content): the layout
 # and sizes stay the base code's (base_format)
 MATRIX_BT709 = 32   # Kr 0.2126, Kb 0.0722
@@ -324,7 +331,8 @@ def nv12_chroma_matrix():
 
 def base_format(fmt):
     """The format without its matrix bit, and BGR24 without its byte-order bit:
-    what decides a frame's size and shape."""
+    what decides a frame's size and shape.  (The plane-layout bit stays: I420
+    and NV12 frames have the same size and not the same shape of planes.)"""
     if fmt == BGR24:
         return RGB24
     return fmt & ~(MATRIX_BT709 | MATRIX_BT2020)

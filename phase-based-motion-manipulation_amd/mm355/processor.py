@@ -8,7 +8,7 @@ import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       MONO_FORMATS, NV12, NV12_FULL, P010, P010_FULL, PACKED422_FORMATS, RGBA8, RGBA8_SRGB, RGBA16F,
-                      RGB24_FORMATS, RGBA32F, Y8, Y210_FORMATS,
+                      I420_FORMATS, RGB24_FORMATS, RGBA32F, Y8, Y210_FORMATS,
                       Handle, MMError, Params, Surface, base_format, convert_supported)
 
 
@@ -76,6 +76,12 @@ def frame_layout(frame, width, height, fmt):
         lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
         lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation (at least 3 W)
         return lay
+    if base_format(fmt) in I420_FORMATS:   # the frame's bytes in NV12's shape: one contiguous [H * 3 / 2, W] array
+        if tuple(frame.shape) != (height * 3 // 2, width) or not str(frame.dtype).endswith("uint8"):
+            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height * 3 // 2, width)} uint8)")
+        if strides != (width, 1):
+            raise MMError(-1, "a three-plane 4:2:0 frame must be contiguous (name a Surface through Handle.process_surface)")
+        return None
     if fmt in MONO_FORMATS:   # [H, W] samples: uint8 (Y8) or uint16
         want = "uint8" if fmt == Y8 else "uint16"
         if tuple(frame.shape) != (height, width) or not str(frame.dtype).endswith(want):
@@ -217,6 +223,9 @@ class MotionMagnificationProcessor:
         on both sides, as cv2 (BGR24), PIL and imageio (RGB24) hand them out:
         device tensors, contiguous or row-strided views that start at any
         byte, or host numpy arrays; such a frame without fmt= raises.
+        fmt=I420 / I420_FULL, with or without a matrix bit: three-plane 4:2:0,
+        one contiguous [H * 3 / 2, W] uint8 array on both sides (the frame's
+        bytes in NV12's shape: H luma rows, then the Cb plane, then the Cr plane).
         dst_fmt (None, or equal to fmt: the above): the destination's format
         where it differs from the source's (mm355.convert_supported): fmt=NV12 /
         P010 codes with dst_fmt=RGBA8, the source one contiguous [H * 3 / 2, W]
@@ -251,8 +260,9 @@ class MotionMagnificationProcessor:
             if _fmt_of(destination, self.srgb) != fmt:
                 raise MMError(-1, "source/destination formats differ")
         elif (fmt not in MONO_FORMATS and base_format(fmt) not in PACKED422_FORMATS and
-              base_format(fmt) not in Y210_FORMATS and fmt not in RGB24_FORMATS):
-            raise MMError(-1, f"fmt={fmt}: only the grayscale, packed 4:2:2 and packed RGB formats are named, "
+              base_format(fmt) not in Y210_FORMATS and fmt not in RGB24_FORMATS and
+              base_format(fmt) not in I420_FORMATS):
+            raise MMError(-1, f"fmt={fmt}: only the grayscale, packed 4:2:2, packed RGB and three-plane 4:2:0 formats are named, "
                               "the others follow the dtype")
         on_dev = _is_device(source)
         if on_dev != _is_device(destination):
@@ -296,7 +306,7 @@ def host_frames(n, h, w, fmt):
     if fmt in RGB24_FORMATS:        # three bytes per pixel, either order
         return np.zeros((n, h, w, 3), np.uint8)
     fmt = base_format(fmt)          # a matrix bit changes no size or shape
-    if fmt in (NV12, NV12_FULL):    # h luma rows, then h/2 rows of interleaved Cb, Cr
+    if fmt in (NV12, NV12_FULL) or fmt in I420_FORMATS:    # h luma rows, then h/2 rows of chroma bytes (one or two planes)
         return np.zeros((n, h * 3 // 2, w), np.uint8)
     if fmt in (P010, P010_FULL):    # the same rows in 16-bit words (10-bit code << 6)
         return np.zeros((n, h * 3 // 2, w), np.uint16)

@@ -48,6 +48,13 @@ legs compare addressing alone (K1's byte-aligned dword loads, K34's 12-byte
 quads without RGBA8's LDS-DMA source staging).  A library from before these
 formats runs without them.
 
+Three-plane 4:2:0 legs (i420, i420_bt709, i420_pitched): the NV12 legs' own
+bytes with the chroma de-interleaved as MM_I420, the same bytes taken as
+MM_I420 | MM_MATRIX_BT709 (K1's matrixed three-plane instance), and the I420
+frames in mm_surface_aligned(256, 16) surfaces; the same 1.5 bytes per pixel
+each way, so NV12 of the same run is the comparison.  A library from before
+this format runs without them.
+
 Convert legs (nv12>rgba8, nv12_bt709>rgba8, p010>rgba8, rgba8>nv12,
 rgba8>nv12_bt709, and their _pitched forms): the NV12 / P010 / RGBA8 legs' own
 frames in as the one format and out as the other through
@@ -159,6 +166,30 @@ def to_surface(torch, src, lay, W, H, planar):
     return buf
 
 
+def nv12_to_i420(torch, nv):
+    """[n][H*3/2][W] NV12 (device) -> the same bytes as I420, in the same shape."""
+    n, H32, W = nv.shape
+    H = H32 * 2 // 3
+    c = nv[:, H:].reshape(n, H // 2, W // 2, 2)
+    return torch.cat([nv[:, :H].reshape(n, -1), c[..., 0].reshape(n, -1), c[..., 1].reshape(n, -1)],
+                     dim=1).reshape(n, H32, W).contiguous()
+
+
+def to_surface_i420(torch, src, lay, W, H):
+    """Tight I420 frames (device) -> one uint8 buffer holding them in layout `lay`
+    (padding zero): the Cr plane chroma_pitch x H/2 after the Cb plane."""
+    n = src.shape[0]
+    flat = src.contiguous().reshape(n, -1)
+    buf = torch.zeros(n * lay.frame_stride, dtype=torch.uint8, device=src.device)
+    buf.as_strided((n, H, W), (lay.frame_stride, lay.pitch, 1)).copy_(flat[:, :W * H].reshape(n, H, W))
+    q = W * H // 4
+    for j in range(2):
+        buf.as_strided((n, H // 2, W // 2), (lay.frame_stride, lay.chroma_pitch, 1),
+                       lay.chroma_offset + j * lay.chroma_pitch * (H // 2)).copy_(
+            flat[:, W * H + j * q:W * H + (j + 1) * q].reshape(n, H // 2, W // 2))
+    return buf
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -204,6 +235,11 @@ def main():
         fmts += [("rgb24", mm355.RGB24), ("bgr24", mm355.BGR24)]
     except (mm355.MMError, AttributeError):
         pass    # a build from before the packed RGB formats
+    try:
+        mm355.frame_bytes(W, H, mm355.I420)
+        fmts += [("i420", mm355.I420), ("i420_bt709", mm355.I420 | mm355.MATRIX_BT709)]
+    except (mm355.MMError, AttributeError):
+        pass    # a build from before the three-plane 4:2:0 format
     for name, fmt in fmts:
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
@@ -211,8 +247,10 @@ def main():
             h.synth(rgba, 0, B, stream=torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
             src = rgba
-        elif name in ("nv12_bt709", "p010_bt2020", "yuy2_bt709", "y210_bt709"):
+        elif name in ("nv12_bt709", "p010_bt2020", "yuy2_bt709", "y210_bt709", "i420_bt709"):
             src = legs[name.split("_")[0]]["src"]
+        elif name == "i420":       # the NV12 leg's bytes, de-interleaved
+            src = nv12_to_i420(torch, legs["nv12"]["src"])
         elif name == "rgb24":      # the RGBA8 leg's pictures without their alpha
             src = rgba[..., :3].contiguous()
         elif name == "bgr24":
@@ -229,11 +267,12 @@ def main():
             src = to_420(torch, rgba, ten_bit=name == "p010")
         legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[], lay=None,
                           bytes_per_frame=mm355.frame_bytes(W, H, fmt))
-        if not a.no_pitched and mm355.has_surfaces() and name != "bgr24":   # (one pitched packed RGB leg)
+        if not a.no_pitched and mm355.has_surfaces() and name not in ("bgr24", "i420_bt709"):   # (one pitched packed RGB leg, one three-plane)
             lay = mm355.Surface.aligned(W, H, fmt, 256, 16)
             h = mm355.Handle(W, H, p)
             h.set_batch(B)
-            buf = to_surface(torch, src, lay, W, H, name.startswith(("nv12", "p010")))
+            buf = (to_surface_i420(torch, src, lay, W, H) if name == "i420" else
+                   to_surface(torch, src, lay, W, H, name.startswith(("nv12", "p010"))))
             legs[name + "_pitched"] = dict(h=h, fmt=fmt, src=buf, dst=torch.zeros_like(buf), fps=[], lay=lay,
                                            bytes_per_frame=lay.frame_stride)
     convs = []
@@ -359,8 +398,17 @@ def main():
         ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
         out["rgb24_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
                                   for n in ("rgb24", "bgr24", "rgba8", "nv12")}
+    if "i420" in out["formats"]:
+        ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
+        for name, base in (("i420", "nv12"), ("i420_bt709", "nv12_bt709"), ("i420_pitched", "nv12_pitched")):
+            if name in out["formats"] and base in out["formats"]:
+                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                    out["formats"][base]["fps_median"], 4)
+        out["i420_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
+                                 for n in ("i420", "nv12", "i420_bt709", "nv12_bt709", "i420_pitched", "nv12_pitched")
+                                 if n in out["formats"]}
     for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16", "yuy2", "uyvy", "yuy2_bt709",
-                 "y210", "y210_bt709", "rgb24"):
+                 "y210", "y210_bt709", "rgb24", "i420"):
         if name + "_pitched" in out["formats"]:
             out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
                                                       out["formats"][name]["fps_median"], 4)
