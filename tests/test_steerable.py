@@ -61,10 +61,11 @@ def test_spec_static_scene_unchanged_by_diff():
 # ---- HIP path (GPU) -------------------------------------------------------------
 
 def gpu_steer(W, H, fr, levels=5, S=10.0, Oo=8, filt=0, rl=0.05, rh=0.4, edge=0, apply=True,
-              batch=4):
+              batch=4, minf=0.05, maxf=0.45, tau=0.01):
     import mm355
     import torch
-    p = mm355.Params.make(levels=levels, phase_scale=S, edge_mode=edge, apply_magnification=apply,
+    p = mm355.Params.make(levels=levels, min_freq=minf, max_freq=maxf, phase_scale=S,
+                          magnitude_threshold=tau, edge_mode=edge, apply_magnification=apply,
                           mode=mm355.MODE_STEERABLE, orientations=Oo, temporal_filter=filt,
                           iir_low=rl, iir_high=rh)
     h = mm355.Handle(W, H, p)
