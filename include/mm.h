@@ -393,10 +393,11 @@ extern "C" {
  * k * mm_frame_bytes.  MM_PLANAR is a plane-layout bit beside the matrix and
  * order bits: MM_I420 = MM_NV12 | MM_PLANAR, and a matrix bit may be OR-ed on
  * as on NV12.  The valid codes are 528, 529, 560, 561, 592 and 593.
- * The bit is valid on the two NV12 codes alone: MM_PLANAR by itself, the bit on
- * an RGBA, single-plane, P010, packed 4:2:2, MM_Y210 or packed RGB code, the
- * bit together with MM_ORDER_BGR, both matrix bits together and any other stray
- * bit (528 | 256, 528 | 1024) are MM_ERR_INVALID from mm_frame_bytes,
+ * The bit is valid on the two NV12 codes alone (and, together with
+ * MM_LOW_BITS, on the two P010 codes: MM_I010 below): MM_PLANAR by itself, the
+ * bit on an RGBA, single-plane, P010, packed 4:2:2, MM_Y210 or packed RGB code,
+ * the bit together with MM_ORDER_BGR, both matrix bits together and any other
+ * stray bit (528 | 256, 528 | 1024) are MM_ERR_INVALID from mm_frame_bytes,
  * mm_surface_* and every frame entry point, before anything is queued.
  * Restrictions, all NV12's: W and H even (else MM_ERR_UNSUPPORTED);
  * show_magnitude / show_phase are refused with MM_ERR_UNSUPPORTED;
@@ -442,13 +443,91 @@ extern "C" {
  * code MM_ERR_UNSUPPORTED; mm_compute_state* takes them.
  * Out of scope: YV12 (the Cr plane first); planes at independent addresses or
  * with padded chroma rows between them (a region of interest narrower in
- * height than its parent needs that); 10-bit planar (yuv420p10le: low-bit
- * words); planar 4:2:2 / 4:4:4; any mixed convert pair; the ring entry points
- * (include/mm_ring.h), the Unity shim and mm_extmem_check; odd sizes and the
- * debug views. */
+ * height than its parent needs that); planar 4:2:2 / 4:4:4 (10-bit three-plane
+ * 4:2:0, yuv420p10le, is MM_I010 below); any mixed convert pair; the ring
+ * entry points (include/mm_ring.h), the Unity shim and mm_extmem_check; odd
+ * sizes and the debug views. */
 #define MM_PLANAR    512                          /* plane-layout bit: Cb and Cr in planes of their own */
 #define MM_I420      (MM_NV12 | MM_PLANAR)        /* 528 */
 #define MM_I420_FULL (MM_NV12_FULL | MM_PLANAR)   /* 529 */
+
+/* 10-bit three-plane 4:2:0 frames (backward-compatible addition to ABI 10: a
+ * caller detects it by mm_frame_bytes(W, H, MM_I010, &n) == MM_OK).  What a
+ * software decoder produces for 10-bit content (libavcodec, dav1d, libvpx on
+ * HEVC Main10, AV1 10-bit, VP9 profile 2), what the x265 and SVT 10-bit inputs
+ * take and what every C420p10 .y4m file holds: ffmpeg's yuv420p10le, I010 in
+ * libyuv and VLC.  Three planes of little-endian 16-bit words with the code in
+ * the word's LOW 10 bits, tightly packed: H rows of W luma words, then H/2 rows
+ * of W/2 Cb words, then H/2 rows of W/2 Cr words, 3 W H bytes in all (6,220,800
+ * at 1920 x 1080, 18,228 at 98 x 62: the frame payload of a C420p10 .y4m as it
+ * lies in the file); frame k of a stream at k * mm_frame_bytes.
+ * MM_LOW_BITS is one more bit beside the matrix, order and plane bits: the code
+ * sits in the word's low bits.  MM_I010 = MM_P010 | MM_PLANAR | MM_LOW_BITS, and
+ * a matrix bit may be OR-ed on as on P010.  The valid codes are 1554, 1555,
+ * 1586, 1587, 1618 and 1619.  The bit is valid only together with MM_PLANAR on
+ * the two P010 codes: MM_LOW_BITS by itself, 18 | 512 and 19 | 512 without it
+ * (high-bit words in three planes: a layout nobody produces), 528 | 1024,
+ * 18 | 1024, the bit on any other family, the bit with MM_ORDER_BGR, both matrix
+ * bits and any other stray bit (1554 | 256, 1554 | 2048) are MM_ERR_INVALID from
+ * mm_frame_bytes, mm_surface_* and every frame entry point, before anything is
+ * queued.
+ * Restrictions, P010's and I420's: W and H even (else MM_ERR_UNSUPPORTED);
+ * show_magnitude / show_phase are refused with MM_ERR_UNSUPPORTED;
+ * in_layout->format == out_layout->format.
+ * The semantics are P010's word for word with v = word in 10-bit code units
+ * instead of word / 64 (ranges, matrices, the chroma sample shared by its 2 x 2
+ * pixels, the out rule, rounding and clamps).  Output words hold the code in
+ * the low 10 bits and their high 6 bits are zero.  The word is neither masked
+ * nor clamped on input: a word above 1023 gives v > 1023 and passes until the
+ * reference's saturate, as MM_Y10 treats its words.  The first frame after
+ * mm_create / mm_reset and apply_magnification = 0 pass all 3 W H bytes through
+ * bitwise, stray high bits included.
+ * Three identities hold bitwise:
+ *   1. for frames whose words are all <= 1023, the output is the MM_P010
+ *      path's output on the frame word << 6 with Cb and Cr interleaved, shifted
+ *      right by 6 and de-interleaved, in every mode (pyramid, standard,
+ *      steerable), call form, batch size, edge mode and layout;
+ *   2. the temporal state (mm_get_state / mm_compute_state*) is bitwise that
+ *      P010 frame's (the word unit is a power of two, so every input-side
+ *      uniform scales exactly);
+ *   3. the state of an MM_I010_FULL frame is bitwise the state of the MM_Y10
+ *      frame that is its luma plane (a surface of the same buffer), with luma
+ *      words above 1023 too.
+ * Surfaces: as MM_I420 in words.  pitch is the luma pitch, chroma_offset the Cb
+ * plane's offset, chroma_pitch the pitch of a Cb row and of a Cr row alike, and
+ * the Cr plane starts chroma_pitch x H/2 bytes after the Cb plane.  The unit u
+ * is 2: device frame pointers, pitch, chroma_offset, chroma_pitch and
+ * frame_stride are multiples of 2.  pitch >= 2 W; chroma_pitch >= W (the bytes
+ * of W/2 words); chroma_offset at or past the end of the last luma row's
+ * samples; the extent is the byte after the last Cr sample, at most 2^32;
+ * frame_stride >= extent when count > 1; size_t overflows are MM_ERR_INVALID;
+ * padding is never read and never written.
+ * mm_surface_tight(1920, 1080, MM_I010): pitch 3,840, chroma_offset 4,147,200,
+ * chroma_pitch 1,920 (the Cr plane at 5,184,000), frame_stride 6,220,800.
+ * mm_surface_tight(98, 62, MM_I010): pitch 196, chroma_offset 12,152,
+ * chroma_pitch 98 (the Cr plane at 15,190), frame_stride 18,228.
+ * mm_surface_aligned: the luma pitch is 2 W rounded up to pitch_align,
+ * chroma_pitch = pitch / 2 (MM_ERR_INVALID where that is odd), rows_align even:
+ * mm_surface_aligned(1920, 1080, MM_I010, 256, 16) has pitch 3,840,
+ * chroma_offset 4,177,920, chroma_pitch 1,920 (the Cr plane at 5,214,720),
+ * frame_stride 6,266,880 and extent 6,251,520.
+ * The fused kernels move a quad's two Cb words and its two Cr words as one
+ * dword per plane and its four luma codes as one 8-byte store at a
+ * dword-aligned address: they run where the output's luma rows and every Cb and
+ * Cr row of every frame of the launch lie on multiples of 4, on both sides
+ * (every tight frame with W % 8 == 0, the decoder layout); any other legal
+ * layout takes the unfused kernels, whose accesses are single words: the same
+ * bytes.
+ * mm_ycbcr_matrix takes the six codes and returns the P010 code's values;
+ * mm_convert_supported(x, x) is MM_OK for them and any mixed pair with one of
+ * them MM_ERR_UNSUPPORTED; mm_compute_state* takes them.
+ * Out of scope: 12-bit planar (yuv420p12le), yuv422p10le and yuv444p10le; the
+ * Cr plane first; planes at independent addresses; any mixed convert pair; the
+ * ring entry points (include/mm_ring.h), the Unity shim and mm_extmem_check;
+ * odd sizes and the debug views; PQ / HLG. */
+#define MM_LOW_BITS  1024                                        /* word-alignment bit: the code in the word's low bits */
+#define MM_I010      (MM_P010 | MM_PLANAR | MM_LOW_BITS)         /* 1554 */
+#define MM_I010_FULL (MM_P010_FULL | MM_PLANAR | MM_LOW_BITS)    /* 1555 */
 
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0  /* usePyramidDecomposition = true (.cs:18, :128-131) */
@@ -582,6 +661,7 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  * an unaligned frame takes the narrower access, never another kernel: a layout
  * aligned like a decoder's runs exactly the tight layout's kernels. */
 typedef struct {
+    /* MM_I420(_FULL) and MM_I010(_FULL) too: every format of the list above */
     int    format;         /* MM_RGBA8 ... MM_UYVY_FULL, MM_Y210(_FULL), MM_RGB24 / MM_BGR24; 4:2:0 and 4:2:2: | MM_MATRIX_* */
     size_t pitch;          /* bytes from one row to the next: RGBA rows, or luma rows */
     size_t chroma_offset;  /* 4:2:0: bytes from the frame's base to the (Cb,Cr) plane; else 0 */

@@ -450,8 +450,9 @@ int mm_surface_aligned(int width, int height, int format, size_t pitch_align, in
     if (fmt_420(format)) {
         t.chroma_offset = planes;
         // (three-plane: Cb and Cr rows of half the luma pitch, which is then even)
-        if (fmt_i420(format) && (pitch & 1)) return MM_ERR_INVALID;
-        t.chroma_pitch = fmt_i420(format) ? pitch / 2 : pitch;
+        // (its 10-bit form: half the luma pitch is whole words)
+        if ((fmt_i420(format) && (pitch & 1)) || (fmt_i010(format) && (pitch & 3))) return MM_ERR_INVALID;
+        t.chroma_pitch = fmt_planes3(format) ? pitch / 2 : pitch;
         if (__builtin_add_overflow(planes, planes / 2, &t.frame_stride)) return MM_ERR_INVALID;
     }
     if (int rc = surf_check(width, height, &t, nullptr)) return rc;
@@ -581,7 +582,7 @@ static int process_surface(mm_handle *h, const void *in, const mm_surface *in_la
         if (fmt_420(format))
             HIPCHK(stage_plane(h->d_stage_in + luma, rc_in, (const uint8_t *)in + in_layout->chroma_offset,
                                in_layout->chroma_pitch, rc_in, hc, hipMemcpyHostToDevice, s));
-        if (fmt_i420(format))   // the Cr plane, chroma_pitch x H/2 after the Cb plane
+        if (fmt_planes3(format))   // the Cr plane, chroma_pitch x H/2 after the Cb plane
             HIPCHK(stage_plane(h->d_stage_in + luma + rc_in * hc, rc_in,
                                (const uint8_t *)in + in_layout->chroma_offset + i420_cr_delta(h->H, in_layout->chroma_pitch),
                                in_layout->chroma_pitch, rc_in, hc, hipMemcpyHostToDevice, s));
@@ -596,7 +597,7 @@ static int process_surface(mm_handle *h, const void *in, const mm_surface *in_la
         if (fmt_420(oformat))
             HIPCHK(stage_plane((uint8_t *)out + out_layout->chroma_offset, out_layout->chroma_pitch,
                                h->d_stage_out + lumao, rc_out, rc_out, hc, hipMemcpyDeviceToHost, s));
-        if (fmt_i420(oformat))
+        if (fmt_planes3(oformat))
             HIPCHK(stage_plane((uint8_t *)out + out_layout->chroma_offset + i420_cr_delta(h->H, out_layout->chroma_pitch),
                                out_layout->chroma_pitch, h->d_stage_out + lumao + rc_out * hc, rc_out, rc_out, hc,
                                hipMemcpyDeviceToHost, s));

@@ -224,7 +224,13 @@ static inline bool fmt_p010(int fmt) { return fmt_base(fmt) == MM_P010 || fmt_ba
 // Cr in planes of their own.  The plane-layout bit is valid on the two NV12
 // codes alone and stays in the base: on any other code the base is no format.
 static inline bool fmt_i420(int fmt) { return fmt_base(fmt) == MM_I420 || fmt_base(fmt) == MM_I420_FULL; }
-static inline bool fmt_420(int fmt) { return fmt_nv12(fmt) || fmt_p010(fmt) || fmt_i420(fmt); }   // planar, not Pix<FMT>
+// three-plane 10-bit 4:2:0 (MM_I010 = MM_P010 | MM_PLANAR | MM_LOW_BITS): P010's
+// codes in the words' low bits, Cb and Cr in planes of their own.  The low-bits
+// bit is valid together with the plane bit on the two P010 codes alone; both
+// stay in the base: on any other code, or one without the other, the base is no format.
+static inline bool fmt_i010(int fmt) { return fmt_base(fmt) == MM_I010 || fmt_base(fmt) == MM_I010_FULL; }
+static inline bool fmt_planes3(int fmt) { return fmt_i420(fmt) || fmt_i010(fmt); }   // Cb and Cr planes of their own
+static inline bool fmt_420(int fmt) { return fmt_nv12(fmt) || fmt_p010(fmt) || fmt_planes3(fmt); }   // planar, not Pix<FMT>
 // packed 8-bit 4:2:2: one plane of four-byte macropixels (YUY2 / UYVY byte order)
 static inline bool fmt_422(int fmt) { return fmt_base(fmt) >= MM_YUY2 && fmt_base(fmt) <= MM_UYVY_FULL; }
 static inline bool fmt_uyvy(int fmt) { return fmt_base(fmt) == MM_UYVY || fmt_base(fmt) == MM_UYVY_FULL; }
@@ -235,7 +241,7 @@ static inline bool fmt_full(int fmt)
 {
     const int b = fmt_base(fmt);
     return b == MM_NV12_FULL || b == MM_P010_FULL || b == MM_YUY2_FULL || b == MM_UYVY_FULL || b == MM_Y210_FULL ||
-           b == MM_I420_FULL;
+           b == MM_I420_FULL || b == MM_I010_FULL;
 }
 // single-plane grayscale: one sample per pixel, a byte (MM_Y8) or a 16-bit word
 static inline bool fmt_mono(int fmt) { return fmt >= MM_Y8 && fmt <= MM_Y16; }
@@ -254,7 +260,7 @@ static inline size_t fmt_frame_bytes(int W, int H, int fmt)
 {
     const size_t px = (size_t)W * (size_t)H;
     // (MM_Y210: 4 bytes per pixel, fmt_bpp's default)
-    return fmt_p010(fmt) ? 3 * px : fmt_nv12(fmt) || fmt_i420(fmt) ? px + px / 2 : fmt_422(fmt) ? 2 * px : px * fmt_bpp(fmt);
+    return fmt_p010(fmt) || fmt_i010(fmt) ? 3 * px : fmt_nv12(fmt) || fmt_i420(fmt) ? px + px / 2 : fmt_422(fmt) ? 2 * px : px * fmt_bpp(fmt);
 }
 // What every frame entry point asks of (format, geometry, parameters) before
 // it queues anything.  NV12 and P010 are 4:2:0: even sizes only; the debug
@@ -274,8 +280,9 @@ static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
 static inline size_t fmt_unit(int fmt)
 {
     // (packed RGB: 1, a real [H, W, 3] array or a region of one starts at any byte)
-    // (three-plane 4:2:0: 1, chroma rows of W / 2 bytes start at any byte)
-    return fmt_nv12(fmt) ? 2 : fmt_p010(fmt) || fmt_422(fmt) ? 4 : fmt_y210(fmt) ? 8 :
+    // (three-plane 4:2:0: 1, chroma rows of W / 2 bytes start at any byte; its
+    // 10-bit form: 2, one word)
+    return fmt_nv12(fmt) || fmt_i010(fmt) ? 2 : fmt_p010(fmt) || fmt_422(fmt) ? 4 : fmt_y210(fmt) ? 8 :
            fmt_rgb24(fmt) || fmt_i420(fmt) ? 1 : fmt_bpp(fmt);
 }
 // sample bytes of one row (4:2:0: of a luma row and of a (Cb, Cr) row alike;
@@ -283,7 +290,7 @@ static inline size_t fmt_unit(int fmt)
 // Cr row has half as many)
 static inline size_t fmt_row_bytes(int W, int fmt)
 {
-    return (size_t)W * (fmt_p010(fmt) || fmt_422(fmt) ? 2 : fmt_nv12(fmt) || fmt_i420(fmt) ? 1 : fmt_bpp(fmt));
+    return (size_t)W * (fmt_p010(fmt) || fmt_422(fmt) || fmt_i010(fmt) ? 2 : fmt_nv12(fmt) || fmt_i420(fmt) ? 1 : fmt_bpp(fmt));
 }
 // Three-plane 4:2:0: the Cr plane's offset from the Cb plane (include/mm.h:
 // derived, mm_surface has one chroma offset)
@@ -295,7 +302,7 @@ static inline int surf_tight(int W, int H, int fmt, mm_surface *s)
     s->format = fmt;
     s->pitch = fmt_row_bytes(W, fmt);
     s->chroma_offset = fmt_420(fmt) ? s->pitch * (size_t)H : 0;
-    s->chroma_pitch = fmt_i420(fmt) ? s->pitch / 2 : fmt_420(fmt) ? s->pitch : 0;
+    s->chroma_pitch = fmt_planes3(fmt) ? s->pitch / 2 : fmt_420(fmt) ? s->pitch : 0;
     s->frame_stride = fmt_frame_bytes(W, H, fmt);
     return MM_OK;
 }
@@ -313,11 +320,13 @@ static inline int surf_check(int W, int H, const mm_surface *s, size_t *extent)
     size_t end;   // the byte after the last sample of the RGBA / luma plane
     if (__builtin_mul_overflow(s->pitch, (size_t)(H - 1), &end) || __builtin_add_overflow(end, rb, &end))
         return MM_ERR_INVALID;
-    if (fmt_i420(fmt)) {
-        // rows of W / 2 bytes; H / 2 Cb rows, then H / 2 Cr rows at the same pitch
+    if (fmt_planes3(fmt)) {
+        // rows of W / 2 samples; H / 2 Cb rows, then H / 2 Cr rows at the same pitch
+        // (u: 1, or the word of the 10-bit form)
         const size_t cb = rb / 2;
         size_t cr;
-        if (s->chroma_pitch < cb || s->chroma_offset < end) return MM_ERR_INVALID;
+        if (s->chroma_pitch < cb || s->chroma_pitch % u || s->chroma_offset % u || s->chroma_offset < end)
+            return MM_ERR_INVALID;
         if (__builtin_mul_overflow(s->chroma_pitch, (size_t)(H / 2), &cr) ||
             __builtin_mul_overflow(s->chroma_pitch, (size_t)(H / 2 - 1), &end) ||
             __builtin_add_overflow(end, cr, &end) || __builtin_add_overflow(end, s->chroma_offset, &end) ||
@@ -409,6 +418,9 @@ static_assert(kFmtY210 == MM_Y210 && kFmtY210M == (MM_Y210 | MM_MATRIX_BT709),
               "the kernels' 10-bit packed 4:2:2 template arguments are the Y210 limited-range codes");
 static_assert(kFmtI420 < 256 && kFmtI420M < 256 && MM_I420 == (MM_NV12 | MM_PLANAR) && !(MM_PLANAR & (kMatrixBits | MM_ORDER_BGR | 255)),
               "the kernels' three-plane template arguments are internal codes below 256 (a code from 256 names a pair)");
+static_assert(kFmtI010 < 256 && kFmtI010M < 256 && MM_I010 == (MM_P010 | MM_PLANAR | MM_LOW_BITS) &&
+                  !(MM_LOW_BITS & (kMatrixBits | MM_ORDER_BGR | MM_PLANAR | 255)),
+              "the kernels' 10-bit three-plane template arguments are internal codes below 256");
 static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && !(MM_ORDER_BGR & kMatrixBits),
               "the kernels' packed RGB template argument is the MM_RGB24 code; the order bit is no matrix bit");
 // Runs the statement with the compile-time format FMT_ of the runtime `fmt`
@@ -431,6 +443,7 @@ static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && 
     case MM_Y210: case MM_Y210_FULL: { constexpr int FMT_ = MM_Y210; __VA_ARGS__; } break; \
     case MM_RGB24: { constexpr int FMT_ = MM_RGB24; __VA_ARGS__; } break;      \
     case MM_I420: case MM_I420_FULL: { constexpr int FMT_ = kFmtI420; __VA_ARGS__; } break; \
+    case MM_I010: case MM_I010_FULL: { constexpr int FMT_ = kFmtI010; __VA_ARGS__; } break; \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
 // ... the compose kernels' (k_compose, k_rows_inv_compose, k_rows_inv_compose4):
@@ -450,6 +463,7 @@ static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && 
 #define MM_FMT_SWITCH_K1(fmt, ...)                                             \
     if (fmt_matrix(fmt) && fmt_nv12(fmt)) { constexpr int FMT_ = kFmtNV12M; __VA_ARGS__; }      \
     else if (fmt_matrix(fmt) && fmt_i420(fmt)) { constexpr int FMT_ = kFmtI420M; __VA_ARGS__; } \
+    else if (fmt_matrix(fmt) && fmt_i010(fmt)) { constexpr int FMT_ = kFmtI010M; __VA_ARGS__; } \
     else if (fmt_matrix(fmt) && fmt_422(fmt)) { constexpr int FMT_ = kFmtYUY2M; __VA_ARGS__; }  \
     else if (fmt_matrix(fmt) && fmt_y210(fmt)) { constexpr int FMT_ = kFmtY210M; __VA_ARGS__; } \
     else if (fmt_matrix(fmt)) { constexpr int FMT_ = kFmtP010M; __VA_ARGS__; }                  \
@@ -458,8 +472,9 @@ static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && 
 // NV12 (bytes) or P010 (words) luma-plane instance with its own uniforms
 // (geo_of: y_off 0, y_unit 1 / max), bit for bit what an instance of its own
 // would compute (mm_kernels.hpp)
-// (a BT.601 three-plane frame too: its luma plane is NV12's, so is the state)
-template <int F> constexpr int kK1Fmt = F == MM_Y8 || F == kFmtI420 ? kFmtNV12 : F == MM_Y16 ? kFmtP010 : F;
+// (a BT.601 three-plane frame too: its luma plane is NV12's, so is the state;
+// its 10-bit form's is P010's in another word unit, which the uniforms carry)
+template <int F> constexpr int kK1Fmt = F == MM_Y8 || F == kFmtI420 ? kFmtNV12 : F == MM_Y16 || F == kFmtI010 ? kFmtP010 : F;
 // ... and the kernels of the odd sizes and the debug views, which the 4:2:0
 // and packed 4:2:2 formats cannot have (refused by fmt_check before any launch): the RGBA and
 // the single-plane instances
@@ -555,10 +570,11 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
     g.li = fr.in;
     g.lo = fr.out;
     if (fmt_ycc(fmt)) {
-        const bool full = fmt_full(fmt), p10 = fmt_p010(fmt) || fmt_y210(fmt);   // (MM_Y210: P010's words)
+        // (MM_Y210: P010's words; MM_I010: its codes in the words' low bits, u = 1)
+        const bool full = fmt_full(fmt), p10 = fmt_p010(fmt) || fmt_y210(fmt) || fmt_i010(fmt);
         const double ys = p10 ? (full ? 1023.0 : 876.0) : (full ? 255.0 : 219.0);
         const double cs = p10 ? (full ? 1023.0 : 896.0) : (full ? 255.0 : 224.0);
-        const double y0 = full ? 0.0 : p10 ? 64.0 : 16.0, u = p10 ? 64.0 : 1.0;
+        const double y0 = full ? 0.0 : p10 ? 64.0 : 16.0, u = p10 && !fmt_i010(fmt) ? 64.0 : 1.0;
         double m[6], kr, kb;
         ycbcr_matrix(fmt, m);
         matrix_krkb(fmt, &kr, &kb);
@@ -826,7 +842,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)k34_lds_bytes<12>(false);
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420, MM_I010})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtNV12toRGBA8>),
@@ -861,7 +877,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 11) {   // k_rows_inv_compose4: four 2048-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 4 * lds_complex<2048>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420, MM_I010})
             MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtNV12toRGBA8>),
@@ -1096,8 +1112,28 @@ static bool i420_quads_aligned(const mm_handle *h, const uint8_t *in, const uint
     if (nframes > 1) luma |= fr.out.stride, chroma |= fr.in.stride | fr.out.stride;
     return (luma & 3u) == 0 && (chroma & 1u) == 0;
 }
+// The 10-bit three-plane form's quads: four luma codes as one 8-byte store at
+// a dword-aligned address (P010's), the quad's two Cb words and its two Cr
+// words as one dword per plane, loads and stores alike.  So the output's luma
+// rows and every Cb and Cr row of every frame of the launch start on multiples
+// of 4, on both sides (every tight frame with W % 8 == 0, the decoder layout).
+// The unit is 2, so a valid layout of a W % 8 == 0 frame may fail this (a base,
+// a pitch or a plane offset at 2 mod 4): it takes the unfused pair, whose
+// accesses are single words.  This rule speaks of row STARTS alone: that a
+// quad's dword of two chroma words ends inside its row is k34_fits' own
+// W % 8 == 0, which refuses a frame such as 98 x 62 whatever this test says
+// (do not lift that condition on the strength of this test).
+static bool i010_quads_aligned(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+    uintptr_t m = b | fr.out.pitch | (a + fr.in.c_off) | fr.in.c_pitch | i420_cr_delta(h->H, fr.in.c_pitch) |
+                  (b + fr.out.c_off) | fr.out.c_pitch | i420_cr_delta(h->H, fr.out.c_pitch);
+    if (nframes > 1) m |= fr.in.stride | fr.out.stride;
+    return (m & 3u) == 0;
+}
 static bool k34_fits(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
+    if (fmt_i010(fr.fmt) && !i010_quads_aligned(h, in, out, fr, nframes)) return false;
     if (fmt_i420(fr.fmt) && !i420_quads_aligned(h, in, out, fr, nframes)) return false;
     if (fr.mixed()) {   // each side by its own format (P010 in, RGBA8 either side: every layout)
         if (fmt_nv12(fr.fmt) && !nv12_in_aligned(in, fr, nframes)) return false;
@@ -1254,7 +1290,7 @@ static int copy_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, con
     // chroma planes as H/2 "luma" rows (Cb) and H/2 chroma rows (Cr) of a
     // geometry whose planes are the Cb and Cr planes
     Geo gc = g;
-    if (fmt_i420(fr.fmt)) {
+    if (fmt_planes3(fr.fmt)) {
         gc.li.pitch = g.li.c_pitch, gc.li.c_off = (unsigned)i420_cr_delta(h->H, g.li.c_pitch);
         gc.lo.pitch = g.lo.c_pitch, gc.lo.c_off = (unsigned)i420_cr_delta(h->H, g.lo.c_pitch);
     }
@@ -1262,11 +1298,11 @@ static int copy_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, con
         const dim3 grid((unsigned)rows, (unsigned)std::min(32768, n - f0));
         const uint8_t *src = in + fr.in.stride * f0;
         uint8_t *dst = out + fr.out.stride * f0;
-        if (fmt_i420(fr.fmt)) {
+        if (fmt_planes3(fr.fmt)) {   // (in the format's unit: bytes, or the words of the 10-bit form)
             const dim3 gy((unsigned)h->H, grid.y);   // H luma rows; H/2 Cb + H/2 Cr rows
-            hipLaunchKernelGGL((k_copy_rows<uint8_t>), gy, dim3(256), 0, s, src, dst, g, rb, h->H);
-            hipLaunchKernelGGL((k_copy_rows<uint8_t>), gy, dim3(256), 0, s, src + fr.in.c_off, dst + fr.out.c_off, gc,
-                               rb / 2, h->H / 2);
+            const auto copy = fmt_unit(fr.fmt) == 1 ? &k_copy_rows<uint8_t> : &k_copy_rows<uint16_t>;
+            hipLaunchKernelGGL(copy, gy, dim3(256), 0, s, src, dst, g, rb, h->H);
+            hipLaunchKernelGGL(copy, gy, dim3(256), 0, s, src + fr.in.c_off, dst + fr.out.c_off, gc, rb / 2, h->H / 2);
         } else if (fmt_unit(fr.fmt) == 1) hipLaunchKernelGGL((k_copy_rows<uint8_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
         else if (fmt_unit(fr.fmt) == 2) hipLaunchKernelGGL((k_copy_rows<uint16_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
         else hipLaunchKernelGGL((k_copy_rows<uint32_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);

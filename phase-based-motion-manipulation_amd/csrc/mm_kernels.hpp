@@ -515,8 +515,27 @@ template <int FMT> constexpr bool kP010 = FMT == kFmtP010 || FMT == kFmtP010M;
 constexpr int kFmtI420 = 144;   // MM_I420* (every range and matrix)
 constexpr int kFmtI420M = 176;  // K1 only: any matrixed MM_I420*
 template <int FMT> constexpr bool kI420 = FMT == kFmtI420 || FMT == kFmtI420M;
-template <int FMT> constexpr bool k420 = kNV12<FMT> || kP010<FMT> || kI420<FMT>;
-template <int FMT> constexpr bool kMatrixed = FMT == kFmtNV12M || FMT == kFmtP010M || FMT == kFmtI420M;
+// 10-bit three-plane 4:2:0 (MM_I010 = MM_P010 | MM_PLANAR | MM_LOW_BITS): P010's
+// codes with bit 7, in the same roles.  The words hold the code in their LOW 10
+// bits (v = word, not word / 64; neither masked nor clamped on input), Cb and Cr
+// in planes of their own as in I420, the Cr plane c_pitch x H/2 bytes after the
+// Cb plane.  Geo::nv is P010's with the word unit 1 instead of 64 (geo_of): the
+// input-side fields differ by exact powers of two, so (float)word - y_off and
+// (float)word - 512 are P010's values over 64 exactly and every sum downstream
+// scales exactly: a BT.601 frame's K1 is kFmtP010's own instance, and output
+// and state are bitwise the P010 path's on the same codes.  The store side is
+// P010's codes without the << 6.  Alignment: frame base, pitches, offsets and
+// strides are multiples of 2 (mm_surface's unit), so the unfused kernels'
+// accesses are single words; the fused kernels' quads (a dword of two Cb words,
+// a dword of two Cr words, an 8-byte store of four luma words at a
+// dword-aligned address) run only where every row they touch starts on a
+// multiple of 4 (i010_quads_aligned, mm_impl.hpp).
+constexpr int kFmtI010 = 146;   // MM_I010* (every range and matrix)
+constexpr int kFmtI010M = 178;  // K1 only: any matrixed MM_I010*
+template <int FMT> constexpr bool kI010 = FMT == kFmtI010 || FMT == kFmtI010M;
+template <int FMT> constexpr bool kPlanes3 = kI420<FMT> || kI010<FMT>;   // Cb and Cr planes of their own
+template <int FMT> constexpr bool k420 = kNV12<FMT> || kP010<FMT> || kPlanes3<FMT>;
+template <int FMT> constexpr bool kMatrixed = FMT == kFmtNV12M || FMT == kFmtP010M || FMT == kFmtI420M || FMT == kFmtI010M;
 // packed 4:2:2 (section below): kFmtYUY2 runs every BT.601 YUY2 / UYVY frame and
 // every compose, kFmtYUY2M is K1's instance for a matrixed one
 constexpr int kFmtYUY2 = 24;   // MM_YUY2
@@ -581,6 +600,11 @@ template <> struct LumaSrc<kFmtI420> : LumaSrc<kFmtNV12> {};
 template <> struct LumaSrc<kFmtI420M> : LumaSrc<kFmtNV12> {};
 template <> struct ChromaSrc<kFmtI420> : ChromaSrc<kFmtNV12> {};
 template <> struct ChromaSrc<kFmtI420M> : ChromaSrc<kFmtNV12> {};
+// (its 10-bit form: P010's luma words; the pixel's Cb and Cr words put together as P010's pair)
+template <> struct LumaSrc<kFmtI010> : LumaSrc<kFmtP010> {};
+template <> struct LumaSrc<kFmtI010M> : LumaSrc<kFmtP010> {};
+template <> struct ChromaSrc<kFmtI010> : ChromaSrc<kFmtP010> {};
+template <> struct ChromaSrc<kFmtI010M> : ChromaSrc<kFmtP010> {};
 // K1's luma of a raw sample and its unit (folded into the resample weights)
 template <int FMT>
 __device__ __forceinline__ float k1_luma(typename LumaSrc<FMT>::raw_t u, const Geo &g)
@@ -594,6 +618,15 @@ template <int FMT> __device__ __forceinline__ float k1_unit(const Geo &g)
     else if constexpr (kRGB24<FMT>) return kLumaUnit<0>;   // RGBA8's integer luma
     else return kLumaUnit<FMT>;
 }
+// A pair of 16-bit words Cb | Cr << 16 as (cb, cr) about the neutral value:
+// 0x8000 where the code sits in the word's high bits (P010, MM_Y210), 512 where
+// it sits in the low bits (the 10-bit three-plane form; the word is not masked,
+// a word above 1023 is that value).  Exactly (0, 0) for neutral chroma.
+template <int FMT> constexpr float kWordMid = kI010<FMT> ? 512.0f : 32768.0f;
+__device__ __forceinline__ void words_cbcr(unsigned u, float mid, float &cb, float &cr)
+{
+    cb = (float)(u & 0xFFFFu) - mid, cr = (float)(u >> 16) - mid;
+}
 // K1, matrixed frames: what a (Cb, Cr) pair adds to the luma of its 2x2
 // pixels, in k1_luma's units; exactly 0 for neutral chroma.  One expression
 // for the three load forms, so their lumas are bitwise equal.
@@ -601,7 +634,7 @@ template <int FMT>
 __device__ __forceinline__ float k1_chroma(typename ChromaSrc<FMT>::raw_t u, const Geo &g)
 {
     float cb, cr;
-    if constexpr (kP010<FMT>) cb = (float)(u & 0xFFFFu) - 32768.0f, cr = (float)(u >> 16) - 32768.0f;
+    if constexpr (kP010<FMT> || kI010<FMT>) words_cbcr(u, kWordMid<FMT>, cb, cr);
     else if constexpr (k422<FMT>) cb = c422_cb(u, g) - 128.0f, cr = c422_cr(u, g) - 128.0f;
     else cb = (float)(u & 255u) - 128.0f, cr = (float)((unsigned)u >> 8) - 128.0f;
     return fmaf(g.nv.lb, cr, g.nv.la * cb);
@@ -624,11 +657,17 @@ __device__ __forceinline__ unsigned i420_ld_pair(const uint8_t *cb, unsigned off
 {
     return (unsigned)ld_off<uint8_t>(cb, off) | (unsigned)ld_off<uint8_t>(cb, off + cr_delta) << 8;
 }
+// (the 10-bit form: one word of each plane as P010's pair Cb | Cr << 16; off in bytes)
+__device__ __forceinline__ unsigned i010_ld_pair(const uint8_t *cb, unsigned off, unsigned cr_delta)
+{
+    return (unsigned)ld_off<uint16_t>(cb, off) | (unsigned)ld_off<uint16_t>(cb, off + cr_delta) << 16;
+}
 // K1's load of pixel column col's (Cb, Cr) from chroma row crow (k1_crow's)
 template <int FMT>
 __device__ __forceinline__ typename ChromaSrc<FMT>::raw_t k1_cld(const uint8_t *crow, unsigned col, [[maybe_unused]] const Geo &g)
 {
     if constexpr (kI420<FMT>) return (uint16_t)i420_ld_pair(crow, col >> 1, i420_cr_delta(g.li, g));
+    else if constexpr (kI010<FMT>) return i010_ld_pair(crow, col & ~1u, i420_cr_delta(g.li, g));
     else return ld_off<typename ChromaSrc<FMT>::raw_t>(crow, k1_ccol<FMT>(col));
 }
 // byte offset of the (Cb, Cr) pair of source pixel (row, col), both already
@@ -644,12 +683,14 @@ __device__ __forceinline__ c2 nv12_iq2(unsigned u, const Geo &g)
     const float cb = (float)(u & 255u) - 128.0f, cr = (float)((u >> 8) & 255u) - 128.0f;
     return mk(g.nv.icb, g.nv.qcb) * cb + mk(g.nv.icr, g.nv.qcr) * cr;
 }
-// ... and of a pair of 16-bit words: exact zero for neutral chroma (0x8000)
-__device__ __forceinline__ c2 p010_iq2(unsigned u, const Geo &g)
+// ... and of a pair of 16-bit words about `mid` (words_cbcr): exact zero for neutral chroma
+__device__ __forceinline__ c2 word_iq2(unsigned u, float mid, const Geo &g)
 {
-    const float cb = (float)(u & 0xFFFFu) - 32768.0f, cr = (float)(u >> 16) - 32768.0f;
+    float cb, cr;
+    words_cbcr(u, mid, cb, cr);
     return mk(g.nv.icb, g.nv.qcb) * cb + mk(g.nv.icr, g.nv.qcr) * cr;
 }
+__device__ __forceinline__ c2 p010_iq2(unsigned u, const Geo &g) { return word_iq2(u, 32768.0f, g); }
 // an MM_Y210 macropixel (dwords Y0 | Cb << 16, Y1 | Cr << 16): its chroma as
 // P010's word pair Cb | Cr << 16, and its (I, Q)
 __device__ __forceinline__ unsigned y210_cword(uint2 m) { return (m.x >> 16) | (m.y & 0xFFFF0000u); }
@@ -659,17 +700,19 @@ template <int FMT> __device__ __forceinline__ unsigned c420_off(const Geo &g, in
 {
     if constexpr (kP010<FMT>) return g.li.c_off + (unsigned)(row >> 1) * g.li.c_pitch + (col & ~1u) * 2u;
     else if constexpr (kI420<FMT>) return g.li.c_off + (unsigned)(row >> 1) * g.li.c_pitch + (col >> 1);   // (the Cb byte)
+    else if constexpr (kI010<FMT>) return g.li.c_off + (unsigned)(row >> 1) * g.li.c_pitch + (col & ~1u);   // (the Cb word)
     else return nv12_c_off(g, row, col);
 }
 // the (Cb, Cr) pair of source pixel (row, col) as the format's raw pair
 template <int FMT> __device__ __forceinline__ unsigned c420_pair(const uint8_t *img, const Geo &g, int row, unsigned col)
 {
     if constexpr (kI420<FMT>) return i420_ld_pair(img, c420_off<FMT>(g, row, col), i420_cr_delta(g.li, g));
+    else if constexpr (kI010<FMT>) return i010_ld_pair(img, c420_off<FMT>(g, row, col), i420_cr_delta(g.li, g));
     else return ld_off<typename ChromaSrc<FMT>::raw_t>(img, c420_off<FMT>(g, row, col));
 }
 template <int FMT> __device__ __forceinline__ c2 c420_iq2(unsigned u, const Geo &g)
 {
-    if constexpr (kP010<FMT>) return p010_iq2(u, g);
+    if constexpr (kP010<FMT> || kI010<FMT>) return word_iq2(u, kWordMid<FMT>, g);
     else return nv12_iq2(u, g);
 }
 __device__ __forceinline__ c2 rgb24_iq2(uint32_t u, const Geo &g);   // (packed RGB section below)
@@ -778,6 +821,32 @@ __device__ __forceinline__ void i420_store_quad(uint8_t *outp, const Geo &g, int
         __builtin_nontemporal_store((uint16_t)cr2, reinterpret_cast<uint16_t *>(cb + i420_cr_delta(g.lo, g)));
     }
 }
+// Its 10-bit form: p010_store_quad with the codes unshifted (the word's high 6
+// bits zero), the two blocks' Cb codes as one dword store to the Cb plane and
+// their Cr codes as one to the Cr plane (X / 2 words is X bytes, X % 4 == 0;
+// chroma rows on multiples of 4: i010_quads_aligned, mm_impl.hpp).  Same
+// codes, same order of sums.
+__device__ __forceinline__ void i010_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
+                                                const float (&rr)[4], const float (&gg)[4],
+                                                const float (&bb)[4], c2 (&cd0)[4])
+{
+    c2 cd[4];
+    unsigned y[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = nv12_ycode(rr[k], gg[k], bb[k], g, cd[k]);
+    p010_st4(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, y[0] | y[1] << 16, y[2] | y[3] << 16);
+    if (!odd) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) cd0[k] = cd[k];
+    } else {
+        const c2 b0 = (cd0[0] + cd[0]) + (cd0[1] + cd[1]), b1 = (cd0[2] + cd[2]) + (cd0[3] + cd[3]);
+        const unsigned cb2 = p010_ccode(b0.x, g.nv.cbo) | p010_ccode(b1.x, g.nv.cbo) << 16;
+        const unsigned cr2 = p010_ccode(b0.y, g.nv.cro) | p010_ccode(b1.y, g.nv.cro) << 16;
+        uint8_t *cb = outp + (size_t)(g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch);
+        st_stream<uint32_t>(cb, (unsigned)X, cb2);
+        st_stream<uint32_t>(cb + i420_cr_delta(g.lo, g), (unsigned)X, cr2);
+    }
+}
 // the fused kernels' quad store for a 4:2:0 format
 template <int FMT>
 __device__ __forceinline__ void c420_store_quad(uint8_t *outp, const Geo &g, int i, int X, bool odd,
@@ -786,6 +855,7 @@ __device__ __forceinline__ void c420_store_quad(uint8_t *outp, const Geo &g, int
 {
     if constexpr (kP010<FMT>) p010_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
     else if constexpr (kI420<FMT>) i420_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
+    else if constexpr (kI010<FMT>) i010_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
     else nv12_store_quad(outp, g, i, X, odd, rr, gg, bb, cd0);
 }
 // the fused kernels' load of the two (Cb, Cr) pairs of the quad X .. X+3 in
@@ -802,6 +872,11 @@ __device__ __forceinline__ void c420_quad_pairs(const uint8_t *img, const Geo &g
         const unsigned cb2 = ld_off<uint16_t>(img, off), cr2 = ld_off<uint16_t>(img, off + i420_cr_delta(g.li, g));
         p0 = (cb2 & 255u) | (cr2 & 255u) << 8;
         p1 = (cb2 >> 8) | (cr2 >> 8) << 8;
+    } else if constexpr (kI010<FMT>) {   // one dword per plane (chroma rows on multiples of 4, X / 2 words = X bytes)
+        const unsigned off = c420_off<FMT>(g, row, X);
+        const unsigned cb2 = ld_off<uint32_t>(img, off), cr2 = ld_off<uint32_t>(img, off + i420_cr_delta(g.li, g));
+        p0 = (cb2 & 0xFFFFu) | cr2 << 16;
+        p1 = (cb2 >> 16) | (cr2 & 0xFFFF0000u);
     } else {                      // one dword (rows dword aligned: nv12_quads_aligned)
         p0 = ld_off<uint32_t>(img, nv12_c_off(g, row, X));
         p1 = p0 >> 16;
@@ -1253,8 +1328,9 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
     // (MM_Y210's matrixed instance, 8-byte loads, at N = 8192, where 1024
     // threads leave 128 VGPRs: two batches too; one batch spilled 21; the
     // matrixed three-plane instance, two chroma byte loads per pair, the same:
-    // one batch spilled 29)
-    constexpr int UB = BPP == 16 || ((FMT == kFmtY210M || FMT == kFmtI420M) && LOG2N == 13) ? 4 : 8;
+    // one batch spilled 29; its 10-bit form, two chroma word loads per pair:
+    // one batch spilled 27)
+    constexpr int UB = BPP == 16 || ((FMT == kFmtY210M || FMT == kFmtI420M || FMT == kFmtI010M) && LOG2N == 13) ? 4 : 8;
     if constexpr (GEN) {
         if (valid) {
             Tap4 ta = rowT[ra];
@@ -2792,7 +2868,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
     // (packed RGB: the byte-aligned dword of the pixel)
     auto ld_src = [&](int row, unsigned col) {
         if constexpr (kRGB24<FI>) return rgb24_px(img, src_off(row, col), col, g);
-        else if constexpr (kI420<FI>) return (raw_t)c420_pair<FI>(img, g, row, col);   // (a byte of each chroma plane)
+        else if constexpr (kPlanes3<FI>) return (raw_t)c420_pair<FI>(img, g, row, col);   // (a sample of each chroma plane)
         else return ld_off<raw_t>(img, src_off(row, col));
     };
     const unsigned colA = (unsigned)wrap_near(min(c0 - 1 + tid, g.W), g.W, g.edge);
@@ -2861,6 +2937,8 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 const unsigned yc = nv12_ycode(rr, gg, bb, g, cd);
                 if constexpr (kP010<FO>) {   // one 16-bit word per lane (always aligned)
                     st_off<uint16_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X * 2u, (uint16_t)(yc << 6));
+                } else if constexpr (kI010<FO>) {   // (the code in the word's low bits)
+                    st_off<uint16_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X * 2u, (uint16_t)yc);
                 } else {
                     st_off<uint8_t>(outp, (unsigned)i * g.lo.pitch + (unsigned)X, (uint8_t)yc);
                 }
@@ -2876,6 +2954,12 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                         const unsigned cc10 = p010_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
                         st_off<uint16_t>(outp, g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch + (unsigned)X * 2u,
                                          (uint16_t)(cc10 << 6));
+                    } else if constexpr (kI010<FO>) {
+                        // (three planes of words: the even lane's Cb is word X / 2
+                        // of the Cb row, the odd lane's Cr the same word of the Cr row)
+                        const unsigned cc10 = p010_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
+                        const unsigned co = ((unsigned)X & ~1u) + (X & 1 ? i420_cr_delta(g.lo, g) : 0u);
+                        st_off<uint16_t>(outp, g.lo.c_off + (unsigned)(i >> 1) * g.lo.c_pitch + co, (uint16_t)cc10);
                     } else {
                         const unsigned cc8 = nv12_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo);
                         // (three planes: the even lane's Cb is byte X / 2 of the

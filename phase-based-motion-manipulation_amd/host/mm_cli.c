@@ -9,7 +9,7 @@
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
  *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
- *          [--yuy2] [--uyvy] [--y210] [--ppm [--bgr]] [--i420] [--out-rgba8] [--out-nv12]
+ *          [--yuy2] [--uyvy] [--y210] [--ppm [--bgr]] [--i420] [--i010] [--out-rgba8] [--out-nv12]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
@@ -102,6 +102,16 @@
  * other format option (--nv12, --p010, --mono, --yuy2, --uyvy, --y210, --ppm),
  * --out-rgba8, --out-nv12, --srgb, the debug views, the ring modes, a .y4m
  * that is not 4:2:0 or is 10-bit, no input at all, and odd sizes.
+ * --i010: a 10-bit 4:2:0 .y4m input (C420p10) goes to the device as its frames
+ * lie in the file, as MM_I010 frames (MM_I010_FULL with --full-range, a matrix
+ * bit with --matrix): three planes of words with the code in the low 10 bits,
+ * no interleave and no shift on the way in, no split on the way out (a C420p10
+ * .y4m; any other extension on either side: the raw I010 frames, -w/-h).  The
+ * output file is --p010's, byte for byte.  -l, -s, -b, --standard,
+ * --surface-align and --checksum as usual.  Refused with every other format
+ * option (--nv12, --p010, --i420, --mono, --yuy2, --uyvy, --y210, --ppm),
+ * --out-rgba8, --out-nv12, --srgb, the debug views, the ring modes, a .y4m
+ * that is not 10-bit 4:2:0, no input at all, and odd sizes.
  * --surface-align P,R: the device frames, input and output, are held in
  * mm_surface_aligned(W, H, format, P, R) surfaces (256,16: a hardware
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
@@ -499,7 +509,7 @@ int main(int argc, char **argv)
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
     int nv12 = 0, p010 = 0, srgb = 0, mono = 0, yuy2 = 0, uyvy = 0, y210 = 0, ppm = 0, bgr = 0;
-    int out_rgba8 = 0, out_nv12 = 0, i420 = 0;
+    int out_rgba8 = 0, out_nv12 = 0, i420 = 0, i010 = 0;
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
@@ -517,6 +527,7 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--ppm")) { ppm = 1; continue; }
         if (!strcmp(a, "--bgr")) { bgr = 1; continue; }
         if (!strcmp(a, "--i420")) { i420 = 1; continue; }
+        if (!strcmp(a, "--i010")) { i010 = 1; continue; }
         if (!strcmp(a, "--out-rgba8")) { out_rgba8 = 1; continue; }
         if (!strcmp(a, "--out-nv12")) { out_nv12 = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
@@ -548,6 +559,17 @@ int main(int argc, char **argv)
         ++i;
     }
     if (B < 1) B = 1;
+    /* --i010 with another format option: refused before any file is opened */
+    if (i010 && (nv12 || p010 || i420 || mono || yuy2 || uyvy || y210 || ppm || out_rgba8 || out_nv12 || srgb || show_mag ||
+                 show_phase || ring_local > 0 || ring_world > 0)) {
+        fprintf(stderr, "--i010 does not go with --nv12, --p010, --i420, --mono, --yuy2, --uyvy, --y210, --ppm, --out-rgba8, "
+                        "--out-nv12, --srgb, the debug views or the ring modes\n");
+        return 2;
+    }
+    if (i010 && !in_path) {
+        fprintf(stderr, "--i010 needs an input (-i): a 10-bit 4:2:0 .y4m (C420p10) or raw I010 frames\n");
+        return 2;
+    }
     /* --i420 with another format option: refused before any file is opened */
     if (i420 && (nv12 || p010 || mono || yuy2 || uyvy || y210 || ppm || out_rgba8 || out_nv12 || srgb || show_mag ||
                  show_phase || ring_local > 0 || ring_world > 0)) {
@@ -560,8 +582,9 @@ int main(int argc, char **argv)
         return 2;
     }
     FILE *fi = in_path ? fopen(in_path, "rb") : NULL;
-    FILE *fo = out_path && !i420 ? fopen(out_path, "wb") : NULL;
-    if ((in_path && !fi) || (out_path && !fo && !i420)) { fprintf(stderr, "cannot open file\n"); return 1; }
+    const int planes3 = i420 || i010;   /* the file's frames go as they lie; the output opens after the refusals */
+    FILE *fo = out_path && !planes3 ? fopen(out_path, "wb") : NULL;
+    if ((in_path && !fi) || (out_path && !fo && !planes3)) { fprintf(stderr, "cannot open file\n"); return 1; }
     const int y4m_in = in_path && ends_with(in_path, ".y4m");
     const int y4m_out = out_path && ends_with(out_path, ".y4m");
     y4m_info yi = {0};
@@ -590,6 +613,24 @@ int main(int argc, char **argv)
             return 2;
         }
         g_fmt = full_range ? MM_I420_FULL : MM_I420;
+        if (out_path && !(fo = fopen(out_path, "wb"))) { fprintf(stderr, "cannot open file\n"); return 1; }
+    }
+    /* --i010: the frames of a C420p10 .y4m are MM_I010 frames as they lie */
+    if (i010) {
+        if (y4m_in && (yi.chroma != Y4M_420 || depth != 10)) {
+            fprintf(stderr, "--i010 needs a 10-bit 4:2:0 .y4m input (C420p10; an 8-bit C420 stream takes --i420), "
+                            "or raw I010 frames under any other extension\n");
+            return 2;
+        }
+        if ((W | H) & 1) {
+            fprintf(stderr, "--i010 needs even width and height (%dx%d)\n", W, H);
+            return 2;
+        }
+        if (matrix_arg && strcmp(matrix_arg, "601") && strcmp(matrix_arg, "709") && strcmp(matrix_arg, "2020")) {
+            fprintf(stderr, "--matrix takes 601, 709 or 2020, not %s (--i010)\n", matrix_arg);
+            return 2;
+        }
+        g_fmt = full_range ? MM_I010_FULL : MM_I010;
         if (out_path && !(fo = fopen(out_path, "wb"))) { fprintf(stderr, "cannot open file\n"); return 1; }
     }
     /* different formats in and out (mm_process_stream_convert) */
@@ -726,7 +767,7 @@ int main(int argc, char **argv)
             return 2;
         }
         g_fmt = full_range ? MM_P010_FULL : MM_P010;
-    } else if (depth != 8 && !mono && !y210) {
+    } else if (depth != 8 && !mono && !y210 && !i010) {
         if (yi.chroma == Y4M_MONO)
             fprintf(stderr, "%s is a %d-bit mono stream (Cmono%d): it needs --mono\n", in_path, depth, depth);
         else
@@ -751,8 +792,8 @@ int main(int argc, char **argv)
     /* the output side's format: the input's, but with --out-rgba8 / --out-nv12 */
     int o_fmt = out_nv12 ? (full_range ? MM_NV12_FULL : MM_NV12) : 0;
     if (matrix_arg) {
-        if (!nv12 && !p010 && !p422 && !y210 && !out_nv12 && !i420) {
-            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2, --uyvy, --y210, --i420 or --out-nv12 (the RGBA conversion of a .y4m is BT.601)\n");
+        if (!nv12 && !p010 && !p422 && !y210 && !out_nv12 && !planes3) {
+            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2, --uyvy, --y210, --i420, --i010 or --out-nv12 (the RGBA conversion of a .y4m is BT.601)\n");
             return 2;
         }
         /* (--out-nv12: the bit names the output code; the input is RGBA8) */
@@ -769,7 +810,8 @@ int main(int argc, char **argv)
     const int convert = o_fmt != g_fmt;
     /* what the output files hold */
     /* (--i420: a C420 file too, its frames written as they lie) */
-    const int w_nv12 = out_nv12 || (nv12 && !out_rgba8) || i420, w_p010 = p010 && !out_rgba8;
+    /* (--i010: a C420p10 file, the same way) */
+    const int w_nv12 = out_nv12 || (nv12 && !out_rgba8) || i420, w_p010 = (p010 && !out_rgba8) || i010;
     mm_params p;
     mm_params_default(&p);
     p.levels = L;
@@ -814,7 +856,7 @@ int main(int argc, char **argv)
     }
 
     size_t fb = (size_t)W * H * 4;
-    if (nv12 || p010 || mono || p422 || y210 || ppm || i420) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
+    if (nv12 || p010 || mono || p422 || y210 || ppm || planes3) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
     /* --surface-align: the frames the operator sees live in `lay` surfaces
      * (d_in, d_out); d_tin / d_tout are tight device frames for the synthetic
      * source and for the checksums and files */
@@ -832,7 +874,7 @@ int main(int argc, char **argv)
             (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK ||
             (rc = mm_surface_aligned(W, H, o_fmt, (size_t)pa, ra, &olay)) != MM_OK) {
             fprintf(stderr, "--surface-align %s: want P,R with P a multiple of the format's unit "
-                            "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, mono: the sample size, --ppm and --i420: 1; --i420: an even pitch) and R >= 1 (4:2:0: even)\n", surf_arg);
+                            "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, mono: the sample size, --ppm and --i420: 1, --i010: 2; --i420: an even pitch, --i010: a multiple of 4) and R >= 1 (4:2:0: even)\n", surf_arg);
             return 2;
         }
         printf("surfaces: pitch %zu  chroma offset %zu  frame stride %zu\n", lay.pitch, lay.chroma_offset,
@@ -876,11 +918,11 @@ int main(int argc, char **argv)
                 /* (mono: the samples are the frame, read straight into place;
                  * --i420: the three planes are the frame, the same way) */
                 const int r = mono ? y4m_read_frame_mono(fi, W, H, depth, host + fb * got)
-                              : i420 ? y4m_read_frame_depth(fi, &yi, depth, host + fb * got)
+                              : planes3 ? y4m_read_frame_depth(fi, &yi, depth, host + fb * got)
                                      : y4m_read_frame_depth(fi, &yi, depth, planes);
                 if (r < 0) { fprintf(stderr, "%s: malformed frame\n", in_path); return 1; }
                 if (r == 0) break;
-                if (mono || i420) continue;
+                if (mono || planes3) continue;
                 if (p010) y4m_420p10_to_p010(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
                 else if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
                 else if (p422) y4m_422_to_packed(W, H, planes, host + fb * got, uyvy);
@@ -951,6 +993,13 @@ int main(int argc, char **argv)
                     }
                     if (i420) {   /* the frame is the file's three planes */
                         if (y4m_write_frame_420(fo, W, H, host + fb * k)) {
+                            fprintf(stderr, "write failed\n");
+                            return 1;
+                        }
+                        continue;
+                    }
+                    if (i010) {   /* ... its three planes of words */
+                        if (y4m_write_frame_420p10(fo, W, H, (const uint16_t *)(host + fb * k))) {
                             fprintf(stderr, "write failed\n");
                             return 1;
                         }

@@ -21,6 +21,7 @@ from .binding import (MMError, lib, load_library, LIB_PATH, RGBA8, RGBA32F, RGBA
                       Y8, Y10, Y12, Y16, MONO_FORMATS, MONO_BITS,
                       RGB24, BGR24, ORDER_BGR, RGB24_FORMATS,
                       I420, I420_FULL, PLANAR, I420_FORMATS,
+                      I010, I010_FULL, LOW_BITS, I010_FORMATS,
                       YUY2, YUY2_FULL, UYVY, UYVY_FULL, PACKED422_FORMATS,
                       Y210, Y210_FULL, Y210_FORMATS,
                       nv12_chroma_matrix, ycbcr_matrix, base_format,
@@ -36,6 +37,7 @@ __all__ = ["MMError", "lib", "load_library", "LIB_PATH", "RGBA8", "RGBA32F", "RG
            "Y8", "Y10", "Y12", "Y16", "MONO_FORMATS", "MONO_BITS",
            "RGB24", "BGR24", "ORDER_BGR", "RGB24_FORMATS",
            "I420", "I420_FULL", "PLANAR", "I420_FORMATS",
+           "I010", "I010_FULL", "LOW_BITS", "I010_FORMATS",
            "YUY2", "YUY2_FULL", "UYVY", "UYVY_FULL", "PACKED422_FORMATS",
            "Y210", "Y210_FULL", "Y210_FORMATS",
            "MATRIX_BT709", "MATRIX_BT2020", "nv12_chroma_matrix", "ycbcr_matrix", "base_format",

@@ -60,6 +60,14 @@ PLANAR = 512        # plane-layout bit: Cb and Cr in planes of their own
 I420 = NV12 | PLANAR            # 528, BT.601 limited range
 I420_FULL = NV12_FULL | PLANAR  # 529, full range
 I420_FORMATS = (I420, I420_FULL)
+# 10-bit three-plane 4:2:0 (I010, ffmpeg's yuv420p10le, a C420p10 .y4m's frames): the
+# same three planes in little-endian 16-bit words with the code in the word's LOW 10
+# bits, P010's codes and semantics; frame_bytes() gives W*H*3.  The low-bits bit is
+# valid only together with the plane bit on the two P010 codes
+LOW_BITS = 1024     # word-alignment bit: the code in the word's low bits
+I010 = P010 | PLANAR | LOW_BITS            # 1554, BT.601 limited range
+I010_FULL = P010_FULL | PLANAR | LOW_BITS  # 1555, full range
+I010_FORMATS = (I010, I010_FULL)
 # one matrix bit, OR-ed onto a 4:2:0 or packed 4:2:2 code above (HD / UHD content): the layout
 # and sizes stay the base code's (base_format)
 MATRIX_BT709 = 32   # Kr 0.2126, Kb 0.0722
@@ -332,7 +340,8 @@ def nv12_chroma_matrix():
 def base_format(fmt):
     """The format without its matrix bit, and BGR24 without its byte-order bit:
     what decides a frame's size and shape.  (The plane-layout bit stays: I420
-    and NV12 frames have the same size and not the same shape of planes.)"""
+    and NV12 frames have the same size and not the same shape of planes; so
+    does the low-bits bit of I010.)"""
     if fmt == BGR24:
         return RGB24
     return fmt & ~(MATRIX_BT709 | MATRIX_BT2020)

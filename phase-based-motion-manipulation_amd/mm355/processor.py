@@ -8,7 +8,7 @@ import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       MONO_FORMATS, NV12, NV12_FULL, P010, P010_FULL, PACKED422_FORMATS, RGBA8, RGBA8_SRGB, RGBA16F,
-                      I420_FORMATS, RGB24_FORMATS, RGBA32F, Y8, Y210_FORMATS,
+                      I010_FORMATS, I420_FORMATS, RGB24_FORMATS, RGBA32F, Y8, Y210_FORMATS,
                       Handle, MMError, Params, Surface, base_format, convert_supported)
 
 
@@ -80,6 +80,12 @@ def frame_layout(frame, width, height, fmt):
         if tuple(frame.shape) != (height * 3 // 2, width) or not str(frame.dtype).endswith("uint8"):
             raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height * 3 // 2, width)} uint8)")
         if strides != (width, 1):
+            raise MMError(-1, "a three-plane 4:2:0 frame must be contiguous (name a Surface through Handle.process_surface)")
+        return None
+    if base_format(fmt) in I010_FORMATS:   # the frame's words in P010's shape: one contiguous [H * 3 / 2, W] array
+        if tuple(frame.shape) != (height * 3 // 2, width) or not str(frame.dtype).endswith("uint16"):
+            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height * 3 // 2, width)} uint16)")
+        if strides != (2 * width, 2):
             raise MMError(-1, "a three-plane 4:2:0 frame must be contiguous (name a Surface through Handle.process_surface)")
         return None
     if fmt in MONO_FORMATS:   # [H, W] samples: uint8 (Y8) or uint16
@@ -226,6 +232,9 @@ class MotionMagnificationProcessor:
         fmt=I420 / I420_FULL, with or without a matrix bit: three-plane 4:2:0,
         one contiguous [H * 3 / 2, W] uint8 array on both sides (the frame's
         bytes in NV12's shape: H luma rows, then the Cb plane, then the Cr plane).
+        fmt=I010 / I010_FULL, with or without a matrix bit: its 10-bit form,
+        one contiguous [H * 3 / 2, W] uint16 array on both sides (the words as
+        they lie, the code in the low 10 bits).
         dst_fmt (None, or equal to fmt: the above): the destination's format
         where it differs from the source's (mm355.convert_supported): fmt=NV12 /
         P010 codes with dst_fmt=RGBA8, the source one contiguous [H * 3 / 2, W]
@@ -261,7 +270,7 @@ class MotionMagnificationProcessor:
                 raise MMError(-1, "source/destination formats differ")
         elif (fmt not in MONO_FORMATS and base_format(fmt) not in PACKED422_FORMATS and
               base_format(fmt) not in Y210_FORMATS and fmt not in RGB24_FORMATS and
-              base_format(fmt) not in I420_FORMATS):
+              base_format(fmt) not in I420_FORMATS and base_format(fmt) not in I010_FORMATS):
             raise MMError(-1, f"fmt={fmt}: only the grayscale, packed 4:2:2, packed RGB and three-plane 4:2:0 formats are named, "
                               "the others follow the dtype")
         on_dev = _is_device(source)
@@ -308,7 +317,7 @@ def host_frames(n, h, w, fmt):
     fmt = base_format(fmt)          # a matrix bit changes no size or shape
     if fmt in (NV12, NV12_FULL) or fmt in I420_FORMATS:    # h luma rows, then h/2 rows of chroma bytes (one or two planes)
         return np.zeros((n, h * 3 // 2, w), np.uint8)
-    if fmt in (P010, P010_FULL):    # the same rows in 16-bit words (10-bit code << 6)
+    if fmt in (P010, P010_FULL) or fmt in I010_FORMATS:    # the same rows in 16-bit words (10-bit code << 6, or in the low bits)
         return np.zeros((n, h * 3 // 2, w), np.uint16)
     if fmt in PACKED422_FORMATS:    # one plane, h rows of w / 2 four-byte macropixels
         return np.zeros((n, h, 2 * w), np.uint8)

@@ -55,6 +55,14 @@ frames in mm_surface_aligned(256, 16) surfaces; the same 1.5 bytes per pixel
 each way, so NV12 of the same run is the comparison.  A library from before
 this format runs without them.
 
+10-bit three-plane 4:2:0 legs (i010, i010_bt709, i010_pitched): the P010 legs'
+own codes, shifted to the words' low bits and de-interleaved, as MM_I010, the
+same words taken as MM_I010 | MM_MATRIX_BT709 (K1's matrixed instance: two word
+loads where P010's takes one pair; p010_bt709 runs beside it), and the I010
+frames in mm_surface_aligned(256, 16) surfaces; the same 3 bytes per pixel each
+way, so P010 of the same run is the comparison, and I420 the 8-bit one.  A
+library from before this format runs without them.
+
 Convert legs (nv12>rgba8, nv12_bt709>rgba8, p010>rgba8, rgba8>nv12,
 rgba8>nv12_bt709, and their _pitched forms): the NV12 / P010 / RGBA8 legs' own
 frames in as the one format and out as the other through
@@ -176,17 +184,19 @@ def nv12_to_i420(torch, nv):
 
 
 def to_surface_i420(torch, src, lay, W, H):
-    """Tight I420 frames (device) -> one uint8 buffer holding them in layout `lay`
-    (padding zero): the Cr plane chroma_pitch x H/2 after the Cb plane."""
+    """Tight I420 or I010 frames (device) -> one uint8 buffer holding them in
+    layout `lay` (padding zero): the Cr plane chroma_pitch x H/2 after the Cb
+    plane.  (Rows in bytes: W samples of the frames' item size.)"""
     n = src.shape[0]
-    flat = src.contiguous().reshape(n, -1)
+    rb = W * src.element_size()
+    flat = src.contiguous().view(torch.uint8).reshape(n, -1)
     buf = torch.zeros(n * lay.frame_stride, dtype=torch.uint8, device=src.device)
-    buf.as_strided((n, H, W), (lay.frame_stride, lay.pitch, 1)).copy_(flat[:, :W * H].reshape(n, H, W))
-    q = W * H // 4
+    buf.as_strided((n, H, rb), (lay.frame_stride, lay.pitch, 1)).copy_(flat[:, :rb * H].reshape(n, H, rb))
+    q = rb * H // 4
     for j in range(2):
-        buf.as_strided((n, H // 2, W // 2), (lay.frame_stride, lay.chroma_pitch, 1),
+        buf.as_strided((n, H // 2, rb // 2), (lay.frame_stride, lay.chroma_pitch, 1),
                        lay.chroma_offset + j * lay.chroma_pitch * (H // 2)).copy_(
-            flat[:, W * H + j * q:W * H + (j + 1) * q].reshape(n, H // 2, W // 2))
+            flat[:, rb * H + j * q:rb * H + (j + 1) * q].reshape(n, H // 2, rb // 2))
     return buf
 
 
@@ -240,6 +250,12 @@ def main():
         fmts += [("i420", mm355.I420), ("i420_bt709", mm355.I420 | mm355.MATRIX_BT709)]
     except (mm355.MMError, AttributeError):
         pass    # a build from before the three-plane 4:2:0 format
+    try:
+        mm355.frame_bytes(W, H, mm355.I010)
+        fmts += [("p010_bt709", mm355.P010 | mm355.MATRIX_BT709), ("i010", mm355.I010),
+                 ("i010_bt709", mm355.I010 | mm355.MATRIX_BT709)]
+    except (mm355.MMError, AttributeError):
+        pass    # a build from before the 10-bit three-plane format
     for name, fmt in fmts:
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
@@ -247,10 +263,13 @@ def main():
             h.synth(rgba, 0, B, stream=torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
             src = rgba
-        elif name in ("nv12_bt709", "p010_bt2020", "yuy2_bt709", "y210_bt709", "i420_bt709"):
+        elif name in ("nv12_bt709", "p010_bt2020", "p010_bt709", "yuy2_bt709", "y210_bt709", "i420_bt709", "i010_bt709"):
             src = legs[name.split("_")[0]]["src"]
         elif name == "i420":       # the NV12 leg's bytes, de-interleaved
             src = nv12_to_i420(torch, legs["nv12"]["src"])
+        elif name == "i010":       # the P010 leg's codes in the words' low bits, de-interleaved
+            words = ((legs["p010"]["src"].to(torch.int32) & 0xFFFF) >> 6).to(torch.int16)
+            src = nv12_to_i420(torch, words)
         elif name == "rgb24":      # the RGBA8 leg's pictures without their alpha
             src = rgba[..., :3].contiguous()
         elif name == "bgr24":
@@ -267,11 +286,11 @@ def main():
             src = to_420(torch, rgba, ten_bit=name == "p010")
         legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[], lay=None,
                           bytes_per_frame=mm355.frame_bytes(W, H, fmt))
-        if not a.no_pitched and mm355.has_surfaces() and name not in ("bgr24", "i420_bt709"):   # (one pitched packed RGB leg, one three-plane)
+        if not a.no_pitched and mm355.has_surfaces() and name not in ("bgr24", "i420_bt709", "p010_bt709", "i010_bt709"):   # (one pitched packed RGB leg, one of each three-plane form)
             lay = mm355.Surface.aligned(W, H, fmt, 256, 16)
             h = mm355.Handle(W, H, p)
             h.set_batch(B)
-            buf = (to_surface_i420(torch, src, lay, W, H) if name == "i420" else
+            buf = (to_surface_i420(torch, src, lay, W, H) if name in ("i420", "i010") else
                    to_surface(torch, src, lay, W, H, name.startswith(("nv12", "p010"))))
             legs[name + "_pitched"] = dict(h=h, fmt=fmt, src=buf, dst=torch.zeros_like(buf), fps=[], lay=lay,
                                            bytes_per_frame=lay.frame_stride)
@@ -407,8 +426,18 @@ def main():
         out["i420_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
                                  for n in ("i420", "nv12", "i420_bt709", "nv12_bt709", "i420_pitched", "nv12_pitched")
                                  if n in out["formats"]}
+    if "i010" in out["formats"]:
+        ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
+        for name, base in (("i010", "p010"), ("i010", "i420"), ("i010_bt709", "p010_bt709"),
+                           ("i010_pitched", "p010_pitched")):
+            if name in out["formats"] and base in out["formats"]:
+                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                    out["formats"][base]["fps_median"], 4)
+        out["i010_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
+                                 for n in ("i010", "p010", "i420", "i010_bt709", "p010_bt709", "i010_pitched",
+                                           "p010_pitched") if n in out["formats"]}
     for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16", "yuy2", "uyvy", "yuy2_bt709",
-                 "y210", "y210_bt709", "rgb24", "i420"):
+                 "y210", "y210_bt709", "rgb24", "i420", "i010"):
         if name + "_pitched" in out["formats"]:
             out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
                                                       out["formats"][name]["fps_median"], 4)
