@@ -387,9 +387,9 @@ int mm_padded_size(const mm_handle *h, int *n)
 
 int mm_frame_bytes(int width, int height, int format, size_t *bytes)
 {
-    if (!bytes || width < 1 || height < 1 || !fmt_valid(format)) return MM_ERR_INVALID;
+    if (!bytes || width < 1 || height < 1) return MM_ERR_INVALID;
     if (int rc = fmt_check(width, height, format, nullptr)) return rc;   // NV12: even sizes
-    *bytes = fmt_frame_bytes(width, height, format);
+    *bytes = fmt_info(format)->frame_bytes(width, height);
     return MM_OK;
 }
 
@@ -402,7 +402,8 @@ int mm_nv12_chroma_matrix(double m[4])
 
 int mm_ycbcr_matrix(int format, double m[6])
 {
-    if (!m || !fmt_valid(format) || !fmt_ycc(format)) return MM_ERR_INVALID;
+    const FmtInfo *f = fmt_info(format);
+    if (!m || !f || !f->ycc()) return MM_ERR_INVALID;
     ycbcr_matrix(format, m);
     return MM_OK;
 }
@@ -436,8 +437,8 @@ int mm_surface_aligned(int width, int height, int format, size_t pitch_align, in
     mm_surface t;
     if (!s || pitch_align < 1 || rows_align < 1) return MM_ERR_INVALID;
     if (int rc = surf_tight(width, height, format, &t)) return rc;
-    const size_t u = fmt_unit(format);
-    if (pitch_align % u || (fmt_420(format) && (rows_align & 1))) return MM_ERR_INVALID;
+    const FmtInfo &f = *fmt_info(format);
+    if (pitch_align % f.unit || (f.planes > 1 && (rows_align & 1))) return MM_ERR_INVALID;
     size_t pitch, rows, planes;
     if (__builtin_add_overflow(t.pitch, pitch_align - 1, &pitch) ||
         __builtin_add_overflow((size_t)height, (size_t)rows_align - 1, &rows))
@@ -447,12 +448,12 @@ int mm_surface_aligned(int width, int height, int format, size_t pitch_align, in
     if (__builtin_mul_overflow(pitch, rows, &planes)) return MM_ERR_INVALID;
     t.pitch = pitch;
     t.frame_stride = planes;
-    if (fmt_420(format)) {
+    if (f.planes > 1) {
         t.chroma_offset = planes;
-        // (three-plane: Cb and Cr rows of half the luma pitch, which is then even)
-        // (its 10-bit form: half the luma pitch is whole words)
-        if ((fmt_i420(format) && (pitch & 1)) || (fmt_i010(format) && (pitch & 3))) return MM_ERR_INVALID;
-        t.chroma_pitch = fmt_planes3(format) ? pitch / 2 : pitch;
+        // (three-plane: Cb and Cr rows of half the luma pitch, which is then
+        // whole units: even, or, the 10-bit form, whole words)
+        if (pitch % ((size_t)f.c_row_div * f.unit)) return MM_ERR_INVALID;
+        t.chroma_pitch = pitch / f.c_row_div;
         if (__builtin_add_overflow(planes, planes / 2, &t.frame_stride)) return MM_ERR_INVALID;
     }
     if (int rc = surf_check(width, height, &t, nullptr)) return rc;
@@ -554,8 +555,7 @@ static int process_surface(mm_handle *h, const void *in, const mm_surface *in_la
     (void)surf_tight(h->W, h->H, format, &t);
     (void)surf_tight(h->W, h->H, oformat, &to);
     const Frames fr = frames_of(h->W, h->H, t, to);
-    const size_t fbo = fmt_frame_bytes(h->W, h->H, oformat), rbo = to.pitch, lumao = rbo * (size_t)h->H;
-    const size_t fb = std::max(fr.fb, fbo), rb = t.pitch, luma = rb * (size_t)h->H;
+    const size_t fbo = to.frame_stride, fb = std::max(fr.fb, fbo);
     DEVICE_SCOPE(h);
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     int ro = order_after_last(h, s);
@@ -569,38 +569,30 @@ static int process_surface(mm_handle *h, const void *in, const mm_surface *in_la
             return MM_ERR_OOM;
         h->stage_bytes = fb;
     }
-    // (a chroma row: W / 2 bytes in each of the two planes of a three-plane frame)
-    const size_t rc_in = t.chroma_pitch, rc_out = to.chroma_pitch, hc = (size_t)(h->H / 2);
-    const bool in_tight = in_layout->pitch == rb && (!fmt_420(format) || (in_layout->chroma_offset == luma &&
-                                                                          in_layout->chroma_pitch == rc_in));
-    const bool out_tight = out_layout->pitch == rbo && (!fmt_420(oformat) || (out_layout->chroma_offset == lumao &&
-                                                                              out_layout->chroma_pitch == rc_out));
-    if (in_tight) {
+    // plane by plane; a frame that lies tight already in one copy
+    Plane pi[3], pt[3], po[3], pto[3];
+    const int npi = surf_planes(h->W, h->H, *in_layout, pi), npo = surf_planes(h->W, h->H, *out_layout, po);
+    (void)surf_planes(h->W, h->H, t, pt);
+    (void)surf_planes(h->W, h->H, to, pto);
+    auto tight = [](const mm_surface &l, const mm_surface &tl) {
+        return l.pitch == tl.pitch && l.chroma_offset == tl.chroma_offset && l.chroma_pitch == tl.chroma_pitch;
+    };
+    if (tight(*in_layout, t)) {
         HIPCHK(hipMemcpyAsync(h->d_stage_in, in, fr.fb, hipMemcpyHostToDevice, s));
     } else {
-        HIPCHK(stage_plane(h->d_stage_in, rb, in, in_layout->pitch, rb, h->H, hipMemcpyHostToDevice, s));
-        if (fmt_420(format))
-            HIPCHK(stage_plane(h->d_stage_in + luma, rc_in, (const uint8_t *)in + in_layout->chroma_offset,
-                               in_layout->chroma_pitch, rc_in, hc, hipMemcpyHostToDevice, s));
-        if (fmt_planes3(format))   // the Cr plane, chroma_pitch x H/2 after the Cb plane
-            HIPCHK(stage_plane(h->d_stage_in + luma + rc_in * hc, rc_in,
-                               (const uint8_t *)in + in_layout->chroma_offset + i420_cr_delta(h->H, in_layout->chroma_pitch),
-                               in_layout->chroma_pitch, rc_in, hc, hipMemcpyHostToDevice, s));
+        for (int k = 0; k < npi; ++k)
+            HIPCHK(stage_plane(h->d_stage_in + pt[k].offset, pt[k].pitch, (const uint8_t *)in + pi[k].offset, pi[k].pitch,
+                               pt[k].row_bytes, pt[k].rows, hipMemcpyHostToDevice, s));
     }
     rc = do_stream(h, h->d_stage_in, h->d_stage_out, 1, fr, s);
     const int rn = note_work(h, s);
     if (rc || (rc = rn)) return rc;
-    if (out_tight) {
+    if (tight(*out_layout, to)) {
         HIPCHK(hipMemcpyAsync(out, h->d_stage_out, fbo, hipMemcpyDeviceToHost, s));
     } else {
-        HIPCHK(stage_plane(out, out_layout->pitch, h->d_stage_out, rbo, rbo, h->H, hipMemcpyDeviceToHost, s));
-        if (fmt_420(oformat))
-            HIPCHK(stage_plane((uint8_t *)out + out_layout->chroma_offset, out_layout->chroma_pitch,
-                               h->d_stage_out + lumao, rc_out, rc_out, hc, hipMemcpyDeviceToHost, s));
-        if (fmt_planes3(oformat))
-            HIPCHK(stage_plane((uint8_t *)out + out_layout->chroma_offset + i420_cr_delta(h->H, out_layout->chroma_pitch),
-                               out_layout->chroma_pitch, h->d_stage_out + lumao + rc_out * hc, rc_out, rc_out, hc,
-                               hipMemcpyDeviceToHost, s));
+        for (int k = 0; k < npo; ++k)
+            HIPCHK(stage_plane((uint8_t *)out + po[k].offset, po[k].pitch, h->d_stage_out + pto[k].offset, pto[k].pitch,
+                               pto[k].row_bytes, pto[k].rows, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
     return MM_OK;

@@ -200,110 +200,38 @@ struct ProfScope {
     }
 };
 
-// Bytes per pixel of a frame format (include/mm.h); the kernels' FMT template
-// argument is the format code itself (Pix<FMT>, mm_kernels.hpp).
-static inline size_t fmt_bpp(int fmt)
-{
-    return fmt == MM_RGBA32F ? 16 : fmt == MM_RGBA16F ? 8 : fmt == MM_Y8 ? 1 : fmt >= MM_Y10 && fmt <= MM_Y16 ? 2 :
-           fmt == MM_RGB24 || fmt == MM_BGR24 ? 3 : 4;
-}
-static constexpr int kMatrixBits = MM_MATRIX_BT709 | MM_MATRIX_BT2020;
-// A 4:2:0 or packed 4:2:2 code may carry one matrix bit (MM_MATRIX_BT709 /
-// MM_MATRIX_BT2020): layout, sizes and units are its base code's, the bit
-// changes coefficients (geo_of) and K1's instance (MM_FMT_SWITCH_K1).
-// The byte-order bit MM_ORDER_BGR is valid on MM_RGB24 alone (MM_BGR24): the
-// base code of both is MM_RGB24, the bit sets the order uniforms (geo_of).  On
-// any other code the bit stays in the base, which is then no format.
-static inline int fmt_base(int fmt) { return fmt == MM_BGR24 ? MM_RGB24 : fmt & ~kMatrixBits; }
-// packed RGB: three bytes per pixel, R G B or B G R
-static inline bool fmt_rgb24(int fmt) { return fmt == MM_RGB24 || fmt == MM_BGR24; }
-static inline int fmt_matrix(int fmt) { return fmt & kMatrixBits; }
-static inline bool fmt_nv12(int fmt) { return fmt_base(fmt) == MM_NV12 || fmt_base(fmt) == MM_NV12_FULL; }
-static inline bool fmt_p010(int fmt) { return fmt_base(fmt) == MM_P010 || fmt_base(fmt) == MM_P010_FULL; }
-// three-plane 8-bit 4:2:0 (MM_I420 = MM_NV12 | MM_PLANAR): NV12's samples, Cb and
-// Cr in planes of their own.  The plane-layout bit is valid on the two NV12
-// codes alone and stays in the base: on any other code the base is no format.
-static inline bool fmt_i420(int fmt) { return fmt_base(fmt) == MM_I420 || fmt_base(fmt) == MM_I420_FULL; }
-// three-plane 10-bit 4:2:0 (MM_I010 = MM_P010 | MM_PLANAR | MM_LOW_BITS): P010's
-// codes in the words' low bits, Cb and Cr in planes of their own.  The low-bits
-// bit is valid together with the plane bit on the two P010 codes alone; both
-// stay in the base: on any other code, or one without the other, the base is no format.
-static inline bool fmt_i010(int fmt) { return fmt_base(fmt) == MM_I010 || fmt_base(fmt) == MM_I010_FULL; }
-static inline bool fmt_planes3(int fmt) { return fmt_i420(fmt) || fmt_i010(fmt); }   // Cb and Cr planes of their own
-static inline bool fmt_420(int fmt) { return fmt_nv12(fmt) || fmt_p010(fmt) || fmt_planes3(fmt); }   // planar, not Pix<FMT>
-// packed 8-bit 4:2:2: one plane of four-byte macropixels (YUY2 / UYVY byte order)
-static inline bool fmt_422(int fmt) { return fmt_base(fmt) >= MM_YUY2 && fmt_base(fmt) <= MM_UYVY_FULL; }
-static inline bool fmt_uyvy(int fmt) { return fmt_base(fmt) == MM_UYVY || fmt_base(fmt) == MM_UYVY_FULL; }
-// packed 10-bit 4:2:2: one plane of eight-byte macropixels, words Y0 Cb Y1 Cr (P010's words)
-static inline bool fmt_y210(int fmt) { return fmt_base(fmt) == MM_Y210 || fmt_base(fmt) == MM_Y210_FULL; }
-static inline bool fmt_ycc(int fmt) { return fmt_420(fmt) || fmt_422(fmt) || fmt_y210(fmt); }   // Y'CbCr: takes a matrix bit
-static inline bool fmt_full(int fmt)
-{
-    const int b = fmt_base(fmt);
-    return b == MM_NV12_FULL || b == MM_P010_FULL || b == MM_YUY2_FULL || b == MM_UYVY_FULL || b == MM_Y210_FULL ||
-           b == MM_I420_FULL || b == MM_I010_FULL;
-}
-// single-plane grayscale: one sample per pixel, a byte (MM_Y8) or a 16-bit word
-static inline bool fmt_mono(int fmt) { return fmt >= MM_Y8 && fmt <= MM_Y16; }
-static inline int mono_max(int fmt) { return fmt == MM_Y8 ? 255 : fmt == MM_Y10 ? 1023 : fmt == MM_Y12 ? 4095 : 65535; }
-static inline bool fmt_valid(int fmt)
-{
-    if (fmt_mono(fmt)) return true;   // (a matrix bit on these codes: no 4:2:0 base, invalid below)
-    if (fmt_rgb24(fmt)) return true;  // (the two exact codes: 14, a matrix bit, the order bit elsewhere stay invalid)
-    if (fmt == MM_RGBA8 || fmt == MM_RGBA32F || fmt == MM_RGBA16F || fmt == MM_RGBA8_SRGB) return true;
-    // (any other bit, a negative code included, leaves a base that is no 4:2:0 code)
-    return fmt_ycc(fmt) && fmt_matrix(fmt) != kMatrixBits;
-}
-// Bytes of one W x H frame (the planar 4:2:0 formats: W H luma samples and half
-// as many chroma samples, of 1 byte (NV12) or 2 (P010); W and H even, fmt_check).
-static inline size_t fmt_frame_bytes(int W, int H, int fmt)
-{
-    const size_t px = (size_t)W * (size_t)H;
-    // (MM_Y210: 4 bytes per pixel, fmt_bpp's default)
-    return fmt_p010(fmt) || fmt_i010(fmt) ? 3 * px : fmt_nv12(fmt) || fmt_i420(fmt) ? px + px / 2 : fmt_422(fmt) ? 2 * px : px * fmt_bpp(fmt);
-}
+// The formats: one row each in mm_format.hpp (fmt_info; null: no format).  A
+// 4:2:0 or packed 4:2:2 code may carry one matrix bit (MM_MATRIX_BT709 /
+// MM_MATRIX_BT2020): layout, sizes and units are its row's, the bit changes
+// coefficients (geo_of) and K1's instance (MM_FMT_SWITCH_K1).
+#include "mm_format.hpp"
 // What every frame entry point asks of (format, geometry, parameters) before
-// it queues anything.  NV12 and P010 are 4:2:0: even sizes only; the debug
-// views are R-channel pictures, which they cannot hold.  (The single-plane
-// formats hold them, and have no subsampling: every size, every view.)
+// it queues anything.  The Y'CbCr formats are subsampled: even sizes only
+// (4:2:2: even H too, include/mm.h); the debug views are R-channel pictures,
+// which they cannot hold.  (The single-plane formats hold them, and have no
+// subsampling: every size, every view.)
 static inline int fmt_check(int W, int H, int fmt, const mm_params *p)
 {
-    if (!fmt_valid(fmt)) return MM_ERR_INVALID;
-    if (fmt_ycc(fmt) && ((W | H) & 1)) return MM_ERR_UNSUPPORTED;   // (4:2:2: even H too, include/mm.h)
-    if (fmt_ycc(fmt) && p && (p->show_magnitude || p->show_phase)) return MM_ERR_UNSUPPORTED;
+    const FmtInfo *f = fmt_info(fmt);
+    if (!f) return MM_ERR_INVALID;
+    if (f->ycc() && ((W | H) & 1)) return MM_ERR_UNSUPPORTED;
+    if (f->ycc() && p && (p->show_magnitude || p->show_phase)) return MM_ERR_UNSUPPORTED;
     return MM_OK;
 }
 // ---- surfaces (mm_surface, include/mm.h) ----------------------------------
-// u: what pitches, offsets, strides and frame pointers are multiples of
-// (the single-plane formats: their sample, 1 or 2 bytes)
-// (packed 4:2:2: one macropixel, 4 bytes or, MM_Y210, 8)
-static inline size_t fmt_unit(int fmt)
-{
-    // (packed RGB: 1, a real [H, W, 3] array or a region of one starts at any byte)
-    // (three-plane 4:2:0: 1, chroma rows of W / 2 bytes start at any byte; its
-    // 10-bit form: 2, one word)
-    return fmt_nv12(fmt) || fmt_i010(fmt) ? 2 : fmt_p010(fmt) || fmt_422(fmt) ? 4 : fmt_y210(fmt) ? 8 :
-           fmt_rgb24(fmt) || fmt_i420(fmt) ? 1 : fmt_bpp(fmt);
-}
-// sample bytes of one row (4:2:0: of a luma row and of a (Cb, Cr) row alike;
-// MM_Y210: 4 W, fmt_bpp's default; three-plane 4:2:0: of a luma row, a Cb or
-// Cr row has half as many)
-static inline size_t fmt_row_bytes(int W, int fmt)
-{
-    return (size_t)W * (fmt_p010(fmt) || fmt_422(fmt) || fmt_i010(fmt) ? 2 : fmt_nv12(fmt) || fmt_i420(fmt) ? 1 : fmt_bpp(fmt));
-}
 // Three-plane 4:2:0: the Cr plane's offset from the Cb plane (include/mm.h:
 // derived, mm_surface has one chroma offset)
 static inline size_t i420_cr_delta(int H, size_t chroma_pitch) { return chroma_pitch * (size_t)(H / 2); }
 static inline int surf_tight(int W, int H, int fmt, mm_surface *s)
 {
-    if (!s || W < 1 || H < 1 || !fmt_valid(fmt)) return MM_ERR_INVALID;
+    if (!s || W < 1 || H < 1) return MM_ERR_INVALID;
     if (int rc = fmt_check(W, H, fmt, nullptr)) return rc;
+    const FmtInfo &f = *fmt_info(fmt);
     s->format = fmt;
-    s->pitch = fmt_row_bytes(W, fmt);
-    s->chroma_offset = fmt_420(fmt) ? s->pitch * (size_t)H : 0;
-    s->chroma_pitch = fmt_planes3(fmt) ? s->pitch / 2 : fmt_420(fmt) ? s->pitch : 0;
-    s->frame_stride = fmt_frame_bytes(W, H, fmt);
+    s->pitch = f.row_bytes(W);
+    s->chroma_offset = f.planes > 1 ? s->pitch * (size_t)H : 0;
+    s->chroma_pitch = f.planes > 1 ? f.chroma_row_bytes(W) : 0;
+    s->frame_stride = f.frame_bytes(W, H);
     return MM_OK;
 }
 // The largest extent the kernels' 32-bit byte offsets from a frame's base
@@ -312,34 +240,19 @@ static constexpr unsigned long long kSurfMaxExtent = 1ull << 32;
 // mm_surface_bytes: the layout's validation and its extent (host only)
 static inline int surf_check(int W, int H, const mm_surface *s, size_t *extent)
 {
-    if (!s || W < 1 || H < 1 || !fmt_valid(s->format)) return MM_ERR_INVALID;
-    const int fmt = s->format;
-    if (int rc = fmt_check(W, H, fmt, nullptr)) return rc;
-    const size_t u = fmt_unit(fmt), rb = fmt_row_bytes(W, fmt);
-    if (s->pitch < rb || s->pitch % u) return MM_ERR_INVALID;
-    size_t end;   // the byte after the last sample of the RGBA / luma plane
-    if (__builtin_mul_overflow(s->pitch, (size_t)(H - 1), &end) || __builtin_add_overflow(end, rb, &end))
-        return MM_ERR_INVALID;
-    if (fmt_planes3(fmt)) {
-        // rows of W / 2 samples; H / 2 Cb rows, then H / 2 Cr rows at the same pitch
-        // (u: 1, or the word of the 10-bit form)
-        const size_t cb = rb / 2;
-        size_t cr;
-        if (s->chroma_pitch < cb || s->chroma_pitch % u || s->chroma_offset % u || s->chroma_offset < end)
+    if (!s || W < 1 || H < 1) return MM_ERR_INVALID;
+    if (int rc = fmt_check(W, H, s->format, nullptr)) return rc;
+    const size_t u = fmt_info(s->format)->unit;
+    Plane pl[3];
+    const int np = surf_planes(W, H, *s, pl);
+    if (!np || (np == 1 && (s->chroma_offset || s->chroma_pitch))) return MM_ERR_INVALID;
+    size_t end = 0;   // the byte after the last sample of the planes so far
+    for (int k = 0; k < np; ++k) {
+        const Plane &q = pl[k];
+        if (q.pitch < q.row_bytes || q.pitch % u || q.offset % u || q.offset < end) return MM_ERR_INVALID;
+        if (__builtin_mul_overflow(q.pitch, q.rows - 1, &end) || __builtin_add_overflow(end, q.offset, &end) ||
+            __builtin_add_overflow(end, q.row_bytes, &end))
             return MM_ERR_INVALID;
-        if (__builtin_mul_overflow(s->chroma_pitch, (size_t)(H / 2), &cr) ||
-            __builtin_mul_overflow(s->chroma_pitch, (size_t)(H / 2 - 1), &end) ||
-            __builtin_add_overflow(end, cr, &end) || __builtin_add_overflow(end, s->chroma_offset, &end) ||
-            __builtin_add_overflow(end, cb, &end))
-            return MM_ERR_INVALID;
-    } else if (fmt_420(fmt)) {
-        if (s->chroma_pitch < rb || s->chroma_pitch % u || s->chroma_offset % u || s->chroma_offset < end)
-            return MM_ERR_INVALID;
-        if (__builtin_mul_overflow(s->chroma_pitch, (size_t)(H / 2 - 1), &end) ||
-            __builtin_add_overflow(end, s->chroma_offset, &end) || __builtin_add_overflow(end, rb, &end))
-            return MM_ERR_INVALID;
-    } else if (s->chroma_offset || s->chroma_pitch) {
-        return MM_ERR_INVALID;
     }
     if (end > kSurfMaxExtent) return MM_ERR_UNSUPPORTED;
     if (extent) *extent = end;
@@ -353,7 +266,7 @@ static inline int surf_check_frames(int W, int H, const void *p, const mm_surfac
 {
     size_t extent;
     if (int rc = surf_check(W, H, s, &extent)) return rc;
-    const size_t u = fmt_unit(s->format);
+    const size_t u = fmt_info(s->format)->unit;
     if (on_device && reinterpret_cast<uintptr_t>(p) % u) return MM_ERR_INVALID;
     if (count > 1 && (s->frame_stride < extent || s->frame_stride % u)) return MM_ERR_INVALID;
     return MM_OK;
@@ -372,11 +285,12 @@ static inline Geo::Lay surf_lay(const mm_surface &s)
 // decode, any NV12 or P010 code to MM_RGBA8; encode, MM_RGBA8 to any NV12 code.
 static inline int convert_supported(int in_fmt, int out_fmt)
 {
-    if (!fmt_valid(in_fmt) || !fmt_valid(out_fmt)) return MM_ERR_INVALID;
+    const FmtInfo *fi = fmt_info(in_fmt), *fo = fmt_info(out_fmt);
+    if (!fi || !fo) return MM_ERR_INVALID;
     if (in_fmt == out_fmt) return MM_OK;
     // (a three-plane code has no mixed pair)
-    if ((fmt_nv12(in_fmt) || fmt_p010(in_fmt)) && out_fmt == MM_RGBA8) return MM_OK;
-    if (in_fmt == MM_RGBA8 && fmt_nv12(out_fmt)) return MM_OK;
+    if ((fi->kfmt == kFmtNV12 || fi->kfmt == kFmtP010) && out_fmt == MM_RGBA8) return MM_OK;
+    if (in_fmt == MM_RGBA8 && fo->kfmt == kFmtNV12) return MM_OK;
     return MM_ERR_UNSUPPORTED;
 }
 // The frames of one call: their formats and where the two sides lie.  fmt is
@@ -384,6 +298,7 @@ static inline int convert_supported(int in_fmt, int out_fmt)
 // ofmt the output side's: the same but in a convert call.
 struct Frames {
     int fmt, ofmt;
+    const FmtInfo *fi, *fo;   // their rows, looked up once per call
     Geo::Lay in, out;
     size_t fb;       // mm_frame_bytes (of fmt)
     bool packed;     // one format, both sides tight, frames back to back: a passthrough is one plain copy
@@ -394,9 +309,11 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
     Frames f;
     f.fmt = li.format;
     f.ofmt = lo.format;
+    f.fi = fmt_info(f.fmt);
+    f.fo = fmt_info(f.ofmt);
     f.in = surf_lay(li);
     f.out = surf_lay(lo);
-    f.fb = fmt_frame_bytes(W, H, f.fmt);
+    f.fb = f.fi->frame_bytes(W, H);
     mm_surface t;
     (void)surf_tight(W, H, f.fmt, &t);
     auto tight = [&](const mm_surface &s) {
@@ -407,67 +324,57 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
     return f;
 }
 
-static_assert(kFmtNV12 == MM_NV12, "the kernels' NV12 template argument is the format code");
-static_assert(kFmtY8 == MM_Y8 && kFmtY16 == MM_Y16, "the kernels' single-plane template arguments are the format codes");
-static_assert(kFmtP010 == MM_P010, "the kernels' P010 template argument is the format code");
-static_assert(kFmtNV12M == (MM_NV12 | MM_MATRIX_BT709) && kFmtP010M == (MM_P010 | MM_MATRIX_BT709),
-              "K1's matrixed template arguments are the BT.709 limited-range codes");
-static_assert(kFmtYUY2 == MM_YUY2 && kFmtYUY2M == (MM_YUY2 | MM_MATRIX_BT709),
-              "the kernels' packed 4:2:2 template arguments are the YUY2 limited-range codes");
-static_assert(kFmtY210 == MM_Y210 && kFmtY210M == (MM_Y210 | MM_MATRIX_BT709),
-              "the kernels' 10-bit packed 4:2:2 template arguments are the Y210 limited-range codes");
-static_assert(kFmtI420 < 256 && kFmtI420M < 256 && MM_I420 == (MM_NV12 | MM_PLANAR) && !(MM_PLANAR & (kMatrixBits | MM_ORDER_BGR | 255)),
-              "the kernels' three-plane template arguments are internal codes below 256 (a code from 256 names a pair)");
-static_assert(kFmtI010 < 256 && kFmtI010M < 256 && MM_I010 == (MM_P010 | MM_PLANAR | MM_LOW_BITS) &&
-                  !(MM_LOW_BITS & (kMatrixBits | MM_ORDER_BGR | MM_PLANAR | 255)),
-              "the kernels' 10-bit three-plane template arguments are internal codes below 256");
-static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && !(MM_ORDER_BGR & kMatrixBits),
-              "the kernels' packed RGB template argument is the MM_RGB24 code; the order bit is no matrix bit");
-// Runs the statement with the compile-time format FMT_ of the runtime `fmt`
-// (both NV12 ranges run the MM_NV12 instances, both P010 ranges the MM_P010
-// instances, whatever the matrix bit, the three word depths of the
-// single-plane formats the MM_Y16 instances, both byte orders and ranges
-// of packed 4:2:2 the MM_YUY2 instances, and both ranges of its 10-bit form the
-// MM_Y210 instances; geo_of sets their uniforms).
-#define MM_FMT_SWITCH(fmt, ...)                                                \
-    switch (fmt_base(fmt)) {                                                   \
-    case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
-    case MM_RGBA32F: { constexpr int FMT_ = MM_RGBA32F; __VA_ARGS__; } break;  \
-    case MM_RGBA16F: { constexpr int FMT_ = MM_RGBA16F; __VA_ARGS__; } break;  \
-    case MM_NV12: case MM_NV12_FULL: { constexpr int FMT_ = MM_NV12; __VA_ARGS__; } break; \
-    case MM_P010: case MM_P010_FULL: { constexpr int FMT_ = MM_P010; __VA_ARGS__; } break; \
-    case MM_Y8: { constexpr int FMT_ = MM_Y8; __VA_ARGS__; } break;            \
-    case MM_Y10: case MM_Y12: case MM_Y16: { constexpr int FMT_ = MM_Y16; __VA_ARGS__; } break; \
-    case MM_YUY2: case MM_YUY2_FULL: case MM_UYVY: case MM_UYVY_FULL:          \
-        { constexpr int FMT_ = MM_YUY2; __VA_ARGS__; } break;                  \
-    case MM_Y210: case MM_Y210_FULL: { constexpr int FMT_ = MM_Y210; __VA_ARGS__; } break; \
-    case MM_RGB24: { constexpr int FMT_ = MM_RGB24; __VA_ARGS__; } break;      \
-    case MM_I420: case MM_I420_FULL: { constexpr int FMT_ = kFmtI420; __VA_ARGS__; } break; \
-    case MM_I010: case MM_I010_FULL: { constexpr int FMT_ = kFmtI010; __VA_ARGS__; } break; \
+// One case of a format switch: the statement with the compile-time instance FMT_
+#define MM_FMT_CASE(F, ...) case F: { constexpr int FMT_ = F; __VA_ARGS__; } break;
+// Runs the statement with the compile-time format FMT_ of the row `fi`: its
+// kernel instance (both ranges and every matrix of a Y'CbCr format run the one
+// instance, the three word depths of the single-plane formats the MM_Y16
+// instances, both byte orders of packed 4:2:2 the MM_YUY2 instances, both of
+// packed RGB the MM_RGB24 instances; geo_of sets their uniforms).
+#define MM_FMT_SWITCH(fi, ...)                                                 \
+    switch ((fi)->kfmt) {                                                      \
+    MM_FMT_CASE(MM_RGBA8, __VA_ARGS__)                                         \
+    MM_FMT_CASE(MM_RGBA32F, __VA_ARGS__)                                       \
+    MM_FMT_CASE(MM_RGBA16F, __VA_ARGS__)                                       \
+    MM_FMT_CASE(kFmtNV12, __VA_ARGS__)                                         \
+    MM_FMT_CASE(kFmtP010, __VA_ARGS__)                                         \
+    MM_FMT_CASE(kFmtY8, __VA_ARGS__)                                           \
+    MM_FMT_CASE(kFmtY16, __VA_ARGS__)                                          \
+    MM_FMT_CASE(kFmtYUY2, __VA_ARGS__)                                         \
+    MM_FMT_CASE(kFmtY210, __VA_ARGS__)                                         \
+    MM_FMT_CASE(kFmtRGB24, __VA_ARGS__)                                        \
+    MM_FMT_CASE(kFmtI420, __VA_ARGS__)                                         \
+    MM_FMT_CASE(kFmtI010, __VA_ARGS__)                                         \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
 // ... the compose kernels' (k_compose, k_rows_inv_compose, k_rows_inv_compose4):
 // FMT_ is the pair's code for the frames of a convert call (mm_kernels.hpp
 // fmt_pair; convert_supported leaves these three), else the format's
+#define MM_MIXED_SWITCH(fr, ...)                                               \
+    switch ((fr).fi->kfmt) {                                                   \
+    case kFmtNV12: { constexpr int FMT_ = kFmtNV12toRGBA8; __VA_ARGS__; } break; \
+    case kFmtP010: { constexpr int FMT_ = kFmtP010toRGBA8; __VA_ARGS__; } break; \
+    default: { constexpr int FMT_ = kFmtRGBA8toNV12; __VA_ARGS__; } break;     \
+    }
 #define MM_PAIR_SWITCH(fr, ...)                                                \
     do {                                                                       \
-        if (!(fr).mixed()) { MM_FMT_SWITCH((fr).fmt, __VA_ARGS__) }            \
-        else if (fmt_nv12((fr).fmt)) { constexpr int FMT_ = kFmtNV12toRGBA8; __VA_ARGS__; } \
-        else if (fmt_p010((fr).fmt)) { constexpr int FMT_ = kFmtP010toRGBA8; __VA_ARGS__; } \
-        else { constexpr int FMT_ = kFmtRGBA8toNV12; __VA_ARGS__; }            \
+        if (!(fr).mixed()) { MM_FMT_SWITCH((fr).fi, __VA_ARGS__) }             \
+        else { MM_MIXED_SWITCH(fr, __VA_ARGS__) }                              \
     } while (0);
-// ... K1's: a code with a matrix bit runs the matrixed NV12 / P010 instance,
-// which reads the chroma plane too (BT.709 and BT.2020, both ranges, share it);
-// a matrixed packed 4:2:2 code the instance that reads whole macropixels (four
-// bytes, or the 10-bit form's eight)
-#define MM_FMT_SWITCH_K1(fmt, ...)                                             \
-    if (fmt_matrix(fmt) && fmt_nv12(fmt)) { constexpr int FMT_ = kFmtNV12M; __VA_ARGS__; }      \
-    else if (fmt_matrix(fmt) && fmt_i420(fmt)) { constexpr int FMT_ = kFmtI420M; __VA_ARGS__; } \
-    else if (fmt_matrix(fmt) && fmt_i010(fmt)) { constexpr int FMT_ = kFmtI010M; __VA_ARGS__; } \
-    else if (fmt_matrix(fmt) && fmt_422(fmt)) { constexpr int FMT_ = kFmtYUY2M; __VA_ARGS__; }  \
-    else if (fmt_matrix(fmt) && fmt_y210(fmt)) { constexpr int FMT_ = kFmtY210M; __VA_ARGS__; } \
-    else if (fmt_matrix(fmt)) { constexpr int FMT_ = kFmtP010M; __VA_ARGS__; }                  \
-    else MM_FMT_SWITCH(fmt, __VA_ARGS__)
+// ... K1's: a code with a matrix bit runs its row's matrixed instance, which
+// reads the chroma samples too (BT.709 and BT.2020, both ranges, share it): the
+// chroma plane or planes, or whole macropixels (four bytes, or the 10-bit
+// form's eight)
+#define MM_FMT_SWITCH_K1(fi, fmt, ...)                                         \
+    switch (fmt_matrix(fmt) ? (fi)->k1m : 0) {                                 \
+    MM_FMT_CASE(kFmtNV12M, __VA_ARGS__)                                        \
+    MM_FMT_CASE(kFmtP010M, __VA_ARGS__)                                        \
+    MM_FMT_CASE(kFmtI420M, __VA_ARGS__)                                        \
+    MM_FMT_CASE(kFmtI010M, __VA_ARGS__)                                        \
+    MM_FMT_CASE(kFmtYUY2M, __VA_ARGS__)                                        \
+    MM_FMT_CASE(kFmtY210M, __VA_ARGS__)                                        \
+    default: MM_FMT_SWITCH(fi, __VA_ARGS__)                                    \
+    }
 // K1's instance of a format: a single-plane frame IS a luma plane and runs the
 // NV12 (bytes) or P010 (words) luma-plane instance with its own uniforms
 // (geo_of: y_off 0, y_unit 1 / max), bit for bit what an instance of its own
@@ -475,18 +382,18 @@ static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && 
 // (a BT.601 three-plane frame too: its luma plane is NV12's, so is the state;
 // its 10-bit form's is P010's in another word unit, which the uniforms carry)
 template <int F> constexpr int kK1Fmt = F == MM_Y8 || F == kFmtI420 ? kFmtNV12 : F == MM_Y16 || F == kFmtI010 ? kFmtP010 : F;
-// ... and the kernels of the odd sizes and the debug views, which the 4:2:0
-// and packed 4:2:2 formats cannot have (refused by fmt_check before any launch): the RGBA and
-// the single-plane instances
-#define MM_FMT_SWITCH_FULLRES(fmt, ...)                                        \
-    switch (fmt) {                                                             \
-    case MM_Y8: { constexpr int FMT_ = MM_Y8; __VA_ARGS__; } break;            \
-    case MM_Y10: case MM_Y12: case MM_Y16: { constexpr int FMT_ = MM_Y16; __VA_ARGS__; } break; \
-    case MM_RGBA8: { constexpr int FMT_ = MM_RGBA8; __VA_ARGS__; } break;      \
-    case MM_RGBA32F: { constexpr int FMT_ = MM_RGBA32F; __VA_ARGS__; } break;  \
-    case MM_RGBA16F: { constexpr int FMT_ = MM_RGBA16F; __VA_ARGS__; } break;  \
-    case MM_RGBA8_SRGB: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break; \
-    case MM_RGB24: case MM_BGR24: { constexpr int FMT_ = MM_RGB24; __VA_ARGS__; } break; \
+// ... and the kernels of the odd sizes and the debug views, which the Y'CbCr
+// formats cannot have (refused by fmt_check before any launch): the RGBA, the
+// packed RGB and the single-plane instances
+#define MM_FMT_SWITCH_FULLRES(fi, ...)                                         \
+    switch ((fi)->kfmt) {                                                      \
+    MM_FMT_CASE(kFmtY8, __VA_ARGS__)                                           \
+    MM_FMT_CASE(kFmtY16, __VA_ARGS__)                                          \
+    MM_FMT_CASE(MM_RGBA8, __VA_ARGS__)                                         \
+    MM_FMT_CASE(MM_RGBA32F, __VA_ARGS__)                                       \
+    MM_FMT_CASE(MM_RGBA16F, __VA_ARGS__)                                       \
+    MM_FMT_CASE(MM_RGBA8_SRGB, __VA_ARGS__)                                    \
+    MM_FMT_CASE(kFmtRGB24, __VA_ARGS__)                                        \
     default: return MM_ERR_UNSUPPORTED;                                        \
     }
 
@@ -555,8 +462,8 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
         // (y_off .. qcr, li.yb) of the in format's geometry, the output-side
         // fields (kr .. cro, lo.yb) of the out format's
         Frames a = fr, b = fr;
-        a.ofmt = fr.fmt;
-        b.fmt = fr.ofmt;
+        a.ofmt = fr.fmt, a.fo = fr.fi;
+        b.fmt = fr.ofmt, b.fi = fr.fo;
         Geo g = geo_of(h, a);
         const Geo go = geo_of(h, b);
         g.nv.kr = go.nv.kr, g.nv.kg = go.nv.kg, g.nv.kb = go.nv.kb;
@@ -567,14 +474,16 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
     }
     Geo g = h->geo;
     const int fmt = fr.fmt;
+    const FmtInfo &f = *fr.fi;
     g.li = fr.in;
     g.lo = fr.out;
-    if (fmt_ycc(fmt)) {
+    // the order uniform, the same on both sides.  Packed 4:2:2: YUY2 is Y0 Cb
+    // Y1 Cr (0), UYVY Cb Y0 Cr Y1 (1).  Packed RGB: 0: R G B, 1: B G R; K1's dot
+    // weights and the compose kernels' byte selectors derive from it.
+    g.li.yb = g.lo.yb = f.order | (fmt & f.opt & MM_ORDER_BGR ? 1u : 0u);
+    if (f.ycc()) {
         // (MM_Y210: P010's words; MM_I010: its codes in the words' low bits, u = 1)
-        const bool full = fmt_full(fmt), p10 = fmt_p010(fmt) || fmt_y210(fmt) || fmt_i010(fmt);
-        const double ys = p10 ? (full ? 1023.0 : 876.0) : (full ? 255.0 : 219.0);
-        const double cs = p10 ? (full ? 1023.0 : 896.0) : (full ? 255.0 : 224.0);
-        const double y0 = full ? 0.0 : p10 ? 64.0 : 16.0, u = p10 && !fmt_i010(fmt) ? 64.0 : 1.0;
+        const auto [ys, cs, y0, u] = code_range(f, f.full(fmt));
         double m[6], kr, kb;
         ycbcr_matrix(fmt, m);
         matrix_krkb(fmt, &kr, &kb);
@@ -596,25 +505,17 @@ static inline Geo geo_of(const mm_handle *h, const Frames &fr)
         // C' = (B - Yl) 0.5 / (1 - Kb), (R - Yl) 0.5 / (1 - Kr) (BT.601: 0.886,
         // 0.701); the mean of four; the code scale
         // (packed 4:2:2: the mean of the macropixel's two)
-        const double mean = fmt_422(fmt) || fmt_y210(fmt) ? 0.5 : 0.25;
-        g.nv.cbo = (float)(mean * cs * 0.5 / (1.0 - kb));
-        g.nv.cro = (float)(mean * cs * 0.5 / (1.0 - kr));
-        // packed 4:2:2 byte order, the same on both sides: YUY2 is Y0 Cb Y1 Cr, UYVY Cb Y0 Cr Y1
-        // (MM_Y210 has the one word order: 0)
-        g.li.yb = g.lo.yb = fmt_uyvy(fmt) ? 1u : 0u;
-    } else if (fmt_mono(fmt)) {
+        g.nv.cbo = (float)(f.mean * cs * 0.5 / (1.0 - kb));
+        g.nv.cro = (float)(f.mean * cs * 0.5 / (1.0 - kr));
+    } else if (f.kfmt == kFmtY8 || f.kfmt == kFmtY16) {
         // v = sample / max in, code = floor(v max + 0.5) clamped to max out:
         // K1 runs the luma-plane instances (no offset), the compose instances
         // read the scale (also their clamp) and the rounding bias
-        const double mx = (double)mono_max(fmt);
+        const double mx = (double)f.max;
         g.nv.y_off = 0.0f;
         g.nv.y_unit = (float)(1.0 / mx);
         g.nv.yo_scale = (float)mx;
         g.nv.yo_bias = 0.5f;
-    } else if (fmt_rgb24(fmt)) {
-        // the byte order, the same on both sides (0: R G B, 1: B G R): K1's dot
-        // weights and the compose kernels' byte selectors derive from it
-        g.li.yb = g.lo.yb = fmt == MM_BGR24 ? 1u : 0u;
     }
     return g;
 }
@@ -843,7 +744,7 @@ static int set_attrs(int W)
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)k34_lds_bytes<12>(false);
         for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420, MM_I010})
-            MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
+            MM_FMT_SWITCH(fmt_info(f), HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtNV12toRGBA8>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -878,7 +779,7 @@ static int set_attrs(int W)
     if constexpr (LOG2N == 11) {   // k_rows_inv_compose4: four 2048-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 4 * lds_complex<2048>());
         for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420, MM_I010})
-            MM_FMT_SWITCH(f, HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
+            MM_FMT_SWITCH(fmt_info(f), HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtNV12toRGBA8>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -893,7 +794,6 @@ static int set_attrs(int W)
 template <int LOG2N>
 static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, const Frames &fr, hipStream_t s, c2 *G)
 {
-    const int fmt = fr.fmt;
     const int ppf = (h->H + 1) / 2;   // odd H: the last pair's second row is zero
     const int total = ppf * nframes;
     // fewer than 2 workgroups per CU at the batch form: the one-pair form
@@ -913,9 +813,9 @@ static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, const Frames 
     const bool gen = h->geo.ox || h->geo.oy;   // odd W/H: taps span i-2 .. i+1
     const Geo g = geo_of(h, fr);
     if (gen) {   // (4:2:0 frames have even sizes; single-plane ones run the luma-plane instances here too)
-        MM_FMT_SWITCH_FULLRES(fmt, MM_K1_LAUNCH(kK1Fmt<FMT_>, true, false))
+        MM_FMT_SWITCH_FULLRES(fr.fi, MM_K1_LAUNCH(kK1Fmt<FMT_>, true, false))
     } else {
-        MM_FMT_SWITCH_K1(fmt, if (lat) MM_K1_LAUNCH(kK1Fmt<FMT_>, false, true);
+        MM_FMT_SWITCH_K1(fr.fi, fr.fmt, if (lat) MM_K1_LAUNCH(kK1Fmt<FMT_>, false, true);
                               else MM_K1_LAUNCH(kK1Fmt<FMT_>, false, false))
     }
 #undef MM_K1_LAUNCH
@@ -1019,128 +919,46 @@ static int place_batch(mm_handle *h, int n, hipStream_t s, int *base)
 static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, int nframes,
                      const Frames &fr, hipStream_t s);
 
-// k_rows_inv_compose's geometry: even sizes whose quads tile the rows (W % 8 == 0
-// puts x0 on a multiple of 4), the horizontal blur's float4 taps inside the
-// canvas, and no vertical blur tap wrapping (list row of output row i + v is i + v)
-// ... and, for NV12, layouts whose quads are dwords: the fused kernels read
-// two (Cb, Cr) pairs and store four luma codes or two pairs as ONE dword at
-// column X % 4 == 0 of a row, so every row they touch must start on a multiple
-// of 4: both frame pointers, the output pitch, both chroma planes' offsets and
-// pitches, and, with more than one frame in the launch, both frame strides
-// (a stream whose frames are 2 mod 4 apart alternates alignment: decided for
-// all its frames here, not from its first one).  NV12's unit is 2, so a valid
-// layout may fail this: it takes the unfused pair, same results.  (RGBA8's and
-// P010's quads are multi-dword accesses at dword-aligned addresses, which the
-// unit, 4, gives every layout: mm_kernels.hpp ld_quad_a4; packed 4:2:2's quads
-// are 8-byte accesses of two macropixels at dword-aligned addresses, and its
-// unit is 4 too; MM_Y210's are 16-byte accesses at 8-byte-aligned addresses,
-// its unit: ld_quad_a8.)
-// The two halves, a side each (a convert call has NV12 on one side only: NV12
-// in asks this of the input's chroma rows, RGBA8 in with NV12 out of the
-// output's luma and chroma rows; the RGBA8 side's quads are dword aligned in
-// every layout).
-static bool nv12_in_aligned(const uint8_t *in, const Frames &fr, int nframes)
+// Whether the row starts of `nframes` frames at p, layout l of format f, are
+// multiples of a_luma (the first plane's) and a_chroma (the chroma planes').  A
+// row start is a sum of the base, a plane offset, pitches, the Cr plane's
+// distance from the Cb plane and, past one frame, frame strides (a stream
+// whose frames are 2 mod 4 apart alternates alignment: decided for all its
+// frames here, not from its first one): all of them multiples, so is every row.
+static bool rows_aligned(const FmtInfo &f, const uint8_t *p, const Geo::Lay &l, int H, int nframes,
+                         unsigned a_luma, unsigned a_chroma)
 {
-    uintptr_t m = (reinterpret_cast<uintptr_t>(in) + fr.in.c_off) | fr.in.c_pitch;
-    if (nframes > 1) m |= fr.in.stride;
-    return (m & 3u) == 0;
-}
-static bool nv12_out_aligned(const uint8_t *out, const Frames &fr, int nframes)
-{
-    const uintptr_t b = reinterpret_cast<uintptr_t>(out);
-    uintptr_t m = b | fr.out.pitch | (b + fr.out.c_off) | fr.out.c_pitch;
-    if (nframes > 1) m |= fr.out.stride;
-    return (m & 3u) == 0;
-}
-static bool nv12_quads_aligned(const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
-{
-    return nv12_in_aligned(in, fr, nframes) && nv12_out_aligned(out, fr, nframes);
-}
-// The single-plane formats' quads are stores only (their compose reads no
-// input): four bytes as one dword, four words as one 8-byte store at a
-// dword-aligned address, so every output row of every frame of the launch
-// starts on a multiple of 4.  Their units are 1 and 2: a valid layout may fail
-// this (98 x 62 MM_Y8: rows 98 bytes apart) and takes the unfused pair, whose
-// stores are single samples.  Same arithmetic, same results.
-static bool mono_quads_aligned(const uint8_t *out, const Frames &fr, int nframes)
-{
-    uintptr_t m = reinterpret_cast<uintptr_t>(out) | fr.out.pitch;
-    if (nframes > 1) m |= fr.out.stride;
-    return (m & 3u) == 0;
+    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
+    uintptr_t luma = b | l.pitch, chroma = 0;
+    if (f.planes > 1) chroma = (b + l.c_off) | l.c_pitch;
+    if (f.planes > 2) chroma |= i420_cr_delta(H, l.c_pitch);
+    if (nframes > 1) luma |= l.stride, chroma |= l.stride;
+    return !(luma & (a_luma - 1)) && !(chroma & (a_chroma - 1));
 }
 // The RGBA8 formats' source rows staged in LDS (k_rows_inv_compose<.., true>):
 // a thread's quad travels as one 16-byte LDS-DMA, taken only where every quad
-// of every source row of the launch is 16-byte aligned (X % 4 == 0: the frame
-// pointer, the pitch and, past one frame, the stride).  Any other layout keeps
-// the register loads, which need dword alignment only.  Same results.
-static bool k34_src_dma(const uint8_t *in, const Frames &fr, int nframes)
+// of every source row of the launch is 16-byte aligned (X % 4 == 0).  Any other
+// layout keeps the register loads, which need dword alignment only.  Same results.
+static bool k34_src_dma(const mm_handle *h, const uint8_t *in, const Frames &fr, int nframes)
 {
-    if (fr.fmt != MM_RGBA8 && fr.fmt != MM_RGBA8_SRGB) return false;
     // (a convert call with MM_RGBA8 in is the encode pair: the same source rows)
-    uintptr_t m = reinterpret_cast<uintptr_t>(in) | fr.in.pitch;
-    if (nframes > 1) m |= fr.in.stride;
-    return (m & 15u) == 0;
+    return (fr.fmt == MM_RGBA8 || fr.fmt == MM_RGBA8_SRGB) && rows_aligned(*fr.fi, in, fr.in, h->H, nframes, 16, 1);
 }
-// Packed RGB's quads are 12 bytes at 3 X (X % 4 == 0) from the row's start,
-// one dwordx3 load and one dwordx3 store typed 4-byte aligned: every row of
-// every frame of the launch starts on a multiple of 4, on both sides (every
-// tight frame with W % 8 == 0: 3 W and 3 W H are multiples of 4).  The unit is
-// 1, so a valid layout may fail this (a region of interest at byte offset 21,
-// a pitch of 3 W + 3): it takes the unfused pair, whose accesses are
-// byte-aligned dword loads and byte stores.  Same arithmetic, same results.
-static bool rgb24_quads_aligned(const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
+// k_rows_inv_compose's layouts: quads at the alignment each side's format asks
+// of its rows (FmtInfo::quad; a convert call: the input numbers of the input
+// format, the output numbers of the output format) ...
+static bool k34_quads_aligned(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
-    uintptr_t m = reinterpret_cast<uintptr_t>(in) | fr.in.pitch | reinterpret_cast<uintptr_t>(out) | fr.out.pitch;
-    if (nframes > 1) m |= fr.in.stride | fr.out.stride;
-    return (m & 3u) == 0;
+    const uint8_t *qi = fr.fi->quad, *qo = fr.fo->quad;
+    return rows_aligned(*fr.fi, in, fr.in, h->H, nframes, qi[0], qi[1]) &&
+           rows_aligned(*fr.fo, out, fr.out, h->H, nframes, qo[2], qo[3]);
 }
-// Three-plane 4:2:0's quads: four luma codes as one dword store, the quad's two
-// Cb samples and its two Cr samples as one 2-byte access per plane, loads and
-// stores alike.  So the output's luma rows start on multiples of 4 (as NV12's;
-// the compose reads no input luma) and every Cb and Cr row of every frame of
-// the launch on a multiple of 2, on both sides: base + offset, chroma_pitch,
-// the Cr plane's chroma_pitch x H/2 and, past one frame, frame_stride (every
-// tight frame with W % 8 == 0).  The unit is 1, so a valid layout may fail this
-// (98 x 62: chroma rows of 49 bytes): it takes the unfused pair, whose chroma
-// accesses are single bytes.  Same arithmetic, same results.
-static bool i420_quads_aligned(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
-    uintptr_t luma = b | fr.out.pitch;
-    uintptr_t chroma = (a + fr.in.c_off) | fr.in.c_pitch | i420_cr_delta(h->H, fr.in.c_pitch) |
-                       (b + fr.out.c_off) | fr.out.c_pitch | i420_cr_delta(h->H, fr.out.c_pitch);
-    if (nframes > 1) luma |= fr.out.stride, chroma |= fr.in.stride | fr.out.stride;
-    return (luma & 3u) == 0 && (chroma & 1u) == 0;
-}
-// The 10-bit three-plane form's quads: four luma codes as one 8-byte store at
-// a dword-aligned address (P010's), the quad's two Cb words and its two Cr
-// words as one dword per plane, loads and stores alike.  So the output's luma
-// rows and every Cb and Cr row of every frame of the launch start on multiples
-// of 4, on both sides (every tight frame with W % 8 == 0, the decoder layout).
-// The unit is 2, so a valid layout of a W % 8 == 0 frame may fail this (a base,
-// a pitch or a plane offset at 2 mod 4): it takes the unfused pair, whose
-// accesses are single words.  This rule speaks of row STARTS alone: that a
-// quad's dword of two chroma words ends inside its row is k34_fits' own
-// W % 8 == 0, which refuses a frame such as 98 x 62 whatever this test says
-// (do not lift that condition on the strength of this test).
-static bool i010_quads_aligned(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
-    uintptr_t m = b | fr.out.pitch | (a + fr.in.c_off) | fr.in.c_pitch | i420_cr_delta(h->H, fr.in.c_pitch) |
-                  (b + fr.out.c_off) | fr.out.c_pitch | i420_cr_delta(h->H, fr.out.c_pitch);
-    if (nframes > 1) m |= fr.in.stride | fr.out.stride;
-    return (m & 3u) == 0;
-}
+// ... and its geometry: even sizes whose quads tile the rows (W % 8 == 0
+// puts x0 on a multiple of 4), the horizontal blur's float4 taps inside the
+// canvas, and no vertical blur tap wrapping (list row of output row i + v is i + v)
 static bool k34_fits(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
-    if (fmt_i010(fr.fmt) && !i010_quads_aligned(h, in, out, fr, nframes)) return false;
-    if (fmt_i420(fr.fmt) && !i420_quads_aligned(h, in, out, fr, nframes)) return false;
-    if (fr.mixed()) {   // each side by its own format (P010 in, RGBA8 either side: every layout)
-        if (fmt_nv12(fr.fmt) && !nv12_in_aligned(in, fr, nframes)) return false;
-        if (fmt_nv12(fr.ofmt) && !nv12_out_aligned(out, fr, nframes)) return false;
-    } else if (fmt_nv12(fr.fmt) && !nv12_quads_aligned(in, out, fr, nframes)) return false;
-    if (fmt_mono(fr.fmt) && !mono_quads_aligned(out, fr, nframes)) return false;
-    if (fmt_rgb24(fr.fmt) && !rgb24_quads_aligned(in, out, fr, nframes)) return false;
+    if (!k34_quads_aligned(h, in, out, fr, nframes)) return false;
     const Geo &g = h->geo;
     return g.N <= 4096 &&   // two transforms per workgroup: 2 N / 8 <= 1024 threads
            !g.ox && !g.oy && g.W % 8 == 0 && g.x0 >= 4 && g.x0 % 4 == 0 &&
@@ -1202,7 +1020,7 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
     }
     if (R >= 4 && k34_fits(h, in, out, fr, nframes)) {   // K3 + K4 fused: Yh stays on chip
         const int strips = (h->H + R - 1) / R, steps = R / 4 + 1;
-        const bool dma = LOG2N <= 12 && k34_src_dma(in, fr, nframes);
+        const bool dma = LOG2N <= 12 && k34_src_dma(h, in, fr, nframes);
         const size_t lds = k34_lds_bytes<LOG2N>(dma);
         const dim3 grid((unsigned)(strips * nout)), block(2 * fft_T<LOG2N>());
         ProfScope ps(h, s, MM_K_ROWS_INV_COMPOSE, nout);
@@ -1249,12 +1067,11 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
 {
     const int nout = nframes - frame0;
     if (nout <= 0) return MM_OK;
-    const int fmt = fr.fmt;
     if (h->geo.ox || h->geo.oy) {   // odd W/H: the crop samples between texels
         const size_t tot = (size_t)nout * h->W * h->H;
         ProfScope ps(h, s, MM_K_COMPOSE, nout);
         const dim3 grid((unsigned)((tot + 255) / 256));
-        MM_FMT_SWITCH_FULLRES(fmt, hipLaunchKernelGGL((k_compose_odd<FMT_>), grid, dim3(256), 0, s, h->d_Yh,
+        MM_FMT_SWITCH_FULLRES(fr.fi, hipLaunchKernelGGL((k_compose_odd<FMT_>), grid, dim3(256), 0, s, h->d_Yh,
                                               h->yh_stride, in, out, frame0, nout, geo_of(h, fr), h->blur,
                                               h->d_col, h->d_row))
         HIPCHK(hipGetLastError());
@@ -1283,14 +1100,17 @@ static int copy_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, con
         HIPCHK(hipMemcpyAsync(out, in, fr.fb * n, hipMemcpyDeviceToDevice, s));
         return MM_OK;
     }
-    const unsigned rb = (unsigned)fmt_row_bytes(h->W, fr.fmt);
-    const int rows = fmt_420(fr.fmt) ? h->H + h->H / 2 : h->H;
+    const FmtInfo &f = *fr.fi;
+    const unsigned rb = (unsigned)f.row_bytes(h->W);
+    const int rows = f.planes == 2 ? h->H + h->H / 2 : h->H;   // (a (Cb, Cr) plane: its rows after the luma rows)
+    // in words of the format's unit: bytes, 16-bit words, or dwords, which divide every larger unit
+    const auto copy = f.unit == 1 ? &k_copy_rows<uint8_t> : f.unit == 2 ? &k_copy_rows<uint16_t> : &k_copy_rows<uint32_t>;
     const Geo g = geo_of(h, fr);
     // three planes of row bytes W, W/2 and W/2: the luma rows, then the two
     // chroma planes as H/2 "luma" rows (Cb) and H/2 chroma rows (Cr) of a
     // geometry whose planes are the Cb and Cr planes
     Geo gc = g;
-    if (fmt_planes3(fr.fmt)) {
+    if (f.planes == 3) {
         gc.li.pitch = g.li.c_pitch, gc.li.c_off = (unsigned)i420_cr_delta(h->H, g.li.c_pitch);
         gc.lo.pitch = g.lo.c_pitch, gc.lo.c_off = (unsigned)i420_cr_delta(h->H, g.lo.c_pitch);
     }
@@ -1298,31 +1118,22 @@ static int copy_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, con
         const dim3 grid((unsigned)rows, (unsigned)std::min(32768, n - f0));
         const uint8_t *src = in + fr.in.stride * f0;
         uint8_t *dst = out + fr.out.stride * f0;
-        if (fmt_planes3(fr.fmt)) {   // (in the format's unit: bytes, or the words of the 10-bit form)
+        if (f.planes == 3) {
             const dim3 gy((unsigned)h->H, grid.y);   // H luma rows; H/2 Cb + H/2 Cr rows
-            const auto copy = fmt_unit(fr.fmt) == 1 ? &k_copy_rows<uint8_t> : &k_copy_rows<uint16_t>;
             hipLaunchKernelGGL(copy, gy, dim3(256), 0, s, src, dst, g, rb, h->H);
             hipLaunchKernelGGL(copy, gy, dim3(256), 0, s, src + fr.in.c_off, dst + fr.out.c_off, gc, rb / 2, h->H / 2);
-        } else if (fmt_unit(fr.fmt) == 1) hipLaunchKernelGGL((k_copy_rows<uint8_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
-        else if (fmt_unit(fr.fmt) == 2) hipLaunchKernelGGL((k_copy_rows<uint16_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
-        else hipLaunchKernelGGL((k_copy_rows<uint32_t>), grid, dim3(256), 0, s, src, dst, g, rb, h->H);
+        } else hipLaunchKernelGGL(copy, grid, dim3(256), 0, s, src, dst, g, rb, h->H);
         HIPCHK(hipGetLastError());
     }
     return MM_OK;
 }
 
-// k_convert's quads: W % 4 == 0 and, on the NV12 side, rows on multiples of 4
-// (the RGBA8 side's 16-byte quads and P010's 8-byte ones are multi-dword
-// accesses at dword-aligned addresses in every layout)
+// k_convert's quads: W % 4 == 0 and the fused compose's alignments, plus one:
+// NV12 in reads a luma dword per row, so its luma rows too start on multiples of 4
 static bool convert_quads_aligned(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int n)
 {
-    if (h->W % 4) return false;
-    if (fmt_nv12(fr.fmt)) {   // luma rows too: a luma dword per row
-        uintptr_t m = reinterpret_cast<uintptr_t>(in) | fr.in.pitch;
-        if (n > 1) m |= fr.in.stride;
-        return (m & 3u) == 0 && nv12_in_aligned(in, fr, n);
-    }
-    return !fmt_nv12(fr.ofmt) || nv12_out_aligned(out, fr, n);
+    return h->W % 4 == 0 && k34_quads_aligned(h, in, out, fr, n) &&
+           (fr.fi->kfmt != kFmtNV12 || rows_aligned(*fr.fi, in, fr.in, h->H, n, 4, 1));
 }
 // The passthrough frames of a convert call: the plain conversion (k_convert),
 // one launch for the n frames.  The decode's coefficients over the chroma code
@@ -1333,10 +1144,10 @@ static int convert_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, 
     if (n <= 0) return MM_OK;
     const Geo g = geo_of(h, fr);
     Cvt cv = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (fmt_420(fr.fmt)) {
+    if (fr.fi->ycc()) {   // (a decode: NV12 or P010 in)
         const int fmt = fr.fmt;
-        const bool full = fmt_full(fmt), p10 = fmt_p010(fmt);
-        const double cs = (p10 ? (full ? 1023.0 : 896.0) : (full ? 255.0 : 224.0)) * (p10 ? 64.0 : 1.0);
+        const CodeRange r = code_range(*fr.fi, fr.fi->full(fmt));
+        const double cs = r.cs * r.u;
         double rcr = 1.402, gcb = -0.344136, gcr = -0.714136, bcb = 1.772;
         if (fmt_matrix(fmt)) {
             double kr, kb;
@@ -1360,9 +1171,7 @@ static int convert_frames(mm_handle *h, const uint8_t *in, uint8_t *out, int n, 
             if (quad) hipLaunchKernelGGL((k_convert<F, true>), grid, dim3(256), 0, s, src, dst, g, cv, m); \
             else hipLaunchKernelGGL((k_convert<F, false>), grid, dim3(256), 0, s, src, dst, g, cv, m);    \
         } while (0)
-        if (fmt_nv12(fr.fmt)) MM_CONVERT_LAUNCH(kFmtNV12toRGBA8);
-        else if (fmt_p010(fr.fmt)) MM_CONVERT_LAUNCH(kFmtP010toRGBA8);
-        else MM_CONVERT_LAUNCH(kFmtRGBA8toNV12);
+        MM_MIXED_SWITCH(fr, MM_CONVERT_LAUNCH(FMT_))
 #undef MM_CONVERT_LAUNCH
         HIPCHK(hipGetLastError());
     }
@@ -1533,7 +1342,6 @@ template <int LOG2N>
 static int run_debug(mm_handle *h, uint8_t *out, int n, int first, const Frames &fr, hipStream_t s,
                      const c2 *G)
 {
-    const int fmt = fr.fmt;
     constexpr int N = 1 << LOG2N;
     if (n <= first) return MM_OK;
     const size_t tex_stride = (size_t)2 * N * N;
@@ -1560,7 +1368,7 @@ static int run_debug(mm_handle *h, uint8_t *out, int n, int first, const Frames 
     HIPCHK(hipGetLastError());
     const size_t tot = (size_t)m * h->W * h->H;
     const dim3 grid((unsigned)((tot + 255) / 256));
-    MM_FMT_SWITCH_FULLRES(fmt, hipLaunchKernelGGL((k_dbg_out<FMT_>), grid, dim3(256), 0, s, h->d_dbg, tex_stride,
+    MM_FMT_SWITCH_FULLRES(fr.fi, hipLaunchKernelGGL((k_dbg_out<FMT_>), grid, dim3(256), 0, s, h->d_dbg, tex_stride,
                                           out, first, m, h->p.show_magnitude, h->p.show_phase, geo_of(h, fr)))
     HIPCHK(hipGetLastError());
     return MM_OK;

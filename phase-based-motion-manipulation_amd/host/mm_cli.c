@@ -41,16 +41,21 @@
  * --srgb: the 8-bit frames are sRGB-encoded (video and display-referred
  * clips are), processed in linear light as Unity's Linear colour space does
  * (MM_RGBA8_SRGB: decoded on read, encoded on write); default UNORM.
+ * The input-format options (--nv12 --p010 --i420 --i010 --mono --yuy2 --uyvy
+ * --y210 --ppm; k_in_opts below has a row each): at most one, and none goes
+ * with --srgb, the ring modes, --out-nv12 or, but for --mono, the debug views;
+ * --out-rgba8 goes with --nv12 and --p010 alone; --matrix and --full-range go
+ * with the Y'CbCr ones (all but --mono and --ppm), which need even sizes.
+ * Each names the one input it takes; every refusal is a usage error (status
+ * 2) before the output file is created and before the device is touched.
  * --nv12: a 4:2:0 .y4m input goes to the device as it is stored, as MM_NV12
  * frames (MM_NV12_FULL with --full-range): the chroma planes are interleaved
  * on the way in and split on the way out (a C420 .y4m; any other extension:
- * the raw NV12 frames), and no colour arithmetic runs on the host.  Not with
- * --srgb, the debug views, the ring modes, 4:4:4 / mono input or odd sizes.
+ * the raw NV12 frames), and no colour arithmetic runs on the host.
  * --p010: the same for a 10-bit 4:2:0 .y4m input (C420p10), sent as MM_P010
  * frames (MM_P010_FULL with --full-range): the chroma planes are interleaved
  * and every sample shifted left by 6 on the way in, the reverse on the way out
- * (a C420p10 .y4m; any other extension: the raw P010 frames).  Refused with
- * what --nv12 is refused with, and with --nv12.  Bit depths are never
+ * (a C420p10 .y4m; any other extension: the raw P010 frames).  Bit depths are never
  * converted silently: an 8-bit input with --p010 and a 10-bit input without it
  * are refused.
  * --matrix 601|709|2020 (default 601): the Y'CbCr matrix of an --nv12,
@@ -63,27 +68,24 @@
  * the device as it is stored, as MM_Y8 / MM_Y10 / MM_Y12 / MM_Y16 frames by the
  * header's depth: one sample per pixel each way, no conversion, odd sizes, the
  * standard and steerable modes and the debug views included.  The output is a
- * .y4m of the same Cmono* type (any other extension: the raw frames).  Refused
- * with a chroma-carrying input, with --nv12, --p010, --srgb, --matrix and
- * --full-range (there is no matrix and no range) and with the ring modes.
+ * .y4m of the same Cmono* type (any other extension: the raw frames).  There
+ * is no matrix and no range: not with --matrix or --full-range.
  * Without --mono a Cmono input is expanded to RGBA8 on the host, as before.
  * --yuy2 / --uyvy: an 8-bit 4:2:2 .y4m input (C422: a capture device's frames,
  * ffmpeg's yuv422p) goes to the device as packed macropixels, Y0 Cb Y1 Cr as
  * MM_YUY2 or Cb Y0 Cr Y1 as MM_UYVY (_FULL with --full-range, a matrix bit
  * with --matrix): the planes are interleaved on the way in and split on the
  * way out (a C422 .y4m, the same file for both flags; any other extension: the
- * raw packed frames), and no colour arithmetic runs on the host.  Refused
- * with --srgb, the debug views, the ring modes, --nv12, --p010, --mono, each
- * other, any other input and odd sizes.  A C422 input needs one of the two
+ * raw packed frames), and no colour arithmetic runs on the host.
+ * A C422 input needs one of the two
  * flags: the host has no 4:2:2 to RGBA conversion.
  * --y210: a 10-bit 4:2:2 .y4m input (C422p10: planar, the code in the low 10
  * bits of each word; ffmpeg's yuv422p10le) goes to the device as MM_Y210
  * frames, words Y0 Cb Y1 Cr with the code << 6 (_FULL with --full-range, a
  * matrix bit with --matrix): the planes are interleaved and shifted on the way
  * in and split on the way out (a C422p10 .y4m; any other extension: the raw
- * Y210 frames), and no colour arithmetic runs on the host.  Refused with
- * --yuy2, --uyvy, --nv12, --p010, --mono, --srgb, the debug views, the ring
- * modes, any other input and odd sizes.  A C422p10 input needs --y210: it is
+ * Y210 frames), and no colour arithmetic runs on the host.
+ * A C422p10 input needs --y210: it is
  * never converted on the host.
  * --ppm: the input (-i) is a stream of concatenated binary PPM images (P6,
  * maxval 255, one size: what ffmpeg -f image2pipe -vcodec ppm writes; host/ppm.h).
@@ -91,27 +93,20 @@
  * way, and -o gets the same container back.  --bgr swaps R and B on read and
  * on write and sends MM_BGR24 (the files are the run without it, byte for
  * byte).  Every size, -l, -s, -b, --standard and --surface-align as usual.
- * Refused with the other format options, --srgb, --matrix, --full-range, the
- * debug views, the ring modes and a .y4m on either side.
+ * Not with --matrix, --full-range or a .y4m on either side.
  * --i420: an 8-bit 4:2:0 .y4m input (C420) goes to the device as its frames lie
  * in the file, as MM_I420 frames (MM_I420_FULL with --full-range, a matrix bit
  * with --matrix): three planes, no interleave on the way in and no split on the
  * way out (a C420 .y4m; any other extension on either side: the raw I420
  * frames, -w/-h).  The output file is --nv12's, byte for byte.  -l, -s, -b,
- * --standard, --surface-align and --checksum as usual.  Refused with every
- * other format option (--nv12, --p010, --mono, --yuy2, --uyvy, --y210, --ppm),
- * --out-rgba8, --out-nv12, --srgb, the debug views, the ring modes, a .y4m
- * that is not 4:2:0 or is 10-bit, no input at all, and odd sizes.
+ * --standard, --surface-align and --checksum as usual.
  * --i010: a 10-bit 4:2:0 .y4m input (C420p10) goes to the device as its frames
  * lie in the file, as MM_I010 frames (MM_I010_FULL with --full-range, a matrix
  * bit with --matrix): three planes of words with the code in the low 10 bits,
  * no interleave and no shift on the way in, no split on the way out (a C420p10
  * .y4m; any other extension on either side: the raw I010 frames, -w/-h).  The
  * output file is --p010's, byte for byte.  -l, -s, -b, --standard,
- * --surface-align and --checksum as usual.  Refused with every other format
- * option (--nv12, --p010, --i420, --mono, --yuy2, --uyvy, --y210, --ppm),
- * --out-rgba8, --out-nv12, --srgb, the debug views, the ring modes, a .y4m
- * that is not 10-bit 4:2:0, no input at all, and odd sizes.
+ * --surface-align and --checksum as usual.
  * --surface-align P,R: the device frames, input and output, are held in
  * mm_surface_aligned(W, H, format, P, R) surfaces (256,16: a hardware
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
@@ -121,14 +116,14 @@
  * in as stored and raw MM_RGBA8 frames come out, through
  * mm_process_stream_convert: -o gets the raw RGBA8 frames, or, a .y4m, the 4:4:4
  * file the default RGBA8 path writes from them.  Refused without --nv12 /
- * --p010, with --out-nv12, and with whatever --nv12 / --p010 are refused with.
+ * --p010 and with --out-nv12.
  * --out-nv12 (with the RGBA8 input path: a synthetic stream, raw RGBA8 frames,
  * or a .y4m the host expands as above): encode on the way out.  MM_RGBA8 frames
  * go in and NV12 frames come out: -o gets a C420 .y4m, or the raw NV12 frames.
  * --full-range and --matrix then name the OUTPUT code (MM_NV12_FULL, a matrix
- * bit) and nothing else: a .y4m input is expanded as BT.601 limited range.  Refused with --out-rgba8, every other format option (--nv12, --p010,
- * --mono, --yuy2, --uyvy, --y210, --ppm), --srgb, the debug views, the ring
- * modes and odd sizes.
+ * bit) and nothing else: a .y4m input is expanded as BT.601 limited range.
+ * Refused with --out-rgba8, every input-format option, --srgb, the debug
+ * views, the ring modes and odd sizes.
  * With either, --surface-align lays out each side in its own format's
  * surface, and --checksum hashes the output frames, as usual.
  */
@@ -218,20 +213,21 @@ static int surf_copy(void *dst, const mm_surface *dl, const void *src, const mm_
         sl->chroma_pitch == t.chroma_pitch && dl->frame_stride == t.frame_stride &&
         sl->frame_stride == t.frame_stride)   /* tight on both sides: one copy */
         return hipMemcpyAsync(dst, src, t.frame_stride * (size_t)n, kind, s) != hipSuccess;
+    /* plane q of a frame: the luma (or only) plane, then the chroma plane or
+     * planes, H / 2 rows of the tight layout's chroma row; three planes: the Cr
+     * plane lies chroma_pitch x H/2 after the Cb plane */
+    const int np = !t.chroma_pitch ? 1 : (dl->format & MM_PLANAR) ? 3 : 2;
+    const size_t hc = (size_t)H / 2;
     for (int k = 0; k < n; ++k) {
         unsigned char *d = (unsigned char *)dst + dl->frame_stride * (size_t)k;
         const unsigned char *a = (const unsigned char *)src + sl->frame_stride * (size_t)k;
-        if (hipMemcpy2DAsync(d, dl->pitch, a, sl->pitch, rb, (size_t)H, kind, s) != hipSuccess) return 1;
-        /* (a chroma row: the luma row's bytes, or, three planes, half of them) */
-        if (t.chroma_pitch && hipMemcpy2DAsync(d + dl->chroma_offset, dl->chroma_pitch, a + sl->chroma_offset,
-                                               sl->chroma_pitch, t.chroma_pitch, (size_t)H / 2, kind, s) != hipSuccess)
-            return 1;
-        /* three planes: the Cr plane lies chroma_pitch x H/2 after the Cb plane */
-        if ((dl->format & MM_PLANAR) &&
-            hipMemcpy2DAsync(d + dl->chroma_offset + dl->chroma_pitch * ((size_t)H / 2), dl->chroma_pitch,
-                             a + sl->chroma_offset + sl->chroma_pitch * ((size_t)H / 2), sl->chroma_pitch,
-                             t.chroma_pitch, (size_t)H / 2, kind, s) != hipSuccess)
-            return 1;
+        for (int q = 0; q < np; ++q) {
+            const size_t doff = q ? dl->chroma_offset + (size_t)(q - 1) * dl->chroma_pitch * hc : 0;
+            const size_t soff = q ? sl->chroma_offset + (size_t)(q - 1) * sl->chroma_pitch * hc : 0;
+            if (hipMemcpy2DAsync(d + doff, q ? dl->chroma_pitch : dl->pitch, a + soff, q ? sl->chroma_pitch : sl->pitch,
+                                 q ? t.chroma_pitch : rb, q ? hc : (size_t)H, kind, s) != hipSuccess)
+                return 1;
+        }
     }
     return 0;
 }
@@ -503,31 +499,104 @@ static int run_ring_local(const mm_params *p, int W, int H, int F, int B, int de
     return rc;
 }
 
+/* ---- the input-format options: one row each ------------------------------ */
+typedef void (*pack_fn)(int W, int H, const void *from, void *to);
+typedef int (*whdr_fn)(FILE *f, int W, int H, int fps_num, int fps_den, int depth);
+typedef int (*wframe_fn)(FILE *f, int W, int H, int depth, const void *planes);
+#define PACK_FN(name, call) static void name(int W, int H, const void *a, void *b) { call; }
+PACK_FN(pack_nv12, y4m_420_to_nv12(W, H, a, b))
+PACK_FN(unpack_nv12, y4m_nv12_to_420(W, H, a, b))
+PACK_FN(pack_p010, y4m_420p10_to_p010(W, H, a, b))
+PACK_FN(unpack_p010, y4m_p010_to_420p10(W, H, a, b))
+PACK_FN(pack_yuy2, y4m_422_to_packed(W, H, a, b, 0))
+PACK_FN(unpack_yuy2, y4m_packed_to_422(W, H, a, b, 0))
+PACK_FN(pack_uyvy, y4m_422_to_packed(W, H, a, b, 1))
+PACK_FN(unpack_uyvy, y4m_packed_to_422(W, H, a, b, 1))
+PACK_FN(pack_y210, y4m_422p10_to_y210(W, H, a, b))
+PACK_FN(unpack_y210, y4m_y210_to_422p10(W, H, a, b))
+/* the .y4m writers of one chroma type under one signature (mono's own take the depth) */
+#define WRITE_FNS(name, hdr, frame)                                                        \
+    static int whdr_##name(FILE *f, int W, int H, int n, int d, int depth) { (void)depth; return hdr(f, W, H, n, d); } \
+    static int wframe_##name(FILE *f, int W, int H, int depth, const void *p) { (void)depth; return frame(f, W, H, p); }
+WRITE_FNS(444, y4m_write_header, y4m_write_frame)
+WRITE_FNS(420, y4m_write_header_420, y4m_write_frame_420)
+WRITE_FNS(420p10, y4m_write_header_420p10, y4m_write_frame_420p10)
+WRITE_FNS(422, y4m_write_header_422, y4m_write_frame_422)
+WRITE_FNS(422p10, y4m_write_header_422p10, y4m_write_frame_422p10)
+
+typedef struct {
+    const char *name;     /* the flag */
+    int chroma, depth;    /* the .y4m it takes: chroma type (-1: none) and bit depth (0: any, the code follows it) */
+    int raw;              /* any other extension: the raw frames (else a .y4m only) */
+    int fmt, fmt_full;    /* the frame format; with --full-range */
+    int ycc;              /* Y'CbCr: takes --matrix and --full-range, needs even sizes */
+    int views;            /* goes with --show-magnitude / --show-phase */
+    int decode;           /* goes with --out-rgba8 */
+    const char *needs;    /* the input it needs, in the refusal's words */
+    pack_fn pack, unpack; /* .y4m planes -> frame and back (NULL: the frame goes as it lies in the file) */
+    whdr_fn whdr;         /* the .y4m it writes */
+    wframe_fn wframe;
+} in_opt;
+static const in_opt k_in_opts[] = {
+    {"--nv12", Y4M_420, 8, 0, MM_NV12, MM_NV12_FULL, 1, 0, 1, "an 8-bit 4:2:0 .y4m input (-i, C420)",
+     pack_nv12, unpack_nv12, whdr_420, wframe_420},
+    {"--p010", Y4M_420, 10, 0, MM_P010, MM_P010_FULL, 1, 0, 1, "a 10-bit input (C420p10), a 4:2:0 .y4m (-i)",
+     pack_p010, unpack_p010, whdr_420p10, wframe_420p10},
+    {"--i420", Y4M_420, 8, 1, MM_I420, MM_I420_FULL, 1, 0, 0,
+     "an 8-bit 4:2:0 .y4m input (-i, C420; a C420p10 stream takes --p010 or --i010), or raw I420 frames under any other extension",
+     NULL, NULL, whdr_420, wframe_420},
+    {"--i010", Y4M_420, 10, 1, MM_I010, MM_I010_FULL, 1, 0, 0,
+     "a 10-bit 4:2:0 .y4m input (-i, C420p10; an 8-bit C420 stream takes --i420), or raw I010 frames under any other extension",
+     NULL, NULL, whdr_420p10, wframe_420p10},
+    {"--mono", Y4M_MONO, 0, 0, MM_Y8, MM_Y8, 0, 1, 0, "a mono .y4m input (-i, Cmono / Cmono10 / Cmono12 / Cmono16)",
+     NULL, NULL, y4m_write_header_mono, y4m_write_frame_mono},
+    {"--yuy2", Y4M_422, 8, 0, MM_YUY2, MM_YUY2_FULL, 1, 0, 0, "an 8-bit 4:2:2 .y4m input (-i, C422)",
+     pack_yuy2, unpack_yuy2, whdr_422, wframe_422},
+    {"--uyvy", Y4M_422, 8, 0, MM_UYVY, MM_UYVY_FULL, 1, 0, 0, "an 8-bit 4:2:2 .y4m input (-i, C422)",
+     pack_uyvy, unpack_uyvy, whdr_422, wframe_422},
+    {"--y210", Y4M_422, 10, 0, MM_Y210, MM_Y210_FULL, 1, 0, 0, "a 10-bit 4:2:2 .y4m input (-i, C422p10)",
+     pack_y210, unpack_y210, whdr_422p10, wframe_422p10},
+    /* (a stream of binary PPM images: its own reader and writer, main's ppm branches; --bgr) */
+    {"--ppm", -1, 8, 1, MM_RGB24, MM_RGB24, 0, 0, 0,
+     "a binary PPM stream as input (-i, P6, maxval 255) and writes one (-o): no .y4m on either side", NULL, NULL, NULL, NULL},
+};
+static const in_opt *const k_opt_nv12 = &k_in_opts[0], *const k_opt_ppm = &k_in_opts[8];
+
+/* The option a .y4m input cannot do without: the host converts 8-bit 4:2:0,
+ * 4:4:4 and mono to RGBA8 and nothing else, and no bit depth silently. */
+static const char *y4m_needs(const y4m_info *yi, int depth)
+{
+    if (yi->chroma == Y4M_422) return depth == 10 ? "--y210" : "--yuy2 or --uyvy";
+    if (depth == 8) return NULL;
+    return yi->chroma == Y4M_MONO ? "--mono" : "--p010";
+}
+
+#define REFUSE(...) do { fprintf(stderr, __VA_ARGS__); return 2; } while (0)
+
 int main(int argc, char **argv)
 {
     int W = 1920, H = 1080, F = 300, L = 5, B = 30, dev = 0;
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
-    int nv12 = 0, p010 = 0, srgb = 0, mono = 0, yuy2 = 0, uyvy = 0, y210 = 0, ppm = 0, bgr = 0;
-    int out_rgba8 = 0, out_nv12 = 0, i420 = 0, i010 = 0;
+    int srgb = 0, bgr = 0, out_rgba8 = 0, out_nv12 = 0;
+    const in_opt *in = NULL;   /* the input-format option: one at most */
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
     const char *in_path = NULL, *out_path = NULL, *ring_id_path = NULL;
     for (int i = 1; i < argc; ++i) {
         const char *a = argv[i];
+        const in_opt *o = NULL;
+        for (size_t k = 0; k < sizeof k_in_opts / sizeof *k_in_opts; ++k)
+            if (!strcmp(a, k_in_opts[k].name)) o = &k_in_opts[k];
+        if (o) {
+            if (in && in != o) REFUSE("%s does not go with %s (one input format)\n", in->name, o->name);
+            in = o;
+            continue;
+        }
         if (!strcmp(a, "--full-range")) { full_range = 1; continue; }
         if (!strcmp(a, "--srgb")) { g_fmt = MM_RGBA8_SRGB; srgb = 1; continue; }
-        if (!strcmp(a, "--nv12")) { nv12 = 1; continue; }
-        if (!strcmp(a, "--p010")) { p010 = 1; continue; }
-        if (!strcmp(a, "--mono")) { mono = 1; continue; }
-        if (!strcmp(a, "--yuy2")) { yuy2 = 1; continue; }
-        if (!strcmp(a, "--uyvy")) { uyvy = 1; continue; }
-        if (!strcmp(a, "--y210")) { y210 = 1; continue; }
-        if (!strcmp(a, "--ppm")) { ppm = 1; continue; }
         if (!strcmp(a, "--bgr")) { bgr = 1; continue; }
-        if (!strcmp(a, "--i420")) { i420 = 1; continue; }
-        if (!strcmp(a, "--i010")) { i010 = 1; continue; }
         if (!strcmp(a, "--out-rgba8")) { out_rgba8 = 1; continue; }
         if (!strcmp(a, "--out-nv12")) { out_nv12 = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
@@ -559,32 +628,36 @@ int main(int argc, char **argv)
         ++i;
     }
     if (B < 1) B = 1;
-    /* --i010 with another format option: refused before any file is opened */
-    if (i010 && (nv12 || p010 || i420 || mono || yuy2 || uyvy || y210 || ppm || out_rgba8 || out_nv12 || srgb || show_mag ||
-                 show_phase || ring_local > 0 || ring_world > 0)) {
-        fprintf(stderr, "--i010 does not go with --nv12, --p010, --i420, --mono, --yuy2, --uyvy, --y210, --ppm, --out-rgba8, "
-                        "--out-nv12, --srgb, the debug views or the ring modes\n");
-        return 2;
+    /* Every refusal below comes before the output file is opened and before the
+     * device is touched.  First what the options say by themselves. */
+    const int views = show_mag || show_phase, ring = ring_local > 0 || ring_world > 0;
+    const int p_ppm = in == k_opt_ppm;
+    if (in) {
+        const char *bad = srgb ? "--srgb" : ring ? "the ring modes (they take RGBA frames)"
+                          : views && !in->views ? "the debug views" : out_nv12 ? "--out-nv12 (it takes the RGBA8 input path)"
+                          : out_rgba8 && !in->decode ? "--out-rgba8 (it takes --nv12 or --p010)"
+                          : matrix_arg && !in->ycc ? "--matrix (there is no matrix)"
+                          : full_range && !in->ycc ? "--full-range (there is no range)" : NULL;
+        if (bad) REFUSE("%s does not go with %s\n", in->name, bad);
+        if (!in_path) REFUSE("%s needs an input (-i): %s\n", in->name, in->needs);
     }
-    if (i010 && !in_path) {
-        fprintf(stderr, "--i010 needs an input (-i): a 10-bit 4:2:0 .y4m (C420p10) or raw I010 frames\n");
-        return 2;
-    }
-    /* --i420 with another format option: refused before any file is opened */
-    if (i420 && (nv12 || p010 || mono || yuy2 || uyvy || y210 || ppm || out_rgba8 || out_nv12 || srgb || show_mag ||
-                 show_phase || ring_local > 0 || ring_world > 0)) {
-        fprintf(stderr, "--i420 does not go with --nv12, --p010, --mono, --yuy2, --uyvy, --y210, --ppm, --out-rgba8, "
-                        "--out-nv12, --srgb, the debug views or the ring modes\n");
-        return 2;
-    }
-    if (i420 && !in_path) {
-        fprintf(stderr, "--i420 needs an input (-i): an 8-bit 4:2:0 .y4m (C420) or raw I420 frames\n");
-        return 2;
-    }
+    if (bgr && !p_ppm) REFUSE("--bgr needs --ppm\n");
+    /* different formats in and out (mm_process_stream_convert) */
+    if (out_rgba8 && out_nv12) REFUSE("--out-rgba8 does not go with --out-nv12\n");
+    if (out_rgba8 && !in) REFUSE("--out-rgba8 needs --nv12 or --p010 (the default path's output is RGBA8 already)\n");
+    if (out_nv12 && (srgb || views || ring))
+        REFUSE("--out-nv12 takes the RGBA8 input path: not with --srgb, the debug views or the ring modes\n");
+    if (matrix_arg && !(in && in->ycc) && !out_nv12)
+        REFUSE("--matrix needs --nv12, --p010, --yuy2, --uyvy, --y210, --i420, --i010 or --out-nv12 (the RGBA conversion of a .y4m is BT.601)\n");
+    if (matrix_arg && strcmp(matrix_arg, "601") && strcmp(matrix_arg, "709") && strcmp(matrix_arg, "2020"))
+        REFUSE("--matrix takes 601, 709 or 2020, not %s (%s)\n", matrix_arg, in ? in->name : "--out-nv12");
+    if (surf_arg && ring) REFUSE("--surface-align does not go with the ring modes (they take tight frames)\n");
+    if (ring_local > 0 && (in_path || out_path)) REFUSE("--ring-local needs a synthetic stream\n");
+    if (ring_world > 0 && ring_local <= 0 && (!ring_id_path || in_path || out_path))
+        REFUSE("--ring-world needs --ring-id and a synthetic stream\n");
+    /* ... then what the input says: the container and the geometry */
     FILE *fi = in_path ? fopen(in_path, "rb") : NULL;
-    const int planes3 = i420 || i010;   /* the file's frames go as they lie; the output opens after the refusals */
-    FILE *fo = out_path && !planes3 ? fopen(out_path, "wb") : NULL;
-    if ((in_path && !fi) || (out_path && !fo && !planes3)) { fprintf(stderr, "cannot open file\n"); return 1; }
+    if (in_path && !fi) { fprintf(stderr, "cannot open file\n"); return 1; }
     const int y4m_in = in_path && ends_with(in_path, ".y4m");
     const int y4m_out = out_path && ends_with(out_path, ".y4m");
     y4m_info yi = {0};
@@ -596,82 +669,18 @@ int main(int argc, char **argv)
         W = yi.width;
         H = yi.height;
     }
-    /* --i420: the frames of a C420 .y4m are MM_I420 frames as they lie (the
-     * output file is opened after the refusals: they write nothing) */
-    if (i420) {
-        if (y4m_in && (yi.chroma != Y4M_420 || depth != 8)) {
-            fprintf(stderr, "--i420 needs an 8-bit 4:2:0 .y4m input (C420; a C420p10 stream takes --p010), "
-                            "or raw I420 frames under any other extension\n");
-            return 2;
-        }
-        if ((W | H) & 1) {
-            fprintf(stderr, "--i420 needs even width and height (%dx%d)\n", W, H);
-            return 2;
-        }
-        if (matrix_arg && strcmp(matrix_arg, "601") && strcmp(matrix_arg, "709") && strcmp(matrix_arg, "2020")) {
-            fprintf(stderr, "--matrix takes 601, 709 or 2020, not %s (--i420)\n", matrix_arg);
-            return 2;
-        }
-        g_fmt = full_range ? MM_I420_FULL : MM_I420;
-        if (out_path && !(fo = fopen(out_path, "wb"))) { fprintf(stderr, "cannot open file\n"); return 1; }
+    const char *hint = y4m_in ? y4m_needs(&yi, depth) : NULL;
+    if (in && ((y4m_in ? yi.chroma != in->chroma || (in->depth && depth != in->depth) : !in->raw) || (p_ppm && y4m_out))) {
+        if (hint) REFUSE("%s needs %s; %s needs %s\n", in->name, in->needs, in_path, hint);
+        REFUSE("%s needs %s\n", in->name, in->needs);
     }
-    /* --i010: the frames of a C420p10 .y4m are MM_I010 frames as they lie */
-    if (i010) {
-        if (y4m_in && (yi.chroma != Y4M_420 || depth != 10)) {
-            fprintf(stderr, "--i010 needs a 10-bit 4:2:0 .y4m input (C420p10; an 8-bit C420 stream takes --i420), "
-                            "or raw I010 frames under any other extension\n");
-            return 2;
-        }
-        if ((W | H) & 1) {
-            fprintf(stderr, "--i010 needs even width and height (%dx%d)\n", W, H);
-            return 2;
-        }
-        if (matrix_arg && strcmp(matrix_arg, "601") && strcmp(matrix_arg, "709") && strcmp(matrix_arg, "2020")) {
-            fprintf(stderr, "--matrix takes 601, 709 or 2020, not %s (--i010)\n", matrix_arg);
-            return 2;
-        }
-        g_fmt = full_range ? MM_I010_FULL : MM_I010;
-        if (out_path && !(fo = fopen(out_path, "wb"))) { fprintf(stderr, "cannot open file\n"); return 1; }
-    }
-    /* different formats in and out (mm_process_stream_convert) */
-    if (out_rgba8 && out_nv12) {
-        fprintf(stderr, "--out-rgba8 does not go with --out-nv12\n");
-        return 2;
-    }
-    if (out_rgba8 && !nv12 && !p010) {
-        fprintf(stderr, "--out-rgba8 needs --nv12 or --p010 (the default path's output is RGBA8 already)\n");
-        return 2;
-    }
-    if (out_nv12) {
-        if (nv12 || p010 || mono || yuy2 || uyvy || y210 || ppm || srgb || show_mag || show_phase || ring_local > 0 ||
-            ring_world > 0) {
-            fprintf(stderr, "--out-nv12 takes the RGBA8 input path: not with --nv12, --p010, --mono, --yuy2, --uyvy, "
-                            "--y210, --ppm, --srgb, the debug views or the ring modes\n");
-            return 2;
-        }
-        if ((W | H) & 1) {
-            fprintf(stderr, "--out-nv12 needs even width and height (%dx%d)\n", W, H);
-            return 2;
-        }
-    }
+    if (!in && hint)
+        REFUSE("%s is a %d-bit %s stream: it needs %s (it is never converted on the host)\n", in_path, depth,
+               yi.chroma == Y4M_422 ? "4:2:2" : yi.chroma == Y4M_MONO ? "mono" : "4:2:0", hint);
     /* --ppm: a stream of binary PPM images is a stream of MM_RGB24 frames */
     ppm_info pi = {0, 0};
     int ppm_pending = 0;   /* the first image's header is read, its pixels are not */
-    if (bgr && !ppm) {
-        fprintf(stderr, "--bgr needs --ppm\n");
-        return 2;
-    }
-    if (ppm) {
-        if (nv12 || p010 || mono || yuy2 || uyvy || y210 || srgb || matrix_arg || full_range || show_mag || show_phase ||
-            ring_local > 0 || ring_world > 0) {
-            fprintf(stderr, "--ppm does not go with --nv12, --p010, --mono, --yuy2, --uyvy, --y210, --srgb, --matrix, "
-                            "--full-range, the debug views or the ring modes\n");
-            return 2;
-        }
-        if (!fi || y4m_in || y4m_out) {
-            fprintf(stderr, "--ppm needs a binary PPM stream as input (-i, P6, maxval 255) and writes one (-o)\n");
-            return 2;
-        }
+    if (p_ppm) {
         const int rc = ppm_read_header(fi, &pi);
         if (rc) {
             fprintf(stderr, "%s: %s\n", in_path,
@@ -682,136 +691,24 @@ int main(int argc, char **argv)
         W = pi.width;
         H = pi.height;
         ppm_pending = 1;
-        g_fmt = bgr ? MM_BGR24 : MM_RGB24;
     }
-    const int p422 = yuy2 || uyvy;   /* packed 4:2:2 */
-    if (y210) {   /* its 10-bit form */
-        if (p422 || nv12 || p010 || mono || srgb || show_mag || show_phase || ring_local > 0 || ring_world > 0) {
-            fprintf(stderr, "--y210 does not go with --yuy2, --uyvy, --nv12, --p010, --mono, --srgb, the debug views "
-                            "or the ring modes\n");
-            return 2;
-        }
-        if (!y4m_in || yi.chroma != Y4M_422 || depth != 10) {
-            fprintf(stderr, "--y210 needs a 10-bit 4:2:2 .y4m input (-i, C422p10)\n");
-            return 2;
-        }
-        if ((W | H) & 1) {
-            fprintf(stderr, "--y210 needs even width and height (%dx%d)\n", W, H);
-            return 2;
-        }
-        g_fmt = full_range ? MM_Y210_FULL : MM_Y210;
-    } else if (y4m_in && yi.chroma == Y4M_422 && depth == 10) {
-        fprintf(stderr, "%s is a 10-bit 4:2:2 stream (C422p10): it needs --y210 "
-                        "(there is no 4:2:2 to RGBA conversion on the host)\n", in_path);
-        return 2;
-    } else if (p422) {
-        const char *opt = yuy2 ? "--yuy2" : "--uyvy";
-        if (yuy2 && uyvy) {
-            fprintf(stderr, "--yuy2 does not go with --uyvy (one byte order)\n");
-            return 2;
-        }
-        if (srgb || show_mag || show_phase || ring_local > 0 || ring_world > 0 || nv12 || p010 || mono) {
-            fprintf(stderr, "%s does not go with --srgb, the debug views, the ring modes, --nv12, --p010 or --mono\n",
-                    opt);
-            return 2;
-        }
-        if (!y4m_in || yi.chroma != Y4M_422) {
-            fprintf(stderr, "%s needs an 8-bit 4:2:2 .y4m input (-i, C422)\n", opt);
-            return 2;
-        }
-        if ((W | H) & 1) {
-            fprintf(stderr, "%s needs even width and height (%dx%d)\n", opt, W, H);
-            return 2;
-        }
-        g_fmt = uyvy ? (full_range ? MM_UYVY_FULL : MM_UYVY) : (full_range ? MM_YUY2_FULL : MM_YUY2);
-    } else if (y4m_in && yi.chroma == Y4M_422) {
-        fprintf(stderr, "%s is a 4:2:2 stream (C422): it needs --yuy2 or --uyvy "
-                        "(there is no 4:2:2 to RGBA conversion on the host)\n", in_path);
-        return 2;
-    }
-    if (mono) {
-        if (nv12 || p010 || srgb || matrix_arg || full_range) {
-            fprintf(stderr, "--mono does not go with --nv12, --p010, --srgb, --matrix or --full-range\n");
-            return 2;
-        }
-        if (ring_local > 0 || ring_world > 0) {
-            fprintf(stderr, "--mono does not go with the ring modes (they take RGBA frames)\n");
-            return 2;
-        }
-        if (!y4m_in || yi.chroma != Y4M_MONO) {
-            fprintf(stderr, "--mono needs a mono .y4m input (-i, Cmono / Cmono10 / Cmono12 / Cmono16)\n");
-            return 2;
-        }
-        g_fmt = depth == 8 ? MM_Y8 : depth == 10 ? MM_Y10 : depth == 12 ? MM_Y12 : MM_Y16;
-    }
-    if (p010) {
-        if (nv12) {
-            fprintf(stderr, "--p010 does not go with --nv12\n");
-            return 2;
-        }
-        if (srgb || show_mag || show_phase || ring_local > 0 || ring_world > 0) {
-            fprintf(stderr, "--p010 does not go with --srgb, the debug views or the ring modes\n");
-            return 2;
-        }
-        if (!y4m_in || yi.chroma != Y4M_420) {
-            fprintf(stderr, "--p010 needs a 10-bit 4:2:0 .y4m input (-i, C420p10)\n");
-            return 2;
-        }
-        if (depth != 10) {
-            fprintf(stderr, "--p010 needs a 10-bit input (C420p10); %s is 8-bit (--nv12 takes it as it is)\n",
-                    in_path);
-            return 2;
-        }
-        if ((W | H) & 1) {
-            fprintf(stderr, "--p010 needs even width and height (%dx%d)\n", W, H);
-            return 2;
-        }
-        g_fmt = full_range ? MM_P010_FULL : MM_P010;
-    } else if (depth != 8 && !mono && !y210 && !i010) {
-        if (yi.chroma == Y4M_MONO)
-            fprintf(stderr, "%s is a %d-bit mono stream (Cmono%d): it needs --mono\n", in_path, depth, depth);
-        else
-            fprintf(stderr, "%s is a 10-bit stream (C420p10): it needs --p010\n", in_path);
-        return 2;
-    }
-    if (nv12) {
-        if (srgb || show_mag || show_phase || ring_local > 0 || ring_world > 0) {
-            fprintf(stderr, "--nv12 does not go with --srgb, the debug views or the ring modes\n");
-            return 2;
-        }
-        if (!y4m_in || yi.chroma != Y4M_420) {
-            fprintf(stderr, "--nv12 needs a 4:2:0 .y4m input (-i)\n");
-            return 2;
-        }
-        if ((W | H) & 1) {
-            fprintf(stderr, "--nv12 needs even width and height (%dx%d)\n", W, H);
-            return 2;
-        }
-        g_fmt = full_range ? MM_NV12_FULL : MM_NV12;
-    }
-    /* the output side's format: the input's, but with --out-rgba8 / --out-nv12 */
-    int o_fmt = out_nv12 ? (full_range ? MM_NV12_FULL : MM_NV12) : 0;
-    if (matrix_arg) {
-        if (!nv12 && !p010 && !p422 && !y210 && !out_nv12 && !planes3) {
-            fprintf(stderr, "--matrix needs --nv12, --p010, --yuy2, --uyvy, --y210, --i420, --i010 or --out-nv12 (the RGBA conversion of a .y4m is BT.601)\n");
-            return 2;
-        }
-        /* (--out-nv12: the bit names the output code; the input is RGBA8) */
-        int *mf = out_nv12 ? &o_fmt : &g_fmt;
-        if (!strcmp(matrix_arg, "709")) *mf |= MM_MATRIX_BT709;
-        else if (!strcmp(matrix_arg, "2020")) *mf |= MM_MATRIX_BT2020;
-        else if (strcmp(matrix_arg, "601")) {
-            fprintf(stderr, "--matrix takes 601, 709 or 2020, not %s\n", matrix_arg);
-            return 2;
-        }
-    }
-    if (out_rgba8) o_fmt = MM_RGBA8;
-    else if (!out_nv12) o_fmt = g_fmt;
+    if (((in && in->ycc) || out_nv12) && ((W | H) & 1))
+        REFUSE("%s needs even width and height (%dx%d)\n", in ? in->name : "--out-nv12", W, H);
+    /* the frame format: the row's code (mono: by the header's depth), the
+     * output side's with --out-rgba8 / --out-nv12; --matrix's bit goes on the
+     * Y'CbCr side (--out-nv12: it names the output code, the input is RGBA8) */
+    const int mbit = !matrix_arg ? 0 : !strcmp(matrix_arg, "709") ? MM_MATRIX_BT709
+                     : !strcmp(matrix_arg, "2020") ? MM_MATRIX_BT2020 : 0;
+    if (in)
+        g_fmt = !in->depth ? (depth == 8 ? MM_Y8 : depth == 10 ? MM_Y10 : depth == 12 ? MM_Y12 : MM_Y16)
+                : p_ppm && bgr ? MM_BGR24 : (full_range ? in->fmt_full : in->fmt) | mbit;
+    const int o_fmt = out_nv12 ? (full_range ? MM_NV12_FULL : MM_NV12) | mbit : out_rgba8 ? MM_RGBA8 : g_fmt;
     const int convert = o_fmt != g_fmt;
-    /* what the output files hold */
-    /* (--i420: a C420 file too, its frames written as they lie) */
-    /* (--i010: a C420p10 file, the same way) */
-    const int w_nv12 = out_nv12 || (nv12 && !out_rgba8) || i420, w_p010 = (p010 && !out_rgba8) || i010;
+    /* what a .y4m output holds, and how its frames are made: the input
+     * option's, --out-nv12: --nv12's, --out-rgba8 or no option: 4:4:4 from RGBA8 */
+    const in_opt *wr = out_nv12 ? k_opt_nv12 : out_rgba8 ? NULL : in;
+    FILE *fo = out_path ? fopen(out_path, "wb") : NULL;
+    if (out_path && !fo) { fprintf(stderr, "cannot open file\n"); return 1; }
     mm_params p;
     mm_params_default(&p);
     p.levels = L;
@@ -821,17 +718,7 @@ int main(int argc, char **argv)
     p.temporal_filter = iir ? MM_FILTER_IIR : MM_FILTER_DIFF;
     p.show_magnitude = show_mag;
     p.show_phase = show_phase;
-    if (surf_arg && (ring_local > 0 || ring_world > 0)) {
-        fprintf(stderr, "--surface-align does not go with the ring modes (they take tight frames)\n");
-        return 2;
-    }
-    if (ring_local > 0) {
-        if (fi || fo) {
-            fprintf(stderr, "--ring-local needs a synthetic stream\n");
-            return 2;
-        }
-        return run_ring_local(&p, W, H, F, B, dev, ring_local, checksum, halo, compare);
-    }
+    if (ring_local > 0) return run_ring_local(&p, W, H, F, B, dev, ring_local, checksum, halo, compare);
     /* mm_create runs on `dev` and gives the caller's current device back:
      * this program's own buffers, events and default stream must be on `dev`
      * too (before its first HIP allocation) */
@@ -845,10 +732,6 @@ int main(int argc, char **argv)
     mm_padded_size(h, &N);
     printf("Original: %dx%d, Padded: %dx%d\n", W, H, N, N);   /* .cs:304 */
     if (ring_world > 0) {
-        if (!ring_id_path || fi || fo) {
-            fprintf(stderr, "--ring-world needs --ring-id and a synthetic stream\n");
-            return 2;
-        }
         CHECK(mm_set_batch(h, B));
         const int rc = run_ring(h, W, H, F, B, dev, ring_world, ring_rank, ring_id_path, checksum, halo);
         mm_destroy(h);
@@ -856,7 +739,7 @@ int main(int argc, char **argv)
     }
 
     size_t fb = (size_t)W * H * 4;
-    if (nv12 || p010 || mono || p422 || y210 || ppm || planes3) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
+    if (in) CHECK(mm_frame_bytes(W, H, g_fmt, &fb));
     /* --surface-align: the frames the operator sees live in `lay` surfaces
      * (d_in, d_out); d_tin / d_tout are tight device frames for the synthetic
      * source and for the checksums and files */
@@ -895,12 +778,7 @@ int main(int argc, char **argv)
         : NULL;
     /* (planes: 3 W H bytes hold a C420p10 frame, 2 bytes per sample, exactly; a
      * C422p10 frame takes 4 W H) */
-    if (y4m_out && (mono   ? y4m_write_header_mono(fo, W, H, yi.fps_num, yi.fps_den, depth)
-                    : w_p010 ? y4m_write_header_420p10(fo, W, H, yi.fps_num, yi.fps_den)
-                    : w_nv12 ? y4m_write_header_420(fo, W, H, yi.fps_num, yi.fps_den)
-                    : p422 ? y4m_write_header_422(fo, W, H, yi.fps_num, yi.fps_den)
-                    : y210 ? y4m_write_header_422p10(fo, W, H, yi.fps_num, yi.fps_den)
-                           : y4m_write_header(fo, W, H, yi.fps_num, yi.fps_den))) {
+    if (y4m_out && (wr ? wr->whdr : whdr_444)(fo, W, H, yi.fps_num, yi.fps_den, depth)) {
         fprintf(stderr, "write failed\n");
         return 1;
     }
@@ -915,25 +793,19 @@ int main(int argc, char **argv)
         if (fi && y4m_in) {
             int got = 0;
             for (; got < n; ++got) {
-                /* (mono: the samples are the frame, read straight into place;
-                 * --i420: the three planes are the frame, the same way) */
-                const int r = mono ? y4m_read_frame_mono(fi, W, H, depth, host + fb * got)
-                              : planes3 ? y4m_read_frame_depth(fi, &yi, depth, host + fb * got)
-                                     : y4m_read_frame_depth(fi, &yi, depth, planes);
+                /* (no pack function: the file's planes are the frame, read straight into place) */
+                unsigned char *frame = host + fb * got;
+                const int r = y4m_read_frame_depth(fi, &yi, depth, in && !in->pack ? frame : planes);
                 if (r < 0) { fprintf(stderr, "%s: malformed frame\n", in_path); return 1; }
                 if (r == 0) break;
-                if (mono || planes3) continue;
-                if (p010) y4m_420p10_to_p010(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
-                else if (nv12) y4m_420_to_nv12(W, H, planes, host + fb * got);
-                else if (p422) y4m_422_to_packed(W, H, planes, host + fb * got, uyvy);
-                else if (y210) y4m_422p10_to_y210(W, H, (const uint16_t *)planes, (uint16_t *)(host + fb * got));
+                if (in && in->pack) in->pack(W, H, planes, frame);
                 /* (--out-nv12: --full-range names the output code, the input is limited range) */
-                else y4m_to_rgba(&yi, planes, host + fb * got, out_nv12 ? 0 : full_range);
+                else if (!in) y4m_to_rgba(&yi, planes, frame, out_nv12 ? 0 : full_range);
             }
             if (got == 0) break;
             n = got;
             if (surf_copy(d_in, &lay, host, &tight, W, H, n, hipMemcpyHostToDevice, s)) return 1;
-        } else if (fi && ppm) {
+        } else if (fi && p_ppm) {
             /* images of the first one's size, as they lie (--bgr: R and B swapped) */
             int got = 0;
             for (; got < n; ++got) {
@@ -984,42 +856,16 @@ int main(int argc, char **argv)
             hipMemcpy(host, d_res, fbo * n, hipMemcpyDeviceToHost);
             if (y4m_out) {
                 for (int k = 0; k < n; ++k) {
-                    if (mono) {
-                        if (y4m_write_frame_mono(fo, W, H, depth, host + fb * k)) {
-                            fprintf(stderr, "write failed\n");
-                            return 1;
-                        }
-                        continue;
-                    }
-                    if (i420) {   /* the frame is the file's three planes */
-                        if (y4m_write_frame_420(fo, W, H, host + fb * k)) {
-                            fprintf(stderr, "write failed\n");
-                            return 1;
-                        }
-                        continue;
-                    }
-                    if (i010) {   /* ... its three planes of words */
-                        if (y4m_write_frame_420p10(fo, W, H, (const uint16_t *)(host + fb * k))) {
-                            fprintf(stderr, "write failed\n");
-                            return 1;
-                        }
-                        continue;
-                    }
-                    if (w_p010) y4m_p010_to_420p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
-                    else if (w_nv12) y4m_nv12_to_420(W, H, host + fbo * k, planes);
-                    else if (p422) y4m_packed_to_422(W, H, host + fb * k, planes, uyvy);
-                    else if (y210) y4m_y210_to_422p10(W, H, (const uint16_t *)(host + fb * k), (uint16_t *)planes);
-                    else y4m_from_rgba(W, H, host + fbo * k, planes, full_range);
-                    if (w_p010   ? y4m_write_frame_420p10(fo, W, H, (const uint16_t *)planes)
-                        : w_nv12 ? y4m_write_frame_420(fo, W, H, planes)
-                        : p422 ? y4m_write_frame_422(fo, W, H, planes)
-                        : y210 ? y4m_write_frame_422p10(fo, W, H, (const uint16_t *)planes)
-                               : y4m_write_frame(fo, W, H, planes)) {
+                    /* (no unpack function: the frame is the file's planes) */
+                    const unsigned char *frame = host + fbo * k;
+                    if (wr && wr->unpack) wr->unpack(W, H, frame, planes);
+                    else if (!wr) y4m_from_rgba(W, H, frame, planes, full_range);
+                    if ((wr ? wr->wframe : wframe_444)(fo, W, H, depth, wr && !wr->unpack ? frame : planes)) {
                         fprintf(stderr, "write failed\n");
                         return 1;
                     }
                 }
-            } else if (ppm) {   /* the same container back */
+            } else if (p_ppm) {   /* the same container back */
                 for (int k = 0; k < n; ++k) {
                     if (bgr) ppm_swap_rb(host + fb * k, (size_t)W * H);
                     if (ppm_write_frame(fo, W, H, host + fb * k)) {

@@ -35,78 +35,75 @@ def _is_device(frame):
     return bool(getattr(frame, "is_cuda", False))
 
 
+# One row per family of formats: what a frame of it looks like as an array.
+#   shape(H, W); dtype name (None: the frame's own, any RGBA dtype); the inner
+#   strides in items, innermost last; whether rows may lie a pitch apart (else
+#   the frame is contiguous: its planes have no room for one); the error's wording
+_CONTIGUOUS_3P = "a three-plane 4:2:0 frame must be contiguous (name a Surface through Handle.process_surface)"
+_FAMILIES = {
+    "rgba": (lambda h, w: (h, w, 4), None, (4, 1), True, "pixels and channels packed"),
+    "rgb24": (lambda h, w: (h, w, 3), "uint8", (3, 1), True, "pixels and channels packed"),   # rows at any byte
+    "y8": (lambda h, w: (h, w), "uint8", (1,), True, "samples packed"),
+    "y16": (lambda h, w: (h, w), "uint16", (1,), True, "samples packed"),
+    # [H, 2 W]: rows of W / 2 macropixels, four bytes or (Y210) four words Y0 Cb Y1 Cr
+    "yuv422": (lambda h, w: (h, 2 * w), "uint8", (1,), True, "bytes packed"),
+    "y210": (lambda h, w: (h, 2 * w), "uint16", (1,), True, "words packed"),
+    # one contiguous [H * 3 / 2, W] array: H luma rows, then H / 2 rows of chroma
+    # (one (Cb, Cr) plane, or a Cb and a Cr plane), in bytes or 16-bit words
+    # (the two-plane rows: shape and dtype only, for _convert_side and host_frames.  Such
+    # a frame is never named to frame_layout, which holds it to the RGBA row.)
+    "nv12": (lambda h, w: (h * 3 // 2, w), "uint8", None, None, None),
+    "p010": (lambda h, w: (h * 3 // 2, w), "uint16", None, None, None),
+    "i420": (lambda h, w: (h * 3 // 2, w), "uint8", (1,), False, _CONTIGUOUS_3P),
+    "i010": (lambda h, w: (h * 3 // 2, w), "uint16", (1,), False, _CONTIGUOUS_3P),
+}
+
+
+def _family(fmt):
+    if fmt in RGB24_FORMATS:
+        return "rgb24"
+    if fmt in MONO_FORMATS:
+        return "y8" if fmt == Y8 else "y16"
+    base = base_format(fmt)         # a matrix bit changes no size or shape
+    for name, codes in (("yuv422", PACKED422_FORMATS), ("y210", Y210_FORMATS), ("i420", I420_FORMATS),
+                        ("i010", I010_FORMATS), ("nv12", (NV12, NV12_FULL)), ("p010", (P010, P010_FULL))):
+        if base in codes:
+            return name
+    return "rgba"
+
+
 def frame_layout(frame, width, height, fmt):
-    """The mm_surface of a row-strided [H, W, 4] frame (torch tensor or numpy
-    array): channels and pixels packed, rows any valid pitch apart, so that a
-    region of interest is ``parent[y:y+H, x:x+W]``.  None for a contiguous
-    frame (the tight entry point); MMError for any other striding.  Needs no GPU."""
+    """The mm_surface of a row-strided frame (torch tensor or numpy array) in
+    its format's shape (RGBA: [H, W, 4]): channels and pixels packed, rows any
+    valid pitch apart, so that a region of interest is ``parent[y:y+H, x:x+W]``.
+    None for a contiguous frame (the tight entry point); MMError for any other
+    striding.  Needs no GPU.  (A two-plane 4:2:0 frame is no frame of this call:
+    it is held to the RGBA shape.)"""
+    fam = _family(fmt)
+    shape, dtype, inner, pitched, packed = _FAMILIES["rgba" if fam in ("nv12", "p010") else fam]
     if isinstance(frame, np.ndarray):
         item = frame.itemsize
         strides = tuple(frame.strides)                       # bytes
     else:
         item = frame.element_size()
         strides = tuple(s * item for s in frame.stride())    # elements -> bytes
-    if base_format(fmt) in PACKED422_FORMATS:   # [H, 2 W] bytes: rows of W / 2 macropixels
-        if tuple(frame.shape) != (height, 2 * width) or not str(frame.dtype).endswith("uint8"):
-            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height, 2 * width)} uint8)")
-        if strides[1] != 1 or strides[0] <= 0:
-            raise MMError(-1, "frames must be contiguous or row-strided (bytes packed)")
-        if strides[0] == 2 * width:
-            return None
-        lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
-        lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation (a multiple of 4)
-        return lay
-    if base_format(fmt) in Y210_FORMATS:   # [H, 2 W] words: rows of W / 2 macropixels Y0 Cb Y1 Cr
-        if tuple(frame.shape) != (height, 2 * width) or not str(frame.dtype).endswith("uint16"):
-            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height, 2 * width)} uint16)")
-        if strides[1] != 2 or strides[0] <= 0:
-            raise MMError(-1, "frames must be contiguous or row-strided (words packed)")
-        if strides[0] == 4 * width:
-            return None
-        lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
-        lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation (a multiple of 8)
-        return lay
-    if fmt in RGB24_FORMATS:   # [H, W, 3] bytes: rows any pitch >= 3 W apart, at any byte
-        if tuple(frame.shape) != (height, width, 3) or not str(frame.dtype).endswith("uint8"):
-            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height, width, 3)} uint8)")
-        if strides[2] != 1 or strides[1] != 3 or strides[0] <= 0:
-            raise MMError(-1, "frames must be contiguous or row-strided (pixels and channels packed)")
-        if strides[0] == 3 * width:
-            return None
-        lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
-        lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation (at least 3 W)
-        return lay
-    if base_format(fmt) in I420_FORMATS:   # the frame's bytes in NV12's shape: one contiguous [H * 3 / 2, W] array
-        if tuple(frame.shape) != (height * 3 // 2, width) or not str(frame.dtype).endswith("uint8"):
-            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height * 3 // 2, width)} uint8)")
-        if strides != (width, 1):
-            raise MMError(-1, "a three-plane 4:2:0 frame must be contiguous (name a Surface through Handle.process_surface)")
+    want = shape(height, width)
+    if dtype is None:
+        if tuple(frame.shape) != want:
+            raise MMError(-1, f"frame shape {tuple(frame.shape)} (want {want})")
+    elif tuple(frame.shape) != want or not str(frame.dtype).endswith(dtype):
+        raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {want} {dtype})")
+    row = item * int(np.prod(want[1:]))
+    if not pitched:
+        if strides != (row, item):
+            raise MMError(-1, packed)
         return None
-    if base_format(fmt) in I010_FORMATS:   # the frame's words in P010's shape: one contiguous [H * 3 / 2, W] array
-        if tuple(frame.shape) != (height * 3 // 2, width) or not str(frame.dtype).endswith("uint16"):
-            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height * 3 // 2, width)} uint16)")
-        if strides != (2 * width, 2):
-            raise MMError(-1, "a three-plane 4:2:0 frame must be contiguous (name a Surface through Handle.process_surface)")
-        return None
-    if fmt in MONO_FORMATS:   # [H, W] samples: uint8 (Y8) or uint16
-        want = "uint8" if fmt == Y8 else "uint16"
-        if tuple(frame.shape) != (height, width) or not str(frame.dtype).endswith(want):
-            raise MMError(-1, f"frame {tuple(frame.shape)} {frame.dtype} (want {(height, width)} {want})")
-        if strides[1] != item or strides[0] <= 0:
-            raise MMError(-1, "frames must be contiguous or row-strided (samples packed)")
-        if strides[0] == item * width:
-            return None
-        lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
-        lay.bytes(width, height)
-        return lay
-    if tuple(frame.shape) != (height, width, 4):
-        raise MMError(-1, f"frame shape {tuple(frame.shape)} (want {(height, width, 4)})")
-    if strides[2] != item or strides[1] != 4 * item or strides[0] <= 0:
-        raise MMError(-1, "frames must be contiguous or row-strided (pixels and channels packed)")
-    if strides[0] == 4 * item * width:
+    if strides[1:] != tuple(i * item for i in inner) or strides[0] <= 0:
+        raise MMError(-1, f"frames must be contiguous or row-strided ({packed})")
+    if strides[0] == row:
         return None
     lay = Surface(format=fmt, pitch=strides[0], chroma_offset=0, chroma_pitch=0, frame_stride=0)
-    lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation
+    lay.bytes(width, height)    # mm_surface_bytes: the pitch's validation (a multiple of the format's unit)
     return lay
 
 
@@ -116,18 +113,15 @@ def _convert_side(frame, width, height, fmt, side):
     codes: the words as they lie); an RGBA8 frame is [H, W, 4] uint8, contiguous
     or row-strided.  -> its Surface.  MMError on any mismatch, before any frame
     call into the library."""
-    base = base_format(fmt)
-    if base in (NV12, NV12_FULL, P010, P010_FULL):
-        want = "uint8" if base in (NV12, NV12_FULL) else "uint16"
-        if tuple(frame.shape) != (height * 3 // 2, width) or not str(frame.dtype).endswith(want):
-            raise MMError(-1, f"{side} {tuple(frame.shape)} {frame.dtype} "
-                              f"(want {(height * 3 // 2, width)} {want} for format {fmt})")
+    fam = _family(fmt)
+    shape, dtype = _FAMILIES[fam][0](height, width), _FAMILIES[fam][1] or "uint8"
+    if tuple(frame.shape) != shape or not str(frame.dtype).endswith(dtype):
+        raise MMError(-1, f"{side} {tuple(frame.shape)} {frame.dtype} (want {shape} {dtype} for format {fmt})")
+    if fam in ("nv12", "p010"):
         contiguous = frame.flags["C_CONTIGUOUS"] if isinstance(frame, np.ndarray) else frame.is_contiguous()
         if not contiguous:
             raise MMError(-1, f"{side}: a 4:2:0 frame must be contiguous (name a Surface through Handle.process_convert)")
         return Surface.tight(width, height, fmt)
-    if tuple(frame.shape) != (height, width, 4) or not str(frame.dtype).endswith("uint8"):
-        raise MMError(-1, f"{side} {tuple(frame.shape)} {frame.dtype} (want {(height, width, 4)} uint8 for format {fmt})")
     return frame_layout(frame, width, height, fmt) or Surface.tight(width, height, fmt)
 
 
@@ -312,18 +306,7 @@ class MotionMagnificationProcessor:
 
 
 def host_frames(n, h, w, fmt):
-    if fmt in RGB24_FORMATS:        # three bytes per pixel, either order
-        return np.zeros((n, h, w, 3), np.uint8)
-    fmt = base_format(fmt)          # a matrix bit changes no size or shape
-    if fmt in (NV12, NV12_FULL) or fmt in I420_FORMATS:    # h luma rows, then h/2 rows of chroma bytes (one or two planes)
-        return np.zeros((n, h * 3 // 2, w), np.uint8)
-    if fmt in (P010, P010_FULL) or fmt in I010_FORMATS:    # the same rows in 16-bit words (10-bit code << 6, or in the low bits)
-        return np.zeros((n, h * 3 // 2, w), np.uint16)
-    if fmt in PACKED422_FORMATS:    # one plane, h rows of w / 2 four-byte macropixels
-        return np.zeros((n, h, 2 * w), np.uint8)
-    if fmt in Y210_FORMATS:         # ... of w / 2 macropixels of four 16-bit words
-        return np.zeros((n, h, 2 * w), np.uint16)
-    if fmt in MONO_FORMATS:         # one plane of samples
-        return np.zeros((n, h, w), np.uint8 if fmt == Y8 else np.uint16)
-    dt = {RGBA8: np.uint8, RGBA8_SRGB: np.uint8, RGBA16F: np.float16}.get(fmt, np.float32)
-    return np.zeros((n, h, w, 4), dt)
+    """n zeroed host frames of a format, in its family's shape and dtype"""
+    shape, dtype = _FAMILIES[_family(fmt)][:2]
+    dtype = dtype or {RGBA8: "uint8", RGBA8_SRGB: "uint8", RGBA16F: "float16"}.get(fmt, "float32")
+    return np.zeros((n,) + shape(h, w), dtype)

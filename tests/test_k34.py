@@ -79,6 +79,67 @@ def _unfused(ran):
     return "k_rows_inv_compose" not in ran and "k_rows_inv" in ran and "k_compose" in ran
 
 
+def _lay(fmt, **kw):
+    """The tight 200 x 120 layout of fmt with some fields replaced"""
+    import mm355
+    s = mm355.Surface.tight(200, 120, fmt)
+    for k, v in kw.items():
+        setattr(s, k, v)
+    return s
+
+
+def _case(fmt, lin=None, lout=None, off_in=0, ofmt=None):
+    return (fmt, lin or {}, off_in, fmt if ofmt is None else ofmt, lout or {})
+
+
+# 200 x 120 (W % 8 == 0), two frames.  What each format's fused compose asks of
+# its row starts, from the rules in csrc/mm_format.hpp: NV12 chroma rows in and
+# every row out on multiples of 4; the single-plane formats' output rows on
+# multiples of 4; packed RGB's rows on multiples of 4 on both sides; three-plane
+# 4:2:0 luma rows out on multiples of 4 and chroma rows, both sides, of 2; its
+# 10-bit form the same with chroma rows on multiples of 4.  A convert call asks
+# each side by its own format, and RGBA8 asks nothing beyond its unit.
+_NV12_C202 = dict(chroma_pitch=202, frame_stride=24000 + 202 * 60)
+_I420_C101 = dict(chroma_pitch=101, frame_stride=24000 + 101 * 120)
+_I010_OFF2 = dict(chroma_offset=48002, frame_stride=72004)
+_PATHS = {
+    "nv12": (_case("NV12"), True), "y8": (_case("Y8"), True), "y16": (_case("Y16"), True),
+    "rgb24": (_case("RGB24"), True), "i420": (_case("I420"), True), "i010": (_case("I010"), True),
+    "nv12-chroma-pitch-202": (_case("NV12", _NV12_C202, _NV12_C202), False),
+    "y8-out-pitch-201": (_case("Y8", lout=dict(pitch=201, frame_stride=201 * 120)), False),
+    "rgb24-in-base-3": (_case("RGB24", off_in=3), False),
+    "i420-chroma-pitch-101": (_case("I420", _I420_C101, _I420_C101), False),
+    "i010-chroma-offset-2-mod-4": (_case("I010", _I010_OFF2, _I010_OFF2), False),
+    # only the NV12 side's numbers count: an RGBA8 pitch of 804 (no multiple of 16) changes nothing
+    "nv12-to-rgba8-out-pitch-804": (_case("NV12", lout=dict(pitch=804, frame_stride=804 * 120), ofmt="RGBA8"), True),
+    "rgba8-in-pitch-804-to-nv12": (_case("RGBA8", dict(pitch=804, frame_stride=804 * 120), ofmt="NV12"), True),
+}
+
+
+@pytest.mark.parametrize("name", list(_PATHS))
+def test_fused_path_by_format_and_alignment(name):
+    """Which compose a layout gets, per format: the tight layout of every format
+    with an alignment rule runs k_rows_inv_compose, one misaligned layout each
+    the unfused pair, and a convert call is judged by each side's own format.
+    Zero frames, outputs not compared: only the kernel names are read."""
+    import torch
+    import mm355
+    (fmt, lin, off_in, ofmt, lout), fused = _PATHS[name]
+    W, H, n = 200, 120, 2
+    li, lo = _lay(getattr(mm355, fmt), **lin), _lay(getattr(mm355, ofmt), **lout)
+    src = torch.zeros(li.frame_stride * n + 64, dtype=torch.uint8, device="cuda")
+    dst = torch.zeros(lo.frame_stride * n + 64, dtype=torch.uint8, device="cuda")
+    with _env(MM_K34_ROWS="64", MM_K34_ONESHOT=None):
+        h = mm355.Handle(W, H, mm355.Params.make(levels=5, phase_scale=25.0))
+    h.profile_begin()
+    call = h.process_stream_surfaces if fmt == ofmt else h.process_stream_convert
+    call(src.data_ptr() + off_in, li, dst, lo, n)
+    torch.cuda.synchronize()
+    ran = {k for k, (ms, launches, f) in h.profile_end().items() if launches}
+    h.close()
+    assert (_fused if fused else _unfused)(ran), ran
+
+
 def test_strip_policy_by_batch():
     """Default policy: the walking strips for many-frame batches; for short
     launches at N <= 1024 the one-shot form k_rows_inv_compose4 when its 4-row
