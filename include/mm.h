@@ -811,6 +811,67 @@ void *mm_stream(mm_handle *h);
 int mm_set_batch(mm_handle *h, int frames);
 int mm_get_batch(const mm_handle *h, int *frames);
 
+/* ---- Several live streams in one call -------------------------------------
+ * (a backward-compatible addition to ABI 10; detect it by the presence of
+ * mm_set_lanes)
+ * mm_process_stream batches consecutive frames of ONE stream, which a live
+ * source never has: a camera hands over one frame per tick.  A rig of M
+ * cameras of one geometry batches over the cameras instead: output t of a
+ * stream depends only on frames t-1 and t of that stream, so one call advances
+ * M streams by one frame each with one launch per kernel.
+ * A lane is one stream's temporal state (G_{t-1}), owned by the handle.  All
+ * lanes share the handle's geometry and mm_params.  Lane state is separate
+ * from the handle's own single-stream state: mm_process*, mm_get_state,
+ * mm_set_state, mm_reset, mm_set_batch and the rest behave exactly as before
+ * and may be interleaved with lane calls on one handle; neither disturbs the
+ * other.
+ * mm_set_lanes(h, lanes), 1 .. MM_LANES_MAX, allocates two G slots and one Q
+ * slot per lane (about 26.6 MB per 1080p lane: the 17.8 MB of a batch frame
+ * plus one more G slot); 0 frees them.  Another count than the current one
+ * drops every lane's state; the same count is a no-op.  Failure-atomic like
+ * mm_set_batch: on MM_ERR_OOM the previous lanes and their state stay.  The old
+ * buffers retire behind this handle's own work, never the device's; call it
+ * between frames.  mm_destroy releases the lanes.
+ * mm_process_lanes advances EVERY lane by one frame: frame k of the call is
+ * lane k's next frame, at in + k * in_layout->frame_stride, its output at
+ * out + k * out_layout->frame_stride.  Device pointers only; asynchronous on
+ * hip_stream and ordered like every other entry point.  The layouts are
+ * validated as mm_process_stream_surfaces validates them with count = lanes;
+ * the formats are equal or a pair of mm_convert_supported (the state after the
+ * call is the in frame's, as for convert calls).
+ * The contract is bitwise: lane k's outputs, and its state after every call,
+ * are those of a handle of its own with the same parameters, fed lane k's
+ * frames through one mm_process_surface / mm_process_convert call each.
+ * A lane without state (after mm_set_lanes, mm_reset_lane, or mm_set_lanes to
+ * another count) passes its frame through bitwise; for a convert pair that is
+ * the plain conversion, as for single calls.  A lane has state after a call or
+ * after mm_set_lane_state.  apply_magnification = 0: every frame passes through
+ * and every lane's state follows its input.  mm_set_params applies to all lanes
+ * from the next call; its edge_mode note holds per lane.
+ * mm_reset_lane(h, lane) is mm_reset for one lane; lane = -1: every lane.
+ * mm_get_lane_state / mm_set_lane_state move mm_state_size() bytes in
+ * mm_get_state's format: a stream moves between a single-stream handle and a
+ * lane, or between lanes, and continues bitwise.  (A lane without state:
+ * MM_ERR_NO_STATE from mm_get_lane_state.)
+ * Refusals, all before anything is queued; the handle and every lane's state
+ * stay as they were.  MM_ERR_UNSUPPORTED: MM_MODE_STEERABLE (its state is
+ * 100-300 MB per stream), show_magnitude or show_phase, from mm_process_lanes
+ * and the two lane-state calls; a handle with N = 8192, from mm_set_lanes; odd
+ * sizes of the Y'CbCr formats, as everywhere.  MM_ERR_INVALID: null pointers, a
+ * lane index out of range, lanes outside 0 .. MM_LANES_MAX, mm_process_lanes
+ * with no lanes set, a `bytes` below mm_state_size(), two different formats that
+ * are no supported pair.
+ * Out of scope: calls that advance a subset of the lanes; lanes of different
+ * sizes or parameters; host-memory frames; the ring entry points. */
+#define MM_LANES_MAX 64
+int mm_set_lanes(mm_handle *h, int lanes);            /* 1..MM_LANES_MAX; 0 frees */
+int mm_get_lanes(const mm_handle *h, int *lanes);
+int mm_process_lanes(mm_handle *h, const void *in, const mm_surface *in_layout,
+                     void *out, const mm_surface *out_layout, void *hip_stream);
+int mm_reset_lane(mm_handle *h, int lane);            /* -1: every lane */
+int mm_get_lane_state(mm_handle *h, int lane, void *dev_buf, size_t bytes, void *hip_stream);
+int mm_set_lane_state(mm_handle *h, int lane, const void *dev_buf, size_t bytes, void *hip_stream);
+
 /* Zero-copy frames (f4): device memory owned by another API — an engine's
  * render target exported as an opaque POSIX fd (Vulkan VK_KHR_external_memory_fd,
  * or a HIP VMM allocation via hipMemExportToShareableHandle) — imported into the

@@ -42,6 +42,10 @@ static int do_compute_state(mm_handle *h, const uint8_t *in, const Frames &fr, v
 {
     MM_DISPATCH(mm_size_compute_state_, h, in, fr, dst, s)
 }
+static int do_lanes(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s)
+{
+    MM_DISPATCH(mm_size_lanes_, h, in, out, fr, s)
+}
 
 // ------------------------------------------------------------------------
 // C ABI
@@ -114,7 +118,7 @@ static void free_handle(mm_handle *h)
     if (h->stream) {
         void *bufs[] = {h->d_col, h->d_row, h->d_col3, h->d_row3, h->d_tw, h->d_ktab, h->d_kmsum, h->d_tw_half,
                         h->d_dbg, h->d_Fb, h->d_T, h->d_sst, h->d_G, h->d_Q, h->d_Yh, h->d_stage_in,
-                        h->d_stage_out};
+                        h->d_stage_out, h->d_LG, h->d_LQ};
         for (void *b : bufs) h_retire(h, b);
         (void)hipStreamSynchronize(h->stream);
     }
@@ -708,6 +712,118 @@ int mm_compute_state(mm_handle *h, const void *in_dev, int format, void *dev_buf
     if (!h || !in_dev || !dev_buf || mm_state_size(h, &need) || bytes < need) return MM_ERR_INVALID;
     if (int rc = surf_tight(h->W, h->H, format, &t)) return rc;
     return mm_compute_state_surface(h, in_dev, &t, dev_buf, bytes, hip_stream);
+}
+
+// ---- several live streams in one call (include/mm.h) ----------------------
+int mm_set_lanes(mm_handle *h, int lanes)
+{
+    if (!h || lanes < 0 || lanes > MM_LANES_MAX) return MM_ERR_INVALID;
+    if (h->N > 4096) return MM_ERR_UNSUPPORTED;   // (k_cols_lanes: the sizes up to N = 4096)
+    if (lanes == h->lanes) return MM_OK;
+    DEVICE_SCOPE(h);
+    c2 *G = nullptr, *Q = nullptr;
+    if (lanes) {
+        // failure-atomic, as alloc_batch: the new buffers first.  The banks are
+        // zeroed: K2 transforms the G_{t-1} slot of a lane without state too.
+        const size_t gb = sizeof(c2) * h->g_stride * 2 * (size_t)lanes;
+        if (h_alloc(h, &G, gb) != hipSuccess ||
+            h_alloc(h, &Q, sizeof(c2) * h->q_stride * (size_t)lanes) != hipSuccess) {
+            h_retire(h, G);
+            return MM_ERR_OOM;
+        }
+        if (hipMemsetAsync(G, 0, gb, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
+            h_retire(h, G);
+            h_retire(h, Q);
+            return MM_ERR_HIP;
+        }
+    }
+    // the old buffers go back behind this handle's in-flight work (last_ev)
+    h_retire(h, h->d_LG);
+    h_retire(h, h->d_LQ);
+    h->d_LG = G;
+    h->d_LQ = Q;
+    h->lanes = lanes;
+    h->lane_bank = 0;
+    h->lane_state.assign((size_t)lanes, 0);
+    return MM_OK;
+}
+
+int mm_get_lanes(const mm_handle *h, int *lanes)
+{
+    if (!h || !lanes) return MM_ERR_INVALID;
+    *lanes = h->lanes;
+    return MM_OK;
+}
+
+// The modes a lane call takes: the steerable state is 100-300 MB per stream,
+// and a debug view is no stream operation
+static int lanes_mode_check(const mm_handle *h)
+{
+    if (h->p.mode == MM_MODE_STEERABLE || h->p.show_magnitude || h->p.show_phase) return MM_ERR_UNSUPPORTED;
+    return MM_OK;
+}
+
+int mm_process_lanes(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                     const mm_surface *out_layout, void *hip_stream)
+{
+    if (!h || !in || !out || !in_layout || !out_layout || h->lanes < 1) return MM_ERR_INVALID;
+    if (int rc = lanes_mode_check(h)) return rc;
+    // two formats that are no pair of mm_convert_supported: invalid here, as for mm_process_stream_surfaces
+    if (in_layout->format != out_layout->format && convert_supported(in_layout->format, out_layout->format))
+        return MM_ERR_INVALID;
+    if (int rc = formats_check(h, in_layout, out_layout, true)) return rc;
+    int rc;
+    if ((rc = surf_check_frames(h->W, h->H, in, in_layout, h->lanes)) ||
+        (rc = surf_check_frames(h->W, h->H, out, out_layout, h->lanes)))
+        return rc;
+    const Frames fr = frames_of(h->W, h->H, *in_layout, *out_layout);
+    hipStream_t s = (hipStream_t)hip_stream;   // NULL: the default stream (HIP convention)
+    DEVICE_SCOPE(h);
+    int ro = order_after_last(h, s);
+    if (ro) return ro;
+    rc = do_lanes(h, (const uint8_t *)in, (uint8_t *)out, fr, s);
+    const int rn = note_work(h, s);
+    return rc ? rc : rn;
+}
+
+int mm_reset_lane(mm_handle *h, int lane)
+{
+    if (!h || lane < -1 || lane >= h->lanes) return MM_ERR_INVALID;
+    if (lane < 0) std::fill(h->lane_state.begin(), h->lane_state.end(), (char)0);
+    else h->lane_state[lane] = 0;
+    return MM_OK;
+}
+
+int mm_get_lane_state(mm_handle *h, int lane, void *dev_buf, size_t bytes, void *hip_stream)
+{
+    if (!h || !dev_buf || lane < 0 || lane >= h->lanes) return MM_ERR_INVALID;
+    if (int rc = lanes_mode_check(h)) return rc;
+    const size_t need = sizeof(c2) * h->g_stride;   // mm_state_size of these modes
+    if (bytes < need) return MM_ERR_INVALID;
+    if (!h->lane_state[lane]) return MM_ERR_NO_STATE;
+    hipStream_t s = (hipStream_t)hip_stream;   // NULL: the default stream (HIP convention)
+    DEVICE_SCOPE(h);
+    int ro = order_after_last(h, s);
+    if (ro) return ro;
+    const c2 *slot = h->d_LG + h->g_stride * ((size_t)h->lanes * h->lane_bank + lane);
+    HIPCHK(hipMemcpyAsync(dev_buf, slot, need, hipMemcpyDeviceToDevice, s));
+    return note_work(h, s);
+}
+
+int mm_set_lane_state(mm_handle *h, int lane, const void *dev_buf, size_t bytes, void *hip_stream)
+{
+    if (!h || !dev_buf || lane < 0 || lane >= h->lanes) return MM_ERR_INVALID;
+    if (int rc = lanes_mode_check(h)) return rc;
+    const size_t need = sizeof(c2) * h->g_stride;
+    if (bytes < need) return MM_ERR_INVALID;
+    hipStream_t s = (hipStream_t)hip_stream;   // NULL: the default stream (HIP convention)
+    DEVICE_SCOPE(h);
+    int ro = order_after_last(h, s);
+    if (ro) return ro;
+    c2 *slot = h->d_LG + h->g_stride * ((size_t)h->lanes * h->lane_bank + lane);
+    HIPCHK(hipMemcpyAsync(slot, dev_buf, need, hipMemcpyDeviceToDevice, s));
+    h->lane_state[lane] = 1;
+    return note_work(h, s);
 }
 
 void mm_destroy(mm_handle *h)

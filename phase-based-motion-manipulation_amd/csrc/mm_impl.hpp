@@ -95,6 +95,16 @@ struct mm_handle {
     int k34_oneshot;            // short launches: k_rows_inv_compose4 when its strips fit one
                                 // workgroup round (MM_K34_ONESHOT: 0 never: K3 -> K4, 2 always)
     int num_cu;                 // compute units of the device
+    // Lanes (mm_set_lanes): the temporal states of `lanes` live streams that
+    // advance one frame each per mm_process_lanes call, apart from the
+    // handle's own state above.  d_LG: two banks of `lanes` G slots.  Bank
+    // lane_bank holds the lanes' G_{t-1}; a call's K1 writes the other bank,
+    // its K2 reads both, then the banks swap: no state copy.  d_LQ: a Q slot
+    // per lane.  lane_state[k]: lane k's slot of bank lane_bank holds its state.
+    int lanes;
+    c2 *d_LG, *d_LQ;
+    int lane_bank;
+    std::vector<char> lane_state;
     // mm_profile_begin/end: HIP events around each launch on its stream
     struct ProfRec { hipEvent_t a, b; int kernel, frames; };
     bool prof;
@@ -823,16 +833,12 @@ static int launch_k1(mm_handle *h, const uint8_t *in, int nframes, const Frames 
     return MM_OK;
 }
 
-// K2 over frames G[0 .. nframes) (K1's row spectra), primed with Gprev = G_{t-1}
-// (the state slot, or frame 0 itself for a stream's first batch, whose frame 0
-// passes through): Q of frame fr to d_Q + fr * q_stride.
+// K2's per-bin tables, stream-ordered before the K2 launch that follows a
+// parameter change
 template <int LOG2N>
-static int launch_k2(mm_handle *h, int nframes, const c2 *Gprev, const c2 *G, hipStream_t s)
+static int refresh_k2_tables(mm_handle *h, hipStream_t s)
 {
-    const int gpw = k2_groups<LOG2N>();
-    const int cols = (1 << LOG2N) / 2;   // f = 0 and f = N/2 share group 0 (k_cols)
-    const int blocks = (cols + gpw - 1) / gpw;
-    // the per-bin tables, stream-ordered before this launch after a parameter change
+    const int cols = (1 << LOG2N) / 2;
     static_assert(ktab_slots(LOG2N) == k2_tab_slots<LOG2N>(), "d_ktab column stride");
     const int tab_mode = h->spec.mode == MM_MODE_STANDARD ? MM_MODE_STANDARD : h->k2_tab ? MM_K2_PYR_TAB : -1;
     if (tab_mode >= 0 && h->ktab_mode != tab_mode) {
@@ -846,6 +852,19 @@ static int launch_k2(mm_handle *h, int nframes, const c2 *Gprev, const c2 *G, hi
         HIPCHK(hipGetLastError());
         h->ktab_mode = tab_mode;
     }
+    return MM_OK;
+}
+
+// K2 over frames G[0 .. nframes) (K1's row spectra), primed with Gprev = G_{t-1}
+// (the state slot, or frame 0 itself for a stream's first batch, whose frame 0
+// passes through): Q of frame fr to d_Q + fr * q_stride.
+template <int LOG2N>
+static int launch_k2(mm_handle *h, int nframes, const c2 *Gprev, const c2 *G, hipStream_t s)
+{
+    const int gpw = k2_groups<LOG2N>();
+    const int cols = (1 << LOG2N) / 2;   // f = 0 and f = N/2 share group 0 (k_cols)
+    const int blocks = (cols + gpw - 1) / gpw;
+    if (int rc = refresh_k2_tables<LOG2N>(h, s)) return rc;
     ProfScope ps(h, s, MM_K_COLS, nframes);
     // the packed block's last k frames go to k_cols_tail (k_cols's critical path)
     int k = nframes >= 24 ? nframes * h->k2_tail_pct / 100 : 0;
@@ -875,6 +894,32 @@ static int launch_k2(mm_handle *h, int nframes, const c2 *Gprev, const c2 *G, hi
     return MM_OK;
 }
 
+// K2 of one frame per lane (k_cols_lanes): lane k's G_t in slot k of G, its
+// G_{t-1} in slot k of Gprev (the two lane banks), its Q to d_LQ + k * q_stride.
+// The modes and their order are launch_k2's.
+template <int LOG2N>
+static int launch_k2_lanes(mm_handle *h, const c2 *Gprev, const c2 *G, hipStream_t s)
+{
+    const int gpw = k2_groups<LOG2N>();
+    const int blocks = ((1 << LOG2N) / 2 + gpw - 1) / gpw;
+    if (int rc = refresh_k2_tables<LOG2N>(h, s)) return rc;
+    ProfScope ps(h, s, MM_K_COLS, h->lanes);
+#define MM_K2_LAUNCH(MODE)                                                                           \
+    do {                                                                                             \
+        const size_t lds = k2_lds_bytes<LOG2N, MODE>();                                              \
+        hipLaunchKernelGGL((k_cols_lanes<LOG2N, MODE>), dim3(blocks, h->lanes), dim3(k2_threads<LOG2N>()), lds, s, \
+                           G, h->g_stride, Gprev, h->d_LQ, h->q_stride, h->geo, h->spec, h->d_tw, h->d_ktab, \
+                           h->d_kmsum);                                                              \
+    } while (0)
+    if (h->spec.mode == MM_MODE_STANDARD) MM_K2_LAUNCH(MM_MODE_STANDARD);
+    else if (h->k2_tab2) MM_K2_LAUNCH(MM_K2_PYR_TAB2);
+    else if (h->k2_tab) MM_K2_LAUNCH(MM_K2_PYR_TAB);
+    else MM_K2_LAUNCH(MM_MODE_PYRAMID);
+#undef MM_K2_LAUNCH
+    HIPCHK(hipGetLastError());
+    return MM_OK;
+}
+
 // Grows a per-batch buffer that only some paths use to `frames` frames of
 // `per_frame` bytes.  The old buffer is retired behind this handle's work
 // (its previous calls and what this call queued on s), not behind the
@@ -891,7 +936,8 @@ static int ensure_frames(mm_handle *h, void **buf, int *have, int frames, size_t
 }
 static int ensure_yh(mm_handle *h, hipStream_t s)
 {
-    return ensure_frames(h, reinterpret_cast<void **>(&h->d_Yh), &h->yh_frames, h->chunk,
+    // (a batch's frames, or a lane call's)
+    return ensure_frames(h, reinterpret_cast<void **>(&h->d_Yh), &h->yh_frames, std::max(h->chunk, h->lanes),
                          sizeof(float) * h->yh_stride, s);
 }
 
@@ -987,8 +1033,10 @@ static int k34_strip_rows(const mm_handle *h, int nout)
     return R >= 16 ? R : 0;
 }
 
+// K3 + K4 of frames [frame0, nframes) whose Q lie at Q + frame * q_stride
+// (a batch's d_Q, or the lanes' d_LQ)
 template <int LOG2N>
-static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, int nframes,
+static int launch_k3(mm_handle *h, const c2 *Q, const uint8_t *in, uint8_t *out, int frame0, int nframes,
                      const Frames &fr, hipStream_t s)
 {
     const int nout = nframes - frame0;
@@ -1012,7 +1060,7 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
         const size_t lds = sizeof(c2) * 4 * lds_complex<(1 << LOG2N)>();
         const dim3 grid((unsigned)(strips * nout)), block(4 * fft_T<LOG2N>());
         ProfScope ps(h, s, MM_K_ROWS_INV_COMPOSE, nout);
-        MM_PAIR_SWITCH(fr, hipLaunchKernelGGL((k_rows_inv_compose4<LOG2N, FMT_>), grid, block, lds, s, h->d_Q,
+        MM_PAIR_SWITCH(fr, hipLaunchKernelGGL((k_rows_inv_compose4<LOG2N, FMT_>), grid, block, lds, s, Q,
                                               h->q_stride, in, out, frame0, strips, geo_of(h, fr), h->blur,
                                               h->d_col3, h->d_row3, h->d_tw))
         HIPCHK(hipGetLastError());
@@ -1025,7 +1073,7 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
         const dim3 grid((unsigned)(strips * nout)), block(2 * fft_T<LOG2N>());
         ProfScope ps(h, s, MM_K_ROWS_INV_COMPOSE, nout);
 #define MM_K34_LAUNCH(F, DMA)                                                                        \
-        hipLaunchKernelGGL((k_rows_inv_compose<LOG2N, F, DMA>), grid, block, lds, s, h->d_Q,          \
+        hipLaunchKernelGGL((k_rows_inv_compose<LOG2N, F, DMA>), grid, block, lds, s, Q,               \
                            h->q_stride, in, out, frame0, strips, steps, geo_of(h, fr), h->blur,      \
                            h->d_col3, h->d_row3, h->d_tw)
         if constexpr (LOG2N <= 12) if (dma) {
@@ -1047,7 +1095,7 @@ static int launch_k3(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
         ProfScope ps(h, s, MM_K_ROWS_INV, nout);
         hipLaunchKernelGGL((k_rows_inv<LOG2N>), dim3((total + gpw - 1) / gpw),
                            dim3(k3_threads<LOG2N>()), sizeof(c2) * (size_t)gpw * lds_complex<(1 << LOG2N)>(),
-                           s, h->d_Q,
+                           s, Q,
                            h->q_stride, h->d_Yh, h->yh_stride, frame0, ppf, total, h->geo,
                            h->blur, h->d_tw);
         HIPCHK(hipGetLastError());
@@ -1418,7 +1466,7 @@ static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const
         else rc = MM_ERR_UNSUPPORTED;
     } else {
         if ((rc = launch_k2<LOG2N>(h, n, Gprev, G, s))) return rc;
-        rc = launch_k3<LOG2N>(h, in, out, first, n, fr, s);
+        rc = launch_k3<LOG2N>(h, h->d_Q, in, out, first, n, fr, s);
     }
     if (rc) return rc;
     h->gs = base + n - 1;   // the state follows the input in every mode (.cs:142)
@@ -1457,6 +1505,43 @@ static int compute_state(mm_handle *h, const uint8_t *in, const Frames &fr, void
     return launch_k1<LOG2N>(h, in, 1, fr, s, reinterpret_cast<c2 *>(dst));
 }
 
+// One frame of every lane (mm_process_lanes): frame k of the call is lane k's
+// next frame.  K1 of the frames into the free bank, one K2 over both banks
+// (k_cols_lanes), then K3 + K4 from the lanes' Q.  A lane without state passes
+// through (its K2 result is computed and not used, as a stream's first frame's
+// is): the compose runs over the runs of lanes that have state, one launch
+// when all have, so a passthrough frame is never composed over first (frames
+// may be processed in place).  The banks swap: no state copy.
+template <int LOG2N>
+static int run_lanes(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s)
+{
+    if constexpr (LOG2N > 12) return MM_ERR_UNSUPPORTED;   // (mm_set_lanes refuses N = 8192)
+    else {
+        const int n = h->lanes;
+        const size_t bank = h->g_stride * (size_t)n;
+        const c2 *Gprev = h->d_LG + bank * h->lane_bank;
+        c2 *G = h->d_LG + bank * (1 - h->lane_bank);
+        int rc;
+        if ((rc = launch_k1<LOG2N>(h, in, n, fr, s, G))) return rc;
+        if (!h->p.apply_magnification) {
+            // Blit(source, destination) (.cs:139); every lane's state follows its input
+            if ((rc = copy_frames(h, in, out, n, fr, s))) return rc;
+        } else {
+            if ((rc = launch_k2_lanes<LOG2N>(h, Gprev, G, s))) return rc;
+            for (int a = 0, b; a < n; a = b) {
+                const bool st = h->lane_state[a] != 0;
+                for (b = a + 1; b < n && (h->lane_state[b] != 0) == st; ++b) {}
+                if (st) rc = launch_k3<LOG2N>(h, h->d_LQ, in, out, a, b, fr, s);
+                else rc = copy_frames(h, in + fr.in.stride * a, out + fr.out.stride * a, b - a, fr, s);
+                if (rc) return rc;
+            }
+        }
+        h->lane_bank ^= 1;
+        std::fill(h->lane_state.begin(), h->lane_state.end(), (char)1);
+        return MM_OK;
+    }
+}
+
 // MM_ONLY_LOG2N=n (experiment builds only): instantiate one padded size, so an
 // A/B variant compiles in a fraction of the full build's time
 
@@ -1467,7 +1552,8 @@ static int compute_state(mm_handle *h, const uint8_t *in, const Frames &fr, void
     int mm_size_stream_##L(mm_handle *h, const uint8_t *in, uint8_t *out, int count,                \
                            const Frames &fr, hipStream_t s);                                        \
     int mm_size_compute_state_##L(mm_handle *h, const uint8_t *in, const Frames &fr, void *dst,     \
-                                  hipStream_t s);
+                                  hipStream_t s);                                                   \
+    int mm_size_lanes_##L(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s);
 #define MM_SIZE_ENTRIES(L) MM_SIZE_ENTRIES_(L)
 #define MM_SIZE_ENTRIES_(L)                                                                         \
     int mm_size_set_attrs_##L(mm_handle *h) { return set_attrs<L>(h->W); }                          \
@@ -1480,6 +1566,10 @@ static int compute_state(mm_handle *h, const uint8_t *in, const Frames &fr, void
                                   hipStream_t s)                                                    \
     {                                                                                               \
         return compute_state<L>(h, in, fr, dst, s);                                                 \
+    }                                                                                               \
+    int mm_size_lanes_##L(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s) \
+    {                                                                                               \
+        return run_lanes<L>(h, in, out, fr, s);                                                     \
     }
 MM_SIZE_DECLS(4)
 MM_SIZE_DECLS(5)

@@ -2689,6 +2689,27 @@ void k_cols_tail(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_
                                    Q + (size_t)fr * q_stride, q_stride, 1, g, sp, tw, ktab, kmsum, 0);
 }
 
+// One frame of each of gridDim.y independent streams (mm_process_lanes): lane
+// y's G_t, G_{t-1} and Q lie y slots into G, Gprev and Q.  Workgroup (x, y) is
+// the one-frame call's k_cols workgroup x on lane y's pointers: the same body
+// instances, nframes = 1, so a lane's Q is bitwise a one-frame call's.  Block x
+// lands on XCD x % 8 within a lane only where gridDim.x % 8 == 0 (a 2-D grid
+// dispatches x fastest); elsewhere a lane's same-XCD blocks no longer own
+// consecutive columns, which costs the merging of Q lines, not results.
+template <int LOG2N, int MODE>
+__global__ __launch_bounds__(k2_threads<LOG2N>()) __attribute__((amdgpu_waves_per_eu(MM_K2_WAVES)))
+void k_cols_lanes(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_stride,   // not restrict, as k_cols
+                  Geo g, Spec sp, const c2 *__restrict__ tw, const float2 *__restrict__ ktab,
+                  const float *__restrict__ kmsum)
+{
+    const int nb = gridDim.x;
+    const int blk = xcd_remap((int)blockIdx.x, nb);
+    const size_t go = (size_t)blockIdx.y * g_stride;
+    c2 *Ql = Q + (size_t)blockIdx.y * q_stride;
+    if (blk == 0) k_cols_body<LOG2N, MODE, true>(G + go, g_stride, Gprev + go, Ql, q_stride, 1, g, sp, tw, ktab, kmsum, blk, nb);
+    else k_cols_body<LOG2N, MODE, false>(G + go, g_stride, Gprev + go, Ql, q_stride, 1, g, sp, tw, ktab, kmsum, blk, nb);
+}
+
 // K2's per-bin tables of every column in LDS slot order ([N/2+1][k2_tab_slots]):
 // the frame-invariant bin_static values (pyramid masks pre-scaled by inv_nn, a
 // power of two: exact), evaluated once per parameter set on the launch stream

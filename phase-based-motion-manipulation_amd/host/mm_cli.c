@@ -11,7 +11,7 @@
  *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
  *          [--yuy2] [--uyvy] [--y210] [--ppm [--bgr]] [--i420] [--i010] [--out-rgba8] [--out-nv12]
  *          [--standard] [--show-magnitude] [--show-phase]
- *          [--orientations O] [--iir] [--halo K] [--surface-align P,R]
+ *          [--orientations O] [--iir] [--halo K] [--surface-align P,R] [--lanes M]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
  *          [--ring-local G [--compare]]
  *
@@ -126,6 +126,14 @@
  * views, the ring modes and odd sizes.
  * With either, --surface-align lays out each side in its own format's
  * surface, and --checksum hashes the output frames, as usual.
+ * --lanes M (1 .. MM_LANES_MAX): the input is M live streams interleaved, input
+ * frame k being stream (lane) k % M's frame k / M, as a rig of M cameras
+ * delivers them tick by tick.  One mm_process_lanes call per M frames (-b is
+ * ignored); the output has the input's order.  Every format option and
+ * --surface-align as usual.  The frame count (-n for a synthetic stream, else
+ * the frames the input holds, -n at most) must be a multiple of M: else status
+ * 2, before the output file is created.  Refused with --orientations / --iir,
+ * the debug views and the ring modes.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -579,7 +587,8 @@ int main(int argc, char **argv)
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
     int srgb = 0, bgr = 0, out_rgba8 = 0, out_nv12 = 0;
-    const in_opt *in = NULL;   /* the input-format option: one at most */
+    const char *lanes_arg = NULL;
+    const in_opt *in = NULL;  /* the input-format option: one at most */
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
     float S = 25.0f;
@@ -624,6 +633,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--halo")) halo = atoi(v);
         else if (!strcmp(a, "--surface-align")) surf_arg = v;
         else if (!strcmp(a, "--matrix")) matrix_arg = v;
+        else if (!strcmp(a, "--lanes")) lanes_arg = v;
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         ++i;
     }
@@ -652,6 +662,12 @@ int main(int argc, char **argv)
     if (matrix_arg && strcmp(matrix_arg, "601") && strcmp(matrix_arg, "709") && strcmp(matrix_arg, "2020"))
         REFUSE("--matrix takes 601, 709 or 2020, not %s (%s)\n", matrix_arg, in ? in->name : "--out-nv12");
     if (surf_arg && ring) REFUSE("--surface-align does not go with the ring modes (they take tight frames)\n");
+    /* several live streams per call (mm_process_lanes) */
+    const int M = lanes_arg ? atoi(lanes_arg) : 0;
+    if (lanes_arg && (M < 1 || M > MM_LANES_MAX)) REFUSE("--lanes takes 1 .. %d, not %s\n", MM_LANES_MAX, lanes_arg);
+    if (M && (orientations > 1 || iir || views || ring))
+        REFUSE("--lanes does not go with --orientations / --iir, the debug views or the ring modes\n");
+    if (M) B = M;
     if (ring_local > 0 && (in_path || out_path)) REFUSE("--ring-local needs a synthetic stream\n");
     if (ring_world > 0 && ring_local <= 0 && (!ring_id_path || in_path || out_path))
         REFUSE("--ring-world needs --ring-id and a synthetic stream\n");
@@ -707,6 +723,31 @@ int main(int argc, char **argv)
     /* what a .y4m output holds, and how its frames are made: the input
      * option's, --out-nv12: --nv12's, --out-rgba8 or no option: 4:4:4 from RGBA8 */
     const in_opt *wr = out_nv12 ? k_opt_nv12 : out_rgba8 ? NULL : in;
+    if (M) {
+        /* --lanes: whole ticks only.  The frames a file holds (-n at most) are
+         * counted by reading it once; the run then starts where this started. */
+        int count = F;
+        if (fi) {
+            size_t cb = (size_t)W * H * 4;
+            if (in && mm_frame_bytes(W, H, g_fmt, &cb) != MM_OK) cb = 0;
+            if (y4m_in && y4m_frame_bytes_depth(&yi, depth) > cb) cb = y4m_frame_bytes_depth(&yi, depth);
+            unsigned char *tmp = cb ? (unsigned char *)malloc(cb) : NULL;
+            const long pos = ftell(fi);
+            ppm_info pc = pi;
+            if (!tmp || pos < 0) { fprintf(stderr, "cannot count the frames of %s\n", in_path); return 1; }
+            for (count = 0; count < F; ++count) {
+                int more;
+                if (y4m_in) more = y4m_read_frame_depth(fi, &yi, depth, tmp) > 0;
+                else if (p_ppm) more = (count == 0 ? ppm_read_pixels(fi, &pc, tmp) : ppm_read_next(fi, &pc, tmp)) == 0;
+                else more = fread(tmp, cb, 1, fi) == 1;
+                if (!more) break;
+            }
+            free(tmp);
+            if (fseek(fi, pos, SEEK_SET)) { fprintf(stderr, "cannot rewind %s\n", in_path); return 1; }
+        }
+        if (count % M) REFUSE("--lanes %d needs a multiple of %d frames, not %d\n", M, M, count);
+        F = count;
+    }
     FILE *fo = out_path ? fopen(out_path, "wb") : NULL;
     if (out_path && !fo) { fprintf(stderr, "cannot open file\n"); return 1; }
     mm_params p;
@@ -731,6 +772,7 @@ int main(int argc, char **argv)
     int N = 0;
     mm_padded_size(h, &N);
     printf("Original: %dx%d, Padded: %dx%d\n", W, H, N, N);   /* .cs:304 */
+    if (M) CHECK(mm_set_lanes(h, M));
     if (ring_world > 0) {
         CHECK(mm_set_batch(h, B));
         const int rc = run_ring(h, W, H, F, B, dev, ring_world, ring_rank, ring_id_path, checksum, halo);
@@ -836,7 +878,8 @@ int main(int argc, char **argv)
             if (surf_arg && surf_copy(d_in, &lay, d_tin, &tight, W, H, n, hipMemcpyDeviceToDevice, s)) return 1;
         }
         hipEventRecord(e0, s);
-        if (convert) CHECK(mm_process_stream_convert(h, d_in, &lay, d_out, &olay, n, s));
+        if (M) CHECK(mm_process_lanes(h, d_in, &lay, d_out, &olay, s));   /* (n == M: whole ticks) */
+        else if (convert) CHECK(mm_process_stream_convert(h, d_in, &lay, d_out, &olay, n, s));
         else if (surf_arg) CHECK(mm_process_stream_surfaces(h, d_in, &lay, d_out, &lay, n, s));
         else CHECK(mm_process_stream(h, d_in, d_out, n, g_fmt, s));
         hipEventRecord(e1, s);

@@ -211,6 +211,25 @@ def convert_supported(in_fmt, out_fmt):
     return _convert_fn("mm_convert_supported")(int(in_fmt), int(out_fmt))
 
 
+# several live streams in one call (include/mm.h "Several live streams in one
+# call"): one frame of each of a handle's lanes per mm_process_lanes
+LANES_SYMBOLS = ("mm_set_lanes", "mm_get_lanes", "mm_process_lanes", "mm_reset_lane",
+                 "mm_get_lane_state", "mm_set_lane_state")
+LANES_MAX = 64      # MM_LANES_MAX
+
+
+def has_lanes():
+    """The loaded library runs lanes (detected, as include/mm.h says, by the
+    presence of mm_set_lanes)."""
+    return hasattr(lib(), "mm_set_lanes")
+
+
+def _lanes_fn(name):
+    if not has_lanes():
+        raise MMError(-2, f"{library_path()} has no {name} (a build from before the lanes)")
+    return getattr(lib(), name)
+
+
 _lib = None
 _lib_path = None
 ABI_VERSION = 10  # include/mm.h MM_ABI_VERSION
@@ -239,6 +258,12 @@ def load_library(path=None):
         "mm_convert_supported": (ci, [ci, ci]),
         "mm_process_convert": (ci, [vp, vp, ps, vp, ps, ci, vp]),
         "mm_process_stream_convert": (ci, [vp, vp, ps, vp, ps, ci, vp]),
+        "mm_set_lanes": (ci, [vp, ci]),
+        "mm_get_lanes": (ci, [vp, ctypes.POINTER(ci)]),
+        "mm_process_lanes": (ci, [vp, vp, ps, vp, ps, vp]),
+        "mm_reset_lane": (ci, [vp, ci]),
+        "mm_get_lane_state": (ci, [vp, ci, vp, sz, vp]),
+        "mm_set_lane_state": (ci, [vp, ci, vp, sz, vp]),
         "mm_abi_version": (ci, []),
         "mm_strerror": (ctypes.c_char_p, [ci]),
         "mm_params_default": (ci, [pp]),
@@ -284,6 +309,8 @@ def load_library(path=None):
             continue    # ... or from before the pitched surfaces
         if name in CONVERT_SYMBOLS and not hasattr(L, name):
             continue    # ... or from before the format conversion
+        if name in LANES_SYMBOLS and not hasattr(L, name):
+            continue    # ... or from before the lanes
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -467,6 +494,33 @@ class Handle:
         check(_convert_fn("mm_process_stream_convert")(self.h, _ptr(src), ctypes.byref(src_layout),
                                                        _ptr(dst), ctypes.byref(dst_layout), count,
                                                        _ptr(stream)), "mm_process_stream_convert")
+
+    def set_lanes(self, n):
+        """mm_set_lanes: n live streams' states on this handle (0 frees them)."""
+        check(_lanes_fn("mm_set_lanes")(self.h, int(n)), "mm_set_lanes")
+
+    def lanes(self):
+        n = ctypes.c_int()
+        check(_lanes_fn("mm_get_lanes")(self.h, ctypes.byref(n)), "mm_get_lanes")
+        return n.value
+
+    def process_lanes(self, src, src_layout, dst, dst_layout, stream=None):
+        """mm_process_lanes: one frame of every lane; lane k's frame at
+        k * frame_stride of its side."""
+        check(_lanes_fn("mm_process_lanes")(self.h, _ptr(src), ctypes.byref(src_layout), _ptr(dst),
+                                            ctypes.byref(dst_layout), _ptr(stream)), "mm_process_lanes")
+
+    def reset_lane(self, lane=-1):
+        """mm_reset_lane: lane's next frame passes through (-1: every lane's)."""
+        check(_lanes_fn("mm_reset_lane")(self.h, int(lane)), "mm_reset_lane")
+
+    def get_lane_state(self, lane, dev_buf, stream=None):
+        check(_lanes_fn("mm_get_lane_state")(self.h, int(lane), _ptr(dev_buf), self.state_bytes,
+                                             _ptr(stream)), "mm_get_lane_state")
+
+    def set_lane_state(self, lane, dev_buf, stream=None):
+        check(_lanes_fn("mm_set_lane_state")(self.h, int(lane), _ptr(dev_buf), self.state_bytes,
+                                             _ptr(stream)), "mm_set_lane_state")
 
     def reset(self):
         check(lib().mm_reset(self.h), "mm_reset")
