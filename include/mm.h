@@ -263,7 +263,7 @@ extern "C" {
  * the extent and 4 GiB rules are unchanged.  Every row of every legal layout
  * is dword aligned, so the fused kernels run under their geometry conditions
  * alone.
- * Out of scope: v210 and P210 (10-bit packed 4:2:2 is MM_Y210 below); planar 4:2:2 and 4:4:4 on the
+ * Out of scope: P210 (10-bit packed 4:2:2 is MM_Y210 and MM_V210 below); planar 4:2:2 and 4:4:4 on the
  * device; odd H; the debug views; chroma siting other than the shared 1 x 2
  * sample; PQ / HLG; the ring entry points (include/mm_ring.h); the Unity shim;
  * a host 4:2:2 to RGBA conversion. */
@@ -321,7 +321,8 @@ extern "C" {
  * macropixels) are 16-byte aligned where base, pitch and stride are, and
  * multi-dword accesses at 8-byte-aligned addresses in any other legal layout:
  * the fused kernels run under their geometry conditions alone.
- * Out of scope: v210 (three 10-bit samples per 32-bit word); v216 / a UYVY
+ * (v210, three 10-bit samples per 32-bit word, is MM_V210 below.)
+ * Out of scope: v216 / a UYVY
  * word order (codes 28..31 stay unknown); P210 and planar 4:2:2; Y410 / 4:4:4;
  * low-bit-aligned words; odd H; the debug views; chroma siting other than the
  * shared 1 x 2 sample; PQ / HLG; the ring entry points (include/mm_ring.h);
@@ -528,6 +529,63 @@ extern "C" {
 #define MM_LOW_BITS  1024                                        /* word-alignment bit: the code in the word's low bits */
 #define MM_I010      (MM_P010 | MM_PLANAR | MM_LOW_BITS)         /* 1554 */
 #define MM_I010_FULL (MM_P010_FULL | MM_PLANAR | MM_LOW_BITS)    /* 1555 */
+
+/* v210 capture frames (backward-compatible addition to ABI 10: a caller detects
+ * it by mm_frame_bytes(W, H, MM_V210, &n) == MM_OK).  The 10-bit frame SDI and
+ * HDMI capture cards deliver by default: every DeckLink, AJA and Bluefish SDK
+ * offers it as the 10-bit mode, QuickTime, AVI and MXF "uncompressed 10-bit"
+ * files hold it, ffmpeg's v210 codec reads and writes it.  MM_Y210's samples at
+ * 2.67 instead of 4 bytes per pixel: each little-endian dword holds three
+ * 10-bit codes in bits 0-9, 10-19 and 20-29 (bits 30-31 unused), and six
+ * pixels make a group of four dwords:
+ *     dword 0:  Cb(0,1)  Y0       Cr(0,1)        (low, middle, high field)
+ *     dword 1:  Y1       Cb(2,3)  Y2
+ *     dword 2:  Cr(2,3)  Y3       Cb(4,5)
+ *     dword 3:  Y4       Cr(4,5)  Y5
+ * (Cb, Y, Cr, Y, ... = 1 .. 12 in this order: 0x00300801, 0x00601404,
+ * 0x00902007, 0x00C02C0A.)  The format is the pack bit MM_PACK_V210 on a Y210
+ * code: MM_V210 = MM_Y210 | 4096 (4118), MM_V210_FULL (4119), with one matrix
+ * bit 4150, 4151, 4182, 4183 (4096: every code below it that is no format
+ * stays MM_ERR_INVALID).  The bit alone, on any other family, with
+ * MM_ORDER_BGR, MM_PLANAR, MM_LOW_BITS, both matrix bits or 256 is
+ * MM_ERR_INVALID from mm_frame_bytes, mm_surface_* and every frame entry point,
+ * before anything is queued.
+ * Semantics are MM_Y210's word for word with v = the 10-bit code: a V210 frame
+ * IS the MM_Y210 frame whose words are code << 6 (P010's ranges, the matrix
+ * bits' matrices, the shared 1 x 2 chroma sample, the out rule, rounding and
+ * clamps), so the output is bitwise the Y210 path's on the unpacked frame,
+ * packed again, and the temporal state (mm_get_state / mm_compute_state*)
+ * bitwise that frame's.  On input bits 30-31 and the unused fields of a partial
+ * last group are ignored; output dwords have bits 30-31 zero and the unused
+ * fields of a written dword zero.  The first frame and apply_magnification = 0
+ * pass every used dword through bitwise, stray bits included.  W and H even
+ * (else MM_ERR_UNSUPPORTED); no debug views; in_layout->format ==
+ * out_layout->format; mm_convert_supported(x, x) is MM_OK and any mixed pair
+ * MM_ERR_UNSUPPORTED; mm_ycbcr_matrix takes the six codes and returns the Y210
+ * code's values.
+ * Rows: the used dwords of a row are D(W) = 4 (W / 6) + {0, 2, 3}[(W % 6) / 2],
+ * so a row is 4 D(W) bytes (1920: 5,120; 1280: 3,416; 98: 264; 64: 172).
+ * mm_surface_tight / mm_frame_bytes use the pitch every SDK and ffmpeg use,
+ * 128 ceil(W / 48): 1920 x 1080 has pitch 5,120 and 5,529,600 bytes, 1280 x 720
+ * pitch 3,456 and 2,488,320 bytes, 98 x 62 pitch 384 and 23,808 bytes; frame k
+ * of a stream at k * mm_frame_bytes.  Everything past a row's 4 D(W) bytes is
+ * padding, never read and never written, in the tight frame too.
+ * Surfaces: the unit u is 16, one group; device frame pointers, pitch and frame
+ * stride are multiples of 16; pitch >= 4 D(W); chroma_offset = chroma_pitch = 0;
+ * the extent is pitch (H - 1) + 4 D(W); the 4 GiB and overflow rules are
+ * unchanged; a region of interest starts on a column that is a multiple of 6.
+ * mm_surface_aligned(1920, 1080, MM_V210, 256, 16): pitch 5,120, frame_stride
+ * 5,570,560; mm_surface_aligned(1280, 720, MM_V210, 128, 1): pitch 3,456.
+ * The forward row kernel loads one dword per tap (BT.601) or the pixel pair's
+ * two dwords (a matrix bit); the compose is always the unfused pair, its
+ * groups stored whole (16 bytes, or a partial last group's 8 or 12).
+ * Out of scope: a fused compose; convert pairs; v216 and a UYVY word order;
+ * P210 and planar 4:2:2; odd sizes and the debug views; regions of interest not
+ * on a multiple of 6 columns; other chroma sitings; PQ / HLG; the ring entry
+ * points (include/mm_ring.h), the Unity shim and mm_extmem_check. */
+#define MM_PACK_V210 4096                                        /* packing bit: three 10-bit codes per dword */
+#define MM_V210      (MM_Y210 | MM_PACK_V210)                    /* 4118 */
+#define MM_V210_FULL (MM_Y210_FULL | MM_PACK_V210)               /* 4119 */
 
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0  /* usePyramidDecomposition = true (.cs:18, :128-131) */

@@ -578,8 +578,10 @@ static int process_surface(mm_handle *h, const void *in, const mm_surface *in_la
     const int npi = surf_planes(h->W, h->H, *in_layout, pi), npo = surf_planes(h->W, h->H, *out_layout, po);
     (void)surf_planes(h->W, h->H, t, pt);
     (void)surf_planes(h->W, h->H, to, pto);
-    auto tight = [](const mm_surface &l, const mm_surface &tl) {
-        return l.pitch == tl.pitch && l.chroma_offset == tl.chroma_offset && l.chroma_pitch == tl.chroma_pitch;
+    // (a tight v210 frame has row padding of its own: plane by plane, like any pitched frame)
+    auto tight = [&](const mm_surface &l, const mm_surface &tl) {
+        return l.pitch == tl.pitch && l.chroma_offset == tl.chroma_offset && l.chroma_pitch == tl.chroma_pitch &&
+               tl.pitch == fmt_info(tl.format)->row_bytes(h->W);
     };
     if (tight(*in_layout, t)) {
         HIPCHK(hipMemcpyAsync(h->d_stage_in, in, fr.fb, hipMemcpyHostToDevice, s));

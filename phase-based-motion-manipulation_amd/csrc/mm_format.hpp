@@ -26,12 +26,15 @@ static_assert(kFmtI420 < 256 && kFmtI420M < 256 && MM_I420 == (MM_NV12 | MM_PLAN
 static_assert(kFmtI010 < 256 && kFmtI010M < 256 && MM_I010 == (MM_P010 | MM_PLANAR | MM_LOW_BITS) &&
                   !(MM_LOW_BITS & (kMatrixBits | MM_ORDER_BGR | MM_PLANAR | 255)),
               "the kernels' 10-bit three-plane template arguments are internal codes below 256");
+static_assert(kFmtV210 < 256 && kFmtV210M < 256 && MM_V210 == (MM_Y210 | MM_PACK_V210) &&
+                  !(MM_PACK_V210 & (kMatrixBits | MM_ORDER_BGR | MM_PLANAR | MM_LOW_BITS | 511)),
+              "the kernels' v210 template arguments are internal codes below 256; the pack bit is no other bit");
 static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && !(MM_ORDER_BGR & kMatrixBits),
               "the kernels' packed RGB template argument is the MM_RGB24 code; the order bit is no matrix bit");
 static_assert((MM_NV12_FULL ^ MM_NV12) == kRangeBit && (MM_P010_FULL ^ MM_P010) == kRangeBit &&
                   (MM_I420_FULL ^ MM_I420) == kRangeBit && (MM_I010_FULL ^ MM_I010) == kRangeBit &&
                   (MM_YUY2_FULL ^ MM_YUY2) == kRangeBit && (MM_UYVY_FULL ^ MM_UYVY) == kRangeBit &&
-                  (MM_Y210_FULL ^ MM_Y210) == kRangeBit,
+                  (MM_Y210_FULL ^ MM_Y210) == kRangeBit && (MM_V210_FULL ^ MM_V210) == kRangeBit,
               "the full-range code of a Y'CbCr format is its limited-range code with bit 0 set");
 
 struct FmtInfo {
@@ -58,14 +61,32 @@ struct FmtInfo {
     // layout that fails takes the unfused pair, whose accesses are single
     // samples: same arithmetic, same results.
     uint8_t quad[4];
+    // A grouped format (v210) has no bytes per pixel (bpp 0): grp_px pixels lie
+    // in grp_bytes bytes, a partial last group takes the whole dwords its pixels'
+    // share of the group needs (2 of 6 pixels: 2 dwords, 4: 3), and the tight
+    // frame's pitch is the row's bytes rounded up to tight_align (v210: the 128
+    // of every SDK).  0, 0, 0: a row is W x bpp bytes, tight rows back to back.
+    // No fused compose reads such a format (k34_fits).
+    uint8_t grp_px, grp_bytes, tight_align;
 
     bool ycc() const { return (opt & kMatrixBits) != 0; }   // Y'CbCr: range and matrix bits, even sizes, no debug view
     bool full(int fmt) const { return ycc() && (fmt & kRangeBit); }
-    size_t row_bytes(int W) const { return (size_t)W * bpp; }
+    size_t row_bytes(int W) const
+    {
+        if (!grp_px) return (size_t)W * bpp;
+        const size_t rem = (size_t)(W % grp_px);
+        return (size_t)(W / grp_px) * grp_bytes + 4 * ((rem * grp_bytes + 4 * grp_px - 1) / (4 * grp_px));
+    }
+    // the tight frame's pitch
+    size_t tight_pitch(int W) const
+    {
+        const size_t rb = row_bytes(W);
+        return tight_align ? (rb + tight_align - 1) / tight_align * tight_align : rb;
+    }
     size_t chroma_row_bytes(int W) const { return row_bytes(W) / c_row_div; }
     size_t frame_bytes(int W, int H) const
     {
-        const size_t luma = row_bytes(W) * (size_t)H;
+        const size_t luma = tight_pitch(W) * (size_t)H;
         return planes == 1 ? luma : luma + (planes - 1) * chroma_row_bytes(W) * (size_t)(H / c_h_div);
     }
 };
@@ -119,6 +140,10 @@ static constexpr FmtInfo kFormats[] = {
     {MM_YUY2,       kYccBits,   kFmtYUY2,      kFmtYUY2M, 1, 4,  2, 1, 1, 1, 0, 0,   255, 0.5,  {1, 1, 1, 1}},
     {MM_UYVY,       kYccBits,   kFmtYUY2,      kFmtYUY2M, 1, 4,  2, 1, 1, 1, 0, 1,   255, 0.5,  {1, 1, 1, 1}},
     {MM_Y210,       kYccBits,   kFmtY210,      kFmtY210M, 2, 8,  4, 1, 1, 1, 6, 0,  1023, 0.5,  {1, 1, 1, 1}},
+    // v210 (MM_Y210 | MM_PACK_V210): Y210's samples, six pixels to a group of four
+    // dwords, the unit; the kernels read a code as Y210's word code << 6 (shift 6:
+    // Y210's uniforms).  Rows of 4 D(W) bytes in a pitch of 128 ceil(W / 48).
+    {MM_V210,       kYccBits,   kFmtV210,      kFmtV210M, 4, 16, 0, 1, 1, 1, 6, 0,  1023, 0.5,  {1, 1, 1, 1}, 6, 16, 128},
 };
 
 // The row of a format code, or null for a code that is no format: a code is

@@ -238,7 +238,7 @@ static inline int surf_tight(int W, int H, int fmt, mm_surface *s)
     if (int rc = fmt_check(W, H, fmt, nullptr)) return rc;
     const FmtInfo &f = *fmt_info(fmt);
     s->format = fmt;
-    s->pitch = f.row_bytes(W);
+    s->pitch = f.tight_pitch(W);   // (the row's bytes; v210: rounded up to 128)
     s->chroma_offset = f.planes > 1 ? s->pitch * (size_t)H : 0;
     s->chroma_pitch = f.planes > 1 ? f.chroma_row_bytes(W) : 0;
     s->frame_stride = f.frame_bytes(W, H);
@@ -330,7 +330,9 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
         return s.pitch == t.pitch && s.chroma_offset == t.chroma_offset && s.chroma_pitch == t.chroma_pitch &&
                s.frame_stride == t.frame_stride;
     };
-    f.packed = !f.mixed() && tight(li) && tight(lo);
+    // (a tight v210 frame whose rows end before its pitch has padding of its
+    // own, which a plain copy would carry along: k_copy_rows)
+    f.packed = !f.mixed() && tight(li) && tight(lo) && t.pitch == f.fi->row_bytes(W);
     return f;
 }
 
@@ -355,6 +357,10 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
     MM_FMT_CASE(kFmtRGB24, __VA_ARGS__)                                        \
     MM_FMT_CASE(kFmtI420, __VA_ARGS__)                                         \
     MM_FMT_CASE(kFmtI010, __VA_ARGS__)                                         \
+    /* a grouped format has no instance of the kernels launched through this  \
+       switch (its K1 and K4 launches name theirs): refused, never another    \
+       format's kernel over its bytes */                                       \
+    case kFmtV210: return MM_ERR_UNSUPPORTED;                                  \
     default: { constexpr int FMT_ = MM_RGBA8_SRGB; __VA_ARGS__; } break;       \
     }
 // ... the compose kernels' (k_compose, k_rows_inv_compose, k_rows_inv_compose4):
@@ -375,8 +381,13 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
 // reads the chroma samples too (BT.709 and BT.2020, both ranges, share it): the
 // chroma plane or planes, or whole macropixels (four bytes, or the 10-bit
 // form's eight)
+// (a grouped format, v210, has K1 instances and no fused compose instance, so
+// MM_FMT_SWITCH refuses it: its row's two K1 instances are cases here, its
+// compose launch_k4's)
 #define MM_FMT_SWITCH_K1(fi, fmt, ...)                                         \
-    switch (fmt_matrix(fmt) ? (fi)->k1m : 0) {                                 \
+    switch (fmt_matrix(fmt) ? (fi)->k1m : (fi)->grp_px ? (fi)->kfmt : 0) {        \
+    MM_FMT_CASE(kFmtV210, __VA_ARGS__)                                         \
+    MM_FMT_CASE(kFmtV210M, __VA_ARGS__)                                        \
     MM_FMT_CASE(kFmtNV12M, __VA_ARGS__)                                        \
     MM_FMT_CASE(kFmtP010M, __VA_ARGS__)                                        \
     MM_FMT_CASE(kFmtI420M, __VA_ARGS__)                                        \
@@ -1004,6 +1015,9 @@ static bool k34_quads_aligned(const mm_handle *h, const uint8_t *in, const uint8
 // canvas, and no vertical blur tap wrapping (list row of output row i + v is i + v)
 static bool k34_fits(const mm_handle *h, const uint8_t *in, const uint8_t *out, const Frames &fr, int nframes)
 {
+    // a grouped format (v210: six pixels to a store unit) has no fused instance
+    // in any form, the walking kernel, the one-shot and the lanes' alike
+    if (fr.fi->grp_px || fr.fo->grp_px) return false;
     if (!k34_quads_aligned(h, in, out, fr, nframes)) return false;
     const Geo &g = h->geo;
     return g.N <= 4096 &&   // two transforms per workgroup: 2 N / 8 <= 1024 threads
@@ -1128,6 +1142,13 @@ static int launch_k4(mm_handle *h, const uint8_t *in, uint8_t *out, int frame0, 
     const int rt = (h->H + kTileRows - 1) / kTileRows, ct = (h->W + kTileCols - 1) / kTileCols;
     const dim3 grid(rt * ct * nout);
     ProfScope ps(h, s, MM_K_COMPOSE, nout);
+    if (fr.fi->kfmt == kFmtV210) {   // column tiles of whole 6-pixel groups (no mixed pair has it)
+        const int ctg = (h->W + kTileColsG - 1) / kTileColsG;
+        hipLaunchKernelGGL((k_compose<kFmtV210>), dim3(rt * ctg * nout), dim3(k4_tile_cols<kFmtV210>), 0, s, h->d_Yh,
+                           h->yh_stride, in, out, frame0, rt, ctg, geo_of(h, fr), h->blur, h->d_col3, h->d_row3);
+        HIPCHK(hipGetLastError());
+        return MM_OK;
+    }
     MM_PAIR_SWITCH(fr, hipLaunchKernelGGL((k4_kernel<FMT_>()), grid, dim3(kTileCols), 0, s, h->d_Yh,
                                           h->yh_stride, in, out, frame0, rt, ct, geo_of(h, fr), h->blur,
                                           h->d_col3, h->d_row3))

@@ -546,6 +546,12 @@ template <int FMT> constexpr bool k422 = FMT == kFmtYUY2 || FMT == kFmtYUY2M;
 constexpr int kFmtY210 = 22;   // MM_Y210
 constexpr int kFmtY210M = 54;  // MM_Y210 | MM_MATRIX_BT709 (K1 only: any matrixed Y210)
 template <int FMT> constexpr bool kY210 = FMT == kFmtY210 || FMT == kFmtY210M;
+// v210 (section below): the same samples, three 10-bit codes to a dword.  The
+// public codes carry MM_PACK_V210 (4096), so the instances are internal codes
+// below 256 (22 | 128, 54 | 128), as the three-plane formats' are
+constexpr int kFmtV210 = 150;   // MM_V210* (every range and matrix)
+constexpr int kFmtV210M = 182;  // K1 only: any matrixed MM_V210*
+template <int FMT> constexpr bool kV210 = FMT == kFmtV210 || FMT == kFmtV210M;
 // packed RGB (section below): kFmtRGB24 runs every MM_RGB24 and MM_BGR24 frame
 constexpr int kFmtRGB24 = 13;  // MM_RGB24
 template <int FMT> constexpr bool kRGB24 = FMT == kFmtRGB24;
@@ -614,7 +620,7 @@ __device__ __forceinline__ float k1_luma(typename LumaSrc<FMT>::raw_t u, const G
 }
 template <int FMT> __device__ __forceinline__ float k1_unit(const Geo &g)
 {
-    if constexpr (k420<FMT> || k422<FMT> || kY210<FMT>) return g.nv.y_unit;
+    if constexpr (k420<FMT> || k422<FMT> || kY210<FMT> || kV210<FMT>) return g.nv.y_unit;
     else if constexpr (kRGB24<FMT>) return kLumaUnit<0>;   // RGBA8's integer luma
     else return kLumaUnit<FMT>;
 }
@@ -723,6 +729,7 @@ __device__ __forceinline__ c2 src_iq2(typename ChromaSrc<FMT>::raw_t u, const Ge
     if constexpr (k420<FMT>) return c420_iq2<FMT>(u, g);
     else if constexpr (k422<FMT>) return c422_iq2(u, g);
     else if constexpr (kY210<FMT>) return y210_iq2(u, g);
+    else if constexpr (kV210<FMT>) return p010_iq2(u, g);   // (staged as P010's word pair: v210_cword)
     else if constexpr (kRGB24<FMT>) return rgb24_iq2(u, g);
     else return chroma_iq2<FMT>(u);
 }
@@ -1108,11 +1115,100 @@ template <> struct LumaSrc<kFmtYUY2M> {    // the pixel's whole macropixel
 };
 template <> struct ChromaSrc<kFmtYUY2> { using raw_t = uint32_t; };    // the macropixel
 template <> struct ChromaSrc<kFmtYUY2M> { using raw_t = uint32_t; };
+// ---- v210 (MM_V210) access ---------------------------------------------------
+// MM_Y210's samples, three 10-bit codes to a little-endian dword (bits 0-9,
+// 10-19, 20-29; bits 30-31 unused) and six pixels to a group of four dwords:
+//   dword 0: Cb(0,1) Y0 Cr(0,1)   dword 1: Y1 Cb(2,3) Y2
+//   dword 2: Cr(2,3) Y3 Cb(4,5)   dword 3: Y4 Cr(4,5) Y5
+// A frame IS the MM_Y210 frame whose words are code << 6: every code read here
+// enters the Y210 / P010 expressions as that word, so state and output codes
+// are bitwise the Y210 path's.  Column c = col % 6 of group q = col / 6 (a
+// multiply-high, no integer divide); pixel pair p = c / 2.
+//   K1, BT.601 (kFmtV210): one aligned dword per tap, dword 4 q + {0, 1, 1, 2,
+//     3, 3}[c], field at bit {10, 0, 20, 10, 0, 20}[c].
+//   K1, matrixed (kFmtV210M), and the compose's source side: the two dwords
+//     p, p + 1 of the group hold the pair's Cb, Cr and both its lumas (one
+//     8-byte load at a dword-aligned address: pair 1 starts at byte 4).  With
+//     v = d[p] | d[p+1] << 32: Cb at bit 10 p, Cr at bit {20, 32, 42}[p], Y at
+//     bit {10, 32, 20, 42, 32, 52}[c].  Eight bytes per tap, as the Y210
+//     instance loads (a whole group per tap, 16 bytes: twice the registers of
+//     the load batch).
+//   compose, store side (k_compose with tiles of kTileColsG columns): a lane holds its pixel's luma code and
+//     its pair's Cb (even lane) or Cr (odd lane) code; a dword mixes the codes
+//     of up to three lanes, so the codes of a tile go through LDS and the first
+//     lane of each group stores the group: one aligned 16-byte store, or the 8
+//     or 12 bytes of a partial last group (W % 6 = 2, 4), unused fields zero.
+// Alignment: frame base, pitch and stride are multiples of 16 (mm_surface's
+// unit, one group), so every group is 16-byte aligned in every legal layout.
+// No fused K34, GEN, k_compose_odd, k_dbg_out or k_convert instance.
+template <> struct LumaSrc<kFmtV210> {     // the dword that holds the pixel's luma
+    using raw_t = uint32_t;
+    static constexpr int bpp = 0;          // (no bytes per pixel: k1_off)
+};
+template <> struct LumaSrc<kFmtV210M> {    // the pair's two dwords
+    using raw_t = uint2;
+    static constexpr int bpp = 0;
+};
+template <> struct ChromaSrc<kFmtV210> { using raw_t = uint32_t; };    // P010's word pair Cb << 6 | Cr << 22
+template <> struct ChromaSrc<kFmtV210M> { using raw_t = uint32_t; };
+__device__ __forceinline__ unsigned v210_group(unsigned col) { return __umulhi(col, 0xAAAAAAABu) >> 2; }   // col / 6
+// byte offset in the row of the dword that holds column col's luma
+__device__ __forceinline__ unsigned v210_y_off(unsigned col)
+{
+    const unsigned q = v210_group(col), c = col - 6u * q;
+    return 16u * q + 4u * ((0x332110u >> (4u * c)) & 3u);
+}
+__device__ __forceinline__ unsigned v210_y_shift(unsigned col)
+{
+    const unsigned c = col - 6u * v210_group(col);
+    return 10u * ((0x861u >> (2u * c)) & 3u);
+}
+// ... of the pair's two dwords
+__device__ __forceinline__ unsigned v210_pair_off(unsigned col)
+{
+    const unsigned q = v210_group(col), c = col - 6u * q;
+    return 16u * q + 4u * (c >> 1);
+}
+// the pair's two dwords (v210_pair_off's) -> column col's luma code, the pair's
+// chroma as P010's word pair
+__device__ __forceinline__ unsigned v210_pair_y(uint2 m, unsigned col)
+{
+    const unsigned c = col - 6u * v210_group(col);
+    const unsigned long long v = (unsigned long long)m.y << 32 | m.x;
+    // bit {10, 32, 20, 42, 32, 52}[c], one byte each
+    return (unsigned)(v >> ((0x34202A14200Aull >> (8u * c)) & 63u)) & 1023u;
+}
+__device__ __forceinline__ unsigned v210_cword(uint2 m, unsigned col)
+{
+    const unsigned p = (col - 6u * v210_group(col)) >> 1;
+    const unsigned long long v = (unsigned long long)m.y << 32 | m.x;
+    const unsigned cb = (unsigned)(v >> (10u * p)) & 1023u;
+    const unsigned cr = (unsigned)(v >> ((0x2A2014u >> (8u * p)) & 63u)) & 1023u;   // bit {20, 32, 42}[p]
+    return cb << 6 | cr << 22;
+}
+// One group of an output row from the six lanes' codes e[k] = Y | C << 16 (C:
+// Cb of an even, Cr of an odd column), `n` of them inside the frame (2, 4, 6)
+__device__ __forceinline__ void v210_store_group(uint8_t *row, unsigned group, const unsigned (&e)[6], int n)
+{
+    const unsigned d0 = e[0] >> 16 | (e[0] & 1023u) << 10 | (e[1] >> 16) << 20;
+    const unsigned d1 = (e[1] & 1023u) | (e[2] >> 16) << 10 | (e[2] & 1023u) << 20;
+    const unsigned d2 = e[3] >> 16 | (e[3] & 1023u) << 10 | (e[4] >> 16) << 20;
+    const unsigned d3 = (e[4] & 1023u) | (e[5] >> 16) << 10 | (e[5] & 1023u) << 20;
+    if (n == 6) {
+        st_stream<uint4>(row, group * 16u, make_uint4(d0, d1, d2, d3));
+    } else {
+        st_stream<uint2>(row, group * 16u, make_uint2(d0, d1));
+        if (n == 4) st_stream<uint32_t>(row, group * 16u + 8u, d2);
+    }
+}
+
 // K1: byte offset of pixel column col's sample in its source row
 template <int FMT> __device__ __forceinline__ unsigned k1_off(unsigned col)
 {
     if constexpr (FMT == kFmtYUY2M) return (col & ~1u) * 2u;
     else if constexpr (FMT == kFmtY210M) return (col & ~1u) * 4u;
+    else if constexpr (FMT == kFmtV210) return v210_y_off(col);
+    else if constexpr (FMT == kFmtV210M) return v210_pair_off(col);
     else return col * (unsigned)LumaSrc<FMT>::bpp;
 }
 // ... of the load for pixel column col (packed RGB: the row's last pixel is
@@ -1127,6 +1223,7 @@ template <int FMT> __device__ __forceinline__ typename LumaSrc<FMT>::raw_t k1_ld
 {
     // (the typedef itself: a template argument would drop its alignment)
     if constexpr (kRGB24<FMT>) return *reinterpret_cast<const u32_a1 *>(reinterpret_cast<const uint8_t *>(row) + off);
+    else if constexpr (FMT == kFmtV210M) return ld_pair_a4(row, off);   // (pair 1 of a group starts at byte 4)
     else return ld_off<typename LumaSrc<FMT>::raw_t>(row, off);
 }
 // K1: the luma of column col's loaded sample (in k1_luma's units).  One
@@ -1144,6 +1241,11 @@ __device__ __forceinline__ float k1_luma_at(typename LumaSrc<FMT>::raw_t u, [[ma
         return k1_luma<kFmtP010M>((uint16_t)yc, g) + k1_chroma<kFmtP010M>(y210_cword(u), g);
     } else if constexpr (FMT == kFmtY210) {
         return k1_luma<kFmtP010>((uint16_t)(u & 0xFFFFu), g);
+    } else if constexpr (FMT == kFmtV210M) {
+        // (the Y210 instance's expression on the words code << 6)
+        return k1_luma<kFmtP010M>((uint16_t)(v210_pair_y(u, col) << 6), g) + k1_chroma<kFmtP010M>(v210_cword(u, col), g);
+    } else if constexpr (FMT == kFmtV210) {
+        return k1_luma<kFmtP010>((uint16_t)(((u >> v210_y_shift(col)) & 1023u) << 6), g);
     } else if constexpr (kRGB24<FMT>) {
         return rgb24_luma_units(rgb24_fix(u, col, g), g);
     } else {
@@ -1330,7 +1432,12 @@ void k_rows_fwd(const uint8_t *__restrict__ frames, int pairs_per_frame,
     // matrixed three-plane instance, two chroma byte loads per pair, the same:
     // one batch spilled 29; its 10-bit form, two chroma word loads per pair:
     // one batch spilled 27)
-    constexpr int UB = BPP == 16 || ((FMT == kFmtY210M || FMT == kFmtI420M || FMT == kFmtI010M) && LOG2N == 13) ? 4 : 8;
+    // (v210's matrixed instance, the same 8 bytes per tap as MM_Y210's plus the
+    // field positions of each column: four batches of two there; two batches
+    // spilled 10 in the one-pair form.  DESIGN.md "v210 capture frames" has the
+    // register table)
+    constexpr int UB = FMT == kFmtV210M && LOG2N == 13 ? 2
+                       : BPP == 16 || ((FMT == kFmtY210M || FMT == kFmtI420M || FMT == kFmtI010M) && LOG2N == 13) ? 4 : 8;
     if constexpr (GEN) {
         if (valid) {
             Tap4 ta = rowT[ra];
@@ -2851,6 +2958,12 @@ void k_rows_inv(const c2 *__restrict__ Q, size_t q_stride, float *__restrict__ Y
 #define MM_K4_COLS 256
 #endif
 constexpr int kTileRows = MM_K4_ROWS, kTileCols = MM_K4_COLS;
+// v210's column tile: whole groups of 6 pixels (a tile that split a group would
+// split a dword between workgroups), three waves.  The instance is launched
+// with that many threads (k4_tile_cols; the launch bound is the larger tile's).
+constexpr int kTileColsG = 192;
+static_assert(kTileColsG <= kTileCols, "k_compose's launch bound is kTileCols: the group tile must fit it");
+template <int FMT> constexpr int k4_tile_cols = kV210<kFmtOut<FMT>> ? kTileColsG : kTileCols;
 template <int FMT>
 __global__ __launch_bounds__(kTileCols)
 void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__restrict__ frames_in,
@@ -2858,7 +2971,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                int col_tiles, Geo g, Blur5 bw, const float4 *__restrict__ colW3,
                const float4 *__restrict__ rowW3)
 {
-    constexpr int TR = kTileRows, TC = kTileCols, WC = TC + 2;
+    constexpr int TR = kTileRows, TC = k4_tile_cols<FMT>, WC = TC + 2;
     constexpr int FI = kFmtIn<FMT>, FO = kFmtOut<FMT>;   // (a plain format: both are FMT)
     static_assert(kFmtPairOk<FMT>, "a format, or one of the three mixed pairs");
     __shared__ c2 iq[(TR + 2) * WC];         // I/Q of the staged source pixels
@@ -2883,12 +2996,15 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
         if constexpr (k420<FI>) return c420_off<FI>(g, row, col);
         else if constexpr (k422<FI>) return c422_off(g, row, col);
         else if constexpr (kY210<FI>) return y210_off(g, row, col);
+        else if constexpr (kV210<FI>) return (unsigned)row * g.li.pitch + v210_pair_off(col);
         else if constexpr (kRGB24<FI>) return (unsigned)row * g.li.pitch;   // (the row: rgb24_px adds the column)
         else return (unsigned)row * g.li.pitch + col * Pix<FI>::bpp;
     };
     // (packed RGB: the byte-aligned dword of the pixel)
+    // (v210: the pair's two dwords, its chroma extracted as P010's word pair)
     auto ld_src = [&](int row, unsigned col) {
         if constexpr (kRGB24<FI>) return rgb24_px(img, src_off(row, col), col, g);
+        else if constexpr (kV210<FI>) return (raw_t)v210_cword(ld_pair_a4(img, src_off(row, col)), col);
         else if constexpr (kPlanes3<FI>) return (raw_t)c420_pair<FI>(img, g, row, col);   // (a sample of each chroma plane)
         else return ld_off<raw_t>(img, src_off(row, col));
     };
@@ -2926,7 +3042,10 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
 #pragma unroll
     for (int sr = 0; sr < TR + 2; ++sr) iq[sr * WC + tid] = src_iq2<FI>(pa[sr], g);
     __syncthreads();
-    if (!vx) return;
+    // (v210: every lane stays for the barrier of the code exchange below; a lane
+    // past W computes from clamped addresses and its codes are not used)
+    if constexpr (!kV210<FO>) if (!vx) return;
+    [[maybe_unused]] unsigned vcode[kV210<FO> ? TR : 1] = {};   // v210: the rows' codes Y | C << 16
     c2 hc[TR + 2];   // horizontally combined (I, Q) of each staged row
 #pragma unroll
     for (int sr = 0; sr < TR + 2; ++sr) {
@@ -3022,10 +3141,51 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)half, 0xB1, 0xF, 0xF, true);
                 if (!(X & 1))
                     st_stream<uint2>(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 4u, make_uint2(half, other));
+            } else if constexpr (kV210<FO>) {
+                // The Y210 branch's codes: the lane pair's chroma sum by the
+                // same exchange (c0, a multiple of 6, and W are even), the lane
+                // keeps its luma code and the pair's Cb (even) or Cr (odd) code
+                // for the group exchange after the row loop.
+                static_assert(TC % 6 == 0, "v210: tiles of whole groups");
+                c2 cd;
+                const unsigned yc = nv12_ycode(rr, gg, bb, g, cd);
+                const float mine = X & 1 ? cd.y : cd.x, send = X & 1 ? cd.x : cd.y;
+                const float theirs = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
+                    __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
+                vcode[r] = yc | p010_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo) << 16;
             } else if constexpr (kRGB24<FO>) {   // three bytes per lane
                 rgb24_store(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, rr, gg, bb, g);
             } else {
                 Pix<FO>::store(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
+            }
+        }
+    }
+    if constexpr (kV210<FO>) {
+        // A dword of a group mixes the codes of up to three lanes, and a group's
+        // six lanes may lie in two waves (64 is no multiple of 6): the tile's
+        // codes go through LDS (over the staged (I, Q), which every lane has
+        // read: the barrier in between), and the first lane of each group reads
+        // its group's six and stores it whole.  Codes of columns past W are
+        // zero: the unused fields of a partial last group.
+        static_assert(sizeof(iq) >= sizeof(unsigned) * TR * TC, "the codes fit the staging area");
+        unsigned *codes = reinterpret_cast<unsigned *>(iq);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < TR; ++r) codes[r * TC + tid] = vx ? vcode[r] : 0u;
+        __syncthreads();
+        const unsigned grp = v210_group((unsigned)tid);
+        if ((unsigned)tid == 6u * grp && vx) {
+            const int n = min(6, g.W - X);
+            const unsigned og = v210_group((unsigned)X);
+#pragma unroll
+            for (int r = 0; r < TR; ++r) {
+                const int i = i0 + r;
+                if (i < g.H) {
+                    unsigned e[6];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) e[k] = codes[r * TC + tid + k];
+                    v210_store_group(outp + (size_t)((unsigned)i * g.lo.pitch), og, e, n);
+                }
             }
         }
     }

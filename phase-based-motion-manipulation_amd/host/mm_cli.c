@@ -9,7 +9,7 @@
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
  *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
- *          [--yuy2] [--uyvy] [--y210] [--ppm [--bgr]] [--i420] [--i010] [--out-rgba8] [--out-nv12]
+ *          [--yuy2] [--uyvy] [--y210] [--v210] [--ppm [--bgr]] [--i420] [--i010] [--out-rgba8] [--out-nv12]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R] [--lanes M]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
@@ -42,7 +42,7 @@
  * clips are), processed in linear light as Unity's Linear colour space does
  * (MM_RGBA8_SRGB: decoded on read, encoded on write); default UNORM.
  * The input-format options (--nv12 --p010 --i420 --i010 --mono --yuy2 --uyvy
- * --y210 --ppm; k_in_opts below has a row each): at most one, and none goes
+ * --y210 --v210 --ppm; k_in_opts below has a row each): at most one, and none goes
  * with --srgb, the ring modes, --out-nv12 or, but for --mono, the debug views;
  * --out-rgba8 goes with --nv12 and --p010 alone; --matrix and --full-range go
  * with the Y'CbCr ones (all but --mono and --ppm), which need even sizes.
@@ -59,10 +59,10 @@
  * converted silently: an 8-bit input with --p010 and a 10-bit input without it
  * are refused.
  * --matrix 601|709|2020 (default 601): the Y'CbCr matrix of an --nv12,
- * --p010, --yuy2, --uyvy or --y210 clip (HD content is BT.709, UHD BT.709 or BT.2020), OR-ed onto the
+ * --p010, --yuy2, --uyvy, --y210 or --v210 clip (HD content is BT.709, UHD BT.709 or BT.2020), OR-ed onto the
  * frame format as MM_MATRIX_BT709 / MM_MATRIX_BT2020.  A .y4m header has no
  * matrix tag, so files are the same whatever the value.  Only with --nv12,
- * --p010, --yuy2, --uyvy or --y210: the host's own RGBA conversion of a .y4m is BT.601.
+ * --p010, --yuy2, --uyvy, --y210 or --v210: the host's own RGBA conversion of a .y4m is BT.601.
  * --mono: a mono .y4m input (Cmono, Cmono10, Cmono12, Cmono16: a grayscale
  * camera's or ffmpeg's gray / gray10le / gray12le / gray16le frames) goes to
  * the device as it is stored, as MM_Y8 / MM_Y10 / MM_Y12 / MM_Y16 frames by the
@@ -85,8 +85,16 @@
  * matrix bit with --matrix): the planes are interleaved and shifted on the way
  * in and split on the way out (a C422p10 .y4m; any other extension: the raw
  * Y210 frames), and no colour arithmetic runs on the host.
- * A C422p10 input needs --y210: it is
+ * A C422p10 input needs --y210 or --v210: it is
  * never converted on the host.
+ * --v210: the same C422p10 .y4m input goes to the device as MM_V210 frames,
+ * the capture cards' layout of three 10-bit codes per dword (include/mm.h),
+ * rows at the standard pitch 128 ceil(W / 48): the container has no v210 tag,
+ * so each frame is packed on the host on the way in and unpacked on the way
+ * out (host/v210.h; shifts only, no colour arithmetic; a C422p10 .y4m; any
+ * other extension: the raw v210 frames).  The output file is --y210's, byte for
+ * byte.  --matrix, --full-range, --surface-align (P a multiple of 16) and
+ * --checksum as usual; --y210's usage errors.
  * --ppm: the input (-i) is a stream of concatenated binary PPM images (P6,
  * maxval 255, one size: what ffmpeg -f image2pipe -vcodec ppm writes; host/ppm.h).
  * Its frames go to the device as MM_RGB24 as they lie, 3 bytes per pixel each
@@ -144,6 +152,7 @@
 #include "mm_ring.h"
 #include "mm_ring_local.h"
 #include "ppm.h"
+#include "v210.h"
 #include "y4m.h"
 
 #include <pthread.h>
@@ -215,8 +224,9 @@ static int surf_copy(void *dst, const mm_surface *dl, const void *src, const mm_
 {
     mm_surface t;
     if (mm_surface_tight(W, H, dl->format, &t)) return 1;
-    const size_t rb = t.pitch;   /* sample bytes of a row */
-    if (dl->pitch == rb && sl->pitch == rb && dl->chroma_offset == t.chroma_offset &&
+    /* sample bytes of a row (v210: the used dwords, short of the tight pitch) */
+    const size_t rb = (dl->format & MM_PACK_V210) ? v210_row_bytes(W) : t.pitch;
+    if (dl->pitch == t.pitch && sl->pitch == t.pitch && dl->chroma_offset == t.chroma_offset &&
         sl->chroma_offset == t.chroma_offset && dl->chroma_pitch == t.chroma_pitch &&
         sl->chroma_pitch == t.chroma_pitch && dl->frame_stride == t.frame_stride &&
         sl->frame_stride == t.frame_stride)   /* tight on both sides: one copy */
@@ -522,6 +532,9 @@ PACK_FN(pack_uyvy, y4m_422_to_packed(W, H, a, b, 1))
 PACK_FN(unpack_uyvy, y4m_packed_to_422(W, H, a, b, 1))
 PACK_FN(pack_y210, y4m_422p10_to_y210(W, H, a, b))
 PACK_FN(unpack_y210, y4m_y210_to_422p10(W, H, a, b))
+/* (the container has no v210 tag: the C422p10 planes are packed on the host, rows at the standard pitch) */
+PACK_FN(pack_v210, (void)v210_pack_422p10(W, H, a, b, v210_pitch(W)))
+PACK_FN(unpack_v210, (void)v210_unpack_422p10(W, H, a, v210_pitch(W), b))
 /* the .y4m writers of one chroma type under one signature (mono's own take the depth) */
 #define WRITE_FNS(name, hdr, frame)                                                        \
     static int whdr_##name(FILE *f, int W, int H, int n, int d, int depth) { (void)depth; return hdr(f, W, H, n, d); } \
@@ -564,17 +577,19 @@ static const in_opt k_in_opts[] = {
      pack_uyvy, unpack_uyvy, whdr_422, wframe_422},
     {"--y210", Y4M_422, 10, 0, MM_Y210, MM_Y210_FULL, 1, 0, 0, "a 10-bit 4:2:2 .y4m input (-i, C422p10)",
      pack_y210, unpack_y210, whdr_422p10, wframe_422p10},
+    {"--v210", Y4M_422, 10, 0, MM_V210, MM_V210_FULL, 1, 0, 0, "a 10-bit 4:2:2 .y4m input (-i, C422p10)",
+     pack_v210, unpack_v210, whdr_422p10, wframe_422p10},
     /* (a stream of binary PPM images: its own reader and writer, main's ppm branches; --bgr) */
     {"--ppm", -1, 8, 1, MM_RGB24, MM_RGB24, 0, 0, 0,
      "a binary PPM stream as input (-i, P6, maxval 255) and writes one (-o): no .y4m on either side", NULL, NULL, NULL, NULL},
 };
-static const in_opt *const k_opt_nv12 = &k_in_opts[0], *const k_opt_ppm = &k_in_opts[8];
+static const in_opt *const k_opt_nv12 = &k_in_opts[0], *const k_opt_ppm = &k_in_opts[9];
 
 /* The option a .y4m input cannot do without: the host converts 8-bit 4:2:0,
  * 4:4:4 and mono to RGBA8 and nothing else, and no bit depth silently. */
 static const char *y4m_needs(const y4m_info *yi, int depth)
 {
-    if (yi->chroma == Y4M_422) return depth == 10 ? "--y210" : "--yuy2 or --uyvy";
+    if (yi->chroma == Y4M_422) return depth == 10 ? "--y210 or --v210" : "--yuy2 or --uyvy";
     if (depth == 8) return NULL;
     return yi->chroma == Y4M_MONO ? "--mono" : "--p010";
 }
@@ -658,7 +673,7 @@ int main(int argc, char **argv)
     if (out_nv12 && (srgb || views || ring))
         REFUSE("--out-nv12 takes the RGBA8 input path: not with --srgb, the debug views or the ring modes\n");
     if (matrix_arg && !(in && in->ycc) && !out_nv12)
-        REFUSE("--matrix needs --nv12, --p010, --yuy2, --uyvy, --y210, --i420, --i010 or --out-nv12 (the RGBA conversion of a .y4m is BT.601)\n");
+        REFUSE("--matrix needs --nv12, --p010, --yuy2, --uyvy, --y210, --v210, --i420, --i010 or --out-nv12 (the RGBA conversion of a .y4m is BT.601)\n");
     if (matrix_arg && strcmp(matrix_arg, "601") && strcmp(matrix_arg, "709") && strcmp(matrix_arg, "2020"))
         REFUSE("--matrix takes 601, 709 or 2020, not %s (%s)\n", matrix_arg, in ? in->name : "--out-nv12");
     if (surf_arg && ring) REFUSE("--surface-align does not go with the ring modes (they take tight frames)\n");
@@ -799,7 +814,7 @@ int main(int argc, char **argv)
             (rc = mm_surface_aligned(W, H, g_fmt, (size_t)pa, ra, &lay)) != MM_OK ||
             (rc = mm_surface_aligned(W, H, o_fmt, (size_t)pa, ra, &olay)) != MM_OK) {
             fprintf(stderr, "--surface-align %s: want P,R with P a multiple of the format's unit "
-                            "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, mono: the sample size, --ppm and --i420: 1, --i010: 2; --i420: an even pitch, --i010: a multiple of 4) and R >= 1 (4:2:0: even)\n", surf_arg);
+                            "(pixel size; NV12 2, P010 and 4:2:2 4, Y210 8, v210 16, mono: the sample size, --ppm and --i420: 1, --i010: 2; --i420: an even pitch, --i010: a multiple of 4) and R >= 1 (4:2:0: even)\n", surf_arg);
             return 2;
         }
         printf("surfaces: pitch %zu  chroma offset %zu  frame stride %zu\n", lay.pitch, lay.chroma_offset,
@@ -811,8 +826,16 @@ int main(int argc, char **argv)
         fprintf(stderr, "hipMalloc failed\n");
         return 1;
     }
+    /* (a tight v210 frame has row padding, which nothing writes: zeroed once, so
+     * that checksums and raw files of whole tight frames are those of every run) */
+    if ((g_fmt & MM_PACK_V210) &&
+        (hipMemset(d_in, 0, lay.frame_stride * B) != hipSuccess || hipMemset(d_out, 0, olay.frame_stride * B) != hipSuccess ||
+         (surf_arg && (hipMemset(d_tin, 0, fb * B) != hipSuccess || hipMemset(d_tout, 0, fbo * B) != hipSuccess)))) {
+        fprintf(stderr, "hipMemset failed\n");
+        return 1;
+    }
     hipStream_t s = (hipStream_t)mm_stream(h);
-    unsigned char *host = (fi || fo) ? (unsigned char *)malloc((fb > fbo ? fb : fbo) * B) : NULL;
+    unsigned char *host = (fi || fo) ? (unsigned char *)calloc((size_t)B, fb > fbo ? fb : fbo) : NULL;
     unsigned char *planes = (y4m_in || y4m_out)
         ? (unsigned char *)malloc(y4m_in ? (y4m_frame_bytes_depth(&yi, depth) > 3 * (size_t)W * H
                                                ? y4m_frame_bytes_depth(&yi, depth) : 3 * (size_t)W * H)

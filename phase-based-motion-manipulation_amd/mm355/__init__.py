@@ -24,6 +24,7 @@ from .binding import (MMError, lib, load_library, LIB_PATH, RGBA8, RGBA32F, RGBA
                       I010, I010_FULL, LOW_BITS, I010_FORMATS,
                       YUY2, YUY2_FULL, UYVY, UYVY_FULL, PACKED422_FORMATS,
                       Y210, Y210_FULL, Y210_FORMATS,
+                      V210, V210_FULL, PACK_V210, V210_FORMATS, FORMAT_GROUP, row_bytes, tight_pitch,
                       nv12_chroma_matrix, ycbcr_matrix, base_format,
                       EDGE_REPEAT, EDGE_CLAMP, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       FILTER_DIFF, FILTER_IIR, Params, Handle, Surface, has_surfaces,
@@ -41,6 +42,7 @@ __all__ = ["MMError", "lib", "load_library", "LIB_PATH", "RGBA8", "RGBA32F", "RG
            "I010", "I010_FULL", "LOW_BITS", "I010_FORMATS",
            "YUY2", "YUY2_FULL", "UYVY", "UYVY_FULL", "PACKED422_FORMATS",
            "Y210", "Y210_FULL", "Y210_FORMATS",
+           "V210", "V210_FULL", "PACK_V210", "V210_FORMATS", "FORMAT_GROUP", "row_bytes", "tight_pitch",
            "MATRIX_BT709", "MATRIX_BT2020", "nv12_chroma_matrix", "ycbcr_matrix", "base_format",
            "EDGE_REPEAT", "EDGE_CLAMP", "MODE_PYRAMID", "MODE_STANDARD", "MODE_STEERABLE",
            "FILTER_DIFF", "FILTER_IIR", "Params", "Handle", "Surface", "has_surfaces",

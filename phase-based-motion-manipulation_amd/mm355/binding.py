@@ -68,6 +68,39 @@ LOW_BITS = 1024     # word-alignment bit: the code in the word's low bits
 I010 = P010 | PLANAR | LOW_BITS            # 1554, BT.601 limited range
 I010_FULL = P010_FULL | PLANAR | LOW_BITS  # 1555, full range
 I010_FORMATS = (I010, I010_FULL)
+# v210 capture frames (SDI / HDMI cards' 10-bit mode, ffmpeg's v210): Y210's samples,
+# three 10-bit codes to a little-endian dword and six pixels to a group of four
+# dwords; rows of row_bytes() in the pitch every SDK uses, 128 * ceil(W / 48).  The
+# pack bit is valid on the two Y210 codes alone, with or without one matrix bit.
+PACK_V210 = 4096    # packing bit: three 10-bit codes per dword
+V210 = Y210 | PACK_V210            # 4118, BT.601 limited range
+V210_FULL = Y210_FULL | PACK_V210  # 4119, full range
+V210_FORMATS = (V210, V210_FULL)
+# the grouped formats (no bytes per pixel, so no FORMAT_BPP entry): pixels and bytes
+# of a group, and what the tight frame's pitch is a multiple of
+FORMAT_GROUP = {V210: (6, 16, 128), V210_FULL: (6, 16, 128)}
+
+
+def row_bytes(width, fmt):
+    """Bytes of the samples of one row (of the first plane) of a FORMAT_BPP or
+    FORMAT_GROUP format.  A grouped format's partial last group takes the whole
+    dwords its pixels need: v210 rows are 4 * (4 * (W // 6) + (0, 2, 3)[W % 6 // 2])."""
+    base = base_format(fmt)
+    if base in FORMAT_GROUP:
+        px, nbytes, _ = FORMAT_GROUP[base]
+        rem = width % px
+        return width // px * nbytes + 4 * ((rem * nbytes + 4 * px - 1) // (4 * px))
+    return width * FORMAT_BPP[base]
+
+
+def tight_pitch(width, fmt):
+    """The row pitch of Surface.tight / frame_bytes: row_bytes, rounded up to the
+    grouped format's pitch multiple (v210: 128 * ceil(W / 48))."""
+    rb = row_bytes(width, fmt)
+    align = FORMAT_GROUP.get(base_format(fmt), (0, 0, 1))[2]
+    return (rb + align - 1) // align * align
+
+
 # one matrix bit, OR-ed onto a 4:2:0 or packed 4:2:2 code above (HD / UHD content): the layout
 # and sizes stay the base code's (base_format)
 MATRIX_BT709 = 32   # Kr 0.2126, Kb 0.0722

@@ -8,8 +8,8 @@ import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       MONO_FORMATS, NV12, NV12_FULL, P010, P010_FULL, PACKED422_FORMATS, RGBA8, RGBA8_SRGB, RGBA16F,
-                      I010_FORMATS, I420_FORMATS, RGB24_FORMATS, RGBA32F, Y8, Y210_FORMATS,
-                      Handle, MMError, Params, Surface, base_format, convert_supported)
+                      I010_FORMATS, I420_FORMATS, RGB24_FORMATS, RGBA32F, V210, V210_FORMATS, Y8, Y210_FORMATS,
+                      Handle, MMError, Params, Surface, base_format, convert_supported, tight_pitch)
 
 
 def _fmt_of(frame, srgb=False):
@@ -48,6 +48,9 @@ _FAMILIES = {
     # [H, 2 W]: rows of W / 2 macropixels, four bytes or (Y210) four words Y0 Cb Y1 Cr
     "yuv422": (lambda h, w: (h, 2 * w), "uint8", (1,), True, "bytes packed"),
     "y210": (lambda h, w: (h, 2 * w), "uint16", (1,), True, "words packed"),
+    # [H, pitch / 4] dwords of three 10-bit codes, pitch = 128 * ceil(W / 48): the
+    # frame as capture SDKs and ffmpeg lay it out, row padding included
+    "v210": (lambda h, w: (h, tight_pitch(w, V210) // 4), "uint32", (1,), True, "dwords packed"),
     # one contiguous [H * 3 / 2, W] array: H luma rows, then H / 2 rows of chroma
     # (one (Cb, Cr) plane, or a Cb and a Cr plane), in bytes or 16-bit words
     # (the two-plane rows: shape and dtype only, for _convert_side and host_frames.  Such
@@ -65,7 +68,8 @@ def _family(fmt):
     if fmt in MONO_FORMATS:
         return "y8" if fmt == Y8 else "y16"
     base = base_format(fmt)         # a matrix bit changes no size or shape
-    for name, codes in (("yuv422", PACKED422_FORMATS), ("y210", Y210_FORMATS), ("i420", I420_FORMATS),
+    for name, codes in (("yuv422", PACKED422_FORMATS), ("y210", Y210_FORMATS), ("v210", V210_FORMATS),
+                        ("i420", I420_FORMATS),
                         ("i010", I010_FORMATS), ("nv12", (NV12, NV12_FULL)), ("p010", (P010, P010_FULL))):
         if base in codes:
             return name
@@ -219,7 +223,11 @@ class MotionMagnificationProcessor:
         [H, 2 W] uint8 on both sides (contiguous or row-strided views).
         fmt=Y210 / Y210_FULL, with or without a matrix bit: 10-bit packed 4:2:2,
         [H, 2 W] uint16 on both sides (P010's convention: the words as they lie;
-        contiguous or row-strided views).  fmt=RGB24 / BGR24: [H, W, 3] uint8
+        contiguous or row-strided views).  fmt=V210 / V210_FULL, with or without a
+        matrix bit: v210 capture frames, [H, pitch / 4] uint32 on both sides with
+        pitch = mm355.tight_pitch(W, fmt) = 128 * ceil(W / 48), the layout of
+        capture SDKs and ffmpeg (contiguous, or row-strided views whose pitch is a
+        multiple of 16); any other shape raises.  fmt=RGB24 / BGR24: [H, W, 3] uint8
         on both sides, as cv2 (BGR24), PIL and imageio (RGB24) hand them out:
         device tensors, contiguous or row-strided views that start at any
         byte, or host numpy arrays; such a frame without fmt= raises.
@@ -263,7 +271,8 @@ class MotionMagnificationProcessor:
             if _fmt_of(destination, self.srgb) != fmt:
                 raise MMError(-1, "source/destination formats differ")
         elif (fmt not in MONO_FORMATS and base_format(fmt) not in PACKED422_FORMATS and
-              base_format(fmt) not in Y210_FORMATS and fmt not in RGB24_FORMATS and
+              base_format(fmt) not in Y210_FORMATS and base_format(fmt) not in V210_FORMATS and
+              fmt not in RGB24_FORMATS and
               base_format(fmt) not in I420_FORMATS and base_format(fmt) not in I010_FORMATS):
             raise MMError(-1, f"fmt={fmt}: only the grayscale, packed 4:2:2, packed RGB and three-plane 4:2:0 formats are named, "
                               "the others follow the dtype")

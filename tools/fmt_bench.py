@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""RGBA8 against NV12, P010, grayscale (Y8, Y16) and packed 4:2:2 (YUY2, UYVY, 10-bit Y210) frames on
+"""RGBA8 against NV12, P010, grayscale (Y8, Y16) and packed 4:2:2 (YUY2, UYVY, 10-bit Y210, v210) frames on
 one GPU, same process, alternating legs.
 
 The flagship stream (1920x1080, 5 levels, phase scale 25, batches of 150
@@ -40,6 +40,14 @@ YUY2 legs' pictures at 10 bits as MM_Y210 macropixels (words Y0 Cb Y1 Cr, code
 << 6), and the same words taken as MM_Y210 | MM_MATRIX_BT709, whose K1 reads
 whole 8-byte macropixels; 4 bytes per pixel each way.  A library from before
 this format runs without them.
+
+v210 legs (v210, v210_bt709, and their _pitched forms): the Y210 legs' own codes
+packed three to a dword as MM_V210 (rows at the standard pitch, 128 ceil(W / 48)),
+and the same dwords taken as MM_V210 | MM_MATRIX_BT709, whose K1 loads the pixel
+pair's two dwords; 2.67 bytes per pixel each way, so Y210 of the same run is the
+comparison.  Their compose is always the unfused pair (k_rows_inv, k_compose:
+no fused K34 instance), whose per-kernel times stand beside Y210's fused
+k_rows_inv_compose.  A library from before this format runs without them.
 
 Packed RGB legs (rgb24, bgr24, rgb24_pitched): the RGBA8 leg's pictures with
 the alpha byte dropped as MM_RGB24, the same pixels byte-swapped as MM_BGR24, 3
@@ -143,6 +151,21 @@ def to_y210(torch, rgba):
         out[k, :, 0::2] = code(yl * 876.0 + 64.0)
         out[k, :, 1::4] = code(((b - yl) * (0.5 / 0.886)).reshape(H, W // 2, 2).mean(dim=2) * 896.0 + 512.0)
         out[k, :, 3::4] = code(((r - yl) * (0.5 / 0.701)).reshape(H, W // 2, 2).mean(dim=2) * 896.0 + 512.0)
+    return out
+
+
+def to_v210(torch, y210, W):
+    """[n][H][2 W] Y210 words (int16 bit patterns, device) -> [n][H][pitch / 4]
+    v210 dwords (int32 bit patterns): the codes word >> 6 in the order Cb Y0 Cr Y1,
+    three to a dword, unused fields and the row padding zero."""
+    n, H, _ = y210.shape
+    D = 4 * (W // 6) + (0, 2, 3)[(W % 6) // 2]
+    codes = ((y210.to(torch.int32) & 0xFFFF) >> 6).reshape(n, H, W // 2, 4)[..., [1, 0, 3, 2]].reshape(n, H, 2 * W)
+    s = torch.zeros((n, H, 3 * D), dtype=torch.int32, device=y210.device)
+    s[..., :2 * W] = codes
+    s = s.reshape(n, H, D, 3)
+    out = torch.zeros((n, H, 32 * ((W + 47) // 48)), dtype=torch.int32, device=y210.device)
+    out[..., :D] = s[..., 0] | s[..., 1] << 10 | s[..., 2] << 20
     return out
 
 
@@ -256,6 +279,11 @@ def main():
                  ("i010_bt709", mm355.I010 | mm355.MATRIX_BT709)]
     except (mm355.MMError, AttributeError):
         pass    # a build from before the 10-bit three-plane format
+    try:
+        mm355.frame_bytes(W, H, mm355.V210)
+        fmts += [("v210", mm355.V210), ("v210_bt709", mm355.V210 | mm355.MATRIX_BT709)]
+    except (mm355.MMError, AttributeError):
+        pass    # a build from before the v210 format
     for name, fmt in fmts:
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
@@ -263,7 +291,7 @@ def main():
             h.synth(rgba, 0, B, stream=torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
             src = rgba
-        elif name in ("nv12_bt709", "p010_bt2020", "p010_bt709", "yuy2_bt709", "y210_bt709", "i420_bt709", "i010_bt709"):
+        elif name in ("nv12_bt709", "p010_bt2020", "p010_bt709", "yuy2_bt709", "y210_bt709", "i420_bt709", "i010_bt709", "v210_bt709"):
             src = legs[name.split("_")[0]]["src"]
         elif name == "i420":       # the NV12 leg's bytes, de-interleaved
             src = nv12_to_i420(torch, legs["nv12"]["src"])
@@ -278,6 +306,8 @@ def main():
             src = to_422(torch, rgba)
         elif name == "y210":
             src = to_y210(torch, rgba)
+        elif name == "v210":       # the Y210 leg's codes, three to a dword
+            src = to_v210(torch, legs["y210"]["src"], W)
         elif name == "uyvy":       # the same picture: every byte pair swapped
             src = legs["yuy2"]["src"].reshape(B, H, W, 2).flip(3).reshape(B, H, 2 * W).contiguous()
         elif name in ("y8", "y16"):
@@ -408,6 +438,17 @@ def main():
         k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
         out["y210_bt709_k1_us"] = {"matrixed": k1("y210_bt709"), "y210": k1("y210"), "yuy2_bt709": k1("yuy2_bt709"),
                                    "p010": k1("p010"), "rgba8": k1("rgba8")}
+    if "v210" in out["formats"]:
+        for name in ("v210", "v210_bt709"):
+            for base in ("rgba8", "y210", "yuy2"):
+                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                    out["formats"][base]["fps_median"], 4)
+        # K1, and K3 + K4 (v210: the unfused pair; the others: the fused K34)
+        kk = lambda n: out["formats"][n]["kernel_us_per_frame"]
+        out["v210_kernel_us"] = {n: {"k_rows_fwd": kk(n).get("k_rows_fwd"),
+                                     "k3_k4": round(sum(kk(n).get(k, 0.0) for k in
+                                                        ("k_rows_inv", "k_compose", "k_rows_inv_compose")), 3)}
+                                 for n in ("v210", "v210_bt709", "y210", "y210_bt709", "yuy2", "rgba8")}
     for name in ("rgb24", "bgr24"):
         if name in out["formats"]:
             for base in ("rgba8", "nv12"):
@@ -437,7 +478,7 @@ def main():
                                  for n in ("i010", "p010", "i420", "i010_bt709", "p010_bt709", "i010_pitched",
                                            "p010_pitched") if n in out["formats"]}
     for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16", "yuy2", "uyvy", "yuy2_bt709",
-                 "y210", "y210_bt709", "rgb24", "i420", "i010"):
+                 "y210", "y210_bt709", "rgb24", "i420", "i010", "v210", "v210_bt709"):
         if name + "_pitched" in out["formats"]:
             out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
                                                       out["formats"][name]["fps_median"], 4)
