@@ -691,10 +691,15 @@ static Blur5 build_blur()
 {
     const double c0 = 0.2270270270, c1 = 0.3162162162, c2w = 0.0702702703;
     const double f1 = 0.5 * 1.3846153846, f2 = 0.5 * 3.2307692308 - 1.0;
+    const double w0 = c0 + 2.0 * c1 * (1.0 - f1), w1 = c1 * f1 + c2w * (1.0 - f2), w2 = c2w * f2;
     Blur5 b;
-    b.w0 = (float)(c0 + 2.0 * c1 * (1.0 - f1));
-    b.w1 = (float)(c1 * f1 + c2w * (1.0 - f2));
-    b.w2 = (float)(c2w * f2);
+    b.w0 = (float)w0;
+    b.w1 = (float)w1;
+    b.w2 = (float)w2;
+    // the RGBA8 compose's vertical blur in code units (yiq_rgba8): 255 x, rounded once
+    b.c0 = (float)(255.0 * w0);
+    b.c1 = (float)(255.0 * w1);
+    b.c2 = (float)(255.0 * w2);
     return b;
 }
 

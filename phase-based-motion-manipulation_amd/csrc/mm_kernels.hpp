@@ -96,7 +96,11 @@ struct Spec {
     float ang_c[8], ang_s[8];
 };
 
-struct Blur5 { float w0, w1, w2; };  // taps at 0, +-1, +-2 texels
+struct Blur5 {
+    float w0, w1, w2;   // taps at 0, +-1, +-2 texels
+    float c0, c1, c2;   // 255 x the taps, each product rounded once from double (build_blur):
+                        // the RGBA8 compose's vertical blur, in code units (yiq_rgba8)
+};
 
 constexpr int ilog2c(int x) { return x <= 1 ? 0 : 1 + ilog2c(x / 2); }
 template <int LOG2N> constexpr int fft_T() { return (1 << LOG2N) / 8; }
@@ -312,6 +316,19 @@ template <> struct Pix<0> {           // RGBA8 UNORM
     {
         st_stream<uint32_t>(base, i * 4u, pack(r, g, b));
     }
+    // r, g, b in code units (255 x the UNORM value), neither saturated nor
+    // rounded: three v_cvt_pk_u8_f32, each clamping to 0 .. 255 and rounding to
+    // nearest even into its byte lane (tools/cvtpk_probe.hip), alpha 255.
+    // (0xff000000 is no inline constant: left to the compiler it sits in a
+    // VGPR for the whole kernel, which at the fused compose's 128-VGPR bound
+    // is a spill; made opaque in a scalar register it stays there.)
+    __device__ static uint32_t pack_codes(float r, float g, float b)
+    {
+        uint32_t alpha = 0xff000000u;
+        asm("" : "+s"(alpha));
+        const uint32_t a = __builtin_amdgcn_cvt_pk_u8_f32(r, 0u, alpha);
+        return __builtin_amdgcn_cvt_pk_u8_f32(b, 2u, __builtin_amdgcn_cvt_pk_u8_f32(g, 1u, a));
+    }
 };
 template <> struct Pix<1> {           // RGBA32F
     static constexpr int bpp = 16;
@@ -464,6 +481,38 @@ __device__ __forceinline__ void yiq_rgb(float yb, c2 cc, float &rr, float &gg, f
     const float b = fmaf(1.703f, cc.y, fmaf(-1.106f, cc.x, yb));
     rr = sat(rg.x); gg = sat(rg.y); bb = sat(b);
 }
+// RGBA8 UNORM out: the same pixel straight to its four bytes, in code units.
+// yc is 255 x Y' (the vertical blur with Blur5::c0 .. c2), the matrix carries
+// the 255 for (I, Q) (each product rounded once, the same in every instance),
+// and YIQToRGB's saturate and the UNORM write's x 255 + round are the clamp and
+// round-to-nearest-even of the packed byte convert (Pix<0>::pack_codes): 3 VALU
+// per pixel behind the matrix instead of 3 saturates, 3 FMAs, 3 converts and
+// the byte merge.  Every compose kernel that writes RGBA8 calls this one
+// definition (k_compose, k_rows_inv_compose, k_rows_inv_compose4), so the
+// fused, one-shot and unfused outputs stay bitwise equal.  Against yiq_rgb +
+// Pix<0>::pack a byte differs by at most one code, only where the code-unit
+// value lies within rounding of a half (or is an exact half: even, not up).
+// (sRGB's encode is not linear in the code: MM_RGBA8_SRGB keeps yiq_rgb.)
+// Packed RGB out (MM_RGB24 / MM_BGR24: "MM_RGBA8's rule, three bytes",
+// include/mm.h) stores three bytes of the same word and stays the RGBA8 path
+// byte for byte (tests/test_rgb24.py).
+template <int FO> constexpr bool kCodeOut = FO == 0 || FO == 13;   // MM_RGBA8, kFmtRGB24 (below)
+constexpr float kCodeRI = (float)(255.0 * 0.956), kCodeGI = (float)(255.0 * -0.272);
+constexpr float kCodeRQ = (float)(255.0 * 0.621), kCodeGQ = (float)(255.0 * -0.647);
+constexpr float kCodeBI = (float)(255.0 * -1.106), kCodeBQ = (float)(255.0 * 1.703);
+__device__ __forceinline__ uint32_t yiq_rgba8(float yc, c2 cc)
+{
+    const c2 rg = mk(yc, yc) + mk(kCodeRI, kCodeGI) * cc.x + mk(kCodeRQ, kCodeGQ) * cc.y;
+    const float b = fmaf(kCodeBQ, cc.y, fmaf(kCodeBI, cc.x, yc));
+    return Pix<0>::pack_codes(rg.x, rg.y, b);
+}
+// the compose kernels' vertical blur taps for output format FO
+struct VBlur { float w0, w1, w2; };
+template <int FO> __device__ __forceinline__ VBlur vblur_w(const Blur5 &b)
+{
+    if constexpr (kCodeOut<FO>) return VBlur{b.c0, b.c1, b.c2};
+    else return VBlur{b.w0, b.w1, b.w2};
+}
 
 // ---- NV12 (planar 4:2:0) access ------------------------------------------
 // A frame is H rows of W luma bytes, then H/2 rows of W bytes of interleaved
@@ -555,6 +604,7 @@ template <int FMT> constexpr bool kV210 = FMT == kFmtV210 || FMT == kFmtV210M;
 // packed RGB (section below): kFmtRGB24 runs every MM_RGB24 and MM_BGR24 frame
 constexpr int kFmtRGB24 = 13;  // MM_RGB24
 template <int FMT> constexpr bool kRGB24 = FMT == kFmtRGB24;
+static_assert(kCodeOut<kFmtRGB24> && kCodeOut<0>, "RGBA8's bytes: composed in code units (yiq_rgba8)");
 // Different formats in and out (mm_process_convert): the compose kernels'
 // FMT names a PAIR.  A plain format code (< 256) is that format on both sides,
 // so the same-format instances keep their names and their code; a mixed pair
@@ -1020,14 +1070,19 @@ __device__ __forceinline__ uint32_t rgb24_canon(uint32_t u, const Geo &g)
     return __builtin_amdgcn_perm(u, u, rgb24_sel(0u, g.li.yb));
 }
 __device__ __forceinline__ c2 rgb24_iq2(uint32_t u, const Geo &g) { return chroma_iq2<0>(rgb24_canon(u, g)); }
-// one output pixel of row `row` (the unfused, odd-size and debug kernels):
-// Pix<0>::pack's bytes in the frame's order, three byte stores
-__device__ __forceinline__ void rgb24_store(uint8_t *row, unsigned X, float r, float gg, float b, const Geo &g)
+// one output pixel of row `row`: its RGBA8 word's bytes in the frame's order,
+// three byte stores (rgb24_store_px: the unfused compose, the word from
+// yiq_rgba8; rgb24_store: the odd-size and debug kernels, from Pix<0>::pack)
+__device__ __forceinline__ void rgb24_store_px(uint8_t *row, unsigned X, uint32_t px, const Geo &g)
 {
-    const uint32_t q = __builtin_amdgcn_perm(0u, Pix<0>::pack(r, gg, b), rgb24_sel(0u, g.lo.yb));
+    const uint32_t q = __builtin_amdgcn_perm(0u, px, rgb24_sel(0u, g.lo.yb));
     st_off<uint8_t>(row, 3u * X, (uint8_t)q);
     st_off<uint8_t>(row, 3u * X + 1u, (uint8_t)(q >> 8));
     st_off<uint8_t>(row, 3u * X + 2u, (uint8_t)(q >> 16));
+}
+__device__ __forceinline__ void rgb24_store(uint8_t *row, unsigned X, float r, float gg, float b, const Geo &g)
+{
+    rgb24_store_px(row, X, Pix<0>::pack(r, gg, b), g);
 }
 // The fused kernels' (I, Q) of source columns X-1 .. X+4 (cl, cr: the outer
 // two, wrapped or clamped) of source row `row`: the quad's 12 bytes as one load
@@ -1050,12 +1105,9 @@ __device__ __forceinline__ void rgb24_quad_iq(const uint8_t *img, const Geo &g, 
 // four packed pixels as 12 bytes, one non-temporal store at a dword-aligned
 // address.  Byte j of output pixel k is byte c(j) of its RGBA8 word, c(j) = j
 // (R G B) or 2 - j (B G R).
-__device__ __forceinline__ void rgb24_store_quad(uint8_t *outp, const Geo &g, int i, int X, const float (&rr)[4],
-                                                 const float (&gg)[4], const float (&bb)[4])
+// (p: the four pixels' RGBA8 words, the compose's yiq_rgba8)
+__device__ __forceinline__ void rgb24_store_quad(uint8_t *outp, const Geo &g, int i, int X, const uint32_t (&p)[4])
 {
-    uint32_t p[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) p[k] = Pix<0>::pack(rr[k], gg[k], bb[k]);
     const bool sw = g.lo.yb != 0;
     u32x3_a4 w;
     w.x = __builtin_amdgcn_perm(p[1], p[0], sw ? 0x06000102u : 0x04020100u);   // c0 c1 c2 | c0
@@ -3053,6 +3105,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
         hc[sr] = wc.x * a + wc.y * m + wc.z * c;
     }
     uint8_t *outp = frames_out + (size_t)frame * g.lo.stride;
+    const VBlur bv = vblur_w<FO>(bw);   // (RGBA8 out: Y' in code units)
     [[maybe_unused]] c2 cd0;   // NV12: the even row's chroma differences
 #pragma unroll
     for (int r = 0; r < TR; ++r) {
@@ -3060,11 +3113,15 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
         if (i < g.H) {
             const float4 wr = rowW3[i];                        // source rows i-1, i, i+1
             const c2 cc = wr.x * hc[r] + wr.y * hc[r + 1] + wr.z * hc[r + 2];   // (ci, cq)
-            const float yb = bw.w0 * yv[r + 2] + bw.w1 * (yv[r + 1] + yv[r + 3]) +
-                             bw.w2 * (yv[r] + yv[r + 4]);
-            float rr, gg, bb;
-            yiq_rgb(yb, cc, rr, gg, bb);
-            if constexpr (k420<FO>) {
+            const float yb = bv.w0 * yv[r + 2] + bv.w1 * (yv[r + 1] + yv[r + 3]) +
+                             bv.w2 * (yv[r] + yv[r + 4]);
+            [[maybe_unused]] float rr, gg, bb;
+            if constexpr (!kCodeOut<FO>) yiq_rgb(yb, cc, rr, gg, bb);
+            if constexpr (kRGB24<FO>) {   // three bytes per lane, of the RGBA8 word
+                rgb24_store_px(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, yiq_rgba8(yb, cc), g);
+            } else if constexpr (kCodeOut<FO>) {   // one dword per lane, packed in code units
+                st_stream<uint32_t>(outp + (unsigned)i * g.lo.pitch, (unsigned)X * 4u, yiq_rgba8(yb, cc));
+            } else if constexpr (k420<FO>) {
                 // One luma byte per pixel.  The 2x2 chroma mean: this column's
                 // two rows (i0 and TR even: r even starts a block; H even: both
                 // rows are inside), plus the neighbour column's from the lane
@@ -3153,8 +3210,6 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
                 const float theirs = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
                     __builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
                 vcode[r] = yc | p010_ccode(mine + theirs, X & 1 ? g.nv.cro : g.nv.cbo) << 16;
-            } else if constexpr (kRGB24<FO>) {   // three bytes per lane
-                rgb24_store(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, rr, gg, bb, g);
             } else {
                 Pix<FO>::store(outp + (unsigned)i * g.lo.pitch, (unsigned)X, rr, gg, bb);
             }
@@ -3403,6 +3458,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
     float yw[8][4];            // list rows i0+4s-4 .. i0+4s+3 of the quad (blurred horizontally)
                                // (as column pairs for a packed vertical blur: +3 spills, not kept)
     [[maybe_unused]] c2 hc[6][4];   // combined (I, Q) of source rows i0+4s-5 .. i0+4s (gray: none)
+    [[maybe_unused]] const VBlur bv = vblur_w<FO>(bw);   // the compose's vertical blur (RGBA8 out: in code units)
     chroma_row(i0 - 1, hc[4]);
     chroma_row(i0, hc[5]);
 #ifdef MM_K34_STAMPS
@@ -3538,22 +3594,28 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                     }
                 } else if (vq && i < g.H) {
                     const float4 wr = rowW3[i];
-                    float rr[4], gg[4], bb[4];
+                    [[maybe_unused]] float rr[4], gg[4], bb[4];
+                    [[maybe_unused]] uint32_t pc[4];   // RGBA8 / packed RGB out: the quad's RGBA8 words, packed in code units
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const c2 cc = wr.x * hc[r][k] + wr.y * hc[r + 1][k] + wr.z * hc[r + 2][k];
-                        const float yb = bw.w0 * yw[r + 2][k] + bw.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
-                                         bw.w2 * (yw[r][k] + yw[r + 4][k]);
-                        yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
+                        const float yb = bv.w0 * yw[r + 2][k] + bv.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
+                                         bv.w2 * (yw[r][k] + yw[r + 4][k]);
+                        if constexpr (kCodeOut<FO>) pc[k] = yiq_rgba8(yb, cc);
+                        else yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
                     }
                     // (in pixels: an RGBA pitch is a multiple of the pixel size)
                     [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bppo) + (unsigned)X;
-                    if constexpr (k422<FO>) {
+                    if constexpr (kRGB24<FO>) {
+                        rgb24_store_quad(outp, g, i, X, pc);
+                    } else if constexpr (kCodeOut<FO>) {
+                        // (scalar row base + the thread's column offset, as below)
+                        st_stream_quad_a4(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X * 4u,
+                                          make_uint4(pc[0], pc[1], pc[2], pc[3]));
+                    } else if constexpr (k422<FO>) {
                         c422_store_quad(outp, g, i, X, rr, gg, bb);
                     } else if constexpr (kY210<FO>) {
                         y210_store_quad(outp, g, i, X, rr, gg, bb);
-                    } else if constexpr (kRGB24<FO>) {
-                        rgb24_store_quad(outp, g, i, X, rr, gg, bb);
                     } else if constexpr (k420<FO>) {
                         c420_store_quad<FO>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
                     } else if constexpr (bppo == 4) {
@@ -3749,6 +3811,7 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
         yw[k][2] = bw.w0 * Z.x + bw.w1 * (P.w + Z.y) + bw.w2 * (P.z + Z.z);
         yw[k][3] = bw.w0 * Z.y + bw.w1 * (Z.x + Z.z) + bw.w2 * (P.w + Z.w);
     }
+    [[maybe_unused]] const VBlur bv = vblur_w<FO>(bw);   // the vertical blur (RGBA8 out: in code units)
     [[maybe_unused]] c2 cd0[4];   // NV12: the even row's chroma differences
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
@@ -3766,21 +3829,25 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
             }
         } else if (vq && i < g.H) {
             const float4 wr = rowW3[i];
-            float rr[4], gg[4], bb[4];
+            [[maybe_unused]] float rr[4], gg[4], bb[4];
+            [[maybe_unused]] uint32_t pc[4];   // RGBA8 / packed RGB out: the quad's RGBA8 words, packed in code units
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const c2 cc = wr.x * hc[r][k] + wr.y * hc[r + 1][k] + wr.z * hc[r + 2][k];
-                const float yb = bw.w0 * yw[r + 2][k] + bw.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
-                                 bw.w2 * (yw[r][k] + yw[r + 4][k]);
-                yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
+                const float yb = bv.w0 * yw[r + 2][k] + bv.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
+                                 bv.w2 * (yw[r][k] + yw[r + 4][k]);
+                if constexpr (kCodeOut<FO>) pc[k] = yiq_rgba8(yb, cc);
+                else yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
             }
             [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bppo) + (unsigned)X;
-            if constexpr (k422<FO>) {
+            if constexpr (kRGB24<FO>) {
+                rgb24_store_quad(outp, g, i, X, pc);
+            } else if constexpr (kCodeOut<FO>) {
+                st_stream_quad_a4(outp, o * 4u, make_uint4(pc[0], pc[1], pc[2], pc[3]));
+            } else if constexpr (k422<FO>) {
                 c422_store_quad(outp, g, i, X, rr, gg, bb);
             } else if constexpr (kY210<FO>) {
                 y210_store_quad(outp, g, i, X, rr, gg, bb);
-            } else if constexpr (kRGB24<FO>) {
-                rgb24_store_quad(outp, g, i, X, rr, gg, bb);
             } else if constexpr (k420<FO>) {
                 c420_store_quad<FO>(outp, g, i, X, r & 1, rr, gg, bb, cd0);
             } else if constexpr (bppo == 4) {
