@@ -919,13 +919,58 @@ int mm_get_batch(const mm_handle *h, int *frames);
  * lane index out of range, lanes outside 0 .. MM_LANES_MAX, mm_process_lanes
  * with no lanes set, a `bytes` below mm_state_size(), two different formats that
  * are no supported pair.
- * Out of scope: calls that advance a subset of the lanes; lanes of different
- * sizes or parameters; host-memory frames; the ring entry points. */
+ * A subset of the lanes per call (a further backward-compatible addition to
+ * ABI 10; detect it by the presence of mm_process_lanes_mask).  Live sources
+ * are not genlocked, drop frames and run at different rates, so
+ * mm_process_lanes_mask advances only the lanes of `mask`: bit k selects lane
+ * k.  The addressing stays lane-indexed whatever the mask, one slot per
+ * camera: lane k's frame at in + k * in_layout->frame_stride, its output at
+ * out + k * out_layout->frame_stride.  Of a lane that is not selected the
+ * input slot is not read, the output slot is not written, and its state, its
+ * has-state flag and a pending mm_set_params edge_mode transition are
+ * untouched.  The bitwise contract above holds per lane over the frames of the
+ * calls that selected it, in order: a handle of its own fed exactly those
+ * frames.  Everything mm_process_lanes promises holds per selected lane
+ * (passthrough without state, apply_magnification = 0, every format, layout
+ * and convert pair, both edge modes, both modes).  A lane call's frames may be
+ * processed in place, in == out with one layout on both sides: the compose
+ * reads source rows beside the ones it writes, so such a call first copies the
+ * frames it composes aside and gives the same bytes as a call with separate
+ * buffers.  That is the one case where a handle with lanes holds more than two
+ * G slots and a Q slot per lane: one tight frame per lane more (8.3 MB per
+ * 1080p RGBA8 lane), allocated at the first such call, before anything is
+ * queued (MM_ERR_OOM then leaves the handle and every lane as they were), and
+ * one frame copy per composed lane and call; a frame copy, not a state copy.
+ * Buffers that overlap in any other way are not supported.  The mask of all
+ * lanes IS mm_process_lanes (which is that call): same bytes, same states; the
+ * two may alternate on one handle with each other, with the single-stream
+ * calls and with the lane-state calls.  mask = 0 returns MM_OK, queues
+ * nothing and changes nothing (in and out may then be anything).  The layouts
+ * are validated with count = (the highest selected lane) + 1: a buffer need
+ * not extend past the last lane the call selects.  mm_lanes_with_state: bit k
+ * of *mask is set where lane k has state.  Refusals as above, and
+ * MM_ERR_INVALID for a mask bit at or above the lane count.
+ * No state is copied, for lanes that advance or for lanes that sit out: each
+ * lane has a bank bit of its own, naming the G slot of its two that holds its
+ * state; a call writes the other slot and flips the bit of the lanes it
+ * selected.  The column kernel runs once per call over any mask.  The row
+ * kernels run once per RUN of consecutive selected lanes; a forward run also
+ * ends where the bank bits of neighbours differ (after a lane sat out an odd
+ * number of calls), a compose run where a lane without state meets one with.
+ * So a fragmented mask costs launches, never results: a caller with rate
+ * groups (30 and 60 fps sources) orders its lanes by group, so that each
+ * group is one run with one bank bit.
+ * Out of scope: one row-kernel launch over a mask with holes; lanes of
+ * different sizes or parameters; host-memory frames; the ring entry points. */
 #define MM_LANES_MAX 64
 int mm_set_lanes(mm_handle *h, int lanes);            /* 1..MM_LANES_MAX; 0 frees */
 int mm_get_lanes(const mm_handle *h, int *lanes);
 int mm_process_lanes(mm_handle *h, const void *in, const mm_surface *in_layout,
                      void *out, const mm_surface *out_layout, void *hip_stream);
+int mm_process_lanes_mask(mm_handle *h, uint64_t mask,
+                          const void *in, const mm_surface *in_layout,
+                          void *out, const mm_surface *out_layout, void *hip_stream);
+int mm_lanes_with_state(const mm_handle *h, uint64_t *mask);   /* bit k: lane k has state */
 int mm_reset_lane(mm_handle *h, int lane);            /* -1: every lane */
 int mm_get_lane_state(mm_handle *h, int lane, void *dev_buf, size_t bytes, void *hip_stream);
 int mm_set_lane_state(mm_handle *h, int lane, const void *dev_buf, size_t bytes, void *hip_stream);

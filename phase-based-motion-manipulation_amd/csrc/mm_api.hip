@@ -42,9 +42,9 @@ static int do_compute_state(mm_handle *h, const uint8_t *in, const Frames &fr, v
 {
     MM_DISPATCH(mm_size_compute_state_, h, in, fr, dst, s)
 }
-static int do_lanes(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s)
+static int do_lanes(mm_handle *h, uint64_t mask, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s)
 {
-    MM_DISPATCH(mm_size_lanes_, h, in, out, fr, s)
+    MM_DISPATCH(mm_size_lanes_, h, mask, in, out, fr, s)
 }
 
 // ------------------------------------------------------------------------
@@ -118,7 +118,7 @@ static void free_handle(mm_handle *h)
     if (h->stream) {
         void *bufs[] = {h->d_col, h->d_row, h->d_col3, h->d_row3, h->d_tw, h->d_ktab, h->d_kmsum, h->d_tw_half,
                         h->d_dbg, h->d_Fb, h->d_T, h->d_sst, h->d_G, h->d_Q, h->d_Yh, h->d_stage_in,
-                        h->d_stage_out, h->d_LG, h->d_LQ};
+                        h->d_stage_out, h->d_LG, h->d_LQ, h->d_Lsrc};
         for (void *b : bufs) h_retire(h, b);
         (void)hipStreamSynchronize(h->stream);
     }
@@ -742,11 +742,14 @@ int mm_set_lanes(mm_handle *h, int lanes)
     // the old buffers go back behind this handle's in-flight work (last_ev)
     h_retire(h, h->d_LG);
     h_retire(h, h->d_LQ);
+    h_retire(h, h->d_Lsrc);
+    h->d_Lsrc = nullptr;
+    h->lsrc_bytes = 0;
     h->d_LG = G;
     h->d_LQ = Q;
     h->lanes = lanes;
     h->lane_bank = 0;
-    h->lane_state.assign((size_t)lanes, 0);
+    h->lane_state = 0;
     return MM_OK;
 }
 
@@ -765,34 +768,54 @@ static int lanes_mode_check(const mm_handle *h)
     return MM_OK;
 }
 
-int mm_process_lanes(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
-                     const mm_surface *out_layout, void *hip_stream)
+static uint64_t lanes_all(const mm_handle *h) { return h->lanes >= 64 ? ~0ull : (1ull << h->lanes) - 1; }
+
+int mm_process_lanes_mask(mm_handle *h, uint64_t mask, const void *in, const mm_surface *in_layout, void *out,
+                          const mm_surface *out_layout, void *hip_stream)
 {
-    if (!h || !in || !out || !in_layout || !out_layout || h->lanes < 1) return MM_ERR_INVALID;
+    if (!h || !in_layout || !out_layout || h->lanes < 1 || (mask & ~lanes_all(h))) return MM_ERR_INVALID;
     if (int rc = lanes_mode_check(h)) return rc;
     // two formats that are no pair of mm_convert_supported: invalid here, as for mm_process_stream_surfaces
     if (in_layout->format != out_layout->format && convert_supported(in_layout->format, out_layout->format))
         return MM_ERR_INVALID;
     if (int rc = formats_check(h, in_layout, out_layout, true)) return rc;
+    if (!mask) return MM_OK;   // nobody advances: nothing queued, no buffer looked at
+    if (!in || !out) return MM_ERR_INVALID;
+    // a caller's buffers end with the last lane it selects
+    const int count = 64 - __builtin_clzll(mask);
     int rc;
-    if ((rc = surf_check_frames(h->W, h->H, in, in_layout, h->lanes)) ||
-        (rc = surf_check_frames(h->W, h->H, out, out_layout, h->lanes)))
+    if ((rc = surf_check_frames(h->W, h->H, in, in_layout, count)) ||
+        (rc = surf_check_frames(h->W, h->H, out, out_layout, count)))
         return rc;
     const Frames fr = frames_of(h->W, h->H, *in_layout, *out_layout);
     hipStream_t s = (hipStream_t)hip_stream;   // NULL: the default stream (HIP convention)
     DEVICE_SCOPE(h);
     int ro = order_after_last(h, s);
     if (ro) return ro;
-    rc = do_lanes(h, (const uint8_t *)in, (uint8_t *)out, fr, s);
+    rc = do_lanes(h, mask, (const uint8_t *)in, (uint8_t *)out, fr, s);
     const int rn = note_work(h, s);
     return rc ? rc : rn;
+}
+
+int mm_process_lanes(mm_handle *h, const void *in, const mm_surface *in_layout, void *out,
+                     const mm_surface *out_layout, void *hip_stream)
+{
+    if (!h || !in || !out || h->lanes < 1) return MM_ERR_INVALID;
+    return mm_process_lanes_mask(h, lanes_all(h), in, in_layout, out, out_layout, hip_stream);
+}
+
+int mm_lanes_with_state(const mm_handle *h, uint64_t *mask)
+{
+    if (!h || !mask) return MM_ERR_INVALID;
+    *mask = h->lane_state;
+    return MM_OK;
 }
 
 int mm_reset_lane(mm_handle *h, int lane)
 {
     if (!h || lane < -1 || lane >= h->lanes) return MM_ERR_INVALID;
-    if (lane < 0) std::fill(h->lane_state.begin(), h->lane_state.end(), (char)0);
-    else h->lane_state[lane] = 0;
+    if (lane < 0) h->lane_state = 0;
+    else h->lane_state &= ~(1ull << lane);
     return MM_OK;
 }
 
@@ -802,12 +825,12 @@ int mm_get_lane_state(mm_handle *h, int lane, void *dev_buf, size_t bytes, void 
     if (int rc = lanes_mode_check(h)) return rc;
     const size_t need = sizeof(c2) * h->g_stride;   // mm_state_size of these modes
     if (bytes < need) return MM_ERR_INVALID;
-    if (!h->lane_state[lane]) return MM_ERR_NO_STATE;
+    if (!((h->lane_state >> lane) & 1)) return MM_ERR_NO_STATE;
     hipStream_t s = (hipStream_t)hip_stream;   // NULL: the default stream (HIP convention)
     DEVICE_SCOPE(h);
     int ro = order_after_last(h, s);
     if (ro) return ro;
-    const c2 *slot = h->d_LG + h->g_stride * ((size_t)h->lanes * h->lane_bank + lane);
+    const c2 *slot = h->d_LG + h->g_stride * ((size_t)h->lanes * ((h->lane_bank >> lane) & 1) + lane);
     HIPCHK(hipMemcpyAsync(dev_buf, slot, need, hipMemcpyDeviceToDevice, s));
     return note_work(h, s);
 }
@@ -822,9 +845,9 @@ int mm_set_lane_state(mm_handle *h, int lane, const void *dev_buf, size_t bytes,
     DEVICE_SCOPE(h);
     int ro = order_after_last(h, s);
     if (ro) return ro;
-    c2 *slot = h->d_LG + h->g_stride * ((size_t)h->lanes * h->lane_bank + lane);
+    c2 *slot = h->d_LG + h->g_stride * ((size_t)h->lanes * ((h->lane_bank >> lane) & 1) + lane);
     HIPCHK(hipMemcpyAsync(slot, dev_buf, need, hipMemcpyDeviceToDevice, s));
-    h->lane_state[lane] = 1;
+    h->lane_state |= 1ull << lane;
     return note_work(h, s);
 }
 

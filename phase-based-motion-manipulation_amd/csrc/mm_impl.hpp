@@ -95,16 +95,21 @@ struct mm_handle {
     int k34_oneshot;            // short launches: k_rows_inv_compose4 when its strips fit one
                                 // workgroup round (MM_K34_ONESHOT: 0 never: K3 -> K4, 2 always)
     int num_cu;                 // compute units of the device
-    // Lanes (mm_set_lanes): the temporal states of `lanes` live streams that
-    // advance one frame each per mm_process_lanes call, apart from the
-    // handle's own state above.  d_LG: two banks of `lanes` G slots.  Bank
-    // lane_bank holds the lanes' G_{t-1}; a call's K1 writes the other bank,
-    // its K2 reads both, then the banks swap: no state copy.  d_LQ: a Q slot
-    // per lane.  lane_state[k]: lane k's slot of bank lane_bank holds its state.
+    // Lanes (mm_set_lanes): the temporal states of `lanes` live streams, apart
+    // from the handle's own state above; a call (mm_process_lanes_mask)
+    // advances the lanes of its mask by one frame each.  d_LG: two banks of
+    // `lanes` G slots.  Bit k of lane_bank: the bank whose slot k holds lane
+    // k's G_{t-1}.  A call's K1 writes a selected lane's other slot, its K2
+    // reads both, then that lane's bit flips: no state copy, and a lane that
+    // sits a call out keeps its slot.  d_LQ: a Q slot per lane.  Bit k of
+    // lane_state: lane k has state.  d_Lsrc (lazily, lsrc_bytes): the source
+    // frames of a lane call whose in and out overlap, tight, for its compose.
     int lanes;
     c2 *d_LG, *d_LQ;
-    int lane_bank;
-    std::vector<char> lane_state;
+    uint64_t lane_bank;
+    uint64_t lane_state;
+    uint8_t *d_Lsrc;
+    size_t lsrc_bytes;
     // mm_profile_begin/end: HIP events around each launch on its stream
     struct ProfRec { hipEvent_t a, b; int kernel, frames; };
     bool prof;
@@ -910,22 +915,36 @@ static int launch_k2(mm_handle *h, int nframes, const c2 *Gprev, const c2 *G, hi
     return MM_OK;
 }
 
-// K2 of one frame per lane (k_cols_lanes): lane k's G_t in slot k of G, its
-// G_{t-1} in slot k of Gprev (the two lane banks), its Q to d_LQ + k * q_stride.
+// K2 of one frame of each lane of `sel`: lane k's G_{t-1} in slot k of the
+// bank that bit k of `banks` names, its G_t in the other bank's slot k, its Q
+// to d_LQ + k * q_stride.  One launch, whatever the mask and the bank bits:
+// k_cols_lanes where every lane is selected and all have one bank bit (every
+// call of a handle that only gets full calls), k_cols_lanes_sel otherwise.
 // The modes and their order are launch_k2's.
 template <int LOG2N>
-static int launch_k2_lanes(mm_handle *h, const c2 *Gprev, const c2 *G, hipStream_t s)
+static int launch_k2_lanes(mm_handle *h, uint64_t sel, uint64_t banks, hipStream_t s)
 {
     const int gpw = k2_groups<LOG2N>();
     const int blocks = ((1 << LOG2N) / 2 + gpw - 1) / gpw;
+    const int nsel = __builtin_popcountll(sel);
+    const uint64_t all = h->lanes >= 64 ? ~0ull : (1ull << h->lanes) - 1;
+    const bool plain = sel == all && ((banks & all) == 0 || (banks & all) == all);
+    const size_t bank = h->g_stride * (size_t)h->lanes;
+    const c2 *Gprev = h->d_LG + bank * (banks & 1), *G = h->d_LG + bank * (1 - (banks & 1));   // (plain)
     if (int rc = refresh_k2_tables<LOG2N>(h, s)) return rc;
-    ProfScope ps(h, s, MM_K_COLS, h->lanes);
+    ProfScope ps(h, s, MM_K_COLS, nsel);
 #define MM_K2_LAUNCH(MODE)                                                                           \
     do {                                                                                             \
         const size_t lds = k2_lds_bytes<LOG2N, MODE>();                                              \
-        hipLaunchKernelGGL((k_cols_lanes<LOG2N, MODE>), dim3(blocks, h->lanes), dim3(k2_threads<LOG2N>()), lds, s, \
-                           G, h->g_stride, Gprev, h->d_LQ, h->q_stride, h->geo, h->spec, h->d_tw, h->d_ktab, \
-                           h->d_kmsum);                                                              \
+        if (plain)                                                                                   \
+            hipLaunchKernelGGL((k_cols_lanes<LOG2N, MODE>), dim3(blocks, h->lanes), dim3(k2_threads<LOG2N>()), lds, s, \
+                               G, h->g_stride, Gprev, h->d_LQ, h->q_stride, h->geo, h->spec, h->d_tw, h->d_ktab, \
+                               h->d_kmsum);                                                          \
+        else                                                                                         \
+            hipLaunchKernelGGL((k_cols_lanes_sel<LOG2N, MODE>), dim3(blocks, nsel), dim3(k2_threads<LOG2N>()), lds, s, \
+                               h->d_LG, h->g_stride, h->d_LQ, h->q_stride, (unsigned long long)sel,  \
+                               (unsigned long long)banks, h->lanes, h->geo, h->spec, h->d_tw, h->d_ktab, \
+                               h->d_kmsum);                                                          \
     } while (0)
     if (h->spec.mode == MM_MODE_STANDARD) MM_K2_LAUNCH(MM_MODE_STANDARD);
     else if (h->k2_tab2) MM_K2_LAUNCH(MM_K2_PYR_TAB2);
@@ -1531,39 +1550,105 @@ static int compute_state(mm_handle *h, const uint8_t *in, const Frames &fr, void
     return launch_k1<LOG2N>(h, in, 1, fr, s, reinterpret_cast<c2 *>(dst));
 }
 
-// One frame of every lane (mm_process_lanes): frame k of the call is lane k's
-// next frame.  K1 of the frames into the free bank, one K2 over both banks
-// (k_cols_lanes), then K3 + K4 from the lanes' Q.  A lane without state passes
-// through (its K2 result is computed and not used, as a stream's first frame's
-// is): the compose runs over the runs of lanes that have state, one launch
-// when all have, so a passthrough frame is never composed over first (frames
-// may be processed in place).  The banks swap: no state copy.
+// One frame of each lane of `mask` (mm_process_lanes_mask; mm_process_lanes
+// is the mask of all lanes): frame k of the buffers is lane k's next frame.  K1
+// of a selected lane writes the slot of the bank that does not hold its state
+// (a lane without state: its neighbour's bank, so that it joins a run), one
+// launch per run of consecutive selected lanes that write one bank; one K2 over
+// the selected lanes (launch_k2_lanes: k_cols_lanes_sel finds each lane's two
+// slots by its bank bit); then K3 + K4 from the lanes' Q.  A lane without
+// state passes through (its K2 result is computed and not used, as a stream's
+// first frame's is): the compose runs over the runs of selected lanes that
+// have state, one launch when all have, so a passthrough frame is never
+// composed over first (in == out).  The selected lanes' bank bits flip: no
+// state copy, and a lane that sits the call out keeps its slot, its bit and
+// its flag.
 template <int LOG2N>
-static int run_lanes(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s)
+static int run_lanes(mm_handle *h, uint64_t mask, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s)
 {
     if constexpr (LOG2N > 12) return MM_ERR_UNSUPPORTED;   // (mm_set_lanes refuses N = 8192)
     else {
         const int n = h->lanes;
+        const auto bit = [](uint64_t m, int k) { return (int)((m >> k) & 1); };
+        // wr: the bank each selected lane's K1 writes
+        uint64_t wr = ~h->lane_bank & h->lane_state & mask;
+        for (int k = 0; k < n; ++k) {
+            if (!bit(mask, k) || bit(h->lane_state, k)) continue;
+            int w;
+            if (k > 0 && bit(mask, k - 1)) w = bit(wr, k - 1);
+            else {
+                int j = k + 1;
+                while (j < n && bit(mask, j) && !bit(h->lane_state, j)) ++j;
+                w = j < n && bit(mask, j) ? bit(wr, j) : 1 - bit(h->lane_bank, k);
+            }
+            wr |= (uint64_t)w << k;
+        }
         const size_t bank = h->g_stride * (size_t)n;
-        const c2 *Gprev = h->d_LG + bank * h->lane_bank;
-        c2 *G = h->d_LG + bank * (1 - h->lane_bank);
+        const bool mag = h->p.apply_magnification != 0;
         int rc;
-        if ((rc = launch_k1<LOG2N>(h, in, n, fr, s, G))) return rc;
-        if (!h->p.apply_magnification) {
-            // Blit(source, destination) (.cs:139); every lane's state follows its input
-            if ((rc = copy_frames(h, in, out, n, fr, s))) return rc;
-        } else {
-            if ((rc = launch_k2_lanes<LOG2N>(h, Gprev, G, s))) return rc;
-            for (int a = 0, b; a < n; a = b) {
-                const bool st = h->lane_state[a] != 0;
-                for (b = a + 1; b < n && (h->lane_state[b] != 0) == st; ++b) {}
-                if (st) rc = launch_k3<LOG2N>(h, h->d_LQ, in, out, a, b, fr, s);
-                else rc = copy_frames(h, in + fr.in.stride * a, out + fr.out.stride * a, b - a, fr, s);
-                if (rc) return rc;
+        // In place (in == out; decided for any overlap of the two buffers'
+        // selected frames): the compose reads source rows next to the ones it
+        // writes, of other workgroups' strips too, so the frames it composes
+        // are copied aside first, tight, and composed from there.  Their
+        // buffer is made before anything is queued: a failed allocation
+        // leaves the handle and every lane as they were.
+        bool aside = false;
+        mm_surface t;
+        (void)surf_tight(h->W, h->H, fr.fmt, &t);
+        if (mag && (mask & h->lane_state)) {
+            const int lo = __builtin_ctzll(mask), hi = 64 - __builtin_clzll(mask);
+            const uint8_t *i0 = in + fr.in.stride * lo, *i1 = in + fr.in.stride * hi;
+            const uint8_t *o0 = out + fr.out.stride * lo, *o1 = out + fr.out.stride * hi;
+            aside = i0 < o1 && o0 < i1;
+            const size_t need = t.frame_stride * (size_t)n;
+            if (aside && h->lsrc_bytes < need) {
+                uint8_t *p = nullptr;
+                if (h_alloc(h, &p, need) != hipSuccess) return MM_ERR_OOM;
+                h_retire(h, h->d_Lsrc, s, true);
+                h->d_Lsrc = p;
+                h->lsrc_bytes = need;
             }
         }
-        h->lane_bank ^= 1;
-        std::fill(h->lane_state.begin(), h->lane_state.end(), (char)1);
+        for (int a = 0, b; a < n; a = b) {
+            b = a + 1;
+            if (!bit(mask, a)) continue;
+            while (b < n && bit(mask, b) && bit(wr, b) == bit(wr, a)) ++b;
+            c2 *G = h->d_LG + bank * bit(wr, a) + h->g_stride * a;
+            if ((rc = launch_k1<LOG2N>(h, in + fr.in.stride * a, b - a, fr, s, G))) return rc;
+        }
+        // (off: Blit(source, destination) (.cs:139); every selected lane's state follows its input)
+        if (mag && (rc = launch_k2_lanes<LOG2N>(h, mask, ~wr & mask, s))) return rc;
+        // (K1 has read the frames by now; a passthrough onto itself is nothing)
+        const uint8_t *src = in;
+        Frames fc = fr;
+        if (aside) {
+            Frames up = fr;   // the caller's frames -> the tight copies
+            up.ofmt = fr.fmt;
+            up.fo = fr.fi;
+            up.out = surf_lay(t);
+            up.packed = !fr.mixed() ? fr.packed : false;
+            fc.in = up.out;
+            fc.packed = false;
+            for (int a = 0, b; a < n; a = b) {
+                b = a + 1;
+                if (!bit(mask & h->lane_state, a)) continue;
+                while (b < n && bit(mask & h->lane_state, b)) ++b;
+                if ((rc = copy_frames(h, in + fr.in.stride * a, h->d_Lsrc + t.frame_stride * a, b - a, up, s)))
+                    return rc;
+            }
+            src = h->d_Lsrc;
+        }
+        for (int a = 0, b; a < n; a = b) {
+            b = a + 1;
+            if (!bit(mask, a)) continue;
+            const bool st = mag && bit(h->lane_state, a);
+            while (b < n && bit(mask, b) && (mag && bit(h->lane_state, b)) == st) ++b;
+            if (st) rc = launch_k3<LOG2N>(h, h->d_LQ, src, out, a, b, fc, s);
+            else rc = copy_frames(h, in + fr.in.stride * a, out + fr.out.stride * a, b - a, fr, s);
+            if (rc) return rc;
+        }
+        h->lane_bank = (h->lane_bank & ~mask) | wr;
+        h->lane_state |= mask;
         return MM_OK;
     }
 }
@@ -1579,7 +1664,7 @@ static int run_lanes(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames
                            const Frames &fr, hipStream_t s);                                        \
     int mm_size_compute_state_##L(mm_handle *h, const uint8_t *in, const Frames &fr, void *dst,     \
                                   hipStream_t s);                                                   \
-    int mm_size_lanes_##L(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s);
+    int mm_size_lanes_##L(mm_handle *h, uint64_t mask, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s);
 #define MM_SIZE_ENTRIES(L) MM_SIZE_ENTRIES_(L)
 #define MM_SIZE_ENTRIES_(L)                                                                         \
     int mm_size_set_attrs_##L(mm_handle *h) { return set_attrs<L>(h->W); }                          \
@@ -1593,9 +1678,9 @@ static int run_lanes(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames
     {                                                                                               \
         return compute_state<L>(h, in, fr, dst, s);                                                 \
     }                                                                                               \
-    int mm_size_lanes_##L(mm_handle *h, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s) \
+    int mm_size_lanes_##L(mm_handle *h, uint64_t mask, const uint8_t *in, uint8_t *out, const Frames &fr, hipStream_t s) \
     {                                                                                               \
-        return run_lanes<L>(h, in, out, fr, s);                                                     \
+        return run_lanes<L>(h, mask, in, out, fr, s);                                                     \
     }
 MM_SIZE_DECLS(4)
 MM_SIZE_DECLS(5)

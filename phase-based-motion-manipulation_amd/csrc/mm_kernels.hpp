@@ -2869,6 +2869,51 @@ void k_cols_lanes(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q
     else k_cols_body<LOG2N, MODE, false>(G + go, g_stride, Gprev + go, Ql, q_stride, 1, g, sp, tw, ktab, kmsum, blk, nb);
 }
 
+// Index of the r-th set bit of m (r < popcount(m)): a binary search over the
+// halves' bit counts.  m and r are workgroup-uniform where k_cols_lanes_sel
+// calls it (a kernel argument and blockIdx.y), so the six steps are scalar work.
+__device__ __forceinline__ int nth_set_bit(unsigned long long m, int r)
+{
+    int at = 0;
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) {
+        const int c = __popcll(m & ((1ull << w) - 1));
+        if (r >= c) {
+            r -= c;
+            m >>= w;
+            at += w;
+        }
+    }
+    return at;
+}
+
+// k_cols_lanes over a subset of the lanes, each with a bank of its own
+// (mm_process_lanes_mask with a mask that leaves lanes out, or lanes whose
+// bank bits differ): workgroup (x, y) takes the lane of the y-th set bit of
+// `sel`.  LG holds two banks of `lanes` G slots; bit k of `banks` is the bank
+// of lane k's G_{t-1}, its G_t is in the other bank's slot k, its Q at
+// Q + k * q_stride.  From there it is k_cols_lanes: the same body instances,
+// nframes = 1.  The selection costs a scalar prologue before the first load
+// (0.05-0.1 us per lane-frame at 1080p), which is why calls of all lanes with
+// one bank bit keep k_cols_lanes.
+template <int LOG2N, int MODE>
+__global__ __launch_bounds__(k2_threads<LOG2N>()) __attribute__((amdgpu_waves_per_eu(MM_K2_WAVES)))
+void k_cols_lanes_sel(const c2 *LG, size_t g_stride, c2 *Q, size_t q_stride,   // not restrict, as k_cols
+                      unsigned long long sel, unsigned long long banks, int lanes,
+                      Geo g, Spec sp, const c2 *__restrict__ tw, const float2 *__restrict__ ktab,
+                      const float *__restrict__ kmsum)
+{
+    const int nb = gridDim.x;
+    const int blk = xcd_remap((int)blockIdx.x, nb);
+    const int lane = nth_set_bit(sel, (int)blockIdx.y);
+    const int pb = (int)((banks >> lane) & 1);
+    const c2 *G = LG + (size_t)(lanes * (1 - pb) + lane) * g_stride;
+    const c2 *Gprev = LG + (size_t)(lanes * pb + lane) * g_stride;
+    c2 *Ql = Q + (size_t)lane * q_stride;
+    if (blk == 0) k_cols_body<LOG2N, MODE, true>(G, g_stride, Gprev, Ql, q_stride, 1, g, sp, tw, ktab, kmsum, blk, nb);
+    else k_cols_body<LOG2N, MODE, false>(G, g_stride, Gprev, Ql, q_stride, 1, g, sp, tw, ktab, kmsum, blk, nb);
+}
+
 // K2's per-bin tables of every column in LDS slot order ([N/2+1][k2_tab_slots]):
 // the frame-invariant bin_static values (pyramid masks pre-scaled by inv_nn, a
 // power of two: exact), evaluated once per parameter set on the launch stream

@@ -142,6 +142,14 @@
  * the frames the input holds, -n at most) must be a multiple of M: else status
  * 2, before the output file is created.  Refused with --orientations / --iir,
  * the debug views and the ring modes.
+ * --lane-drop L:T[,L:T...] (with --lanes and an input file): lane L's frame of
+ * tick T, input frame T * M + L, is a frame that never arrived.  It is not
+ * uploaded, and that tick's call (mm_process_lanes_mask) leaves bit L clear:
+ * the lane sits the tick out and continues from the frame before.  The output
+ * keeps whole ticks; a dropped slot holds the passthrough of its input frame (a
+ * host copy).  Status 2, before the output file is created, without --lanes,
+ * for a lane >= M, for a malformed list, and without -i or with --checksum,
+ * --out-rgba8 or --out-nv12 (the host copy is no conversion).
  */
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -246,6 +254,58 @@ static int surf_copy(void *dst, const mm_surface *dl, const void *src, const mm_
                                  q ? t.chroma_pitch : rb, q ? hc : (size_t)H, kind, s) != hipSuccess)
                 return 1;
         }
+    }
+    return 0;
+}
+
+/* --lane-drop: the (lane, tick) slots of frames that never arrived */
+typedef struct { int lane, tick; } lane_drop;
+
+/* "L:T[,L:T...]", L in 0 .. M-1, T >= 0; NULL (and *n = -1) for anything else */
+static lane_drop *parse_lane_drops(const char *arg, int M, int *n)
+{
+    size_t cap = 1;
+    for (const char *c = arg; *c; ++c) cap += *c == ',';
+    lane_drop *d = (lane_drop *)malloc(sizeof *d * cap);
+    *n = 0;
+    for (const char *c = arg; d;) {
+        char *e;
+        if (*c < '0' || *c > '9') break;
+        const long l = strtol(c, &e, 10);
+        if (*e != ':' || e[1] < '0' || e[1] > '9' || l >= M) break;
+        const long t = strtol(e + 1, &e, 10);
+        if (t > 0x3fffffff) break;
+        d[*n].lane = (int)l;
+        d[(*n)++].tick = (int)t;
+        if (!*e) return d;
+        if (*e != ',') break;
+        c = e + 1;
+    }
+    free(d);
+    *n = -1;
+    return NULL;
+}
+
+/* the lanes of tick `tick` that take a frame */
+static uint64_t tick_mask(const lane_drop *d, int nd, int M, int tick)
+{
+    uint64_t m = M >= 64 ? ~0ull : (1ull << M) - 1;
+    for (int k = 0; k < nd; ++k)
+        if (d[k].tick == tick) m &= ~(1ull << d[k].lane);
+    return m;
+}
+
+/* surf_copy of the frames of `mask` among n (all of them: one copy, as ever) */
+static int surf_copy_mask(void *dst, const mm_surface *dl, const void *src, const mm_surface *sl, int W, int H, int n,
+                          uint64_t mask, hipMemcpyKind kind, hipStream_t s)
+{
+    for (int a = 0, b; a < n; a = b) {
+        b = a + 1;
+        if (!((mask >> (a & 63)) & 1)) continue;
+        while (b < n && ((mask >> (b & 63)) & 1)) ++b;
+        if (surf_copy((unsigned char *)dst + dl->frame_stride * (size_t)a, dl,
+                      (const unsigned char *)src + sl->frame_stride * (size_t)a, sl, W, H, b - a, kind, s))
+            return 1;
     }
     return 0;
 }
@@ -602,7 +662,7 @@ int main(int argc, char **argv)
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
     int srgb = 0, bgr = 0, out_rgba8 = 0, out_nv12 = 0;
-    const char *lanes_arg = NULL;
+    const char *lanes_arg = NULL, *drop_arg = NULL;
     const in_opt *in = NULL;  /* the input-format option: one at most */
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
@@ -649,6 +709,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--surface-align")) surf_arg = v;
         else if (!strcmp(a, "--matrix")) matrix_arg = v;
         else if (!strcmp(a, "--lanes")) lanes_arg = v;
+        else if (!strcmp(a, "--lane-drop")) drop_arg = v;
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         ++i;
     }
@@ -683,6 +744,16 @@ int main(int argc, char **argv)
     if (M && (orientations > 1 || iir || views || ring))
         REFUSE("--lanes does not go with --orientations / --iir, the debug views or the ring modes\n");
     if (M) B = M;
+    /* frames that never arrived (mm_process_lanes_mask) */
+    lane_drop *drops = NULL;
+    int ndrops = 0;
+    if (drop_arg) {
+        if (!M) REFUSE("--lane-drop needs --lanes\n");
+        if (!in_path || checksum || out_rgba8 || out_nv12)
+            REFUSE("--lane-drop needs an input file (-i) and does not go with --checksum, --out-rgba8 or --out-nv12\n");
+        drops = parse_lane_drops(drop_arg, M, &ndrops);
+        if (!drops) REFUSE("--lane-drop takes L:T[,L:T...] with lanes 0 .. %d, not %s\n", M - 1, drop_arg);
+    }
     if (ring_local > 0 && (in_path || out_path)) REFUSE("--ring-local needs a synthetic stream\n");
     if (ring_world > 0 && ring_local <= 0 && (!ring_id_path || in_path || out_path))
         REFUSE("--ring-world needs --ring-id and a synthetic stream\n");
@@ -836,6 +907,9 @@ int main(int argc, char **argv)
     }
     hipStream_t s = (hipStream_t)mm_stream(h);
     unsigned char *host = (fi || fo) ? (unsigned char *)calloc((size_t)B, fb > fbo ? fb : fbo) : NULL;
+    /* --lane-drop: a tick's input frames, kept for its dropped slots of the output */
+    unsigned char *kept = ndrops && fo ? (unsigned char *)malloc((size_t)B * fb) : NULL;
+    if (ndrops && fo && !kept) { fprintf(stderr, "out of memory\n"); return 1; }
     unsigned char *planes = (y4m_in || y4m_out)
         ? (unsigned char *)malloc(y4m_in ? (y4m_frame_bytes_depth(&yi, depth) > 3 * (size_t)W * H
                                                ? y4m_frame_bytes_depth(&yi, depth) : 3 * (size_t)W * H)
@@ -855,6 +929,7 @@ int main(int argc, char **argv)
     hipEventCreate(&e1);
     while (done < F) {
         int n = F - done < B ? F - done : B;
+        const uint64_t mask = M ? tick_mask(drops, ndrops, M, done / M) : 0;
         if (fi && y4m_in) {
             int got = 0;
             for (; got < n; ++got) {
@@ -869,7 +944,7 @@ int main(int argc, char **argv)
             }
             if (got == 0) break;
             n = got;
-            if (surf_copy(d_in, &lay, host, &tight, W, H, n, hipMemcpyHostToDevice, s)) return 1;
+            if (surf_copy_mask(d_in, &lay, host, &tight, W, H, n, M ? mask : ~0ull, hipMemcpyHostToDevice, s)) return 1;
         } else if (fi && p_ppm) {
             /* images of the first one's size, as they lie (--bgr: R and B swapped) */
             int got = 0;
@@ -890,18 +965,20 @@ int main(int argc, char **argv)
             }
             if (got == 0) break;
             n = got;
-            if (surf_copy(d_in, &lay, host, &tight, W, H, n, hipMemcpyHostToDevice, s)) return 1;
+            if (surf_copy_mask(d_in, &lay, host, &tight, W, H, n, M ? mask : ~0ull, hipMemcpyHostToDevice, s)) return 1;
         } else if (fi) {
             size_t got = fread(host, fb, (size_t)n, fi);
             if (got == 0) break;
             n = (int)got;
-            if (surf_copy(d_in, &lay, host, &tight, W, H, n, hipMemcpyHostToDevice, s)) return 1;
+            if (surf_copy_mask(d_in, &lay, host, &tight, W, H, n, M ? mask : ~0ull, hipMemcpyHostToDevice, s)) return 1;
         } else {
             CHECK(mm_synth_frames(surf_arg ? d_tin : d_in, W, H, done, n, 0x5EED0000ull, 0, s));
             if (surf_arg && surf_copy(d_in, &lay, d_tin, &tight, W, H, n, hipMemcpyDeviceToDevice, s)) return 1;
         }
+        if (kept) memcpy(kept, host, (size_t)n * fb);   /* (`host` takes the output frames below) */
         hipEventRecord(e0, s);
-        if (M) CHECK(mm_process_lanes(h, d_in, &lay, d_out, &olay, s));   /* (n == M: whole ticks) */
+        if (ndrops) CHECK(mm_process_lanes_mask(h, mask, d_in, &lay, d_out, &olay, s));
+        else if (M) CHECK(mm_process_lanes(h, d_in, &lay, d_out, &olay, s));   /* (n == M: whole ticks) */
         else if (convert) CHECK(mm_process_stream_convert(h, d_in, &lay, d_out, &olay, n, s));
         else if (surf_arg) CHECK(mm_process_stream_surfaces(h, d_in, &lay, d_out, &lay, n, s));
         else CHECK(mm_process_stream(h, d_in, d_out, n, g_fmt, s));
@@ -920,6 +997,8 @@ int main(int argc, char **argv)
         if (checksum) print_checksums((const unsigned char *)d_res, fbo, n, done);
         if (fo) {
             hipMemcpy(host, d_res, fbo * n, hipMemcpyDeviceToHost);
+            for (int k = 0; kept && k < n; ++k)   /* a dropped slot: its input, passed through (fbo == fb) */
+                if (!((mask >> k) & 1)) memcpy(host + fb * k, kept + fb * k, fb);
             if (y4m_out) {
                 for (int k = 0; k < n; ++k) {
                     /* (no unpack function: the frame is the file's planes) */
@@ -954,6 +1033,8 @@ int main(int argc, char **argv)
     if (fi) fclose(fi);
     if (fo) fclose(fo);
     free(host);
+    free(kept);
+    free(drops);
     free(planes);
     hipFree(d_in);
     hipFree(d_out);

@@ -263,6 +263,23 @@ def _lanes_fn(name):
     return getattr(lib(), name)
 
 
+# a subset of the lanes per call (a later addition: a tuple of its own, so that
+# a library from before it still loads and has_lanes() still answers for it)
+LANES_MASK_SYMBOLS = ("mm_process_lanes_mask", "mm_lanes_with_state")
+
+
+def has_lanes_mask():
+    """The loaded library advances a subset of the lanes per call (detected, as
+    include/mm.h says, by the presence of mm_process_lanes_mask)."""
+    return hasattr(lib(), "mm_process_lanes_mask")
+
+
+def _lanes_mask_fn(name):
+    if not has_lanes_mask():
+        raise MMError(-2, f"{library_path()} has no {name} (a build from before the lane masks)")
+    return getattr(lib(), name)
+
+
 _lib = None
 _lib_path = None
 ABI_VERSION = 10  # include/mm.h MM_ABI_VERSION
@@ -297,6 +314,8 @@ def load_library(path=None):
         "mm_reset_lane": (ci, [vp, ci]),
         "mm_get_lane_state": (ci, [vp, ci, vp, sz, vp]),
         "mm_set_lane_state": (ci, [vp, ci, vp, sz, vp]),
+        "mm_process_lanes_mask": (ci, [vp, ctypes.c_uint64, vp, ps, vp, ps, vp]),
+        "mm_lanes_with_state": (ci, [vp, ctypes.POINTER(ctypes.c_uint64)]),
         "mm_abi_version": (ci, []),
         "mm_strerror": (ctypes.c_char_p, [ci]),
         "mm_params_default": (ci, [pp]),
@@ -344,6 +363,8 @@ def load_library(path=None):
             continue    # ... or from before the format conversion
         if name in LANES_SYMBOLS and not hasattr(L, name):
             continue    # ... or from before the lanes
+        if name in LANES_MASK_SYMBOLS and not hasattr(L, name):
+            continue    # ... or from before the lane masks
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -542,6 +563,19 @@ class Handle:
         k * frame_stride of its side."""
         check(_lanes_fn("mm_process_lanes")(self.h, _ptr(src), ctypes.byref(src_layout), _ptr(dst),
                                             ctypes.byref(dst_layout), _ptr(stream)), "mm_process_lanes")
+
+    def process_lanes_mask(self, mask, src, src_layout, dst, dst_layout, stream=None):
+        """mm_process_lanes_mask: one frame of each lane whose bit of `mask` is
+        set; lane k's frame at k * frame_stride of its side, whatever the mask."""
+        check(_lanes_mask_fn("mm_process_lanes_mask")(self.h, int(mask), _ptr(src), ctypes.byref(src_layout),
+                                                      _ptr(dst), ctypes.byref(dst_layout), _ptr(stream)),
+              "mm_process_lanes_mask")
+
+    def lanes_with_state(self):
+        """mm_lanes_with_state: bit k set where lane k has state."""
+        m = ctypes.c_uint64()
+        check(_lanes_mask_fn("mm_lanes_with_state")(self.h, ctypes.byref(m)), "mm_lanes_with_state")
+        return m.value
 
     def reset_lane(self, lane=-1):
         """mm_reset_lane: lane's next frame passes through (-1: every lane's)."""
