@@ -21,7 +21,8 @@
  *     video frames, planar Y'CbCr 4:2:0, and MM_P010 / MM_P010_FULL their
  *     10-bit form, BT.601 or with a matrix bit BT.709 / BT.2020 (see the
  *     format list); MM_YUY2 / MM_UYVY are packed 4:2:2 capture frames and
- *     MM_Y210 / MM_Y210_FULL their 10-bit form.  The handle
+ *     MM_Y210 / MM_Y210_FULL their 10-bit form; MM_BGRA8 / MM_BGRA8_SRGB are
+ *     MM_RGBA8 / MM_RGBA8_SRGB in the byte order B G R A.  The handle
  *     owns all device scratch and the one-frame temporal state.
  *   - A handle is not thread-safe: one handle per video stream, calls in frame
  *     order (Unity calls OnRenderImage serially on its render thread).
@@ -65,8 +66,9 @@ extern "C" {
 /* frame formats (every entry point that takes frames takes each of them;
  * the NV12 and P010 pairs for even W and H and without the debug views; the
  * single-plane grayscale formats MM_Y8 .. MM_Y16, packed 4:2:2 MM_YUY2 /
- * MM_UYVY, 10-bit packed 4:2:2 MM_Y210 and packed RGB MM_RGB24 / MM_BGR24
- * further down) */
+ * MM_UYVY, 10-bit packed 4:2:2 MM_Y210, packed RGB MM_RGB24 / MM_BGR24, the
+ * three-plane MM_I420 / MM_I010, MM_V210 and the B G R A orders MM_BGRA8 /
+ * MM_BGRA8_SRGB further down) */
 #define MM_RGBA8   0       /* 4 B/px, UNORM: v = byte / 255; out round(saturate(v) * 255) */
 #define MM_RGBA32F 1       /* 16 B/px, linear float                                       */
 /* The frames the reference actually receives (since ABI 10): its camera
@@ -375,8 +377,10 @@ extern "C" {
  * multiples of 4 on both sides (every tight frame with W % 8 == 0); any other
  * legal layout takes the unfused kernels: the same bytes.  3 bytes per pixel
  * travel each way and nobody widens a frame to RGBA8 or strips an alpha.
- * Out of scope: BGRA8 / BGRA8 sRGB (MM_ORDER_BGR on MM_RGBA8 / MM_RGBA8_SRGB
- * is where they can live later; today MM_ERR_INVALID); RGB48; planar RGB; an
+ * Out of scope here: BGRA8 / BGRA8 sRGB, which are formats of their own
+ * (MM_ORDER_BGRA, "BGRA frames" below: MM_ORDER_BGR on MM_RGBA8 / MM_RGBA8_SRGB
+ * stays MM_ERR_INVALID, because every code below 4096 that was no format stays
+ * none); RGB48; planar RGB; an
  * sRGB-decoded RGB24; MM_RGB24 in with MM_BGR24 out; the LDS-DMA staging of the
  * fused kernels' source rows (MM_RGBA8's alone: 4-byte pixels); the ring
  * entry points (include/mm_ring.h); the Unity shim; mm_extmem_check. */
@@ -587,6 +591,64 @@ extern "C" {
 #define MM_V210      (MM_Y210 | MM_PACK_V210)                    /* 4118 */
 #define MM_V210_FULL (MM_Y210_FULL | MM_PACK_V210)               /* 4119 */
 
+/* BGRA frames (a backward-compatible addition to ABI 10: a caller detects it by
+ * mm_frame_bytes(W, H, MM_BGRA8, &n) == MM_OK).  The four-byte pixel B G R A
+ * that desktop, capture and display paths hand out: D3D and Vulkan swap chains
+ * and DXGI desktop duplication (B8G8R8A8_UNORM / _SRGB), CoreVideo's 32BGRA,
+ * NDI's BGRA / BGRX, DeckLink's 8-bit BGRA mode, GDI, Qt's Format_ARGB32, Cairo,
+ * libyuv's and WebRTC's "ARGB", OpenCV's four-channel mats.  The format is the
+ * byte-order bit MM_ORDER_BGRA on a 4-byte UNORM code: MM_BGRA8 = MM_RGBA8 |
+ * 8192 (8192), MM_BGRA8_SRGB = MM_RGBA8_SRGB | 8192 (8195).  Sizes, modes,
+ * views and call forms are MM_RGBA8's: 4 W bytes per row and 4 W H per frame,
+ * odd W and H, pyramid, standard and steerable mode, the debug views.
+ * A BGRA frame IS the MM_RGBA8 (MM_RGBA8_SRGB) frame with bytes 0 and 2 of every
+ * pixel exchanged; byte 3 is alpha.  BGRX is the same format: the operator gives
+ * alpha weight 0, and the output alpha after the first frame is 255.  With
+ * swap() for that exchange, three identities hold bitwise, in every mode, view
+ * (the split screen included), call form (single, stream, host-memory, lanes),
+ * edge mode, batch size, size and layout:
+ *   1. out_BGRA8(x) == swap(out_RGBA8(swap(x))), alpha byte included, and the
+ *      same for the sRGB pair (a debug view's value lies in byte 2);
+ *   2. the temporal state (mm_get_state, mm_compute_state*, a lane's state) is
+ *      bitwise that RGBA8 frame's;
+ *   3. the first frame after mm_create / mm_reset and apply_magnification = 0
+ *      pass all 4 W H bytes through bitwise.  Padding is never read or written.
+ * The bit is valid on codes 0 and 3 alone: 8193 and 8194 (float BGRA: nobody
+ * produces it), the bit on any Y'CbCr, single-plane, packed RGB, planar or v210
+ * code, the bit together with MM_ORDER_BGR, a matrix bit, MM_PLANAR,
+ * MM_LOW_BITS, MM_PACK_V210 or 256, 16384 and every higher stray bit, and
+ * negative codes are MM_ERR_INVALID from mm_frame_bytes, mm_surface_* and every
+ * frame entry point, before anything is queued.  (MM_RGBA8 | 128 stays
+ * MM_ERR_INVALID too: see "Packed RGB frames".)  mm_ycbcr_matrix refuses both
+ * codes, as it does MM_RGBA8.
+ * Surfaces: the unit u is 4 and every rule is MM_RGBA8's: chroma_offset =
+ * chroma_pitch = 0 (else MM_ERR_INVALID), pitch >= 4 W, device frame pointers,
+ * pitch and frame_stride multiples of 4.  mm_surface_tight and
+ * mm_surface_aligned return MM_RGBA8's numbers with the BGRA code:
+ * mm_surface_aligned(1920, 1080, MM_BGRA8, 256, 16) has pitch 7,680 and
+ * frame_stride 8,355,840, mm_surface_aligned(97, 63, MM_BGRA8, 256, 16) pitch
+ * 512 and frame_stride 32,768.  The fused kernels and the LDS-DMA staging of
+ * their source rows run under exactly MM_RGBA8's conditions.
+ * in_layout->format == out_layout->format, as everywhere: MM_RGBA8 in with
+ * MM_BGRA8 out is MM_ERR_INVALID from the same-format entry points and
+ * MM_ERR_UNSUPPORTED from mm_convert_supported.
+ * Convert pairs (see "Different formats in and out"), what a display path and a
+ * screen-capture encoder need: any MM_NV12 or MM_P010 code in with MM_BGRA8
+ * out, and MM_BGRA8 in with any MM_NV12 code out.  Bitwise,
+ * X -> BGRA8 == swap(X -> RGBA8) and BGRA8 -> NV12 (x) == RGBA8 -> NV12
+ * (swap(x)); the state is the in format's; passthrough frames are the plain
+ * conversion.  MM_BGRA8_SRGB has no mixed pair, as MM_RGBA8_SRGB has none.
+ * The exchange is made where the kernels are compiled (instances of their own,
+ * which name other bytes and constants in the same instructions), so a BGRA
+ * frame costs what its RGBA8 twin costs and nobody swizzles a frame.
+ * Out of scope: float BGRA; ARGB / ABGR byte orders; BGR-ordered 10-bit
+ * (A2R10G10B10); RGBA8 <-> BGRA8 and RGB24 <-> BGRA8 transcodes; MM_BGRA8_SRGB
+ * in a mixed pair; P010 out; mm_synth_frames (it stays MM_RGBA8); the ring entry
+ * points (include/mm_ring.h), the Unity shim and mm_extmem_check. */
+#define MM_ORDER_BGRA 8192                             /* byte-order bit of the 4-byte UNORM formats: B G R A */
+#define MM_BGRA8      (MM_RGBA8 | MM_ORDER_BGRA)       /* 8192 */
+#define MM_BGRA8_SRGB (MM_RGBA8_SRGB | MM_ORDER_BGRA)  /* 8195 */
+
 /* mm_params.mode */
 #define MM_MODE_PYRAMID   0  /* usePyramidDecomposition = true (.cs:18, :128-131) */
 #define MM_MODE_STANDARD  1   /* usePyramidDecomposition = false (.cs:132-135, :208-232) */
@@ -693,7 +755,8 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  *     modes, host-memory frames, stream ordering, aliasing) follows them.
  * Validation (mm_surface_bytes; every frame entry point applies it before it
  * queues anything; no GPU needed).  With the unit u = the pixel size of an RGBA
- * format (4, 16, 8, 4), 2 for NV12 (a (Cb, Cr) pair), 4 for P010 and packed
+ * format (4, 16, 8, 4; MM_BGRA8 / MM_BGRA8_SRGB: 4, and every rule of
+ * MM_RGBA8's), 2 for NV12 (a (Cb, Cr) pair), 4 for P010 and packed
  * 4:2:2, 8 for MM_Y210 (a macropixel each) and the sample
  * size of a single-plane format (1 for MM_Y8, 2 for MM_Y10 / Y12 / Y16), 1 for
  * packed RGB (MM_RGB24 / MM_BGR24: any byte):
@@ -720,7 +783,7 @@ int mm_frame_bytes(int width, int height, int format, size_t *bytes);
  * aligned like a decoder's runs exactly the tight layout's kernels. */
 typedef struct {
     /* MM_I420(_FULL) and MM_I010(_FULL) too: every format of the list above */
-    int    format;         /* MM_RGBA8 ... MM_UYVY_FULL, MM_Y210(_FULL), MM_RGB24 / MM_BGR24; 4:2:0 and 4:2:2: | MM_MATRIX_* */
+    int    format;         /* MM_RGBA8 ... MM_UYVY_FULL, MM_Y210(_FULL), MM_RGB24 / MM_BGR24, MM_BGRA8(_SRGB); 4:2:0 and 4:2:2: | MM_MATRIX_* */
     size_t pitch;          /* bytes from one row to the next: RGBA rows, or luma rows */
     size_t chroma_offset;  /* 4:2:0: bytes from the frame's base to the (Cb,Cr) plane; else 0 */
     size_t chroma_pitch;   /* 4:2:0: bytes from one (Cb,Cr) row to the next; else 0 */
@@ -775,7 +838,10 @@ int mm_process_stream_surfaces(mm_handle *h, const void *in, const mm_surface *i
  * Y'CbCr side):
  *   decode: any MM_NV12 code (16, 17, 48, 49, 80, 81) or MM_P010 code (18, 19,
  *           50, 51, 82, 83) in, MM_RGBA8 out;
- *   encode: MM_RGBA8 in, any MM_NV12 code out.
+ *   encode: MM_RGBA8 in, any MM_NV12 code out;
+ *   and both with MM_BGRA8 in MM_RGBA8's place ("BGRA frames"): the output of
+ *   a decode is the MM_RGBA8 decode's with bytes 0 and 2 of every pixel
+ *   exchanged, an encode's is the MM_RGBA8 encode's on the exchanged frame.
  * With equal formats they ARE the existing calls: same bytes, same state, same
  * kernels.  mm_convert_supported(in, out) needs no GPU: MM_OK for the pairs
  * above and any valid equal pair, MM_ERR_UNSUPPORTED for every other pair of
@@ -813,7 +879,8 @@ int mm_process_stream_surfaces(mm_handle *h, const void *in, const mm_surface *i
  * Any other legal layout takes the unfused kernels: the same bytes.
  * Out of scope: any pair not listed (packed 4:2:2 or MM_Y210 to MM_RGBA8,
  * MM_RGBA8 to P010, P010 to MM_RGBA16F, MM_RGB24 / MM_BGR24 on either side of a
- * mixed pair, MM_RGB24 to MM_BGR24 included, MM_RGBA8_SRGB, grayscale, Y'CbCr
+ * mixed pair, MM_RGB24 to MM_BGR24 included, MM_RGBA8 to MM_BGRA8,
+ * MM_RGBA8_SRGB and MM_BGRA8_SRGB, grayscale, Y'CbCr
  * to Y'CbCr transcodes such as NV12 to P010 or a matrix change); scaling or
  * cropping between the sides; chroma siting other than the shared 2 x 2
  * sample; PQ / HLG; odd sizes; the debug views; the ring entry points

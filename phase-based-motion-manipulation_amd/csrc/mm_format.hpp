@@ -31,6 +31,10 @@ static_assert(kFmtV210 < 256 && kFmtV210M < 256 && MM_V210 == (MM_Y210 | MM_PACK
               "the kernels' v210 template arguments are internal codes below 256; the pack bit is no other bit");
 static_assert(kFmtRGB24 == MM_RGB24 && MM_BGR24 == (MM_RGB24 | MM_ORDER_BGR) && !(MM_ORDER_BGR & kMatrixBits),
               "the kernels' packed RGB template argument is the MM_RGB24 code; the order bit is no matrix bit");
+static_assert(kFmtBGRA8 < 256 && kFmtBGRA8S < 256 && MM_BGRA8 == (MM_RGBA8 | MM_ORDER_BGRA) &&
+                  MM_BGRA8_SRGB == (MM_RGBA8_SRGB | MM_ORDER_BGRA) &&
+                  !(MM_ORDER_BGRA & (kMatrixBits | MM_ORDER_BGR | MM_PLANAR | MM_LOW_BITS | MM_PACK_V210 | 511)),
+              "the kernels' BGRA template arguments are internal codes below 256; the order bit is no other bit");
 static_assert((MM_NV12_FULL ^ MM_NV12) == kRangeBit && (MM_P010_FULL ^ MM_P010) == kRangeBit &&
                   (MM_I420_FULL ^ MM_I420) == kRangeBit && (MM_I010_FULL ^ MM_I010) == kRangeBit &&
                   (MM_YUY2_FULL ^ MM_YUY2) == kRangeBit && (MM_UYVY_FULL ^ MM_UYVY) == kRangeBit &&
@@ -100,6 +104,10 @@ static constexpr FmtInfo kFormats[] = {
     {MM_RGBA32F,    0,          MM_RGBA32F,    0,        4, 16, 16, 1, 1, 1, 0, 0,     0, 0.0,  {1, 1, 1, 1}},
     {MM_RGBA16F,    0,          MM_RGBA16F,    0,        2,  8,  8, 1, 1, 1, 0, 0,     0, 0.0,  {1, 1, 1, 1}},
     {MM_RGBA8_SRGB, 0,          MM_RGBA8_SRGB, 0,        1,  4,  4, 1, 1, 1, 0, 0,   255, 0.0,  {1, 1, 1, 1}},
+    // B G R A (MM_ORDER_BGRA on the two 4-byte UNORM codes): MM_RGBA8's fields,
+    // instances of their own (the order is compiled in, mm_kernels.hpp PixU8)
+    {MM_BGRA8,      0,          kFmtBGRA8,     0,        1,  4,  4, 1, 1, 1, 0, 0,   255, 0.0,  {1, 1, 1, 1}},
+    {MM_BGRA8_SRGB, 0,          kFmtBGRA8S,    0,        1,  4,  4, 1, 1, 1, 0, 0,   255, 0.0,  {1, 1, 1, 1}},
     // Single-plane grayscale: the compose reads no input; its quads are stores
     // alone, four bytes as one dword, four words as one 8-byte store at a
     // dword-aligned address.  Units 1 and 2: 98 x 62 MM_Y8 (rows 98 bytes apart) fails.

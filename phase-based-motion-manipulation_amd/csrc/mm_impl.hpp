@@ -297,15 +297,16 @@ static inline Geo::Lay surf_lay(const mm_surface &s)
     return l;
 }
 // The pairs of different formats mm_process_convert takes (include/mm.h):
-// decode, any NV12 or P010 code to MM_RGBA8; encode, MM_RGBA8 to any NV12 code.
+// decode, any NV12 or P010 code to MM_RGBA8; encode, MM_RGBA8 to any NV12 code;
+// and both with MM_BGRA8 as the 4-byte side.
 static inline int convert_supported(int in_fmt, int out_fmt)
 {
     const FmtInfo *fi = fmt_info(in_fmt), *fo = fmt_info(out_fmt);
     if (!fi || !fo) return MM_ERR_INVALID;
     if (in_fmt == out_fmt) return MM_OK;
     // (a three-plane code has no mixed pair)
-    if ((fi->kfmt == kFmtNV12 || fi->kfmt == kFmtP010) && out_fmt == MM_RGBA8) return MM_OK;
-    if (in_fmt == MM_RGBA8 && fo->kfmt == kFmtNV12) return MM_OK;
+    if ((fi->kfmt == kFmtNV12 || fi->kfmt == kFmtP010) && (out_fmt == MM_RGBA8 || out_fmt == MM_BGRA8)) return MM_OK;
+    if ((in_fmt == MM_RGBA8 || in_fmt == MM_BGRA8) && fo->kfmt == kFmtNV12) return MM_OK;
     return MM_ERR_UNSUPPORTED;
 }
 // The frames of one call: their formats and where the two sides lie.  fmt is
@@ -362,6 +363,8 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
     MM_FMT_CASE(kFmtRGB24, __VA_ARGS__)                                        \
     MM_FMT_CASE(kFmtI420, __VA_ARGS__)                                         \
     MM_FMT_CASE(kFmtI010, __VA_ARGS__)                                         \
+    MM_FMT_CASE(kFmtBGRA8, __VA_ARGS__)                                        \
+    MM_FMT_CASE(kFmtBGRA8S, __VA_ARGS__)                                       \
     /* a grouped format has no instance of the kernels launched through this  \
        switch (its K1 and K4 launches name theirs): refused, never another    \
        format's kernel over its bytes */                                       \
@@ -370,11 +373,14 @@ static inline Frames frames_of(int W, int H, const mm_surface &li, const mm_surf
     }
 // ... the compose kernels' (k_compose, k_rows_inv_compose, k_rows_inv_compose4):
 // FMT_ is the pair's code for the frames of a convert call (mm_kernels.hpp
-// fmt_pair; convert_supported leaves these three), else the format's
+// fmt_pair; convert_supported leaves these six), else the format's
 #define MM_MIXED_SWITCH(fr, ...)                                               \
-    switch ((fr).fi->kfmt) {                                                   \
+    switch ((fr).fi->kfmt | ((fr).fo->kfmt == kFmtBGRA8 ? 256 : 0)) {          \
     case kFmtNV12: { constexpr int FMT_ = kFmtNV12toRGBA8; __VA_ARGS__; } break; \
     case kFmtP010: { constexpr int FMT_ = kFmtP010toRGBA8; __VA_ARGS__; } break; \
+    case kFmtNV12 | 256: { constexpr int FMT_ = kFmtNV12toBGRA8; __VA_ARGS__; } break; \
+    case kFmtP010 | 256: { constexpr int FMT_ = kFmtP010toBGRA8; __VA_ARGS__; } break; \
+    case kFmtBGRA8: { constexpr int FMT_ = kFmtBGRA8toNV12; __VA_ARGS__; } break; \
     default: { constexpr int FMT_ = kFmtRGBA8toNV12; __VA_ARGS__; } break;     \
     }
 #define MM_PAIR_SWITCH(fr, ...)                                                \
@@ -420,6 +426,8 @@ template <int F> constexpr int kK1Fmt = F == MM_Y8 || F == kFmtI420 ? kFmtNV12 :
     MM_FMT_CASE(MM_RGBA16F, __VA_ARGS__)                                       \
     MM_FMT_CASE(MM_RGBA8_SRGB, __VA_ARGS__)                                    \
     MM_FMT_CASE(kFmtRGB24, __VA_ARGS__)                                        \
+    MM_FMT_CASE(kFmtBGRA8, __VA_ARGS__)                                        \
+    MM_FMT_CASE(kFmtBGRA8S, __VA_ARGS__)                                       \
     default: return MM_ERR_UNSUPPORTED;                                        \
     }
 
@@ -771,10 +779,16 @@ static int set_attrs(int W)
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<LOG2N, kFmtRGBA8toNV12, true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<LOG2N, kFmtBGRA8, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<LOG2N, kFmtBGRA8S, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<LOG2N, kFmtBGRA8toNV12, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
     if constexpr (LOG2N == 12) {   // k_rows_inv_compose: two 4096-point groups, 73.7 KB
         const int lds = (int)k34_lds_bytes<12>(false);
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420, MM_I010})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420, MM_I010, MM_BGRA8, MM_BGRA8_SRGB})
             MM_FMT_SWITCH(fmt_info(f), HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtNV12toRGBA8>),
@@ -782,6 +796,12 @@ static int set_attrs(int W)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtP010toRGBA8>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtRGBA8toNV12>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtNV12toBGRA8>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtP010toBGRA8>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose<12, kFmtBGRA8toNV12>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         // k_sb_cols: exchange buffer (36.9 KB) + its own staging, past 64 KB for
         // frames taller than ~3,570 rows (run_steer's bound)
@@ -809,7 +829,7 @@ static int set_attrs(int W)
     }
     if constexpr (LOG2N == 11) {   // k_rows_inv_compose4: four 2048-point groups, 73.7 KB
         const int lds = (int)(sizeof(c2) * 4 * lds_complex<2048>());
-        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420, MM_I010})
+        for (int f : {MM_RGBA8, MM_RGBA32F, MM_RGBA16F, MM_RGBA8_SRGB, MM_NV12, MM_P010, MM_Y8, MM_Y16, MM_YUY2, MM_Y210, MM_RGB24, MM_I420, MM_I010, MM_BGRA8, MM_BGRA8_SRGB})
             MM_FMT_SWITCH(fmt_info(f), HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, FMT_>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds)))
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtNV12toRGBA8>),
@@ -817,6 +837,12 @@ static int set_attrs(int W)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtP010toRGBA8>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtRGBA8toNV12>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtNV12toBGRA8>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtP010toBGRA8>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rows_inv_compose4<11, kFmtBGRA8toNV12>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
     return MM_OK;
@@ -1016,14 +1042,15 @@ static bool rows_aligned(const FmtInfo &f, const uint8_t *p, const Geo::Lay &l, 
     if (nframes > 1) luma |= l.stride, chroma |= l.stride;
     return !(luma & (a_luma - 1)) && !(chroma & (a_chroma - 1));
 }
-// The RGBA8 formats' source rows staged in LDS (k_rows_inv_compose<.., true>):
+// The RGBA8 and BGRA8 formats' source rows staged in LDS (k_rows_inv_compose<.., true>):
 // a thread's quad travels as one 16-byte LDS-DMA, taken only where every quad
 // of every source row of the launch is 16-byte aligned (X % 4 == 0).  Any other
 // layout keeps the register loads, which need dword alignment only.  Same results.
 static bool k34_src_dma(const mm_handle *h, const uint8_t *in, const Frames &fr, int nframes)
 {
-    // (a convert call with MM_RGBA8 in is the encode pair: the same source rows)
-    return (fr.fmt == MM_RGBA8 || fr.fmt == MM_RGBA8_SRGB) && rows_aligned(*fr.fi, in, fr.in, h->H, nframes, 16, 1);
+    // (a convert call with MM_RGBA8 or MM_BGRA8 in is the encode pair: the same source rows)
+    return (fr.fmt == MM_RGBA8 || fr.fmt == MM_RGBA8_SRGB || fr.fmt == MM_BGRA8 || fr.fmt == MM_BGRA8_SRGB) &&
+           rows_aligned(*fr.fi, in, fr.in, h->H, nframes, 16, 1);
 }
 // k_rows_inv_compose's layouts: quads at the alignment each side's format asks
 // of its rows (FmtInfo::quad; a convert call: the input numbers of the input
@@ -1115,8 +1142,11 @@ static int launch_k3(mm_handle *h, const c2 *Q, const uint8_t *in, uint8_t *out,
                            h->q_stride, in, out, frame0, strips, steps, geo_of(h, fr), h->blur,      \
                            h->d_col3, h->d_row3, h->d_tw)
         if constexpr (LOG2N <= 12) if (dma) {
-            if (fr.mixed()) MM_K34_LAUNCH(kFmtRGBA8toNV12, true);
+            if (fr.mixed() && fmt == MM_BGRA8) MM_K34_LAUNCH(kFmtBGRA8toNV12, true);
+            else if (fr.mixed()) MM_K34_LAUNCH(kFmtRGBA8toNV12, true);
             else if (fmt == MM_RGBA8) MM_K34_LAUNCH(MM_RGBA8, true);
+            else if (fmt == MM_BGRA8) MM_K34_LAUNCH(kFmtBGRA8, true);
+            else if (fmt == MM_BGRA8_SRGB) MM_K34_LAUNCH(kFmtBGRA8S, true);
             else MM_K34_LAUNCH(MM_RGBA8_SRGB, true);
         }
         if (!dma) MM_PAIR_SWITCH(fr, MM_K34_LAUNCH(FMT_, false))

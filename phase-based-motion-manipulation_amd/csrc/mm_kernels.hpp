@@ -292,8 +292,22 @@ __device__ __forceinline__ size_t q_index(const Geo &g, int k, int f)
 
 // ---- pixel access -------------------------------------------------------
 template <int FMT> struct Pix;
-template <> struct Pix<0> {           // RGBA8 UNORM
+// The 4-byte UNORM pixel in either byte order: R G B A (ORD 0: MM_RGBA8) or
+// B G R A (ORD 1: MM_BGRA8 = MM_RGBA8 | MM_ORDER_BGRA).  A BGRA frame IS the
+// RGBA8 frame with bytes 0 and 2 of every pixel exchanged (include/mm.h), and
+// the exchange is made at compile time: the order names which byte each
+// convert, shift and dot weight touches, never how many instructions there are,
+// and every value computed from (r, g, b) is the other order's bit for bit.
+// The public codes carry MM_ORDER_BGRA (8192), so the instances are internal
+// codes below 256 (0 | 128, 3 | 128), as the three-plane formats' are.
+constexpr int kFmtBGRA8 = 128;    // MM_BGRA8
+constexpr int kFmtBGRA8S = 131;   // MM_BGRA8_SRGB
+template <int FMT> constexpr bool kBGRA = FMT == kFmtBGRA8 || FMT == kFmtBGRA8S;
+template <int FMT> constexpr bool kRGBA8u = FMT == 0 || FMT == kFmtBGRA8;   // linear UNORM bytes, either order
+template <int ORD> struct PixU8 {     // RGBA8 / BGRA8 UNORM
     static constexpr int bpp = 4;
+    static constexpr unsigned rb = ORD ? 2u : 0u, bb = ORD ? 0u : 2u;   // the bytes of R and B (G: 1, A: 3)
+    static constexpr unsigned rs = 8u * rb, bs = 8u * bb;
     using raw_t = uint32_t;             // keep loads raw in registers, convert at use
     __device__ static raw_t raw(const uint8_t *base, size_t i)
     {
@@ -302,15 +316,15 @@ template <> struct Pix<0> {           // RGBA8 UNORM
     __device__ static float4 cvt(raw_t u)
     {
         const float s = 1.0f / 255.0f;
-        return make_float4((float)(u & 255u) * s, (float)((u >> 8) & 255u) * s,
-                           (float)((u >> 16) & 255u) * s, (float)(u >> 24) * s);
+        return make_float4((float)((u >> rs) & 255u) * s, (float)((u >> 8) & 255u) * s,
+                           (float)((u >> bs) & 255u) * s, (float)(u >> 24) * s);
     }
     __device__ static float4 load(const uint8_t *base, size_t i) { return cvt(raw(base, i)); }
     __device__ static uint32_t pack(float r, float g, float b)
     {
         uint32_t R = (uint32_t)(r * 255.0f + 0.5f), G = (uint32_t)(g * 255.0f + 0.5f),
                  B = (uint32_t)(b * 255.0f + 0.5f);
-        return R | (G << 8) | (B << 16) | (255u << 24);
+        return (R << rs) | (G << 8) | (B << bs) | (255u << 24);
     }
     __device__ static void store(uint8_t *base, unsigned i, float r, float g, float b)
     {
@@ -326,10 +340,12 @@ template <> struct Pix<0> {           // RGBA8 UNORM
     {
         uint32_t alpha = 0xff000000u;
         asm("" : "+s"(alpha));
-        const uint32_t a = __builtin_amdgcn_cvt_pk_u8_f32(r, 0u, alpha);
-        return __builtin_amdgcn_cvt_pk_u8_f32(b, 2u, __builtin_amdgcn_cvt_pk_u8_f32(g, 1u, a));
+        const uint32_t a = __builtin_amdgcn_cvt_pk_u8_f32(r, rb, alpha);
+        return __builtin_amdgcn_cvt_pk_u8_f32(b, bb, __builtin_amdgcn_cvt_pk_u8_f32(g, 1u, a));
     }
 };
+template <> struct Pix<0> : PixU8<0> {};
+template <> struct Pix<kFmtBGRA8> : PixU8<1> {};
 template <> struct Pix<1> {           // RGBA32F
     static constexpr int bpp = 16;
     using raw_t = float4;
@@ -383,8 +399,9 @@ template <> struct Pix<2> {
 // encode of a saturated value: 255 srgb(v) rounded, found from the pow
 // approximation and corrected by one step against the exact thresholds
 // kSrgbThr (the approximation is within one code of the exact one).
-template <> struct Pix<3> {
+template <int ORD> struct PixS8 {     // ORD as PixU8's: 0 R G B A, 1 B G R A (MM_BGRA8_SRGB)
     static constexpr int bpp = 4;
+    static constexpr unsigned rs = PixU8<ORD>::rs, bs = PixU8<ORD>::bs;
     using raw_t = uint32_t;
     __device__ static raw_t raw(const uint8_t *base, size_t i)
     {
@@ -392,7 +409,7 @@ template <> struct Pix<3> {
     }
     __device__ static float4 cvt(raw_t u)
     {
-        return make_float4(kSrgbDec[u & 255u], kSrgbDec[(u >> 8) & 255u], kSrgbDec[(u >> 16) & 255u],
+        return make_float4(kSrgbDec[(u >> rs) & 255u], kSrgbDec[(u >> 8) & 255u], kSrgbDec[(u >> bs) & 255u],
                            (float)(u >> 24) * (1.0f / 255.0f));
     }
     __device__ static uint32_t enc(float v)
@@ -405,15 +422,17 @@ template <> struct Pix<3> {
     }
     __device__ static uint32_t pack(float r, float g, float b)
     {
-        return enc(r) | (enc(g) << 8) | (enc(b) << 16) | (255u << 24);
+        return (enc(r) << rs) | (enc(g) << 8) | (enc(b) << bs) | (255u << 24);
     }
     __device__ static void store(uint8_t *base, unsigned i, float r, float g, float b)
     {
         st_stream<uint32_t>(base, i * 4u, pack(r, g, b));
     }
 };
-// saturated before the store: the UNORM destinations (RGBA8, RGBA8 sRGB)
-template <int FMT> constexpr bool kUnorm = FMT == 0 || FMT == 3;
+template <> struct Pix<3> : PixS8<0> {};
+template <> struct Pix<kFmtBGRA8S> : PixS8<1> {};
+// saturated before the store: the UNORM destinations (RGBA8, RGBA8 sRGB, in either byte order)
+template <int FMT> constexpr bool kUnorm = FMT == 0 || FMT == 3 || kBGRA<FMT>;
 
 // RGBToYIQ.shader:46-50 rows
 __device__ __forceinline__ float luma(float4 c) { return 0.299f * c.x + 0.587f * c.y + 0.114f * c.z; }
@@ -426,13 +445,17 @@ __device__ __forceinline__ float sat(float v) { return fminf(fmaxf(v, 0.0f), 1.0
 // 299 R + 587 G + 114 B (two v_dot4_u32_u8: 299 = 256 + 43, 587 = 2 * 256 + 75,
 // and one convert; RGBToYIQ's 0.299/0.587/0.114 of R/255 ... times 255000),
 // whose unit 1/255000 folds into the resample weights; RGBA32F as luma().
-template <int FMT> constexpr float kLumaUnit = FMT == 0 ? 1.0f / 255000.0f : 1.0f;
+template <int FMT> constexpr float kLumaUnit = kRGBA8u<FMT> ? 1.0f / 255000.0f : 1.0f;
 template <int FMT>
 __device__ __forceinline__ float luma_units(typename Pix<FMT>::raw_t u)
 {
-    if constexpr (FMT == 0) {
-        const unsigned hi = __builtin_amdgcn_udot4(u, 0x00000201u, 0u, false);    // R + 2 G
-        return (float)__builtin_amdgcn_udot4(u, 0x00724B2Bu, hi << 8, false);   // + 43 R + 75 G + 114 B
+    if constexpr (kRGBA8u<FMT>) {   // (B G R A: the weights on the other bytes, rgb24_luma_units' for that order)
+        constexpr unsigned w_hi = 2u << 8 | 1u << Pix<FMT>::rs;
+        constexpr unsigned w_lo = 43u << Pix<FMT>::rs | 75u << 8 | 114u << Pix<FMT>::bs;
+        static_assert(FMT != 0 || (w_hi == 0x00000201u && w_lo == 0x00724B2Bu), "MM_RGBA8's weights");
+        static_assert(FMT == 0 || (w_hi == 0x00010200u && w_lo == 0x002B4B72u), "MM_BGRA8's weights");
+        const unsigned hi = __builtin_amdgcn_udot4(u, w_hi, 0u, false);    // R + 2 G
+        return (float)__builtin_amdgcn_udot4(u, w_lo, hi << 8, false);   // + 43 R + 75 G + 114 B
     } else {
         return luma(Pix<FMT>::cvt(u));
     }
@@ -443,9 +466,10 @@ __device__ __forceinline__ float luma_units(typename Pix<FMT>::raw_t u)
 template <int FMT>
 __device__ __forceinline__ float2 chroma_iq(typename Pix<FMT>::raw_t u)
 {
-    if constexpr (FMT == 0) {
+    if constexpr (kRGBA8u<FMT>) {
         constexpr float k = 1.0f / 255.0f;
-        const float r = (float)(u & 255u), gg = (float)((u >> 8) & 255u), b = (float)((u >> 16) & 255u);
+        const float r = (float)((u >> Pix<FMT>::rs) & 255u), gg = (float)((u >> 8) & 255u),
+                    b = (float)((u >> Pix<FMT>::bs) & 255u);
         return make_float2((0.596f * k) * r + (-0.274f * k) * gg + (-0.322f * k) * b,
                            (0.211f * k) * r + (-0.523f * k) * gg + (0.312f * k) * b);
     } else {
@@ -462,9 +486,10 @@ __device__ __forceinline__ float2 chroma_iq(typename Pix<FMT>::raw_t u)
 template <int FMT>
 __device__ __forceinline__ c2 chroma_iq2(typename Pix<FMT>::raw_t u)
 {
-    if constexpr (FMT == 0) {
+    if constexpr (kRGBA8u<FMT>) {
         constexpr float k = 1.0f / 255.0f;
-        const float r = (float)(u & 255u), gg = (float)((u >> 8) & 255u), b = (float)((u >> 16) & 255u);
+        const float r = (float)((u >> Pix<FMT>::rs) & 255u), gg = (float)((u >> 8) & 255u),
+                    b = (float)((u >> Pix<FMT>::bs) & 255u);
         return mk(0.596f * k, 0.211f * k) * r + mk(-0.274f * k, -0.523f * k) * gg + mk(-0.322f * k, 0.312f * k) * b;
     } else {
         const float4 c = Pix<FMT>::cvt(u);
@@ -496,15 +521,16 @@ __device__ __forceinline__ void yiq_rgb(float yb, c2 cc, float &rr, float &gg, f
 // Packed RGB out (MM_RGB24 / MM_BGR24: "MM_RGBA8's rule, three bytes",
 // include/mm.h) stores three bytes of the same word and stays the RGBA8 path
 // byte for byte (tests/test_rgb24.py).
-template <int FO> constexpr bool kCodeOut = FO == 0 || FO == 13;   // MM_RGBA8, kFmtRGB24 (below)
+template <int FO> constexpr bool kCodeOut = FO == 0 || FO == 13 || FO == kFmtBGRA8;   // MM_RGBA8, kFmtRGB24 (below), MM_BGRA8
 constexpr float kCodeRI = (float)(255.0 * 0.956), kCodeGI = (float)(255.0 * -0.272);
 constexpr float kCodeRQ = (float)(255.0 * 0.621), kCodeGQ = (float)(255.0 * -0.647);
 constexpr float kCodeBI = (float)(255.0 * -1.106), kCodeBQ = (float)(255.0 * 1.703);
-__device__ __forceinline__ uint32_t yiq_rgba8(float yc, c2 cc)
+// (FO: the byte order of the word; packed RGB takes RGBA8's and picks its three bytes)
+template <int FO = 0> __device__ __forceinline__ uint32_t yiq_rgba8(float yc, c2 cc)
 {
     const c2 rg = mk(yc, yc) + mk(kCodeRI, kCodeGI) * cc.x + mk(kCodeRQ, kCodeGQ) * cc.y;
     const float b = fmaf(kCodeBQ, cc.y, fmaf(kCodeBI, cc.x, yc));
-    return Pix<0>::pack_codes(rg.x, rg.y, b);
+    return Pix<FO == kFmtBGRA8 ? kFmtBGRA8 : 0>::pack_codes(rg.x, rg.y, b);
 }
 // the compose kernels' vertical blur taps for output format FO
 struct VBlur { float w0, w1, w2; };
@@ -619,8 +645,13 @@ template <int FMT> constexpr int kFmtOut = FMT < 256 ? FMT : (FMT >> 8) - 1;
 constexpr int kFmtNV12toRGBA8 = fmt_pair(kFmtNV12, 0);   // decode: MM_NV12* in, MM_RGBA8 out
 constexpr int kFmtP010toRGBA8 = fmt_pair(kFmtP010, 0);   // decode: MM_P010* in, MM_RGBA8 out
 constexpr int kFmtRGBA8toNV12 = fmt_pair(0, kFmtNV12);   // encode: MM_RGBA8 in, MM_NV12* out
+// ... and the same three with MM_BGRA8 as the 4-byte side
+constexpr int kFmtNV12toBGRA8 = fmt_pair(kFmtNV12, kFmtBGRA8);
+constexpr int kFmtP010toBGRA8 = fmt_pair(kFmtP010, kFmtBGRA8);
+constexpr int kFmtBGRA8toNV12 = fmt_pair(kFmtBGRA8, kFmtNV12);
 template <int FMT> constexpr bool kFmtPairOk = FMT < 256 || FMT == kFmtNV12toRGBA8 || FMT == kFmtP010toRGBA8 ||
-                                               FMT == kFmtRGBA8toNV12;
+                                               FMT == kFmtRGBA8toNV12 || FMT == kFmtNV12toBGRA8 ||
+                                               FMT == kFmtP010toBGRA8 || FMT == kFmtBGRA8toNV12;
 // an input macropixel's chroma bytes (byte order: Geo::li.yb; the shifts are uniform)
 __device__ __forceinline__ float c422_cb(unsigned u, const Geo &g) { return (float)((u >> (8u - 8u * g.li.yb)) & 255u); }
 __device__ __forceinline__ float c422_cr(unsigned u, const Geo &g) { return (float)((u >> (24u - 8u * g.li.yb)) & 255u); }
@@ -3165,7 +3196,7 @@ void k_compose(const float *__restrict__ Yh, size_t yh_stride, const uint8_t *__
             if constexpr (kRGB24<FO>) {   // three bytes per lane, of the RGBA8 word
                 rgb24_store_px(outp + (size_t)((unsigned)i * g.lo.pitch), (unsigned)X, yiq_rgba8(yb, cc), g);
             } else if constexpr (kCodeOut<FO>) {   // one dword per lane, packed in code units
-                st_stream<uint32_t>(outp + (unsigned)i * g.lo.pitch, (unsigned)X * 4u, yiq_rgba8(yb, cc));
+                st_stream<uint32_t>(outp + (unsigned)i * g.lo.pitch, (unsigned)X * 4u, yiq_rgba8<FO>(yb, cc));
             } else if constexpr (k420<FO>) {
                 // One luma byte per pixel.  The 2x2 chroma mean: this column's
                 // two rows (i0 and TR even: r even starts a block; H even: both
@@ -3377,7 +3408,8 @@ __device__ unsigned long long mm_k34_stamps[65536 * 8];
 // (the last reader of the rows); each wave waits for its own copies before the
 // barrier that ends the blur, and the compose reads after that barrier.
 // (... and the encode pair's, MM_RGBA8 in with NV12 out: the same 4-byte source pixels)
-template <int FMT> constexpr bool k34_dma_fmt = FMT == MM_RGBA8 || FMT == MM_RGBA8_SRGB || FMT == kFmtRGBA8toNV12;
+template <int FMT> constexpr bool k34_dma_fmt = FMT == MM_RGBA8 || FMT == MM_RGBA8_SRGB || FMT == kFmtRGBA8toNV12 ||
+                                                FMT == kFmtBGRA8 || FMT == kFmtBGRA8S || FMT == kFmtBGRA8toNV12;
 template <int LOG2N> constexpr int k34_src_bytes() { return 4 * 4 * (1 << LOG2N); }
 template <int LOG2N, int FMT, bool SRCDMA = false>
 __global__ __launch_bounds__(2 * fft_T<LOG2N>()) __attribute__((amdgpu_waves_per_eu(4)))
@@ -3646,7 +3678,7 @@ void k_rows_inv_compose(const c2 *__restrict__ Q, size_t q_stride,
                         const c2 cc = wr.x * hc[r][k] + wr.y * hc[r + 1][k] + wr.z * hc[r + 2][k];
                         const float yb = bv.w0 * yw[r + 2][k] + bv.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
                                          bv.w2 * (yw[r][k] + yw[r + 4][k]);
-                        if constexpr (kCodeOut<FO>) pc[k] = yiq_rgba8(yb, cc);
+                        if constexpr (kCodeOut<FO>) pc[k] = yiq_rgba8<FO>(yb, cc);
                         else yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
                     }
                     // (in pixels: an RGBA pitch is a multiple of the pixel size)
@@ -3881,7 +3913,7 @@ void k_rows_inv_compose4(const c2 *__restrict__ Q, size_t q_stride,
                 const c2 cc = wr.x * hc[r][k] + wr.y * hc[r + 1][k] + wr.z * hc[r + 2][k];
                 const float yb = bv.w0 * yw[r + 2][k] + bv.w1 * (yw[r + 1][k] + yw[r + 3][k]) +
                                  bv.w2 * (yw[r][k] + yw[r + 4][k]);
-                if constexpr (kCodeOut<FO>) pc[k] = yiq_rgba8(yb, cc);
+                if constexpr (kCodeOut<FO>) pc[k] = yiq_rgba8<FO>(yb, cc);
                 else yiq_rgb(yb, cc, rr[k], gg[k], bb[k]);
             }
             [[maybe_unused]] const unsigned o = (unsigned)i * (g.lo.pitch / bppo) + (unsigned)X;
@@ -4126,7 +4158,7 @@ __global__ __launch_bounds__(256)
 void k_convert(const uint8_t *__restrict__ frames_in, uint8_t *__restrict__ frames_out, Geo g, Cvt cv, int nframes)
 {
     constexpr int FI = kFmtIn<FMT>, FO = kFmtOut<FMT>;
-    static_assert(FMT >= 256 && kFmtPairOk<FMT>, "one of the three mixed pairs");
+    static_assert(FMT >= 256 && kFmtPairOk<FMT>, "one of the mixed pairs");
     const unsigned bw = (unsigned)(g.W + 3) / 4u;            // blocks per row pair
     const size_t nb = (size_t)bw * (unsigned)(g.H / 2);     // ... per frame
     const size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -4184,7 +4216,8 @@ void k_convert(const uint8_t *__restrict__ frames_in, uint8_t *__restrict__ fram
                     rr[r][k] = sat(y + dr); gg[r][k] = sat(y + dg); bb[r][k] = sat(y + db);
                 }
         }
-    } else {   // RGBA8 in: byte / 255 (in [0, 1] already), alpha ignored
+    } else {   // RGBA8 / BGRA8 in: byte / 255 (in [0, 1] already), alpha ignored
+        static_assert(kRGBA8u<FI>, "the 4-byte side of a mixed pair is MM_RGBA8 or MM_BGRA8");
         constexpr float s = 1.0f / 255.0f;
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
@@ -4199,28 +4232,28 @@ void k_convert(const uint8_t *__restrict__ frames_in, uint8_t *__restrict__ fram
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                rr[r][k] = (float)(px[k] & 255u) * s;
+                rr[r][k] = (float)((px[k] >> Pix<FI>::rs) & 255u) * s;
                 gg[r][k] = (float)((px[k] >> 8) & 255u) * s;
-                bb[r][k] = (float)((px[k] >> 16) & 255u) * s;
+                bb[r][k] = (float)((px[k] >> Pix<FI>::bs) & 255u) * s;
             }
         }
     }
 
-    if constexpr (FO == 0) {   // RGBA8 out: Pix<0>::pack, alpha 255
+    if constexpr (kRGBA8u<FO>) {   // RGBA8 / BGRA8 out: Pix<FO>::pack, alpha 255
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             uint8_t *row = outp + (size_t)((Y + r) * g.lo.pitch);
             if constexpr (QUAD) {
                 uint4 px;
-                px.x = Pix<0>::pack(rr[r][0], gg[r][0], bb[r][0]);
-                px.y = Pix<0>::pack(rr[r][1], gg[r][1], bb[r][1]);
-                px.z = Pix<0>::pack(rr[r][2], gg[r][2], bb[r][2]);
-                px.w = Pix<0>::pack(rr[r][3], gg[r][3], bb[r][3]);
+                px.x = Pix<FO>::pack(rr[r][0], gg[r][0], bb[r][0]);
+                px.y = Pix<FO>::pack(rr[r][1], gg[r][1], bb[r][1]);
+                px.z = Pix<FO>::pack(rr[r][2], gg[r][2], bb[r][2]);
+                px.w = Pix<FO>::pack(rr[r][3], gg[r][3], bb[r][3]);
                 st_stream_quad_a4(row, X * 4u, px);
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (k < nc) st_off<uint32_t>(row, (X + k) * 4u, Pix<0>::pack(rr[r][k], gg[r][k], bb[r][k]));
+                    if (k < nc) st_off<uint32_t>(row, (X + k) * 4u, Pix<FO>::pack(rr[r][k], gg[r][k], bb[r][k]));
             }
         }
     } else {   // NV12 out: the compose kernels' codes (nv12_ycode, nv12_ccode) and their order of sums

@@ -9,7 +9,7 @@
  *   mm_cli [-w W] [-h H] [-n frames] [-l levels] [-s phase_scale]
  *          [-b frames_per_call] [-i in.{rgba,y4m}] [-o out.{rgba,y4m}] [-d device]
  *          [--full-range] [--srgb] [--nv12] [--p010] [--matrix 601|709|2020] [--mono]
- *          [--yuy2] [--uyvy] [--y210] [--v210] [--ppm [--bgr]] [--i420] [--i010] [--out-rgba8] [--out-nv12]
+ *          [--yuy2] [--uyvy] [--y210] [--v210] [--ppm [--bgr | --bgra]] [--i420] [--i010] [--out-rgba8 | --out-bgra8] [--out-nv12]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R] [--lanes M]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
@@ -98,7 +98,10 @@
  * --ppm: the input (-i) is a stream of concatenated binary PPM images (P6,
  * maxval 255, one size: what ffmpeg -f image2pipe -vcodec ppm writes; host/ppm.h).
  * Its frames go to the device as MM_RGB24 as they lie, 3 bytes per pixel each
- * way, and -o gets the same container back.  --bgr swaps R and B on read and
+ * way, and -o gets the same container back.  --bgra widens every image on the
+ * host to B G R 255 and processes it as MM_BGRA8, the alpha dropped on write:
+ * the output file is --ppm's byte for byte (it shows the BGRA path; not with
+ * --bgr).  --bgr swaps R and B on read and
  * on write and sends MM_BGR24 (the files are the run without it, byte for
  * byte).  Every size, -l, -s, -b, --standard and --surface-align as usual.
  * Not with --matrix, --full-range or a .y4m on either side.
@@ -120,6 +123,9 @@
  * decoder's layout) and go through mm_process_stream_surfaces; for every input
  * format, --nv12, --p010, --yuy2, --uyvy and --y210 included.  Files and checksums are those of the
  * run without the flag, byte for byte.  Not with the ring modes.
+ * --out-bgra8 (with --nv12 or --p010): --out-rgba8 with MM_BGRA8 as the output
+ * format, raw frames only: --out-rgba8's output with bytes 0 and 2 of every
+ * pixel exchanged.
  * --out-rgba8 (with --nv12 or --p010): decode on the way out.  The frames go
  * in as stored and raw MM_RGBA8 frames come out, through
  * mm_process_stream_convert: -o gets the raw RGBA8 frames, or, a .y4m, the 4:4:4
@@ -654,6 +660,23 @@ static const char *y4m_needs(const y4m_info *yi, int depth)
     return yi->chroma == Y4M_MONO ? "--mono" : "--p010";
 }
 
+/* --ppm --bgra: an image's R G B pixels widened in place to B G R 255
+ * (MM_BGRA8; the buffer holds 4 bytes per pixel), and back, the alpha dropped */
+static void ppm_widen_bgra(unsigned char *p, size_t npx)
+{
+    for (size_t i = npx; i-- > 0;) {
+        const unsigned char r = p[3 * i], g = p[3 * i + 1], b = p[3 * i + 2];
+        p[4 * i] = b, p[4 * i + 1] = g, p[4 * i + 2] = r, p[4 * i + 3] = 255;
+    }
+}
+static void ppm_narrow_bgra(unsigned char *p, size_t npx)
+{
+    for (size_t i = 0; i < npx; ++i) {
+        const unsigned char b = p[4 * i], g = p[4 * i + 1], r = p[4 * i + 2];
+        p[3 * i] = r, p[3 * i + 1] = g, p[3 * i + 2] = b;
+    }
+}
+
 #define REFUSE(...) do { fprintf(stderr, __VA_ARGS__); return 2; } while (0)
 
 int main(int argc, char **argv)
@@ -661,7 +684,7 @@ int main(int argc, char **argv)
     int W = 1920, H = 1080, F = 300, L = 5, B = 30, dev = 0;
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
-    int srgb = 0, bgr = 0, out_rgba8 = 0, out_nv12 = 0;
+    int srgb = 0, bgr = 0, bgra = 0, out_rgba8 = 0, out_bgra8 = 0, out_nv12 = 0;
     const char *lanes_arg = NULL, *drop_arg = NULL;
     const in_opt *in = NULL;  /* the input-format option: one at most */
     const char *matrix_arg = NULL;
@@ -681,7 +704,9 @@ int main(int argc, char **argv)
         if (!strcmp(a, "--full-range")) { full_range = 1; continue; }
         if (!strcmp(a, "--srgb")) { g_fmt = MM_RGBA8_SRGB; srgb = 1; continue; }
         if (!strcmp(a, "--bgr")) { bgr = 1; continue; }
+        if (!strcmp(a, "--bgra")) { bgra = 1; continue; }
         if (!strcmp(a, "--out-rgba8")) { out_rgba8 = 1; continue; }
+        if (!strcmp(a, "--out-bgra8")) { out_bgra8 = 1; continue; }
         if (!strcmp(a, "--out-nv12")) { out_nv12 = 1; continue; }
         if (!strcmp(a, "--standard")) { standard = 1; continue; }
         if (!strcmp(a, "--show-magnitude")) { show_mag = 1; continue; }
@@ -718,19 +743,26 @@ int main(int argc, char **argv)
      * device is touched.  First what the options say by themselves. */
     const int views = show_mag || show_phase, ring = ring_local > 0 || ring_world > 0;
     const int p_ppm = in == k_opt_ppm;
+    /* --out-bgra8 is --out-rgba8 with MM_BGRA8 as the output code: one set of rules */
+    if (out_rgba8 && out_bgra8) REFUSE("--out-rgba8 does not go with --out-bgra8 (one output format)\n");
+    const char *out4 = out_bgra8 ? "--out-bgra8" : "--out-rgba8";
+    out_rgba8 |= out_bgra8;
     if (in) {
         const char *bad = srgb ? "--srgb" : ring ? "the ring modes (they take RGBA frames)"
                           : views && !in->views ? "the debug views" : out_nv12 ? "--out-nv12 (it takes the RGBA8 input path)"
-                          : out_rgba8 && !in->decode ? "--out-rgba8 (it takes --nv12 or --p010)"
+                          : out_rgba8 && !in->decode ? (out_bgra8 ? "--out-bgra8 (it takes --nv12 or --p010)"
+                                                                   : "--out-rgba8 (it takes --nv12 or --p010)")
                           : matrix_arg && !in->ycc ? "--matrix (there is no matrix)"
                           : full_range && !in->ycc ? "--full-range (there is no range)" : NULL;
         if (bad) REFUSE("%s does not go with %s\n", in->name, bad);
         if (!in_path) REFUSE("%s needs an input (-i): %s\n", in->name, in->needs);
     }
     if (bgr && !p_ppm) REFUSE("--bgr needs --ppm\n");
+    if (bgra && !p_ppm) REFUSE("--bgra needs --ppm\n");
+    if (bgra && bgr) REFUSE("--bgra does not go with --bgr (one byte order)\n");
     /* different formats in and out (mm_process_stream_convert) */
-    if (out_rgba8 && out_nv12) REFUSE("--out-rgba8 does not go with --out-nv12\n");
-    if (out_rgba8 && !in) REFUSE("--out-rgba8 needs --nv12 or --p010 (the default path's output is RGBA8 already)\n");
+    if (out_rgba8 && out_nv12) REFUSE("%s does not go with --out-nv12\n", out4);
+    if (out_rgba8 && !in) REFUSE("%s needs --nv12 or --p010 (the default path takes and gives RGBA8)\n", out4);
     if (out_nv12 && (srgb || views || ring))
         REFUSE("--out-nv12 takes the RGBA8 input path: not with --srgb, the debug views or the ring modes\n");
     if (matrix_arg && !(in && in->ycc) && !out_nv12)
@@ -762,6 +794,7 @@ int main(int argc, char **argv)
     if (in_path && !fi) { fprintf(stderr, "cannot open file\n"); return 1; }
     const int y4m_in = in_path && ends_with(in_path, ".y4m");
     const int y4m_out = out_path && ends_with(out_path, ".y4m");
+    if (out_bgra8 && y4m_out) REFUSE("--out-bgra8 writes raw B G R A frames, no .y4m (the .y4m writer takes RGBA8: --out-rgba8)\n");
     y4m_info yi = {0};
     yi.fps_num = 25;
     yi.fps_den = 1;
@@ -803,8 +836,8 @@ int main(int argc, char **argv)
                      : !strcmp(matrix_arg, "2020") ? MM_MATRIX_BT2020 : 0;
     if (in)
         g_fmt = !in->depth ? (depth == 8 ? MM_Y8 : depth == 10 ? MM_Y10 : depth == 12 ? MM_Y12 : MM_Y16)
-                : p_ppm && bgr ? MM_BGR24 : (full_range ? in->fmt_full : in->fmt) | mbit;
-    const int o_fmt = out_nv12 ? (full_range ? MM_NV12_FULL : MM_NV12) | mbit : out_rgba8 ? MM_RGBA8 : g_fmt;
+                : p_ppm && bgr ? MM_BGR24 : p_ppm && bgra ? MM_BGRA8 : (full_range ? in->fmt_full : in->fmt) | mbit;
+    const int o_fmt = out_nv12 ? (full_range ? MM_NV12_FULL : MM_NV12) | mbit : out_bgra8 ? MM_BGRA8 : out_rgba8 ? MM_RGBA8 : g_fmt;
     const int convert = o_fmt != g_fmt;
     /* what a .y4m output holds, and how its frames are made: the input
      * option's, --out-nv12: --nv12's, --out-rgba8 or no option: 4:4:4 from RGBA8 */
@@ -962,6 +995,7 @@ int main(int argc, char **argv)
                     return 1;
                 }
                 if (bgr) ppm_swap_rb(host + fb * got, (size_t)W * H);
+                if (bgra) ppm_widen_bgra(host + fb * got, (size_t)W * H);
             }
             if (got == 0) break;
             n = got;
@@ -1013,6 +1047,7 @@ int main(int argc, char **argv)
             } else if (p_ppm) {   /* the same container back */
                 for (int k = 0; k < n; ++k) {
                     if (bgr) ppm_swap_rb(host + fb * k, (size_t)W * H);
+                    if (bgra) ppm_narrow_bgra(host + fb * k, (size_t)W * H);
                     if (ppm_write_frame(fo, W, H, host + fb * k)) {
                         fprintf(stderr, "write failed\n");
                         return 1;

@@ -19,7 +19,7 @@ construction/Start raises ``MMError`` — loudly, never silently.
 from .binding import (MMError, lib, load_library, LIB_PATH, RGBA8, RGBA32F, RGBA16F, RGBA8_SRGB,
                       NV12, NV12_FULL, P010, P010_FULL, MATRIX_BT709, MATRIX_BT2020, FORMAT_BPP, frame_bytes,
                       Y8, Y10, Y12, Y16, MONO_FORMATS, MONO_BITS,
-                      RGB24, BGR24, ORDER_BGR, RGB24_FORMATS,
+                      RGB24, BGR24, ORDER_BGR, RGB24_FORMATS, BGRA8, BGRA8_SRGB, ORDER_BGRA, BGRA_FORMATS, has_bgra,
                       I420, I420_FULL, PLANAR, I420_FORMATS,
                       I010, I010_FULL, LOW_BITS, I010_FORMATS,
                       YUY2, YUY2_FULL, UYVY, UYVY_FULL, PACKED422_FORMATS,
@@ -37,7 +37,7 @@ from .ring import Ring, new_ring_id, ring_lib
 __all__ = ["MMError", "lib", "load_library", "LIB_PATH", "RGBA8", "RGBA32F", "RGBA16F",
            "RGBA8_SRGB", "NV12", "NV12_FULL", "P010", "P010_FULL", "FORMAT_BPP", "frame_bytes",
            "Y8", "Y10", "Y12", "Y16", "MONO_FORMATS", "MONO_BITS",
-           "RGB24", "BGR24", "ORDER_BGR", "RGB24_FORMATS",
+           "RGB24", "BGR24", "ORDER_BGR", "RGB24_FORMATS", "BGRA8", "BGRA8_SRGB", "ORDER_BGRA", "BGRA_FORMATS", "has_bgra",
            "I420", "I420_FULL", "PLANAR", "I420_FORMATS",
            "I010", "I010_FULL", "LOW_BITS", "I010_FORMATS",
            "YUY2", "YUY2_FULL", "UYVY", "UYVY_FULL", "PACKED422_FORMATS",

@@ -38,13 +38,23 @@ Y210_FULL = 23      # full range
 Y210_FORMATS = (Y210, Y210_FULL)
 # packed RGB, what cv2 / PIL / imageio / torchvision / ffmpeg rgb24, bgr24 / PPM
 # hand out: [H, W, 3] bytes, no alpha; every size, mode and debug view.  The
-# byte-order bit is valid on RGB24 alone (BGRA orders are not taken).
+# byte-order bit is valid on RGB24 alone (the B G R A orders are formats of their
+# own with a bit of their own, ORDER_BGRA below).
 RGB24 = 13          # bytes R G B, v = byte / 255 as RGBA8
 ORDER_BGR = 128     # byte-order bit: B G R (OpenCV's order)
 BGR24 = RGB24 | ORDER_BGR
 RGB24_FORMATS = (RGB24, BGR24)
+# B G R A, what D3D / Vulkan swap chains, DXGI desktop duplication, CoreVideo (32BGRA),
+# NDI, DeckLink's 8-bit BGRA mode, Qt, Cairo and OpenCV's four-channel mats hand out:
+# [H, W, 4] bytes, the RGBA8 (RGBA8_SRGB) frame with bytes 0 and 2 of every pixel
+# exchanged; every size, mode and debug view.  The bit is valid on those two codes alone.
+ORDER_BGRA = 8192   # byte-order bit of the 4-byte UNORM formats: B G R A
+BGRA8 = RGBA8 | ORDER_BGRA              # 8192
+BGRA8_SRGB = RGBA8_SRGB | ORDER_BGRA    # 8195
+BGRA_FORMATS = (BGRA8, BGRA8_SRGB)
 FORMAT_BPP = {RGBA8: 4, RGBA32F: 16, RGBA16F: 8, RGBA8_SRGB: 4, Y8: 1, Y10: 2, Y12: 2, Y16: 2,
-              YUY2: 2, YUY2_FULL: 2, UYVY: 2, UYVY_FULL: 2, Y210: 4, Y210_FULL: 4, RGB24: 3, BGR24: 3}
+              YUY2: 2, YUY2_FULL: 2, UYVY: 2, UYVY_FULL: 2, Y210: 4, Y210_FULL: 4, RGB24: 3, BGR24: 3,
+              BGRA8: 4, BGRA8_SRGB: 4}
 # video frames, planar 8-bit Y'CbCr 4:2:0 (H rows of W luma bytes, then H/2 rows
 # of W interleaved Cb, Cr bytes; W and H even): frame_bytes() gives W*H*3/2
 NV12 = 16           # BT.601 limited ("video") range
@@ -221,7 +231,7 @@ def _surface_fn(name):
 
 
 # different formats in and out (include/mm.h "Different formats in and out"):
-# NV12 / P010 codes in with RGBA8 out, RGBA8 in with an NV12 code out
+# NV12 / P010 codes in with RGBA8 or BGRA8 out, RGBA8 or BGRA8 in with an NV12 code out
 CONVERT_SYMBOLS = ("mm_convert_supported", "mm_process_convert", "mm_process_stream_convert")
 
 
@@ -242,6 +252,13 @@ def convert_supported(in_fmt, out_fmt):
     out_fmt, -2 (MM_ERR_UNSUPPORTED) for any other pair of valid codes, -1
     (MM_ERR_INVALID) if either code is unknown.  Needs no GPU."""
     return _convert_fn("mm_convert_supported")(int(in_fmt), int(out_fmt))
+
+
+def has_bgra():
+    """The loaded library takes B G R A frames (detected, as include/mm.h says, by
+    mm_frame_bytes(W, H, MM_BGRA8, &n) == MM_OK).  Needs no GPU."""
+    n = ctypes.c_size_t()
+    return lib().mm_frame_bytes(2, 2, BGRA8, ctypes.byref(n)) == 0
 
 
 # several live streams in one call (include/mm.h "Several live streams in one
@@ -422,7 +439,8 @@ def base_format(fmt):
     """The format without its matrix bit, and BGR24 without its byte-order bit:
     what decides a frame's size and shape.  (The plane-layout bit stays: I420
     and NV12 frames have the same size and not the same shape of planes; so
-    does the low-bits bit of I010.)"""
+    does the low-bits bit of I010.  So does ORDER_BGRA: BGRA8 and BGRA8_SRGB have
+    FORMAT_BPP entries of their own and are named with fmt=, which RGBA8 is not.)"""
     if fmt == BGR24:
         return RGB24
     return fmt & ~(MATRIX_BT709 | MATRIX_BT2020)

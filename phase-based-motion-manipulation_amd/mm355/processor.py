@@ -8,7 +8,7 @@ import numpy as np
 
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       MONO_FORMATS, NV12, NV12_FULL, P010, P010_FULL, PACKED422_FORMATS, RGBA8, RGBA8_SRGB, RGBA16F,
-                      I010_FORMATS, I420_FORMATS, RGB24_FORMATS, RGBA32F, V210, V210_FORMATS, Y8, Y210_FORMATS,
+                      BGRA_FORMATS, I010_FORMATS, I420_FORMATS, RGB24_FORMATS, RGBA32F, V210, V210_FORMATS, Y8, Y210_FORMATS,
                       Handle, MMError, Params, Surface, base_format, convert_supported, tight_pitch)
 
 
@@ -43,6 +43,7 @@ _CONTIGUOUS_3P = "a three-plane 4:2:0 frame must be contiguous (name a Surface t
 _FAMILIES = {
     "rgba": (lambda h, w: (h, w, 4), None, (4, 1), True, "pixels and channels packed"),
     "rgb24": (lambda h, w: (h, w, 3), "uint8", (3, 1), True, "pixels and channels packed"),   # rows at any byte
+    "bgra": (lambda h, w: (h, w, 4), "uint8", (4, 1), True, "pixels and channels packed"),    # RGBA8's rows, bytes B G R A
     "y8": (lambda h, w: (h, w), "uint8", (1,), True, "samples packed"),
     "y16": (lambda h, w: (h, w), "uint16", (1,), True, "samples packed"),
     # [H, 2 W]: rows of W / 2 macropixels, four bytes or (Y210) four words Y0 Cb Y1 Cr
@@ -65,6 +66,8 @@ _FAMILIES = {
 def _family(fmt):
     if fmt in RGB24_FORMATS:
         return "rgb24"
+    if fmt in BGRA_FORMATS:
+        return "bgra"
     if fmt in MONO_FORMATS:
         return "y8" if fmt == Y8 else "y16"
     base = base_format(fmt)         # a matrix bit changes no size or shape
@@ -231,6 +234,10 @@ class MotionMagnificationProcessor:
         on both sides, as cv2 (BGR24), PIL and imageio (RGB24) hand them out:
         device tensors, contiguous or row-strided views that start at any
         byte, or host numpy arrays; such a frame without fmt= raises.
+        fmt=BGRA8 / BGRA8_SRGB: [H, W, 4] uint8 on both sides, bytes B G R A as
+        swap chains, desktop duplication, CoreVideo, NDI and OpenCV's four-channel
+        mats hand them out: device tensors, contiguous or row-strided views, or
+        host numpy arrays, as for RGBA8 (a bare uint8 frame is RGBA8: name BGRA).
         fmt=I420 / I420_FULL, with or without a matrix bit: three-plane 4:2:0,
         one contiguous [H * 3 / 2, W] uint8 array on both sides (the frame's
         bytes in NV12's shape: H luma rows, then the Cb plane, then the Cr plane).
@@ -241,7 +248,8 @@ class MotionMagnificationProcessor:
         where it differs from the source's (mm355.convert_supported): fmt=NV12 /
         P010 codes with dst_fmt=RGBA8, the source one contiguous [H * 3 / 2, W]
         uint8 / uint16 array and the destination [H, W, 4] uint8; or an [H, W, 4]
-        uint8 source (fmt None or RGBA8) with dst_fmt an NV12 code.  Each side's
+        uint8 source (fmt None or RGBA8) with dst_fmt an NV12 code; BGRA8 stands
+        wherever RGBA8 does (dst_fmt=BGRA8, or fmt=BGRA8 with an NV12 dst_fmt).  Each side's
         shape and dtype are checked by that side's format, before any frame
         call into the library."""
         if dst_fmt is not None and dst_fmt != (fmt if fmt is not None else _fmt_of(source, self.srgb)):
@@ -272,9 +280,9 @@ class MotionMagnificationProcessor:
                 raise MMError(-1, "source/destination formats differ")
         elif (fmt not in MONO_FORMATS and base_format(fmt) not in PACKED422_FORMATS and
               base_format(fmt) not in Y210_FORMATS and base_format(fmt) not in V210_FORMATS and
-              fmt not in RGB24_FORMATS and
+              fmt not in RGB24_FORMATS and fmt not in BGRA_FORMATS and
               base_format(fmt) not in I420_FORMATS and base_format(fmt) not in I010_FORMATS):
-            raise MMError(-1, f"fmt={fmt}: only the grayscale, packed 4:2:2, packed RGB and three-plane 4:2:0 formats are named, "
+            raise MMError(-1, f"fmt={fmt}: only the grayscale, packed 4:2:2, packed RGB, BGRA and three-plane 4:2:0 formats are named, "
                               "the others follow the dtype")
         on_dev = _is_device(source)
         if on_dev != _is_device(destination):

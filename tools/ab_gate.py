@@ -6,7 +6,8 @@ new 1, parent 2, new 2; `--order new`: the new library first), every step a
 process of its own with MM355_LIB naming the parent's library or unset:
 
   bench.py --gpus 1 --steps 3 --warmup 2 --no-cpu-baseline      frames/s
-  tools/fmt_bench.py (tight legs, no convert legs)              median frames/s of RGBA8, NV12, P010
+  tools/fmt_bench.py (tight legs, no convert or BGRA legs: the  median frames/s of RGBA8, NV12, P010
+                      same legs in every round for both)
   tools/lanes_bench.py --lanes 8,16,64 --no-formats             leg c (mm_process_lanes): the mean of a run's
                                                                 passes, and K2's device time per lane-frame
 
@@ -42,7 +43,7 @@ def one_run(lib, tmp):
     txt = step(["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"], lib, 150)
     out["bench_py"] = next(json.loads(l)["value"] for l in reversed(txt.splitlines()) if l.lstrip().startswith("{"))
     f = os.path.join(tmp, "fmt.json")
-    step(["tools/fmt_bench.py", "--rounds", "3", "--leg-seconds", "0.3", "--no-pitched", "--no-convert", "--out", f], lib, 240)
+    step(["tools/fmt_bench.py", "--rounds", "3", "--leg-seconds", "0.3", "--no-pitched", "--no-convert", "--no-bgra", "--out", f], lib, 240)
     fm = json.load(open(f))["formats"]
     for name in ("rgba8", "nv12", "p010"):
         out["fmt_bench_" + name] = fm[name]["fps_median"]

@@ -84,7 +84,22 @@ the mixed leg: two passes against one.  A library from before the conversion
 runs without them; --no-convert gives this library that leg set (an A/B of the
 existing legs alone, with the same number of legs in every round).
 
-usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--no-convert] [--out FILE.json]
+B G R A legs (bgra8, bgra8_pitched, bgra8_srgb, nv12>bgra8, bgra8>nv12 and their
+_plain / _pitched forms): the RGBA8 leg's pictures with bytes 0 and 2 of every
+pixel exchanged as MM_BGRA8, the same bytes taken as MM_BGRA8_SRGB, and the
+convert pairs with MM_BGRA8 as the 4-byte side.  Each runs instances that differ
+from its RGBA twin's in byte indices and constants alone, so the yardstick of
+each is its twin of the same run: rgba8, rgba8_pitched, rgba8_srgb (the RGBA8
+leg's bytes taken as MM_RGBA8_SRGB), nv12>rgba8, rgba8>nv12; "bgra_twins" sets
+them side by side with K1's and the compose's times.  A library from before these
+formats runs without them; --no-bgra gives this library that leg set (an A/B of
+the existing legs alone: the sRGB legs spend 50 us per frame in their encode, and
+a round that holds them is not the round the parent's library runs).
+
+--only a,b,c: time these legs alone (every leg is still built, since legs take
+their frames from one another; the others are closed before the warm-up).
+
+usage: fmt_bench.py [--rounds 5] [--leg-seconds 0.6] [--no-pitched] [--no-convert] [--no-bgra] [--only LEGS] [--out FILE.json]
 """
 import argparse
 import json
@@ -233,6 +248,9 @@ def main():
     ap.add_argument("--no-pitched", action="store_true")
     ap.add_argument("--no-convert", action="store_true",
                     help="leave the convert legs out (the leg set of a library from before the conversion)")
+    ap.add_argument("--no-bgra", action="store_true",
+                    help="leave the B G R A legs and rgba8_srgb out (the leg set of a library from before them)")
+    ap.add_argument("--only", default=None, help="comma-separated leg names: time these alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -284,6 +302,14 @@ def main():
         fmts += [("v210", mm355.V210), ("v210_bt709", mm355.V210 | mm355.MATRIX_BT709)]
     except (mm355.MMError, AttributeError):
         pass    # a build from before the v210 format
+    bgra = False
+    if not a.no_bgra:
+        try:
+            mm355.frame_bytes(W, H, mm355.BGRA8)
+            fmts += [("rgba8_srgb", mm355.RGBA8_SRGB), ("bgra8", mm355.BGRA8), ("bgra8_srgb", mm355.BGRA8_SRGB)]
+            bgra = True
+        except (mm355.MMError, AttributeError):
+            pass    # a build from before the B G R A formats
     for name, fmt in fmts:
         h = mm355.Handle(W, H, p)
         h.set_batch(B)
@@ -298,6 +324,12 @@ def main():
         elif name == "i010":       # the P010 leg's codes in the words' low bits, de-interleaved
             words = ((legs["p010"]["src"].to(torch.int32) & 0xFFFF) >> 6).to(torch.int16)
             src = nv12_to_i420(torch, words)
+        elif name == "rgba8_srgb":  # the RGBA8 leg's bytes, taken as sRGB-encoded
+            src = rgba
+        elif name == "bgra8":      # the RGBA8 leg's pictures, bytes 0 and 2 of every pixel exchanged
+            src = rgba[..., [2, 1, 0, 3]].contiguous()
+        elif name == "bgra8_srgb":
+            src = legs["bgra8"]["src"]
         elif name == "rgb24":      # the RGBA8 leg's pictures without their alpha
             src = rgba[..., :3].contiguous()
         elif name == "bgr24":
@@ -316,7 +348,7 @@ def main():
             src = to_420(torch, rgba, ten_bit=name == "p010")
         legs[name] = dict(h=h, fmt=fmt, src=src, dst=torch.empty_like(src), fps=[], lay=None,
                           bytes_per_frame=mm355.frame_bytes(W, H, fmt))
-        if not a.no_pitched and mm355.has_surfaces() and name not in ("bgr24", "i420_bt709", "p010_bt709", "i010_bt709"):   # (one pitched packed RGB leg, one of each three-plane form)
+        if not a.no_pitched and mm355.has_surfaces() and name not in ("bgr24", "i420_bt709", "p010_bt709", "i010_bt709", "rgba8_srgb", "bgra8_srgb"):   # (one pitched packed RGB leg, one of each three-plane form)
             lay = mm355.Surface.aligned(W, H, fmt, 256, 16)
             h = mm355.Handle(W, H, p)
             h.set_batch(B)
@@ -331,10 +363,13 @@ def main():
                  ("p010>rgba8", "p010", mm355.P010, mm355.RGBA8),
                  ("rgba8>nv12", "rgba8", mm355.RGBA8, mm355.NV12),
                  ("rgba8>nv12_bt709", "rgba8", mm355.RGBA8, mm355.NV12 | mm355.MATRIX_BT709)]
+        if bgra:
+            convs += [("nv12>bgra8", "nv12", mm355.NV12, mm355.BGRA8), ("bgra8>nv12", "bgra8", mm355.BGRA8, mm355.NV12)]
+    px4 = (mm355.RGBA8, getattr(mm355, "BGRA8", mm355.RGBA8))   # the 4-byte side of a pair
     p_off = mm355.Params.make(levels=5, phase_scale=25.0, apply_magnification=False)
 
     def out_of(fo):
-        return torch.empty((B, H, W, 4) if fo == mm355.RGBA8 else (B, H * 3 // 2, W), dtype=torch.uint8, device="cuda")
+        return torch.empty((B, H, W, 4) if fo in px4 else (B, H * 3 // 2, W), dtype=torch.uint8, device="cuda")
 
     for name, base, fi, fo in convs:
         src = legs[base]["src"]
@@ -348,8 +383,8 @@ def main():
             h.set_batch(B)
             li, lo = mm355.Surface.tight(W, H, fi), mm355.Surface.tight(W, H, fo)
             s_in, s_out = src, out_of(fo)
-            if pitched:   # the Y'CbCr side as a decoder lays it out, the RGBA8 side tight
-                if fi != mm355.RGBA8:
+            if pitched:   # the Y'CbCr side as a decoder lays it out, the RGBA8 / BGRA8 side tight
+                if fi not in px4:
                     li = mm355.Surface.aligned(W, H, fi, 256, 16)
                     s_in = to_surface(torch, src, li, W, H, True)
                 else:
@@ -357,6 +392,14 @@ def main():
                     s_out = torch.zeros(B * lo.frame_stride, dtype=torch.uint8, device="cuda")
             legs[leg_name] = dict(h=h, fmt=fi, ofmt=fo, src=s_in, dst=s_out, fps=[], lay=li, olay=lo, convert=True,
                                   bytes_per_frame=mm355.frame_bytes(W, H, fi) + mm355.frame_bytes(W, H, fo))
+    if a.only:
+        keep = set(a.only.split(","))
+        missing = keep - set(legs)
+        if missing:
+            sys.exit(f"--only: no leg named {sorted(missing)} (legs: {sorted(legs)})")
+        for name in [n for n in legs if n not in keep]:
+            legs.pop(name)["h"].close()
+        torch.cuda.empty_cache()
     st = torch.cuda.Stream()
 
     def call(L):
@@ -406,94 +449,110 @@ def main():
             "kernel_us_per_frame": {k: round(1e3 * ms / fr, 3) for k, (ms, n, fr) in prof.items() if n},
         }
         L["h"].close()
-    r = out["formats"]["rgba8"]
-    for name in ("nv12", "p010"):
-        out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
-    for name, base in (("nv12_bt709", "nv12"), ("p010_bt2020", "p010")):
-        if name in out["formats"]:
-            out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
-                                                out["formats"][base]["fps_median"], 4)
+    if bgra:   # each B G R A leg beside its RGBA twin of the same run
+        ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
+        out["bgra_twins"] = {}
+        for name, twin in (("bgra8", "rgba8"), ("bgra8_pitched", "rgba8_pitched"), ("bgra8_srgb", "rgba8_srgb"),
+                           ("nv12>bgra8", "nv12>rgba8"), ("bgra8>nv12", "rgba8>nv12"),
+                           ("nv12>bgra8_plain", "nv12>rgba8_plain"), ("bgra8>nv12_plain", "rgba8>nv12_plain"),
+                           ("nv12>bgra8_pitched", "nv12>rgba8_pitched"), ("bgra8>nv12_pitched", "rgba8>nv12_pitched")):
+            if name in out["formats"] and twin in out["formats"]:
+                x, y = out["formats"][name], out["formats"][twin]
+                out["bgra_twins"][name] = {
+                    "twin": twin, "fps_median": x["fps_median"], "twin_fps_median": y["fps_median"],
+                    "over_twin": round(x["fps_median"] / y["fps_median"], 4),
+                    "twin_fps_min": y["fps_min"], "twin_fps_max": y["fps_max"],
+                    "inside_twin_range": y["fps_min"] <= x["fps_median"] <= y["fps_max"],
+                    "kernel_us": {n: {k: ku(n, k) for k in ("k_rows_fwd", "k_rows_inv_compose")} for n in (name, twin)}}
+    if not a.only:   # (these set whole families of legs against one another)
+        r = out["formats"]["rgba8"]
+        for name in ("nv12", "p010"):
+            out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
+        for name, base in (("nv12_bt709", "nv12"), ("p010_bt2020", "p010")):
+            if name in out["formats"]:
+                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                    out["formats"][base]["fps_median"], 4)
+                k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
+                out[name + "_k1_us"] = {"matrixed": k1(name), base: k1(base), "rgba8": k1("rgba8")}
+        for name in ("y8", "y16"):
+            if name in out["formats"]:
+                out[name + "_over_nv12"] = round(out["formats"][name]["fps_median"] /
+                                                 out["formats"]["nv12"]["fps_median"], 4)
+                out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
+        for name in ("yuy2", "uyvy", "yuy2_bt709"):
+            if name in out["formats"]:
+                out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
+                out[name + "_over_nv12"] = round(out["formats"][name]["fps_median"] /
+                                                 out["formats"]["nv12"]["fps_median"], 4)
+        if "yuy2_bt709" in out["formats"]:
             k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
-            out[name + "_k1_us"] = {"matrixed": k1(name), base: k1(base), "rgba8": k1("rgba8")}
-    for name in ("y8", "y16"):
-        if name in out["formats"]:
-            out[name + "_over_nv12"] = round(out["formats"][name]["fps_median"] /
-                                             out["formats"]["nv12"]["fps_median"], 4)
-            out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
-    for name in ("yuy2", "uyvy", "yuy2_bt709"):
-        if name in out["formats"]:
-            out[name + "_over_rgba8"] = round(out["formats"][name]["fps_median"] / r["fps_median"], 4)
-            out[name + "_over_nv12"] = round(out["formats"][name]["fps_median"] /
-                                             out["formats"]["nv12"]["fps_median"], 4)
-    if "yuy2_bt709" in out["formats"]:
-        k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
-        out["yuy2_bt709_k1_us"] = {"matrixed": k1("yuy2_bt709"), "yuy2": k1("yuy2"), "nv12_bt709": k1("nv12_bt709"),
-                                   "rgba8": k1("rgba8")}
-    for name in ("y210", "y210_bt709"):
-        if name in out["formats"]:
-            for base in ("rgba8", "p010", "yuy2"):
-                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
-                                                    out["formats"][base]["fps_median"], 4)
-    if "y210_bt709" in out["formats"]:
-        k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
-        out["y210_bt709_k1_us"] = {"matrixed": k1("y210_bt709"), "y210": k1("y210"), "yuy2_bt709": k1("yuy2_bt709"),
-                                   "p010": k1("p010"), "rgba8": k1("rgba8")}
-    if "v210" in out["formats"]:
-        for name in ("v210", "v210_bt709"):
-            for base in ("rgba8", "y210", "yuy2"):
-                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
-                                                    out["formats"][base]["fps_median"], 4)
-        # K1, and K3 + K4 (v210: the unfused pair; the others: the fused K34)
-        kk = lambda n: out["formats"][n]["kernel_us_per_frame"]
-        out["v210_kernel_us"] = {n: {"k_rows_fwd": kk(n).get("k_rows_fwd"),
-                                     "k3_k4": round(sum(kk(n).get(k, 0.0) for k in
-                                                        ("k_rows_inv", "k_compose", "k_rows_inv_compose")), 3)}
-                                 for n in ("v210", "v210_bt709", "y210", "y210_bt709", "yuy2", "rgba8")}
-    for name in ("rgb24", "bgr24"):
-        if name in out["formats"]:
-            for base in ("rgba8", "nv12"):
-                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
-                                                    out["formats"][base]["fps_median"], 4)
-    if "rgb24" in out["formats"]:
-        ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
-        out["rgb24_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
-                                  for n in ("rgb24", "bgr24", "rgba8", "nv12")}
-    if "i420" in out["formats"]:
-        ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
-        for name, base in (("i420", "nv12"), ("i420_bt709", "nv12_bt709"), ("i420_pitched", "nv12_pitched")):
-            if name in out["formats"] and base in out["formats"]:
-                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
-                                                    out["formats"][base]["fps_median"], 4)
-        out["i420_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
-                                 for n in ("i420", "nv12", "i420_bt709", "nv12_bt709", "i420_pitched", "nv12_pitched")
-                                 if n in out["formats"]}
-    if "i010" in out["formats"]:
-        ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
-        for name, base in (("i010", "p010"), ("i010", "i420"), ("i010_bt709", "p010_bt709"),
-                           ("i010_pitched", "p010_pitched")):
-            if name in out["formats"] and base in out["formats"]:
-                out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
-                                                    out["formats"][base]["fps_median"], 4)
-        out["i010_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
-                                 for n in ("i010", "p010", "i420", "i010_bt709", "p010_bt709", "i010_pitched",
-                                           "p010_pitched") if n in out["formats"]}
-    for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16", "yuy2", "uyvy", "yuy2_bt709",
-                 "y210", "y210_bt709", "rgb24", "i420", "i010", "v210", "v210_bt709"):
-        if name + "_pitched" in out["formats"]:
-            out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
-                                                      out["formats"][name]["fps_median"], 4)
-    # two passes against one: the same-format stream plus a conversion pass of its own, against the mixed leg
-    us = lambda n: 1e6 / out["formats"][n]["fps_median"]
-    for name, same in (("nv12>rgba8", "nv12"), ("p010>rgba8", "p010"), ("rgba8>nv12", "rgba8")):
-        if name in out["formats"] and name + "_plain" in out["formats"]:
-            conv_us = us(name + "_plain")
-            out[name + "_two_pass"] = {
-                "same_format_us_per_frame": round(us(same), 3), "convert_pass_us_per_frame": round(conv_us, 3),
-                "two_pass_us_per_frame": round(us(same) + conv_us, 3), "mixed_us_per_frame": round(us(name), 3),
-                "mixed_over_two_pass": round(us(name) / (us(same) + conv_us), 4),
-                "convert_pass_GBps": round(out["formats"][name]["bytes_per_frame"] / conv_us * 1e-3, 1),
-            }
-            out[name + "_kernel_us"] = {n: out["formats"][n]["kernel_us_per_frame"] for n in (name, "rgba8", "nv12")}
+            out["yuy2_bt709_k1_us"] = {"matrixed": k1("yuy2_bt709"), "yuy2": k1("yuy2"), "nv12_bt709": k1("nv12_bt709"),
+                                       "rgba8": k1("rgba8")}
+        for name in ("y210", "y210_bt709"):
+            if name in out["formats"]:
+                for base in ("rgba8", "p010", "yuy2"):
+                    out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                        out["formats"][base]["fps_median"], 4)
+        if "y210_bt709" in out["formats"]:
+            k1 = lambda n: out["formats"][n]["kernel_us_per_frame"]["k_rows_fwd"]
+            out["y210_bt709_k1_us"] = {"matrixed": k1("y210_bt709"), "y210": k1("y210"), "yuy2_bt709": k1("yuy2_bt709"),
+                                       "p010": k1("p010"), "rgba8": k1("rgba8")}
+        if "v210" in out["formats"]:
+            for name in ("v210", "v210_bt709"):
+                for base in ("rgba8", "y210", "yuy2"):
+                    out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                        out["formats"][base]["fps_median"], 4)
+            # K1, and K3 + K4 (v210: the unfused pair; the others: the fused K34)
+            kk = lambda n: out["formats"][n]["kernel_us_per_frame"]
+            out["v210_kernel_us"] = {n: {"k_rows_fwd": kk(n).get("k_rows_fwd"),
+                                         "k3_k4": round(sum(kk(n).get(k, 0.0) for k in
+                                                            ("k_rows_inv", "k_compose", "k_rows_inv_compose")), 3)}
+                                     for n in ("v210", "v210_bt709", "y210", "y210_bt709", "yuy2", "rgba8")}
+        for name in ("rgb24", "bgr24"):
+            if name in out["formats"]:
+                for base in ("rgba8", "nv12"):
+                    out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                        out["formats"][base]["fps_median"], 4)
+        if "rgb24" in out["formats"]:
+            ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
+            out["rgb24_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
+                                      for n in ("rgb24", "bgr24", "rgba8", "nv12")}
+        if "i420" in out["formats"]:
+            ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
+            for name, base in (("i420", "nv12"), ("i420_bt709", "nv12_bt709"), ("i420_pitched", "nv12_pitched")):
+                if name in out["formats"] and base in out["formats"]:
+                    out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                        out["formats"][base]["fps_median"], 4)
+            out["i420_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
+                                     for n in ("i420", "nv12", "i420_bt709", "nv12_bt709", "i420_pitched", "nv12_pitched")
+                                     if n in out["formats"]}
+        if "i010" in out["formats"]:
+            ku = lambda n, k: out["formats"][n]["kernel_us_per_frame"].get(k)
+            for name, base in (("i010", "p010"), ("i010", "i420"), ("i010_bt709", "p010_bt709"),
+                               ("i010_pitched", "p010_pitched")):
+                if name in out["formats"] and base in out["formats"]:
+                    out[name + "_over_" + base] = round(out["formats"][name]["fps_median"] /
+                                                        out["formats"][base]["fps_median"], 4)
+            out["i010_kernel_us"] = {n: {"k_rows_fwd": ku(n, "k_rows_fwd"), "k_rows_inv_compose": ku(n, "k_rows_inv_compose")}
+                                     for n in ("i010", "p010", "i420", "i010_bt709", "p010_bt709", "i010_pitched",
+                                               "p010_pitched") if n in out["formats"]}
+        for name in ("rgba8", "nv12", "p010", "nv12_bt709", "p010_bt2020", "y8", "y16", "yuy2", "uyvy", "yuy2_bt709",
+                     "y210", "y210_bt709", "rgb24", "i420", "i010", "v210", "v210_bt709"):
+            if name + "_pitched" in out["formats"]:
+                out[name + "_pitched_over_tight"] = round(out["formats"][name + "_pitched"]["fps_median"] /
+                                                          out["formats"][name]["fps_median"], 4)
+        # two passes against one: the same-format stream plus a conversion pass of its own, against the mixed leg
+        us = lambda n: 1e6 / out["formats"][n]["fps_median"]
+        for name, same in (("nv12>rgba8", "nv12"), ("p010>rgba8", "p010"), ("rgba8>nv12", "rgba8")):
+            if name in out["formats"] and name + "_plain" in out["formats"]:
+                conv_us = us(name + "_plain")
+                out[name + "_two_pass"] = {
+                    "same_format_us_per_frame": round(us(same), 3), "convert_pass_us_per_frame": round(conv_us, 3),
+                    "two_pass_us_per_frame": round(us(same) + conv_us, 3), "mixed_us_per_frame": round(us(name), 3),
+                    "mixed_over_two_pass": round(us(name) / (us(same) + conv_us), 4),
+                    "convert_pass_GBps": round(out["formats"][name]["bytes_per_frame"] / conv_us * 1e-3, 1),
+                }
+                out[name + "_kernel_us"] = {n: out["formats"][n]["kernel_us_per_frame"] for n in (name, "rgba8", "nv12")}
     txt = json.dumps(out, indent=1)
     print(txt)
     if a.out:
