@@ -1042,6 +1042,64 @@ int mm_reset_lane(mm_handle *h, int lane);            /* -1: every lane */
 int mm_get_lane_state(mm_handle *h, int lane, void *dev_buf, size_t bytes, void *hip_stream);
 int mm_set_lane_state(mm_handle *h, int lane, const void *dev_buf, size_t bytes, void *hip_stream);
 
+/* ---- Held reference frame --------------------------------------------------
+ * (a backward-compatible addition to ABI 10; detect it by the presence of
+ * mm_set_hold)
+ * By default the state is G_{t-1}: it follows the input on every call, and the
+ * operator magnifies the phase change between two consecutive frames (the
+ * reference's behaviour).  Measuring displacement against a rest frame (a
+ * structure against its unloaded picture, a pipe against the frame before the
+ * pump started) wants every frame paired with ONE reference frame R instead.
+ * mm_set_hold(h, 1) does that, from the next call on:
+ * While hold is set, frames do not advance the handle's single-stream state:
+ * every frame of every call pairs with the state R the handle had when the
+ * call began.  The contract is bitwise: the output of frame x is the output a
+ * handle of its own with the same parameters gives for mm_set_state(R)
+ * followed by one one-frame call on x, with the same formats and layouts;
+ * mm_get_state after the call returns R bit for bit.  It holds in pyramid and
+ * standard mode, both edge modes, every size, format, layout and convert pair,
+ * for the one-frame, stream, host-memory and lane calls, and for every batch
+ * size and batch boundary.  Inside a batch the column kernel transforms R once
+ * per workgroup and launch, not once per frame (1080p: a held stream runs at
+ * the rolling stream's rate, 2.9 times the mm_set_state-per-frame pattern's).
+ * Without state (after mm_create, mm_reset, mm_reset_lane) the first frame
+ * passes through, as always, and becomes R; the remaining frames of the same
+ * call already pair with it.  mm_reset plus hold therefore means "the next
+ * frame is the reference".
+ * apply_magnification = 0: every frame passes through.  With state nothing
+ * else happens (no kernel but the copy runs; in a lane call, none for the held
+ * lanes that have state); without state the first frame of the call becomes R.
+ * Switching hold off: the next call behaves as always, its first frame pairs
+ * with R and the state follows the input again.  Re-referencing every k frames
+ * is therefore "one frame with hold off": no passthrough frame, no further
+ * entry point.  mm_set_state, or mm_compute_state plus mm_set_state, installs
+ * any frame as the reference.
+ * Other calls: mm_set_params applies as always, and its edge_mode note reads
+ * "the held R keeps the tables it was built with until the caller
+ * re-references".  mm_set_batch keeps R bit for bit.  mm_compute_state* is
+ * unaffected.
+ * Lanes hold one by one: bit k of mm_set_lanes_hold's mask makes lane k hold.
+ * mm_set_lanes to another count clears the mask, the same count keeps it.  A
+ * held lane's forward row kernel writes the slot of the bank that does not
+ * hold its state, the column kernel reads both, and the lane's bank bit is not
+ * flipped: no state is copied and no memory is added.  A held lane without
+ * state passes through, gets state and its bank bit as always.  Held and
+ * rolling lanes side by side end up with different bank bits every second
+ * call, which splits forward runs: it costs launches, never results.  As with
+ * rate groups, a caller orders its lanes by hold group.
+ * Refusals, all before anything is queued; state and flags stay as they were.
+ * With hold set, MM_MODE_STEERABLE and show_magnitude / show_phase give
+ * MM_ERR_UNSUPPORTED from every frame entry point (the flag itself may be set
+ * in any mode).  MM_ERR_INVALID: null pointers, a hold value other than 0 or
+ * 1, a mask bit at or above the lane count.
+ * Out of scope: a lag of k frames (k interleaved streams: lanes); a temporal
+ * band-pass in pyramid mode; hold in steerable mode and the debug views; the
+ * ring entry points. */
+int mm_set_hold(mm_handle *h, int hold);              /* 0 | 1, else MM_ERR_INVALID; applies from the next call */
+int mm_get_hold(const mm_handle *h, int *hold);
+int mm_set_lanes_hold(mm_handle *h, uint64_t mask);   /* bit k: lane k holds; a bit at or above the lane count: MM_ERR_INVALID */
+int mm_get_lanes_hold(const mm_handle *h, uint64_t *mask);
+
 /* Zero-copy frames (f4): device memory owned by another API — an engine's
  * render target exported as an opaque POSIX fd (Vulkan VK_KHR_external_memory_fd,
  * or a HIP VMM allocation via hipMemExportToShareableHandle) — imported into the

@@ -227,6 +227,8 @@ static int upload_tables(mm_handle *h)
     return MM_OK;
 }
 
+static uint64_t lanes_all(const mm_handle *h) { return h->lanes >= 64 ? ~0ull : (1ull << h->lanes) - 1; }
+
 int mm_create(int width, int height, const mm_params *p, int hip_device, mm_handle **out)
 {
     if (!out) return MM_ERR_INVALID;
@@ -475,8 +477,12 @@ int mm_surface_bytes(int width, int height, const mm_surface *s, size_t *extent)
 // (mm_process_surface / mm_process_stream_surfaces: anything else is invalid),
 // or, `convert`, a pair convert_supported takes, each side within its own
 // format's restrictions (the union: even sizes, no debug view).
+// A held reference (mm_set_hold) exists in pyramid and standard mode only:
+// refused here, before anything is queued, from every frame entry point.
 static int formats_check(const mm_handle *h, const mm_surface *in_layout, const mm_surface *out_layout, bool convert)
 {
+    if (h->hold && (h->p.mode == MM_MODE_STEERABLE || h->p.show_magnitude || h->p.show_phase))
+        return MM_ERR_UNSUPPORTED;
     if (!convert || in_layout->format == out_layout->format) {
         if (int rc = fmt_check(h->W, h->H, in_layout->format, &h->p)) return rc;
         return in_layout->format != out_layout->format ? MM_ERR_INVALID : MM_OK;
@@ -633,6 +639,35 @@ int mm_reset(mm_handle *h)
     return MM_OK;
 }
 
+// ---- held reference frame (include/mm.h) -----------------------------------
+int mm_set_hold(mm_handle *h, int hold)
+{
+    if (!h || (hold != 0 && hold != 1)) return MM_ERR_INVALID;
+    h->hold = hold != 0;
+    return MM_OK;
+}
+
+int mm_get_hold(const mm_handle *h, int *hold)
+{
+    if (!h || !hold) return MM_ERR_INVALID;
+    *hold = h->hold ? 1 : 0;
+    return MM_OK;
+}
+
+int mm_set_lanes_hold(mm_handle *h, uint64_t mask)
+{
+    if (!h || (mask & ~lanes_all(h))) return MM_ERR_INVALID;
+    h->lane_hold = mask;
+    return MM_OK;
+}
+
+int mm_get_lanes_hold(const mm_handle *h, uint64_t *mask)
+{
+    if (!h || !mask) return MM_ERR_INVALID;
+    *mask = h->lane_hold;
+    return MM_OK;
+}
+
 int mm_state_size(const mm_handle *h, size_t *bytes)
 {
     if (!h || !bytes) return MM_ERR_INVALID;
@@ -750,6 +785,7 @@ int mm_set_lanes(mm_handle *h, int lanes)
     h->lanes = lanes;
     h->lane_bank = 0;
     h->lane_state = 0;
+    h->lane_hold = 0;
     return MM_OK;
 }
 
@@ -767,8 +803,6 @@ static int lanes_mode_check(const mm_handle *h)
     if (h->p.mode == MM_MODE_STEERABLE || h->p.show_magnitude || h->p.show_phase) return MM_ERR_UNSUPPORTED;
     return MM_OK;
 }
-
-static uint64_t lanes_all(const mm_handle *h) { return h->lanes >= 64 ? ~0ull : (1ull << h->lanes) - 1; }
 
 int mm_process_lanes_mask(mm_handle *h, uint64_t mask, const void *in, const mm_surface *in_layout, void *out,
                           const mm_surface *out_layout, void *hip_stream)

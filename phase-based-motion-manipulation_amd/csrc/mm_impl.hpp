@@ -86,6 +86,7 @@ struct mm_handle {
     uint8_t *d_stage_in, *d_stage_out;
     size_t stage_bytes;
     bool has_state;
+    bool hold;                  // frames pair with the state and do not advance it (mm_set_hold)
     bool g_valid;               // the G slot gs holds G_{t-1} (K1 or a non-steerable mm_set_state
                                 // wrote it; a steerable mm_set_state sets only the local phases)
     int k2_tail_pct;            // share of a batch's frames of k_cols's packed block run by k_cols_tail
@@ -108,6 +109,7 @@ struct mm_handle {
     c2 *d_LG, *d_LQ;
     uint64_t lane_bank;
     uint64_t lane_state;
+    uint64_t lane_hold;         // bit k: lane k holds its reference (mm_set_lanes_hold)
     uint8_t *d_Lsrc;
     size_t lsrc_bytes;
     // mm_profile_begin/end: HIP events around each launch on its stream
@@ -819,7 +821,9 @@ static int set_attrs(int W)
         (void)x;
 #define MM_SET_K2(MODE)                                                                                  \
         HIPCHK(set(reinterpret_cast<const void *>(&k_cols<13, MODE>), k2_lds_bytes<13, MODE>()));        \
-        HIPCHK(set(reinterpret_cast<const void *>(&k_cols_tail<13, MODE>), k2_lds_bytes<13, MODE>()))
+        HIPCHK(set(reinterpret_cast<const void *>(&k_cols_tail<13, MODE>), k2_lds_bytes<13, MODE>()));   \
+        HIPCHK(set(reinterpret_cast<const void *>(&k_cols_hold<13, MODE>), k2_lds_bytes<13, MODE>()));   \
+        HIPCHK(set(reinterpret_cast<const void *>(&k_cols_tail_hold<13, MODE>), k2_lds_bytes<13, MODE>()))
         MM_SET_K2(MM_MODE_PYRAMID);
         MM_SET_K2(MM_MODE_STANDARD);
         MM_SET_K2(MM_K2_PYR_TAB);
@@ -905,9 +909,12 @@ static int refresh_k2_tables(mm_handle *h, hipStream_t s)
 // K2 over frames G[0 .. nframes) (K1's row spectra), primed with Gprev = G_{t-1}
 // (the state slot, or frame 0 itself for a stream's first batch, whose frame 0
 // passes through): Q of frame fr to d_Q + fr * q_stride.
+// hold: every frame pairs with Gprev (k_cols_hold, k_cols_tail_hold; the same
+// tail split).  One frame rolls nothing: it keeps the rolling instance.
 template <int LOG2N>
-static int launch_k2(mm_handle *h, int nframes, const c2 *Gprev, const c2 *G, hipStream_t s)
+static int launch_k2(mm_handle *h, int nframes, const c2 *Gprev, const c2 *G, hipStream_t s, bool hold = false)
 {
+    hold = hold && nframes >= 2;
     const int gpw = k2_groups<LOG2N>();
     const int cols = (1 << LOG2N) / 2;   // f = 0 and f = N/2 share group 0 (k_cols)
     const int blocks = (cols + gpw - 1) / gpw;
@@ -920,23 +927,29 @@ static int launch_k2(mm_handle *h, int nframes, const c2 *Gprev, const c2 *G, hi
     // columns in extra blocks (MM_K2_TAIL2 percent)
     const int k2t = nframes >= 24 && blocks >= 2 ? std::min(nframes * h->k2_tail2_pct / 100, nframes - 2) : 0;
     const int tb = k2t > 0 ? blocks / 2 : 0;
-#define MM_K2_LAUNCH(MODE)                                                                           \
+#define MM_K2_LAUNCH_(MODE, COLS, TAIL)                                                              \
     do {                                                                                             \
         /* exchange buffers + per-bin tables + the packed group's */                                 \
         const size_t lds = k2_lds_bytes<LOG2N, MODE>();                                              \
-        hipLaunchKernelGGL((k_cols<LOG2N, MODE>), dim3(blocks + tb), dim3(k2_threads<LOG2N>()), lds, s, G, \
+        hipLaunchKernelGGL((COLS<LOG2N, MODE>), dim3(blocks + tb), dim3(k2_threads<LOG2N>()), lds, s, G, \
                            h->g_stride, Gprev, h->d_Q, h->q_stride, nframes, h->geo, h->spec, h->d_tw, h->d_ktab, \
                            h->d_kmsum, nframes - k, tb, k2t);                                        \
         if (k)                                                                                       \
-            hipLaunchKernelGGL((k_cols_tail<LOG2N, MODE>), dim3(k), dim3(k2_threads<LOG2N>()), lds, s, G, \
+            hipLaunchKernelGGL((TAIL<LOG2N, MODE>), dim3(k), dim3(k2_threads<LOG2N>()), lds, s, G,   \
                                h->g_stride, Gprev, h->d_Q, h->q_stride, nframes - k, h->geo, h->spec, h->d_tw, \
                                h->d_ktab, h->d_kmsum);                                               \
+    } while (0)
+#define MM_K2_LAUNCH(MODE)                                                                           \
+    do {                                                                                             \
+        if (hold) MM_K2_LAUNCH_(MODE, k_cols_hold, k_cols_tail_hold);                                \
+        else MM_K2_LAUNCH_(MODE, k_cols, k_cols_tail);                                               \
     } while (0)
     if (h->spec.mode == MM_MODE_STANDARD) MM_K2_LAUNCH(MM_MODE_STANDARD);
     else if (h->k2_tab2) MM_K2_LAUNCH(MM_K2_PYR_TAB2);
     else if (h->k2_tab) MM_K2_LAUNCH(MM_K2_PYR_TAB);
     else MM_K2_LAUNCH(MM_MODE_PYRAMID);
 #undef MM_K2_LAUNCH
+#undef MM_K2_LAUNCH_
     HIPCHK(hipGetLastError());
     return MM_OK;
 }
@@ -1510,8 +1523,13 @@ static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const
     const bool steer = !dbg && h->p.mode == MM_MODE_STEERABLE;
     const bool have = h->has_state && (steer || h->g_valid);
     const int first = have ? 0 : 1;
+    // Held reference (mm_set_hold; pyramid and standard mode only: the entry
+    // points refuse the rest): the batch pairs with the state slot and leaves
+    // it where it is; without state, frame 0 becomes the reference.
+    const bool hold = h->hold;
     int rc, base;
     if (first && (rc = copy_frames(h, in, out, 1, fr, s))) return rc;
+    if (hold && !mag && have) return copy_frames(h, in, out, n, fr, s);   // nothing else happens: no K1
     if ((rc = place_batch(h, n, s, &base))) return rc;
     c2 *G = h->d_G + h->g_stride * base;
     // G_{t-1}: the state slot; a stream's first frame primes with itself (its
@@ -1525,7 +1543,8 @@ static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const
         if (n > from &&
             (rc = copy_frames(h, in + fr.in.stride * from, out + fr.out.stride * from, n - from, fr, s)))
             return rc;
-        if ((rc = launch_k1<LOG2N>(h, in + fr.in.stride * (n - 1), 1, fr, s, G))) return rc;
+        // (hold, no state yet: the call's first frame is the reference)
+        if ((rc = launch_k1<LOG2N>(h, in + fr.in.stride * (hold ? 0 : n - 1), 1, fr, s, G))) return rc;
         h->gs = base;
         h->has_state = h->g_valid = true;
         return MM_OK;
@@ -1540,11 +1559,12 @@ static int run_chunk(mm_handle *h, const uint8_t *in, uint8_t *out, int n, const
         if constexpr (LOG2N <= 12) rc = run_steer<LOG2N>(h, in, out, n, fr, nullptr, mag, s, G);
         else rc = MM_ERR_UNSUPPORTED;
     } else {
-        if ((rc = launch_k2<LOG2N>(h, n, Gprev, G, s))) return rc;
+        if ((rc = launch_k2<LOG2N>(h, n, Gprev, G, s, hold))) return rc;
         rc = launch_k3<LOG2N>(h, h->d_Q, in, out, first, n, fr, s);
     }
     if (rc) return rc;
-    h->gs = base + n - 1;   // the state follows the input in every mode (.cs:142)
+    if (hold && have) return MM_OK;   // gs stays: the batch's slots are clear of it (place_batch)
+    h->gs = hold ? base : base + n - 1;   // the state follows the input in every mode (.cs:142)
     h->has_state = h->g_valid = true;
     return MM_OK;
 }
@@ -1639,10 +1659,13 @@ static int run_lanes(mm_handle *h, uint64_t mask, const uint8_t *in, uint8_t *ou
                 h->lsrc_bytes = need;
             }
         }
+        // (magnification off: a held lane that has state is copied through and
+        // nothing else happens to it: no K1)
+        const uint64_t k1 = mag ? mask : mask & ~(h->lane_hold & h->lane_state);
         for (int a = 0, b; a < n; a = b) {
             b = a + 1;
-            if (!bit(mask, a)) continue;
-            while (b < n && bit(mask, b) && bit(wr, b) == bit(wr, a)) ++b;
+            if (!bit(k1, a)) continue;
+            while (b < n && bit(k1, b) && bit(wr, b) == bit(wr, a)) ++b;
             c2 *G = h->d_LG + bank * bit(wr, a) + h->g_stride * a;
             if ((rc = launch_k1<LOG2N>(h, in + fr.in.stride * a, b - a, fr, s, G))) return rc;
         }
@@ -1677,7 +1700,10 @@ static int run_lanes(mm_handle *h, uint64_t mask, const uint8_t *in, uint8_t *ou
             else rc = copy_frames(h, in + fr.in.stride * a, out + fr.out.stride * a, b - a, fr, s);
             if (rc) return rc;
         }
-        h->lane_bank = (h->lane_bank & ~mask) | wr;
+        // a held lane that had state keeps its bank bit: its K1 wrote the
+        // other slot, K2 read both, and the next call overwrites that slot
+        const uint64_t flip = mask & ~(h->lane_hold & h->lane_state);
+        h->lane_bank = (h->lane_bank & ~flip) | (wr & flip);
         h->lane_state |= mask;
         return MM_OK;
     }

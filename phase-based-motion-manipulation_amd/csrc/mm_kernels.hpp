@@ -2307,7 +2307,15 @@ __device__ __forceinline__ float2 tab_ld(const float2 *p)
     return make_float2(v.x, v.y);
 }
 
-template <int LOG2N, int MODE, bool BLK0>
+//
+// HOLD (mm_set_hold, a held lane's stream form): the prime's F is the held
+// reference F_ref and no later frame overwrites it, so every frame of the
+// launch pairs with Gprev and the frames stop depending on each other.  The
+// prime is the rolling form's (same runtime passthrough test: F_ref has the
+// rolling prime's bits); what goes is every roll of the state: the generic
+// op's prev[j] = v[j], the packed-pair ops' write-back (they get copies), the
+// packed group's three branches and column N/2's real bins in ldsX.
+template <int LOG2N, int MODE, bool BLK0, bool HOLD = false>
 __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q,
                                             size_t q_stride, int nframes, const Geo &g,
                                             const Spec &sp, const c2 *__restrict__ tw,
@@ -2578,6 +2586,18 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
             wt[i] = wtw[i];
             if (tw_slot_used_wl(LOG2N, i)) asm volatile("" : "+v"(wt[i]));
         }
+        // hold: F_ref is loop-invariant, and so is what the ops derive from it
+        // alone (|F_ref|^2 per bin): the compiler hoists that, which saves the
+        // VALU per frame and keeps up to 12 more VGPRs live than the rolling
+        // twin has.  That fits the 128 of four waves per SIMD without a spill
+        // at every size but N = 8192 (tabled op: 6 spilled), where an opaque
+        // per-iteration copy in place (no v_mov) undoes the hoisting.  (At the
+        // other sizes the copy costs registers instead: the pairs it pins at
+        // N = 2048 made three of the four instances spill.)
+        if constexpr (HOLD && LOG2N == 13) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(prev[j]));
+        }
         K2_STAMP(2);
         MM_MARK("M1_fwd_start");
         fft_dif<LOG2N, -1>(v, t, lds, wt);
@@ -2607,7 +2627,12 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                     if (j % MM_K2_OPX2G == 0) __builtin_amdgcn_sched_barrier(0);
                     const float2 mt0 = tab_ld(j < 4 ? tlo + j * (N / 8) / C : thi + (N - j * (N / 8)) / C);
                     const float2 mt1 = tab_ld(j + 1 < 4 ? tlo + (j + 1) * (N / 8) / C : thi + (N - (j + 1) * (N / 8)) / C);
-                    pyramid_op_1band_x2(v[j], prev[j], mt0, v[j + 1], prev[j + 1], mt1, sp);
+                    if constexpr (HOLD) {   // F_ref stays: the op rolls copies
+                        c2 p0 = prev[j], p1 = prev[j + 1];
+                        pyramid_op_1band_x2(v[j], p0, mt0, v[j + 1], p1, mt1, sp);
+                    } else {
+                        pyramid_op_1band_x2(v[j], prev[j], mt0, v[j + 1], prev[j + 1], mt1, sp);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             } else if (MODE == MM_K2_PYR_TAB2) {
@@ -2626,7 +2651,12 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                     const int i1 = j + 1 < 4 ? (j + 1) * (N / 8) / C : (N - (j + 1) * (N / 8)) / C;
                     const float2 mt0 = tab_ld(j < 4 ? tlo + i0 : thi + i0), mt1 = tab_ld(j + 1 < 4 ? tlo + i1 : thi + i1);
                     const float s0 = j < 4 ? mlo[i0] : mhi[i0], s1 = j + 1 < 4 ? mlo[i1] : mhi[i1];
-                    pyramid_op_2band_x2(v[j], prev[j], mt0, s0, v[j + 1], prev[j + 1], mt1, s1, sp);
+                    if constexpr (HOLD) {
+                        c2 p0 = prev[j], p1 = prev[j + 1];
+                        pyramid_op_2band_x2(v[j], p0, mt0, s0, v[j + 1], p1, mt1, s1, sp);
+                    } else {
+                        pyramid_op_2band_x2(v[j], prev[j], mt0, s0, v[j + 1], prev[j + 1], mt1, s1, sp);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             } else {
@@ -2635,7 +2665,7 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                     // one bin at a time: keeps the 8 op instances from being interleaved
                     __builtin_amdgcn_sched_barrier(0);
                     const c2 a = k2_op<LOG2N, MODE>(v[j], prev[j], f, fft_bin<LOG2N>(t, j), sp, tab0);
-                    prev[j] = v[j];
+                    if constexpr (!HOLD) prev[j] = v[j];
                     v[j] = a;
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -2670,7 +2700,7 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                             const c2 c = v[j];
                             const float2 mt = pk_col0(j, fy) ? tab0[k2_tix<LOG2N>(fy)] : tabN[k2_tix<LOG2N>(N - fy)];
                             v[j] = pyramid_op_1band(c, prev[j], sp, mt);
-                            prev[j] = c;
+                            if constexpr (!HOLD) prev[j] = c;
                         }
                     } else if (MODE == MM_K2_PYR_TAB2) {   // two-band waves
 #pragma unroll
@@ -2681,7 +2711,7 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                             const int ix = k2_tix<LOG2N>(c0 ? fy : N - fy);
                             const c2 c = v[j];
                             v[j] = pyramid_op_2band(c, prev[j], sp, c0 ? tab0[ix] : tabN[ix], c0 ? ms0[ix] : msN[ix]);
-                            prev[j] = c;
+                            if constexpr (!HOLD) prev[j] = c;
                         }
                     } else {
 #pragma unroll
@@ -2691,7 +2721,7 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                             const c2 c = v[j];
                             v[j] = pk_col0(j, fy) ? k2_op<LOG2N, MODE>(c, prev[j], 0, fy, sp, tab0)
                                                   : k2_op<LOG2N, MODE>(c, prev[j], N / 2, N - fy, sp, tabN);
-                            prev[j] = c;
+                            if constexpr (!HOLD) prev[j] = c;
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -2711,7 +2741,7 @@ __device__ __forceinline__ void k_cols_body(const c2 *G, size_t g_stride, const 
                         const c2 z = lds[zslot<LOG2N>(fyx)];
                         const c2 fn = mk(0.5f * (z.y + z.y), -0.5f * (z.x - z.x));
                         if (!pass_frame) ldsX[2 + x] = k2_op<LOG2N, MODE>(fn, ldsX[x], N / 2, fyx, sp, tabN);
-                        ldsX[x] = fn;
+                        if (!HOLD || pass_frame) ldsX[x] = fn;
                     }
                 }
             } else {
@@ -2859,6 +2889,32 @@ void k_cols(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_strid
     }
 }
 
+// k_cols against a held reference (mm_set_hold): every frame of the launch
+// pairs with Gprev, which each workgroup transforms once, in its prime, and no
+// frame overwrites (k_cols_body's HOLD form).  The grid and the tail split are
+// k_cols's; a tail block primes with Gprev like every other workgroup, not
+// with the frame before its first.  (A kernel of its own, not a template
+// parameter of k_cols: the rolling instances keep their symbols and text.)
+template <int LOG2N, int MODE>
+__global__ __launch_bounds__(k2_threads<LOG2N>()) __attribute__((amdgpu_waves_per_eu(MM_K2_WAVES)))
+void k_cols_hold(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_stride,   // not restrict, as k_cols
+                 int nframes, Geo g, Spec sp, const c2 *__restrict__ tw, const float2 *__restrict__ ktab,
+                 const float *__restrict__ kmsum, int nframes_blk0, int tail_blocks, int ktail)
+{
+    const int nb = gridDim.x - tail_blocks;
+    const bool tail = (int)blockIdx.x >= nb;
+    const int p = tail ? nb / 2 + ((int)blockIdx.x - nb) : (int)blockIdx.x;
+    const int blk = xcd_remap(p, nb);
+    if (blk == 0) {
+        k_cols_body<LOG2N, MODE, true, true>(G, g_stride, Gprev, Q, q_stride, nframes_blk0, g, sp, tw, ktab, kmsum, blk, nb);
+    } else {
+        const int f0 = tail ? nframes - ktail : 0;
+        const int nf = tail ? ktail : (p >= nb / 2 && p - nb / 2 < tail_blocks ? nframes - ktail : nframes);
+        k_cols_body<LOG2N, MODE, false, true>(G + (size_t)f0 * g_stride, g_stride, Gprev,
+                                              Q + (size_t)f0 * q_stride, q_stride, nf, g, sp, tw, ktab, kmsum, blk, nb);
+    }
+}
+
 // The packed block's last frames, one workgroup per frame, after k_cols.
 // Block 0 carries the packed group's extra exchanges and is k_cols's critical
 // path, so the other blocks would idle at the end of the launch (rocprofv3:
@@ -2876,6 +2932,19 @@ void k_cols_tail(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_
     const int fr = f0 + (int)blockIdx.x;   // frame 0 primes with the state slot
     k_cols_body<LOG2N, MODE, true>(G + (size_t)fr * g_stride, g_stride,
                                    fr > 0 ? G + (size_t)(fr - 1) * g_stride : Gprev,
+                                   Q + (size_t)fr * q_stride, q_stride, 1, g, sp, tw, ktab, kmsum, 0);
+}
+
+// k_cols_tail against a held reference: every workgroup primes with Gprev.
+// One frame per workgroup rolls nothing, so the body is the rolling one: a
+// one-frame call's, on the held state.
+template <int LOG2N, int MODE>
+__global__ __launch_bounds__(k2_threads<LOG2N>()) __attribute__((amdgpu_waves_per_eu(MM_K2_WAVES)))
+void k_cols_tail_hold(const c2 *G, size_t g_stride, const c2 *Gprev, c2 *Q, size_t q_stride, int f0, Geo g, Spec sp,
+                      const c2 *__restrict__ tw, const float2 *__restrict__ ktab, const float *__restrict__ kmsum)
+{
+    const int fr = f0 + (int)blockIdx.x;
+    k_cols_body<LOG2N, MODE, true>(G + (size_t)fr * g_stride, g_stride, Gprev,
                                    Q + (size_t)fr * q_stride, q_stride, 1, g, sp, tw, ktab, kmsum, 0);
 }
 

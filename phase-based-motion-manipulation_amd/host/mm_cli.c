@@ -12,6 +12,7 @@
  *          [--yuy2] [--uyvy] [--y210] [--v210] [--ppm [--bgr | --bgra]] [--i420] [--i010] [--out-rgba8 | --out-bgra8] [--out-nv12]
  *          [--standard] [--show-magnitude] [--show-phase]
  *          [--orientations O] [--iir] [--halo K] [--surface-align P,R] [--lanes M]
+ *          [--hold R]
  *          [--checksum] [--ring-world G --ring-rank R --ring-id FILE]
  *          [--ring-local G [--compare]]
  *
@@ -156,8 +157,16 @@
  * host copy).  Status 2, before the output file is created, without --lanes,
  * for a lane >= M, for a malformed list, and without -i or with --checksum,
  * --out-rgba8 or --out-nv12 (the host copy is no conversion).
+ * --hold R: a held reference frame (mm_set_hold).  R = 0: the clip's first
+ * frame is the reference throughout.  R > 0: a new reference every R frames;
+ * the stream calls are split there and frames R, 2 R, ... run alone with hold
+ * off (each still pairs with the old reference and becomes the new one).  Every
+ * format option, --surface-align and --lanes as usual; with --lanes every lane
+ * holds and R counts ticks.  Refused (status 2) with --orientations / --iir,
+ * the debug views and the ring modes.
  */
 #include <hip/hip_runtime_api.h>
+#include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -685,7 +694,7 @@ int main(int argc, char **argv)
     int full_range = 0, standard = 0, show_mag = 0, show_phase = 0, checksum = 0;
     int ring_world = 0, ring_rank = 0, ring_local = 0, orientations = 1, iir = 0, halo = -1, compare = 0;
     int srgb = 0, bgr = 0, bgra = 0, out_rgba8 = 0, out_bgra8 = 0, out_nv12 = 0;
-    const char *lanes_arg = NULL, *drop_arg = NULL;
+    const char *lanes_arg = NULL, *drop_arg = NULL, *hold_arg = NULL;
     const in_opt *in = NULL;  /* the input-format option: one at most */
     const char *matrix_arg = NULL;
     const char *surf_arg = NULL;
@@ -735,6 +744,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--matrix")) matrix_arg = v;
         else if (!strcmp(a, "--lanes")) lanes_arg = v;
         else if (!strcmp(a, "--lane-drop")) drop_arg = v;
+        else if (!strcmp(a, "--hold")) hold_arg = v;
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         ++i;
     }
@@ -786,6 +796,14 @@ int main(int argc, char **argv)
         drops = parse_lane_drops(drop_arg, M, &ndrops);
         if (!drops) REFUSE("--lane-drop takes L:T[,L:T...] with lanes 0 .. %d, not %s\n", M - 1, drop_arg);
     }
+    /* a held reference frame (mm_set_hold) */
+    char *hold_end = NULL;
+    const long hold_l = hold_arg ? strtol(hold_arg, &hold_end, 10) : -1;
+    const int hold_R = hold_arg && isdigit((unsigned char)hold_arg[0]) && !*hold_end && hold_l <= 1000000000L ? (int)hold_l : -1;
+    if (hold_arg && hold_R < 0)
+        REFUSE("--hold takes 0 (the first frame is the reference throughout) or R > 0 (a new reference every R frames), not %s\n", hold_arg);
+    if (hold_arg && (orientations > 1 || iir || views || ring))
+        REFUSE("--hold does not go with --orientations / --iir, the debug views or the ring modes\n");
     if (ring_local > 0 && (in_path || out_path)) REFUSE("--ring-local needs a synthetic stream\n");
     if (ring_world > 0 && ring_local <= 0 && (!ring_id_path || in_path || out_path))
         REFUSE("--ring-world needs --ring-id and a synthetic stream\n");
@@ -1011,11 +1029,28 @@ int main(int argc, char **argv)
         }
         if (kept) memcpy(kept, host, (size_t)n * fb);   /* (`host` takes the output frames below) */
         hipEventRecord(e0, s);
+        /* --hold R with --lanes: every lane holds; tick R, 2 R, ... runs with hold off */
+        if (M && hold_R >= 0)
+            CHECK(mm_set_lanes_hold(h, hold_R > 0 && done > 0 && (done / M) % hold_R == 0 ? 0 : M >= 64 ? ~0ull : (1ull << M) - 1));
         if (ndrops) CHECK(mm_process_lanes_mask(h, mask, d_in, &lay, d_out, &olay, s));
         else if (M) CHECK(mm_process_lanes(h, d_in, &lay, d_out, &olay, s));   /* (n == M: whole ticks) */
-        else if (convert) CHECK(mm_process_stream_convert(h, d_in, &lay, d_out, &olay, n, s));
-        else if (surf_arg) CHECK(mm_process_stream_surfaces(h, d_in, &lay, d_out, &lay, n, s));
-        else CHECK(mm_process_stream(h, d_in, d_out, n, g_fmt, s));
+        else {
+            /* --hold R: the calls are split at frames R, 2 R, ..., each of which
+             * runs alone with hold off: it still pairs with the old reference and
+             * leaves its own state behind as the new one */
+            for (int k = 0, m; k < n; k += m) {
+                const int g = done + k;
+                const int reref = hold_R > 0 && g > 0 && g % hold_R == 0;
+                m = reref ? 1 : n - k;
+                if (hold_R > 0 && !reref && hold_R - g % hold_R < m) m = hold_R - g % hold_R;
+                if (hold_R >= 0) CHECK(mm_set_hold(h, !reref));
+                const unsigned char *ki = (const unsigned char *)d_in + lay.frame_stride * (size_t)k;
+                unsigned char *ko = (unsigned char *)d_out + olay.frame_stride * (size_t)k;
+                if (convert) CHECK(mm_process_stream_convert(h, ki, &lay, ko, &olay, m, s));
+                else if (surf_arg) CHECK(mm_process_stream_surfaces(h, ki, &lay, ko, &lay, m, s));
+                else CHECK(mm_process_stream(h, ki, ko, m, g_fmt, s));
+            }
+        }
         hipEventRecord(e1, s);
         hipEventSynchronize(e1);
         float ms = 0.0f;

@@ -28,7 +28,7 @@ from .binding import (MMError, lib, load_library, LIB_PATH, RGBA8, RGBA32F, RGBA
                       nv12_chroma_matrix, ycbcr_matrix, base_format,
                       EDGE_REPEAT, EDGE_CLAMP, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       FILTER_DIFF, FILTER_IIR, Params, Handle, Surface, has_surfaces,
-                      convert_supported, has_convert, has_lanes, has_lanes_mask, LANES_MAX, abi_symbols, resample_table,
+                      convert_supported, has_convert, has_lanes, has_lanes_mask, has_hold, LANES_MAX, abi_symbols, resample_table,
                       strerror)
 from .processor import MotionMagnificationProcessor, frame_layout
 from .stream import ShardedStream, shard_range
@@ -46,7 +46,7 @@ __all__ = ["MMError", "lib", "load_library", "LIB_PATH", "RGBA8", "RGBA32F", "RG
            "MATRIX_BT709", "MATRIX_BT2020", "nv12_chroma_matrix", "ycbcr_matrix", "base_format",
            "EDGE_REPEAT", "EDGE_CLAMP", "MODE_PYRAMID", "MODE_STANDARD", "MODE_STEERABLE",
            "FILTER_DIFF", "FILTER_IIR", "Params", "Handle", "Surface", "has_surfaces",
-           "convert_supported", "has_convert", "has_lanes", "has_lanes_mask", "LANES_MAX",
+           "convert_supported", "has_convert", "has_lanes", "has_lanes_mask", "has_hold", "LANES_MAX",
            "frame_layout", "abi_symbols",
            "resample_table", "strerror", "MotionMagnificationProcessor",
            "ShardedStream", "shard_range", "Ring", "new_ring_id", "ring_lib"]

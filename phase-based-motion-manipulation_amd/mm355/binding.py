@@ -297,6 +297,23 @@ def _lanes_mask_fn(name):
     return getattr(lib(), name)
 
 
+# a held reference frame (include/mm.h "Held reference frame"): frames pair with
+# the state and do not advance it
+HOLD_SYMBOLS = ("mm_set_hold", "mm_get_hold", "mm_set_lanes_hold", "mm_get_lanes_hold")
+
+
+def has_hold():
+    """The loaded library holds a reference frame (detected, as include/mm.h
+    says, by the presence of mm_set_hold)."""
+    return hasattr(lib(), "mm_set_hold")
+
+
+def _hold_fn(name):
+    if not has_hold():
+        raise MMError(-2, f"{library_path()} has no {name} (a build from before the held reference)")
+    return getattr(lib(), name)
+
+
 _lib = None
 _lib_path = None
 ABI_VERSION = 10  # include/mm.h MM_ABI_VERSION
@@ -333,6 +350,10 @@ def load_library(path=None):
         "mm_set_lane_state": (ci, [vp, ci, vp, sz, vp]),
         "mm_process_lanes_mask": (ci, [vp, ctypes.c_uint64, vp, ps, vp, ps, vp]),
         "mm_lanes_with_state": (ci, [vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "mm_set_hold": (ci, [vp, ci]),
+        "mm_get_hold": (ci, [vp, ctypes.POINTER(ci)]),
+        "mm_set_lanes_hold": (ci, [vp, ctypes.c_uint64]),
+        "mm_get_lanes_hold": (ci, [vp, ctypes.POINTER(ctypes.c_uint64)]),
         "mm_abi_version": (ci, []),
         "mm_strerror": (ctypes.c_char_p, [ci]),
         "mm_params_default": (ci, [pp]),
@@ -382,6 +403,8 @@ def load_library(path=None):
             continue    # ... or from before the lanes
         if name in LANES_MASK_SYMBOLS and not hasattr(L, name):
             continue    # ... or from before the lane masks
+        if name in HOLD_SYMBOLS and not hasattr(L, name):
+            continue    # ... or from before the held reference
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -606,6 +629,25 @@ class Handle:
     def set_lane_state(self, lane, dev_buf, stream=None):
         check(_lanes_fn("mm_set_lane_state")(self.h, int(lane), _ptr(dev_buf), self.state_bytes,
                                              _ptr(stream)), "mm_set_lane_state")
+
+    def set_hold(self, on):
+        """mm_set_hold: from the next call, frames pair with the state the
+        handle has and do not advance it (a held reference frame)."""
+        check(_hold_fn("mm_set_hold")(self.h, int(on)), "mm_set_hold")
+
+    def hold(self):
+        v = ctypes.c_int()
+        check(_hold_fn("mm_get_hold")(self.h, ctypes.byref(v)), "mm_get_hold")
+        return bool(v.value)
+
+    def set_lanes_hold(self, mask):
+        """mm_set_lanes_hold: bit k set makes lane k hold its reference."""
+        check(_hold_fn("mm_set_lanes_hold")(self.h, int(mask)), "mm_set_lanes_hold")
+
+    def lanes_hold(self):
+        m = ctypes.c_uint64()
+        check(_hold_fn("mm_get_lanes_hold")(self.h, ctypes.byref(m)), "mm_get_lanes_hold")
+        return m.value
 
     def reset(self):
         check(lib().mm_reset(self.h), "mm_reset")

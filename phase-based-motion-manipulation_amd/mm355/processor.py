@@ -9,7 +9,7 @@ import numpy as np
 from .binding import (EDGE_REPEAT, FILTER_DIFF, MODE_PYRAMID, MODE_STANDARD, MODE_STEERABLE,
                       MONO_FORMATS, NV12, NV12_FULL, P010, P010_FULL, PACKED422_FORMATS, RGBA8, RGBA8_SRGB, RGBA16F,
                       BGRA_FORMATS, I010_FORMATS, I420_FORMATS, RGB24_FORMATS, RGBA32F, V210, V210_FORMATS, Y8, Y210_FORMATS,
-                      Handle, MMError, Params, Surface, base_format, convert_supported, tight_pitch)
+                      Handle, MMError, Params, Surface, base_format, convert_supported, has_hold, tight_pitch)
 
 
 def _fmt_of(frame, srgb=False):
@@ -146,7 +146,7 @@ class MotionMagnificationProcessor:
                  low_frequency_cutoff=0.05, high_frequency_cutoff=0.4, filter_steepness=3.0,
                  motion_sensitivity=1.5, enhance_edges=True, edge_enhancement=0.8,
                  edge_mode=EDGE_REPEAT, orientations=1, temporal_filter=FILTER_DIFF,
-                 iir_low=None, iir_high=None, srgb=False, device=0):
+                 iir_low=None, iir_high=None, srgb=False, hold_reference=False, device=0):
         self.width, self.height, self.device = width, height, device
         # 8-bit frames are sRGB-encoded render targets under Unity's Linear colour
         # space (ProjectSettings/ProjectSettings.asset:50): decoded to linear light
@@ -175,6 +175,12 @@ class MotionMagnificationProcessor:
         self.orientations = orientations
         self.temporal_filter = temporal_filter
         self.iir_low, self.iir_high = iir_low, iir_high
+        # held reference frame (no reference counterpart, include/mm.h "Held
+        # reference frame"): every frame pairs with one reference frame, the
+        # first after Start() / reset() or the one rehold() names, instead of
+        # with the frame before it; applied in Start() / OnValidate()
+        self.hold_reference = hold_reference
+        self._rehold = False
         self._handle = None
 
     # -- reference lifecycle -------------------------------------------------
@@ -209,12 +215,17 @@ class MotionMagnificationProcessor:
     def Start(self):
         """Start -> InitializeProcessor (.cs:90-94, :289-342). Raises on failure."""
         self._handle = Handle(self.width, self.height, self._params(), self.device)
+        if self.hold_reference:
+            self._handle.set_hold(True)
         return self
 
     def OnValidate(self):
         """OnValidate (.cs:78-88): push edited fields; effective next frame."""
         if self._handle is not None:
             self._handle.set_params(self._params())
+            # (a library from before the hold has nothing to switch off)
+            if self.hold_reference or has_hold():
+                self._handle.set_hold(self.hold_reference)
 
     def OnRenderImage(self, source, destination, fmt=None, dst_fmt=None):
         """OnRenderImage (.cs:101-143). source/destination: [H, W, 4] uint8,
@@ -252,6 +263,19 @@ class MotionMagnificationProcessor:
         wherever RGBA8 does (dst_fmt=BGRA8, or fmt=BGRA8 with an NV12 dst_fmt).  Each side's
         shape and dtype are checked by that side's format, before any frame
         call into the library."""
+        if self._rehold and self._handle is not None:
+            # rehold(): this frame runs with hold off (it still pairs with the
+            # old reference) and leaves its own state behind as the new one
+            # (a frame that is refused does not use the re-reference up)
+            self._rehold = False
+            self._handle.set_hold(False)
+            try:
+                return self.OnRenderImage(source, destination, fmt, dst_fmt)
+            except Exception:
+                self._rehold = True
+                raise
+            finally:
+                self._handle.set_hold(self.hold_reference)
         if dst_fmt is not None and dst_fmt != (fmt if fmt is not None else _fmt_of(source, self.srgb)):
             if fmt is None:
                 fmt = _fmt_of(source, self.srgb)
@@ -312,6 +336,11 @@ class MotionMagnificationProcessor:
     def reset(self):
         """isFirstFrame = true (.cs:75): next frame passes through."""
         self._handle.reset()
+
+    def rehold(self):
+        """With hold_reference: the next frame becomes the new reference (one
+        frame with hold off: no passthrough frame)."""
+        self._rehold = True
 
     @property
     def handle(self):
